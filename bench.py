@@ -456,12 +456,21 @@ def multitask_measure(dev, batch_per_gpu, rank, world, steps=6, warm=3, find=Fal
                     "AdamW; cfg-A, synthetic collate_fn-shaped batch; forward + backward + optimizer step"}
 
 
+def detached(step_outputs):
+    """(lift output, render outputs) of a step without their autograd graph: a graph kept alive keeps the parameters'
+    gradient accumulators -- and the stream they were made on -- into the next step, and a capture on another stream
+    then faults (seen as a segmentation fault in the capture)."""
+    vox, outs = step_outputs
+    return vox.detach(), [o.detach() for o in outs]
+
+
 def capture_step(model, batch, train_step):
     """One training step (without the DDP wrapper) captured into a HIP graph; the replay must
-    reproduce the eager gradients."""
+    reproduce the eager gradients.  `g.step_outputs` holds the captured step's (lift output, render
+    outputs): every replay rewrites them."""
     def raw_step():
         model.zero_grad(set_to_none=True)
-        train_step(model, batch)
+        return detached(train_step(model, batch))
 
     cur = torch.cuda.current_stream()
     side = torch.cuda.Stream()
@@ -477,7 +486,7 @@ def capture_step(model, batch, train_step):
     g = torch.cuda.CUDAGraph()
     # thread_local: calls of other threads (the RCCL watchdog polls its events) must not fail the capture
     with torch.cuda.graph(g, stream=side, capture_error_mode="thread_local"):
-        raw_step()
+        g.step_outputs = raw_step()
     torch.cuda.synchronize()
     g.replay()
     torch.cuda.synchronize()
@@ -566,6 +575,38 @@ def replay_rate(model, batch, train_step, steps, world, dev, vdist, sync_wrapper
     return vdist.max_over_ranks(time.perf_counter() - t0, dev), ("hip_graph" if graph is not None else "eager")
 
 
+RENDER_OUTPUTS = ["rgb_preds", "seg_logits_preds", "depth_preds", "bev_rgb_preds",
+                  "bev_seg_logits_preds", "bev_height_preds", "voxel_density", "voxel_output"]
+DUMP_MAX_ELEMENTS = 1 << 19          # per array: 17 arrays of at most 2 MiB stay under the 64 MB the dump may take
+
+
+def dump_outputs(out_dir, model, batch, vox, outs):
+    """What a caller of the timed step receives -- the lift output, the eight render outputs and the gradients of
+    the step's inputs and of beta -- as <out_dir>/<name>.npy in float32.  An array of more than DUMP_MAX_ELEMENTS
+    elements is written as a fixed sample of them: the flat indices drawn by a generator seeded from the array's
+    position in the list (sorted, with repeats), so that two builds run with the same arguments write the same
+    elements of the same inputs."""
+    import numpy as np
+    arrays = [("lift_output", vox)] + list(zip(RENDER_OUTPUTS, outs))
+    arrays += [("grad_depth", batch.depth.grad), ("grad_feat", batch.feat.grad)]
+    arrays += [("grad_" + n, v.grad) for n, v in zip(("density_feature", "semantic_logits", "base", "rgb"), batch.vols)]
+    arrays.append(("grad_beta", model.beta.grad))
+    os.makedirs(out_dir, exist_ok=True)
+    total = 0
+    for i, (name, t) in enumerate(arrays):
+        if t is None:                                      # (no beta gradient under density_mode="naive")
+            continue
+        t = t.detach().float()
+        if t.numel() > DUMP_MAX_ELEMENTS:
+            g = torch.Generator(device="cpu").manual_seed(1000 + i)
+            idx = torch.randint(0, t.numel(), (DUMP_MAX_ELEMENTS,), generator=g).sort().values
+            t = t.reshape(-1)[idx.to(t.device)]
+        a = t.cpu().numpy()
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+        total += a.nbytes
+    assert total <= 64 * 10 ** 6, f"dump of {total} bytes"
+
+
 _T0 = time.perf_counter()
 
 
@@ -590,7 +631,12 @@ def main():
     ap.add_argument("--layers", action="store_true", help="(accepted for compatibility: the layered step is always timed unless --no-extra)")
     ap.add_argument("--miopen-find", action="store_true",
                     help="let MIOpen tune the convolutions of the layered / multi-task legs (6.5 minutes on a fresh box)")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="after the timed steps, write what the last timed step computed (outputs and gradients, "
+                         "float32, a fixed sample of the large ones) as DIR/<name>.npy, e.g. DIR=bench_outputs")
     a = ap.parse_args()
+    if a.steps < 1:
+        ap.error("--steps must be at least 1")
 
     world = int(os.environ.get("WORLD_SIZE", "1"))
     rank = int(os.environ.get("RANK", "0"))
@@ -623,9 +669,11 @@ def main():
     step_model = vdist.wrap_ddp(model, dev)
     batch = SyntheticBatch(cfg, a.batch, dev, seed=vdist.shard_seed(0, rank), dtype=dtype)
 
+    last = {}
+
     def one_step():
         model.zero_grad(set_to_none=True)
-        train_step(step_model, batch)
+        last["outputs"] = detached(train_step(step_model, batch))
 
     def fence():
         vdist.barrier()
@@ -708,6 +756,10 @@ def main():
     elapsed = time.perf_counter() - t0
     _capi.profile_enable(False)
     elapsed = vdist.max_over_ranks(elapsed, dev)
+    if a.dump_outputs and rank == 0:
+        # (before the eager profile steps below replace the gradients)
+        dump_outputs(a.dump_outputs, model, batch, *(graph.step_outputs if graph is not None else last["outputs"]))
+        _mark("outputs dumped")
     if graph is not None:
         # the dominant kernel's launches, timed with HIP events in K eager one-stream steps
         model.hp.impl["overlap"] = False
@@ -776,13 +828,18 @@ def main():
     _mark("step matrix done")
     bs8 = None
     if not a.no_extra and a.batch != 8:
+        # a model of its own, as extra_config builds one: the headline model's HotPath keeps its batch-1 workspaces (which
+        # the headline's captured graph still points at), side stream and call state, and driving it at batch 8 ended the
+        # process with a segmentation fault
+        model8 = LiftRenderStep(cfg, dev)
+        step_model8 = vdist.wrap_ddp(model8, dev)
         batch8 = SyntheticBatch(cfg, 8, dev, seed=vdist.shard_seed(1, rank), dtype=dtype)
-        el8, mode8 = replay_rate(model, batch8, train_step, a.steps, world, dev, vdist,
-                                 sync_wrapper=step_model if step_model is not model else None)
+        el8, mode8 = replay_rate(model8, batch8, train_step, a.steps, world, dev, vdist,
+                                 sync_wrapper=step_model8 if step_model8 is not model8 else None)
         bs8 = {"value": 8 * world * a.steps / el8, "unit": "samples/s", "ms_per_step": el8 / a.steps * 1e3,
                "per_gpu_batch": 8, "global_batch": 8 * world, "n_gpus": world, "steps": a.steps, "launch": mode8,
                "scaling": "weak"}
-        del batch8
+        del batch8, step_model8, model8
     # SURVEY 8(e) / BASELINE configs[4]: the step with a real gradient bucket and the full multi-task step,
     # always in the line (a few seconds; --no-extra skips them for profile runs)
     _mark("bs8 done")
