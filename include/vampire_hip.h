@@ -27,7 +27,8 @@
 extern "C" {
 #endif
 
-#define VAMP_ABI_VERSION 6   /* bumped whenever entry points or flags are added (round 2: 2, round 3: 3, round 4: 4, round 5: 5, round 6: 6) */
+#define VAMP_ABI_VERSION 7   /* bumped whenever entry points or flags are added (round 2: 2, round 3: 3, round 4: 4, round 5: 5, round 6: 6;
+                                 7: segmentation metrics) */
 
 enum {
   VAMP_OK = 0,
@@ -753,6 +754,52 @@ int vamp_conv3d_half_backward_data(const VampConvDesc* d, int32_t dtype, const v
                                    void* grad_in, void* stream);
 int vamp_conv3d_half_backward_weight(const VampConvDesc* d, int32_t dtype, const void* in, const void* grad_out,
                                      float* grad_weight, void* workspace, size_t workspace_bytes, void* stream);
+
+/* --------------------------------------------------------------------------
+ * Segmentation metrics (base_exp.py:370-382 training, :634-663 validation, :835-840 submission labels).
+ *
+ * vamp_confusion_update: for every element i with mask[i] != 0 (mask may be NULL) and, when use_ignore,
+ * target[i] != ignore_index, the prediction p = lo + argmax(logits[i, lo:hi]) (torch.argmax: the first
+ * maximal index, a NaN above every number and the first NaN wins; bf16 compared after exact conversion to
+ * fp32) -- or pred[i] itself for integer predictions -- is counted as
+ *     confmat[t, p] += 1   if 0 <= t = target[i] < Kc and 0 <= p < Kc,   else invalid[0] += 1.
+ * confmat [Kc, Kc] and invalid [1] are int64 and ACCUMULATED.  Logit layouts, n = B * S elements:
+ *   VAMP_SEG_ROWS   logits [n, K], the classes of an element contiguous (point logits);
+ *   VAMP_SEG_PLANES logits [B, K, S], element i = b * S + s (the channel-first volume behind the
+ *                   backbone's occ_logits.permute(0, 2, 3, 4, 1) view: class stride S = X * Y * Z).
+ * target [n] (target_dtype), mask [n] (bool bytes).  Integer predictions: pred [n], layout ROWS, K = 1,
+ * lo / hi unused.  Per-workgroup LDS histograms stored to slabs of the workspace
+ * (vamp_confusion_workspace_bytes) and added in a fixed order by a second launch: exact, no float atomics,
+ * no synchronisation, capturable.  n < 2^31 per call.
+ * -------------------------------------------------------------------------- */
+enum { VAMP_I64 = 3, VAMP_I32 = 4, VAMP_U8 = 5 };     /* integer tensors of the metric entry points */
+enum { VAMP_SEG_ROWS = 0, VAMP_SEG_PLANES = 1 };
+typedef struct VampConfDesc {
+  int64_t B, S;          /* n = B * S elements (ROWS: B = 1)                                 */
+  int32_t K;             /* classes of a logit row (the class dimension); integer predictions: 1 */
+  int32_t layout;        /* VAMP_SEG_ROWS | VAMP_SEG_PLANES                                  */
+  int32_t pred_dtype;    /* VAMP_F32 | VAMP_BF16 logits, VAMP_I64 | VAMP_I32 predictions       */
+  int32_t target_dtype;  /* VAMP_I64 | VAMP_I32 | VAMP_U8                                    */
+  int32_t Kc;            /* confusion-matrix classes, 1..32                                   */
+  int32_t lo, hi;        /* class window: 0 <= lo < hi <= K and hi - 1 < Kc                   */
+  int32_t ignore_index;  /* targets equal to it are skipped when use_ignore = 1               */
+  int32_t use_ignore;
+  int32_t reserved;      /* 0 */
+} VampConfDesc;
+size_t vamp_confusion_workspace_bytes(const VampConfDesc* d);
+int vamp_confusion_update(const VampConfDesc* d, const void* pred, const void* target, const uint8_t* mask,
+                          int64_t* confmat, int64_t* invalid, void* workspace, size_t workspace_bytes,
+                          void* stream);
+/* vamp_lidarseg_predict: ref_logits[r] = fp32 sum, in increasing point order, of pts_logits[p] (row of K,
+ * dtype VAMP_F32 | VAMP_BF16) over the points p with ref_index[p] == r (the reference's zeros + index_add_),
+ * labels[r] = lo + argmax(ref_logits[r, lo:hi]) as int64 (a reference point no point maps to has zero logits:
+ * label lo).  Points whose index lies outside [0, num_ref) are not summed; their count is written to
+ * invalid[0] (int64).  labels [num_ref] and invalid are overwritten.  hi - lo <= 64; P, num_ref < 2^31.
+ * Deterministic and bit-exact against a sequential CPU index_add_. */
+size_t vamp_lidarseg_workspace_bytes(int64_t P, int64_t num_ref);
+int vamp_lidarseg_predict(int64_t P, int32_t K, int32_t dtype, int32_t lo, int32_t hi, const void* pts_logits,
+                          const int64_t* ref_index, int64_t num_ref, int64_t* labels, int64_t* invalid,
+                          void* workspace, size_t workspace_bytes, void* stream);
 
 #ifdef __cplusplus
 }

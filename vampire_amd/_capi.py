@@ -9,10 +9,12 @@ import os
 
 from .build import lib_path
 
-ABI_VERSION = 6
+ABI_VERSION = 7
 
 VAMP_F32, VAMP_BF16, VAMP_F16 = 0, 1, 2
 VAMP_DENSITY_SIGMOID, VAMP_DENSITY_SDF_LAPLACE = 0, 1
+VAMP_I64, VAMP_I32, VAMP_U8 = 3, 4, 5
+VAMP_SEG_ROWS, VAMP_SEG_PLANES = 0, 1
 
 
 class VampLiftDesc(C.Structure):
@@ -57,6 +59,13 @@ class VampSampleDesc(C.Structure):
 
 
 VAMP_PAD_ZEROS, VAMP_PAD_BORDER = 0, 1
+class VampConfDesc(C.Structure):
+    _fields_ = [("B", C.c_int64), ("S", C.c_int64), ("K", C.c_int32), ("layout", C.c_int32),
+                ("pred_dtype", C.c_int32), ("target_dtype", C.c_int32), ("Kc", C.c_int32),
+                ("lo", C.c_int32), ("hi", C.c_int32), ("ignore_index", C.c_int32), ("use_ignore", C.c_int32),
+                ("reserved", C.c_int32)]
+
+
 # flag bits of vamp_lift_backward_ex / vamp_render_camera_backward_acc (include/vampire_hip.h)
 VAMP_LIFTFWD_EMIT_PAIRS, VAMP_LIFTFWD_CELLS_CLEAN, VAMP_LIFTFWD_FEAT_CHANNEL_LAST, VAMP_LIFTFWD_DEFER_SCAN = 1, 2, 4, 8
 VAMP_LIFTBWD_CELLS_VALID, VAMP_LIFTBWD_SPLAT = 1, 2
@@ -78,6 +87,7 @@ _LD = C.POINTER(VampLiftDesc)
 _RD = C.POINTER(VampRenderDesc)
 _SD = C.POINTER(VampSampleDesc)
 _CD = C.POINTER(VampConvDesc)
+_QD = C.POINTER(VampConfDesc)
 
 # name -> (restype, argtypes); must list every symbol declared in include/vampire_hip.h
 SIGNATURES = {
@@ -160,6 +170,11 @@ SIGNATURES = {
                                   + [_P] * 6),
     "vamp_gate_conv1x1_backward": (C.c_int, [C.c_int64, C.c_int32, C.c_int32, C.c_int64, C.c_int32, C.c_int32]
                                    + [_P] * 9 + [C.c_size_t, _P]),
+    "vamp_confusion_workspace_bytes": (C.c_size_t, [_QD]),
+    "vamp_confusion_update": (C.c_int, [_QD] + [_P] * 5 + [_P, C.c_size_t, _P]),
+    "vamp_lidarseg_workspace_bytes": (C.c_size_t, [C.c_int64, C.c_int64]),
+    "vamp_lidarseg_predict": (C.c_int, [C.c_int64, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _P, _P, C.c_int64,
+                                        _P, _P, _P, C.c_size_t, _P]),
 }
 
 _lib = None

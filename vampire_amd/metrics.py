@@ -1,0 +1,147 @@
+"""Segmentation evaluation of the multi-task model: lidar-segmentation mIoU and Occ3D occupancy mIoU
+(the reference's src/exps/nuscenes/base_exp.py:286-290 metric objects, :370-382 `training_step`,
+:634-663 `validation_step`, :835-840 submission labels, :851-910 epoch ends).
+
+The reference counts with torchmetrics' `JaccardIndex`, after a boolean index (`occ_logits[mask_camera]`:
+a host synchronisation and a copy of half the logits) and an argmax.  Here the counting is the HIP
+confusion-matrix pass of `ops.confusion_update` over the logits in place, and the per-reference-point
+prediction is `ops.lidarseg_predict`; nothing leaves the device until `compute()`.
+"""
+import numpy as np
+import torch
+import torch.distributed as dist
+
+from . import ops
+
+# base_exp.py:222-224 (label_17_names): the 18 classes of the lidar-seg / Occ3D label space
+CLASS_NAMES = ["other", "barrier", "bicycle", "bus", "car", "construction_vehicle", "motorcycle", "pedestrian",
+               "traffic_cone", "trailer", "truck", "driveable_surface", "other_flat", "sidewalk", "terrain",
+               "manmade", "vegetation", "free"]
+
+
+class JaccardIndex:
+    """Per-class intersection over union from an int64 confusion matrix (torchmetrics' multiclass
+    `JaccardIndex(num_classes, ignore_index, average='none')`, the version the reference pins: 0.11.0).
+
+    State: `confmat[target, pred]` and `invalid` (elements whose target -- or integer prediction -- lies
+    outside [0, num_classes), which torchmetrics rejects).  This project's definition of the result:
+
+        IoU_c = cm[c, c] / (sum_p cm[c, p] + sum_t cm[t, c] - cm[c, c]),   and 0.0 when that union is 0,
+
+    as float64.  `compute()` raises ValueError while `invalid` is non-zero.  Elements whose target equals
+    `ignore_index` are not counted; the entry AT `ignore_index` is unspecified (callers drop it)."""
+
+    def __init__(self, num_classes, ignore_index=None, device="cuda"):
+        self.num_classes, self.ignore_index = int(num_classes), ignore_index
+        self.confmat = torch.zeros(self.num_classes, self.num_classes, dtype=torch.int64, device=device)
+        self.invalid = torch.zeros((), dtype=torch.int64, device=device)
+
+    def update(self, logits_or_preds, target, mask=None, class_window=None):
+        """Logits [..., K] (prediction lo + argmax over `class_window` = (lo, hi), default all classes) or
+        integer predictions shaped like `target`; `mask` (bool, like target) selects the elements counted."""
+        ops.confusion_update(self.confmat, self.invalid, logits_or_preds, target, mask, class_window=class_window,
+                             ignore_index=self.ignore_index)
+
+    def reset(self):
+        self.confmat.zero_()
+        self.invalid.zero_()
+
+    def sync(self, group=None):
+        """Sum the state over the process group (what torchmetrics does at compute() under DDP); a no-op
+        when torch.distributed is not initialised."""
+        if dist.is_available() and dist.is_initialized():
+            dist.all_reduce(self.confmat, op=dist.ReduceOp.SUM, group=group)
+            dist.all_reduce(self.invalid, op=dist.ReduceOp.SUM, group=group)
+
+    def compute(self):
+        if int(self.invalid) != 0:
+            raise ValueError(f"{int(self.invalid)} elements had a target (or prediction) outside "
+                             f"[0, {self.num_classes})")
+        cm = self.confmat.double()
+        inter = cm.diagonal()
+        union = cm.sum(1) + cm.sum(0) - inter
+        return torch.where(union > 0, inter / union.clamp(min=1), torch.zeros_like(inter))
+
+
+class SegEvaluator:
+    """The reference's four metric objects (base_exp.py:286-290) and the code around them: lidar-seg IoU
+    over num_seg_classes - 1 classes with class 0 ignored (predictions are 1 + argmax over classes 1:-1),
+    occupancy IoU over num_seg_classes classes (the last one, "free", is left out of the mean)."""
+
+    def __init__(self, num_seg_classes=len(CLASS_NAMES), class_names=None, device="cuda"):
+        K = self.num_seg_classes = int(num_seg_classes)
+        names = list(CLASS_NAMES if class_names is None else class_names)
+        if len(names) != K:
+            raise ValueError(f"{len(names)} class names for {K} classes")
+        self.lidar_names, self.occ_names = names[1:-1], names          # unique_label_str, occ_label_str
+        self.train_iou = JaccardIndex(K - 1, ignore_index=0, device=device)
+        self.occ_train_iou = JaccardIndex(K, device=device)
+        self.val_iou = JaccardIndex(K - 1, ignore_index=0, device=device)
+        self.occ_val_iou = JaccardIndex(K, device=device)
+        self.best_miou = self.best_occ_miou = 0.0
+
+    @property
+    def window(self):
+        return (1, self.num_seg_classes - 1)
+
+    def update_train(self, outputs, batch):
+        """base_exp.py:370-382 on the 12 model outputs of a training forward and the 20-entry train batch."""
+        pts_logits, occ_logits = outputs[8], outputs[10]
+        inrange_labels, occ_semantics, mask_camera = batch[12], batch[16], batch[19]
+        for logits, labels in zip(pts_logits, inrange_labels):
+            self.train_iou.update(logits, labels, class_window=self.window)
+        self.occ_train_iou.update(occ_logits, occ_semantics, mask_camera)
+
+    def update_val(self, outputs, batch):
+        """base_exp.py:645-660 on the (pts_logits, occ_logits, occ_density) of a lidar_seg=True forward and the
+        15-entry validation batch."""
+        pts_logits, occ_logits = outputs[0], outputs[1]
+        ref_labels, ref_index, occ_semantics, mask_camera = batch[8], batch[9], batch[11], batch[14]
+        for logits, idx, labels in zip(pts_logits, ref_index, ref_labels):
+            dev = logits.device
+            pred, bad = ops.lidarseg_predict(logits, idx.to(dev, non_blocking=True), len(labels), self.window)
+            self.val_iou.update(pred, labels.to(dev, non_blocking=True))
+            self.val_iou.invalid += bad                  # index_add_ rejects an index out of range
+        self.occ_val_iou.update(occ_logits, occ_semantics, mask_camera)
+
+    def validation_step(self, model, batch):
+        """base_exp.py:634-663: the model in eval mode without gradients, lidar_seg=True, then update_val."""
+        was_training = model.training
+        model.eval()
+        try:
+            with torch.no_grad():
+                outputs = model(batch[0], batch[1], inrange_pts=batch[6], lidar_seg=True)
+            self.update_val(outputs, batch)
+        finally:
+            model.train(was_training)
+        return outputs
+
+    def epoch_end(self, prefix="val"):
+        """base_exp.py:851-910: sync, {prefix}/mIoU = nanmean(iou[1:]), {prefix}/occ_mIoU = nanmean(occ_iou[:-1]),
+        the per-class IoUs by name; best values are kept for prefix 'val'; the metrics are reset."""
+        lidar, occ = (self.val_iou, self.occ_val_iou) if prefix == "val" else (self.train_iou, self.occ_train_iou)
+        lidar.sync()
+        occ.sync()
+        iou = lidar.compute()[1:].cpu().numpy()
+        occ_iou = occ.compute()[:-1].cpu().numpy()
+        miou, occ_miou = float(np.nanmean(iou)), float(np.nanmean(occ_iou))
+        if prefix == "val":
+            self.best_miou = max(self.best_miou, miou)
+            self.best_occ_miou = max(self.best_occ_miou, occ_miou)
+        out = {f"{prefix}/mIoU": miou, f"{prefix}/occ_mIoU": occ_miou}
+        out.update({f"{prefix}/iou/{n}": float(v) for n, v in zip(self.lidar_names, iou)})
+        out.update({f"{prefix}/occ_iou/{n}": float(v) for n, v in zip(self.occ_names, occ_iou)})
+        lidar.reset()
+        occ.reset()
+        return out
+
+    def lidarseg_labels(self, pts_logits_batch, ref_index, ref_labels):
+        """The submission labels of base_exp.py:835-840 (uint8, 1 .. K - 2 per reference point), one device
+        tensor per sample; no files are written.  Raises ValueError on a reference index out of range."""
+        out = []
+        for logits, idx, labels in zip(pts_logits_batch, ref_index, ref_labels):
+            pred, bad = ops.lidarseg_predict(logits, idx.to(logits.device), len(labels), self.window)
+            if int(bad):
+                raise ValueError(f"{int(bad)} points map outside the {len(labels)} reference points")
+            out.append(pred.to(torch.uint8))
+        return out

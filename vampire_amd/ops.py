@@ -1353,3 +1353,113 @@ class _Conv3dFn(torch.autograd.Function):
             _capi.check(lib.vamp_conv3d_backward_weight(C.byref(d), _ptr(x), _ptr(g), _ptr(gw), _ptr(ws),
                                                         ws.numel(), _stream()), "vamp_conv3d_backward_weight")
         return gx, gw
+
+
+# ===========================================================================
+# segmentation metrics (base_exp.py:370-382, :634-663, :835-840)
+# ===========================================================================
+_metric_ws = {}
+_TARGET_CODES = {torch.int64: _capi.VAMP_I64, torch.int32: _capi.VAMP_I32, torch.uint8: _capi.VAMP_U8}
+_PRED_CODES = {torch.float32: _capi.VAMP_F32, torch.bfloat16: _capi.VAMP_BF16,
+               torch.int64: _capi.VAMP_I64, torch.int32: _capi.VAMP_I32}
+
+
+def _metric_workspace(kind, device, nbytes):
+    key = (kind, device, torch.cuda.current_stream(device).cuda_stream)
+    ws = _metric_ws.get(key)
+    if ws is None or ws.numel() < nbytes:
+        ws = _metric_ws[key] = torch.empty(max(nbytes, 256), dtype=torch.uint8, device=device)
+    return ws
+
+
+def _logit_layout(x):
+    """(layout, B, S, x) for logits [..., K]: rows when contiguous, planes when the memory is channel-first
+    ([B, K, ...] behind a permute(0, 2, .., 1) view, the backbone's occ_logits), else a contiguous copy."""
+    if x.is_contiguous():
+        return _capi.VAMP_SEG_ROWS, 1, x.numel() // max(x.shape[-1], 1), x
+    if x.dim() == 2 and x.t().is_contiguous():
+        return _capi.VAMP_SEG_PLANES, 1, x.shape[0], x
+    if x.dim() >= 3 and x.movedim(-1, 1).is_contiguous():
+        return _capi.VAMP_SEG_PLANES, x.shape[0], math.prod(x.shape[1:-1]), x
+    x = x.contiguous()
+    return _capi.VAMP_SEG_ROWS, 1, x.numel() // max(x.shape[-1], 1), x
+
+
+def confusion_update(confmat, invalid, logits_or_preds, target, mask=None, *, class_window=None, ignore_index=None):
+    """confmat[t, p] += 1 for every element with mask true and target t != ignore_index, where p =
+    lo + argmax(logits[..., lo:hi]) (torch.argmax ties and NaNs) or the integer prediction itself; targets
+    (and integer predictions) outside [0, Kc) add 1 to `invalid` instead.  confmat: int64 [Kc, Kc], invalid:
+    int64 with one element, both device tensors, accumulated.  logits [..., K] fp32 | bf16 (fp16 promoted),
+    target / mask shaped like logits[..., 0] (or like the integer predictions); target int64 | int32 | uint8.
+    One HIP pass on the current stream; no host synchronisation, capturable in a graph."""
+    x = logits_or_preds
+    if not (confmat.is_cuda and invalid.is_cuda and x.is_cuda and target.is_cuda and (mask is None or mask.is_cuda)):
+        raise _capi.VampireHipError("confusion_update needs device tensors (no CPU fallback)")
+    if confmat.dtype != torch.int64 or confmat.dim() != 2 or confmat.shape[0] != confmat.shape[1] \
+            or not confmat.is_contiguous():
+        raise ValueError("confmat must be a contiguous int64 [Kc, Kc] tensor")
+    if invalid.dtype != torch.int64 or invalid.numel() != 1:
+        raise ValueError("invalid must be a one-element int64 tensor")
+    Kc = confmat.shape[0]
+    integer = not x.is_floating_point()
+    if integer:
+        if tuple(x.shape) != tuple(target.shape):
+            raise ValueError(f"predictions {tuple(x.shape)} and target {tuple(target.shape)} differ in shape")
+        if x.dtype not in (torch.int64, torch.int32):
+            x = x.long()
+        layout, B, S, x, K = _capi.VAMP_SEG_ROWS, 1, x.numel(), x.contiguous(), 1
+        lo, hi = 0, 1
+    else:
+        x = _accept(x)
+        if tuple(x.shape[:-1]) != tuple(target.shape):
+            raise ValueError(f"logits {tuple(x.shape)} do not match target {tuple(target.shape)}")
+        K = x.shape[-1]
+        lo, hi = (0, K) if class_window is None else (int(class_window[0]), int(class_window[1]))
+        layout, B, S, x = _logit_layout(x)
+    if target.dtype not in _TARGET_CODES:
+        target = target.long()
+    target = target.contiguous()
+    if mask is not None:
+        if tuple(mask.shape) != tuple(target.shape):
+            raise ValueError(f"mask {tuple(mask.shape)} does not match target {tuple(target.shape)}")
+        mask = (mask if mask.dtype == torch.bool else mask != 0).contiguous()
+    d = _capi.VampConfDesc(B, S, K, layout, _PRED_CODES[x.dtype], _TARGET_CODES[target.dtype], Kc, lo, hi,
+                           0 if ignore_index is None else int(ignore_index), 0 if ignore_index is None else 1, 0)
+    lib = _capi.load()
+    nbytes = lib.vamp_confusion_workspace_bytes(C.byref(d))
+    if nbytes == 0:
+        _capi.check(lib.vamp_confusion_update(C.byref(d), None, None, None, None, None, None, 0, None),
+                    "vamp_confusion_update")
+    with torch.cuda.device(x.device):
+        ws = _metric_workspace("confusion", x.device, nbytes)
+        _capi.check(lib.vamp_confusion_update(C.byref(d), _ptr(x), _ptr(target), _ptr(mask), _ptr(confmat),
+                                              _ptr(invalid), _ptr(ws), ws.numel(), _stream()),
+                    "vamp_confusion_update")
+    return confmat
+
+
+def lidarseg_predict(pts_logits, ref_index, num_ref, class_window):
+    """The reference's lidar-segmentation prediction (base_exp.py:645-649, :835-838): zeros [num_ref, K],
+    index_add_(0, ref_index, pts_logits), then lo + argmax over classes [lo, hi).  Sums run in increasing
+    point order (bit-exact against a sequential CPU index_add_).  Returns (labels int64 [num_ref], invalid
+    int64 0-dim: the number of points whose index lies outside [0, num_ref)).  HIP kernels on the current
+    stream; no host synchronisation."""
+    if not (pts_logits.is_cuda and ref_index.is_cuda):
+        raise _capi.VampireHipError("lidarseg_predict needs device tensors (no CPU fallback)")
+    if pts_logits.dim() != 2 or ref_index.dim() != 1 or ref_index.shape[0] != pts_logits.shape[0]:
+        raise ValueError(f"expected pts_logits [P, K] and ref_index [P], got {tuple(pts_logits.shape)} "
+                         f"and {tuple(ref_index.shape)}")
+    x = _accept(pts_logits).contiguous()
+    idx = ref_index.long().contiguous()
+    P, K = x.shape
+    lo, hi = int(class_window[0]), int(class_window[1])
+    num_ref = int(num_ref)
+    labels = torch.empty(num_ref, dtype=torch.int64, device=x.device)
+    invalid = torch.empty((), dtype=torch.int64, device=x.device)
+    lib = _capi.load()
+    with torch.cuda.device(x.device):
+        ws = _metric_workspace("lidarseg", x.device, lib.vamp_lidarseg_workspace_bytes(P, num_ref))
+        _capi.check(lib.vamp_lidarseg_predict(P, K, _dtype_code(x), lo, hi, _ptr(x), _ptr(idx), num_ref, _ptr(labels),
+                                              _ptr(invalid), _ptr(ws), ws.numel(), _stream()),
+                    "vamp_lidarseg_predict")
+    return labels, invalid
