@@ -1,7 +1,10 @@
 #!/usr/bin/env python3
 """Debug aid (GPU box): per-tile phase stamps of the one-kernel camera forward.
 Build the diagnostic library first:  tools/ablate.sh render_cam_direct.hip stamps=-DVAMP_DIRECT_STAMPS
-Run:  VAMPIRE_HIP_LIB=vampire_amd/_lib/abl_stamps.so python tools/debug/cam_stamps.py [noert]"""
+Run:  VAMPIRE_HIP_LIB=vampire_amd/_lib/abl_stamps.so python tools/debug/cam_stamps.py [noert]
+The camera tiles of the merged training launch (ranks drawn, sample rows kept) instead:
+      tools/ablate.sh render_fwd_merged.hip mdstamps=-DVAMP_DIRECT_STAMPS
+      VAMPIRE_HIP_LIB=vampire_amd/_lib/abl_mdstamps.so python tools/debug/cam_stamps.py train"""
 import ctypes as C, os, sys
 import numpy as np
 import torch
@@ -14,18 +17,27 @@ dev = torch.device("cuda:0")
 model = LiftRenderStep(cfg, dev)
 batch = SyntheticBatch(cfg, 1, dev, seed=0)
 hp = model.hp
-hp.impl["ert"] = not (len(sys.argv) > 1 and sys.argv[1] == "noert")
-hp.impl["fwd_merged"] = False          # (the stamps live in the stand-alone kernel's translation unit)
-hp.impl["cam_direct"] = True
-with torch.no_grad():
+train = len(sys.argv) > 1 and sys.argv[1] == "train"
+if train:
+    from vampire_amd.step import train_step
     for _ in range(5):
-        hp.render(*batch.vols, model.beta, render_mats=batch.render_mats)
+        model.zero_grad(set_to_none=True)
+        train_step(model, batch)
     torch.cuda.synchronize()
+else:
+    hp.impl["ert"] = not (len(sys.argv) > 1 and sys.argv[1] == "noert")
+    hp.impl["fwd_merged"] = False          # (the stamps live in the stand-alone kernel's translation unit)
+    hp.impl["cam_direct"] = True
+    with torch.no_grad():
+        for _ in range(5):
+            hp.render(*batch.vols, model.beta, render_mats=batch.render_mats)
+        torch.cuda.synchronize()
 lib = _capi.load()
 n = 1056
 buf = (C.c_longlong * (n * 8))()
-lib.vamp_debug_direct_stamps.argtypes = [C.c_void_p, C.c_size_t]
-assert lib.vamp_debug_direct_stamps(buf, n * 8) == 0
+rd = lib.vamp_debug_merged_direct_stamps if train else lib.vamp_debug_direct_stamps
+rd.argtypes = [C.c_void_p, C.c_size_t]
+assert rd(buf, n * 8) == 0
 a = np.frombuffer(buf, dtype=np.int64).reshape(n, 8)
 t = a[:, :6].astype(np.float64)
 # s_memtime counts shader-clock cycles (2.4 GHz here), and every XCD has its own counter: tile durations are

@@ -274,6 +274,7 @@ cam_fwd_direct_tile(const unsigned bid, const RenderParams& P, const float* __re
   __shared__ float part_s[2][NW][64];
   __shared__ unsigned char act_s[kPlanMax + 8];                  // the active depth indices, in order (then S)
   __shared__ unsigned char actf_s[kPlanMax];                     // 1 = active depth index
+  __shared__ float dd_s[kPlanMax], mid_s[kPlanMax];               // bin lengths ds[i + 1] - ds[i] and mids[i], for the scan
   float* wbuf = dyn;                                                // [S][64]
   const int sub = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
   const int lane = threadIdx.x & 63;
@@ -395,6 +396,7 @@ cam_fwd_direct_tile(const unsigned bid, const RenderParams& P, const float* __re
     // masked samples carry density(0) (Q6): optical depth per unit of depth of the skipped bins
     tunit_s[lane] = density_fast(dp, 0.f) * ray_len;
   }
+  if (threadIdx.x < S) { dd_s[threadIdx.x] = ds[threadIdx.x + 1] - ds[threadIdx.x]; mid_s[threadIdx.x] = mids[threadIdx.x]; }
   __syncthreads();
   VAMP_STAMP(1);
 
@@ -492,11 +494,25 @@ cam_fwd_direct_tile(const unsigned bid, const RenderParams& P, const float* __re
     // an ulp of ~10 per step, i.e. 1e-6 relative on every later weight, and sum w mid + (1 - sum w) d_far a few ulp
     // of 70 m -- together 4e-5 m of depth that depend on how the samples fall into the four segments, i.e. on where
     // early termination cut the tile.  The reference's fp32 cumsum has noise of the same size around the same value.)
+    // (a lane walks up to S / SEG bins in each of the two passes below; every bin's inputs come from LDS, read four bins
+    // at a time ahead of the arithmetic: with ds and mids read from global memory inside the loop, each bin waited one
+    // L2 round trip, and a tile whose rays never saturate -- S_eff = S, 22 bins per lane at cfg-B -- spent 14 us here)
+    constexpr int SB = 4;
     double part = 0.0;
-    for (int i = a0; i < a1; ++i) {
-      const float tau = actf_s[i] ? wbuf[i * 64 + r] : tu * (ds[i + 1] - ds[i]);
-      wbuf[i * 64 + r] = tau;
-      part += (double) tau;
+    for (int i0 = a0; i0 < a1; i0 += SB) {
+      float tb[SB];
+#pragma unroll
+      for (int k = 0; k < SB; ++k) {
+        const int i = min(i0 + k, a1 - 1);
+        tb[k] = actf_s[i] ? wbuf[i * 64 + r] : tu * dd_s[i];
+      }
+#pragma unroll
+      for (int k = 0; k < SB; ++k) {
+        if (i0 + k < a1) {
+          wbuf[(i0 + k) * 64 + r] = tb[k];
+          part += (double) tb[k];
+        }
+      }
     }
     // exclusive prefix over the segments of the ray (bv2:431-433: exclusive cumsum)
     double incl = part;
@@ -508,15 +524,28 @@ cam_fwd_direct_tile(const unsigned bid, const RenderParams& P, const float* __re
     double cum = incl - part;
     int keep = S;
     double aw = 0.0, ad = 0.0;
-    for (int i = a0; i < a1; ++i) {
-      const float tau = wbuf[i * 64 + r];
-      const float wgt = composite_weight(tau, (float) cum);        // bv2:430-434
-      wbuf[i * 64 + r] = wgt;
-      aw += (double) wgt;
-      ad = __builtin_fma((double) wgt, (double) mids[i], ad);
-      cum += (double) tau;
-      // samples 0 .. i are kept; the optical depth in front of sample i + 1 is `cum`
-      if (ERT && keep == S && !(cum < (double) kTermOpticalDepth)) keep = i + 1;
+    for (int i0 = a0; i0 < a1; i0 += SB) {
+      float tb[SB], mb[SB];
+#pragma unroll
+      for (int k = 0; k < SB; ++k) {
+        const int i = min(i0 + k, a1 - 1);
+        tb[k] = wbuf[i * 64 + r];
+        mb[k] = mid_s[i];
+      }
+#pragma unroll
+      for (int k = 0; k < SB; ++k) {
+        if (i0 + k < a1) {
+          const int i = i0 + k;
+          const float tau = tb[k];
+          const float wgt = composite_weight(tau, (float) cum);    // bv2:430-434
+          wbuf[i * 64 + r] = wgt;
+          aw += (double) wgt;
+          ad = __builtin_fma((double) wgt, (double) mb[k], ad);
+          cum += (double) tau;
+          // samples 0 .. i are kept; the optical depth in front of sample i + 1 is `cum`
+          if (ERT && keep == S && !(cum < (double) kTermOpticalDepth)) keep = i + 1;
+        }
+      }
     }
 #pragma unroll
     for (int o = RPW; o < 64; o <<= 1) {

@@ -60,6 +60,13 @@ extern "C" int vamp_debug_merged_stamps(long long* host, size_t n) {
 }
 #endif
 
+#ifdef VAMP_DIRECT_STAMPS
+// diagnostic build only (tools/debug/cam_stamps.py ... train): the camera tiles' phase stamps of this launch
+extern "C" int vamp_debug_merged_direct_stamps(long long* host, size_t n) {
+  return (int) hipMemcpyFromSymbol(host, HIP_SYMBOL(g_direct_stamps), n * sizeof(long long), 0, hipMemcpyDeviceToHost);
+}
+#endif
+
 // a field group of the kernel-argument segment into registers (scalar loads from the constant address space)
 template <typename S, typename KS>
 __device__ __forceinline__ S kernarg_copy(KS src) {
