@@ -23,6 +23,11 @@ import torch.nn.functional as F
 bv2 = "src/layers/backbones/base_vampire2.py"
 
 
+def _to(t, dtype):
+    """``t`` in the evaluation dtype of a ``compute_dtype`` argument (None: unchanged)."""
+    return t if dtype is None or t is None else t.to(dtype)
+
+
 # --------------------------------------------------------------------------
 # geometry: get_geometry (bv2:314-349) and get_pixel (bv2:351-388)
 # --------------------------------------------------------------------------
@@ -95,15 +100,20 @@ def lift_valid_and_grid(pix, final_dim, d_bound, use_depth=True, clamp_extreme=T
     return ok.float(), torch.stack([nx, ny, nz], dim=-1)
 
 
-def lift_from_frustum_feats(frustum_feats, pix, final_dim, d_bound, use_depth=True):
-    """bv2:507-516.  frustum_feats [B,N,C,D,fH,fW] -> voxel mean [B,C,Z,Y,X]."""
+def lift_from_frustum_feats(frustum_feats, pix, final_dim, d_bound, use_depth=True, compute_dtype=None):
+    """bv2:507-516.  frustum_feats [B,N,C,D,fH,fW] -> voxel mean [B,C,Z,Y,X].
+
+    ``compute_dtype`` (e.g. torch.float64): mask and grid are still formed from ``pix`` in its own
+    dtype, so the taps are the ones the default evaluation takes; sampling, mask and mean run in
+    ``compute_dtype``.  None: the reference's fp32 sequence, bit for bit."""
     B, N, C, D, H, W = frustum_feats.shape
     Z, Y, X = pix.shape[2:5]
     valid, grid = lift_valid_and_grid(pix, final_dim, d_bound, use_depth)
-    s = F.grid_sample(frustum_feats.reshape(B * N, C, D, H, W),
+    valid, grid = _to(valid, compute_dtype), _to(grid, compute_dtype)
+    s = F.grid_sample(_to(frustum_feats, compute_dtype).reshape(B * N, C, D, H, W),
                       grid.reshape(B * N, Z, Y, X, 3), align_corners=False)
     s = s.reshape(B, N, C, Z, Y, X) * valid.unsqueeze(2)
-    hit = (s.abs() > 0).float()
+    hit = (s.abs() > 0).to(s.dtype)
     return s.sum(dim=1) / (hit.sum(dim=1) + 1e-6)
 
 
@@ -113,10 +123,13 @@ def outer_depth_feat(depth, feat):
 
 
 def lift(depth, feat, voxel_coords, sensor2ego, intrin, ida, bda, final_dim, d_bound,
-         prepared=None):
-    """bv2:550-563 end to end (outer product + get_pixel + get_voxel_feats)."""
+         prepared=None, compute_dtype=None):
+    """bv2:550-563 end to end (outer product + get_pixel + get_voxel_feats).  ``compute_dtype``:
+    the projection stays fp32 (same taps), the outer product and everything behind the grid
+    runs in that dtype (lift_from_frustum_feats)."""
     pix = ego_to_pixel(voxel_coords, sensor2ego, intrin, ida, bda, prepared)
-    return lift_from_frustum_feats(outer_depth_feat(depth, feat), pix, final_dim, d_bound)
+    ff = outer_depth_feat(_to(depth, compute_dtype), _to(feat, compute_dtype))
+    return lift_from_frustum_feats(ff, pix, final_dim, d_bound, compute_dtype=compute_dtype)
 
 
 def lift_tap_indices(pix, final_dim, d_bound, frustum_shape):
@@ -163,12 +176,19 @@ def _composite(sigma_delta, dim):
 
 def render(geom, density_feature, semantic_logits, base, rgb, *, seg_bounds, output_coords,
            camera_mids, bev_mids, d_far, z_step_det, num_classes, density_mode,
-           beta_param=None, sdf_bias=-1.0, cat_seg=False):
+           beta_param=None, sdf_bias=-1.0, cat_seg=False, compute_dtype=None):
     """bv2:391-467.  Returns the reference's 8-tuple.
 
     geom [B,N,D,fH,fW,3] (already nan_to_num'ed with -1e3 as at bv2:612);
     volumes [B,c,Z,Y,X]; seg_bounds = (x_bound_seg, y_bound_seg, z_bound_seg).
+
+    ``compute_dtype`` (e.g. torch.float64): the sample coordinates (``g``, ``inside``, ``delta``,
+    the BEV grid) are still formed in the dtype of ``geom`` exactly as the reference does -- the
+    taps stay those of the default evaluation -- and everything behind them (sampling,
+    nan_to_num, density, compositing, sums) runs in ``compute_dtype``.  None: the reference's
+    fp32 sequence, bit for bit.
     """
+    cd = compute_dtype
     B, N, D, H, W, _ = geom.shape
     K = num_classes
     vol = torch.cat([density_feature, semantic_logits, rgb, base], dim=1)   # bv2:396
@@ -179,22 +199,23 @@ def render(geom, density_feature, semantic_logits, base, rgb, *, seg_bounds, out
     g = (geom[:, :, :-1] - lo) / span
     g = g * 2.0 - 1.0
     inside = ((g >= -1.0) & (g <= 1.0)).all(dim=-1)
-    S = F.grid_sample(vol, g.reshape(B, -1, H, W, 3), align_corners=True)
+    vol, beta_param = _to(vol, cd), _to(beta_param, cd)
+    S = F.grid_sample(vol, _to(g, cd).reshape(B, -1, H, W, 3), align_corners=True)
     S = S.reshape(B, -1, N, D - 1, H, W).permute(0, 2, 1, 3, 4, 5) * inside.unsqueeze(2)
     S = torch.nan_to_num(S)
     sigma = density_apply(S[:, :, :1], density_mode, beta_param, sdf_bias)
-    delta = torch.norm(geom[:, :, 1:] - geom[:, :, :-1], dim=-1)
+    delta = _to(torch.norm(geom[:, :, 1:] - geom[:, :, :-1], dim=-1), cd)
     wts = _composite(sigma * delta.unsqueeze(2), dim=3)
     acc = wts.sum(dim=3)
     rgb_preds = (wts * S[:, :, K + 1:K + 4]).sum(dim=3)
     seg_preds = (wts * S[:, :, 1:K + 1]).sum(dim=3)
-    depth_preds = (wts * camera_mids[None, None, None, :, None, None]).sum(dim=3) \
+    depth_preds = (wts * _to(camera_mids, cd)[None, None, None, :, None, None]).sum(dim=3) \
         + (1 - acc) * d_far                                                 # bv2:436,440
 
     # ---- BEV branch (bv2:408-418, 442-461) ----
     og = (output_coords[..., :3] - lo) / span
     og = (og * 2.0 - 1.0)[None].expand(B, *og.shape)
-    Vs = torch.flip(F.grid_sample(vol, og, align_corners=True), dims=[2])
+    Vs = torch.flip(F.grid_sample(vol, _to(og, cd), align_corners=True), dims=[2])
     v_sigma = density_apply(Vs[:, :1], density_mode, beta_param, sdf_bias)
     v_out = Vs[:, K + 4:]
     if cat_seg:
@@ -202,7 +223,7 @@ def render(geom, density_feature, semantic_logits, base, rgb, *, seg_bounds, out
     v_w = _composite(v_sigma * (torch.ones_like(v_sigma) * z_step_det), dim=2)
     bev_rgb = (v_w * Vs[:, K + 1:K + 4]).sum(dim=2)
     bev_seg = (v_w * Vs[:, 1:K + 1]).sum(dim=2)
-    bev_height = (v_w * bev_mids[None, None, :, None, None]).sum(dim=2)
+    bev_height = (v_w * _to(bev_mids, cd)[None, None, :, None, None]).sum(dim=2)
     return rgb_preds, seg_preds, depth_preds, bev_rgb, bev_seg, bev_height, v_sigma, v_out
 
 

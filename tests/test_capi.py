@@ -92,3 +92,38 @@ def test_new_entry_points_reject_bad_arguments_without_gpu(lib):
     assert lib.vamp_upsample_trilinear_forward(0, 1, 1, 1, 2, 2, 2, None, None, None) == -1
     assert lib.vamp_depth_softmax_forward(1, 0, 4, None, 0, None, None) == -1
     assert lib.vamp_density_gate_forward(1, 4, 8, 7, None, None, None, None) == -1
+
+
+RENDER_ENTRIES = ["vamp_render_camera_forward_ex", "vamp_render_camera_backward_acc", "vamp_render_bev_forward_ex",
+                  "vamp_render_forward_merged", "vamp_render_camera_terminate", "vamp_render_camera_prepare_ex"]
+
+
+def _null_args(fn, d):
+    """A descriptor and nothing else: NULL for every pointer, 0 for every count and flag word."""
+    simple = (C.c_int, C.c_size_t, C.c_float, C.c_long)
+    return [C.byref(d)] + [0 if t in simple else None for t in fn.argtypes[1:]]
+
+
+@pytest.mark.parametrize("field,value,message", [("K", 0, b"1 <= K <= 28"), ("K", 29, b"1 <= K <= 28"),
+                                                 ("C", 65, b"0 <= C <= 64"), ("D", 1, b"D > 1")])
+def test_render_descriptor_limits_are_rejected_without_gpu(lib, field, value, message):
+    """The render entry points refuse a class count outside 1 .. 28, more than 64 mid channels or a single depth plane
+    with a negative code and the descriptor check's message, before any device work (every pointer is NULL: a call
+    that went on would fail differently); the same calls on the valid descriptor stop at their pointer checks."""
+    from vampire_amd.config import CFG_TINY
+    from vampire_amd.ops import render_desc
+    ok = render_desc(CFG_TINY, 2, 6, _capi.VAMP_F32)
+    heights = (C.c_float * 3)(-0.0, 0.8, 1.6)
+    for name in RENDER_ENTRIES:
+        fn = getattr(lib, name)
+        assert fn(*_null_args(fn, ok)) < 0, name
+        err = lib.vamp_last_error()
+        assert (b"null pointer" in err or b"need geom" in err or b"workspace 0 <" in err), (name, err)
+    bad = render_desc(CFG_TINY, 2, 6, _capi.VAMP_F32)
+    setattr(bad, field, value)
+    for name in RENDER_ENTRIES:
+        fn = getattr(lib, name)
+        assert fn(*_null_args(fn, bad)) < 0, name
+        assert message in lib.vamp_last_error(), (name, lib.vamp_last_error())
+    assert lib.vamp_render_forward_merged_supported(C.byref(bad), heights) == 0
+    assert lib.vamp_render_workspace_bytes(C.byref(ok)) > 0

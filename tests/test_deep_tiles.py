@@ -35,11 +35,12 @@ def scene(dev):
     return cfg, [v.detach().requires_grad_(True) for v in vols], rm
 
 
-def _term(hp, cfg):
-    d = hp.render_desc(1, cfg.num_cams, _capi.VAMP_F32)
+def _term(hp, cfg, B=1):
+    """The termination table the last render call of `hp` left in its workspace: [B * N, fH, fW]."""
+    d = hp.render_desc(B, cfg.num_cams, _capi.VAMP_F32)
     off = hp.lib.vamp_render_term_offset(C.byref(d))
-    n = cfg.num_cams * cfg.fH * cfg.fW
-    return hp._ws["render"][off:off + 4 * n].view(torch.int32).clone().view(cfg.num_cams, cfg.fH, cfg.fW)
+    n = B * cfg.num_cams * cfg.fH * cfg.fW
+    return hp._ws["render"][off:off + 4 * n].view(torch.int32).clone().view(B * cfg.num_cams, cfg.fH, cfg.fW)
 
 
 def _forward(cfg, vols, rm, dev, merged):

@@ -242,3 +242,57 @@ def test_oracle_density_regimes_full_size():
             tot = float(o.double().abs().sum())
             assert abs(tot - st["abs_sum"]) <= 1e-6 * st["abs_sum"] + 1e-6, (regime, name, tot, st["abs_sum"])
             assert abs(float(o.max()) - st["max"]) <= 1e-6 * max(1.0, abs(st["max"])), (regime, name)
+
+
+@pytest.mark.parametrize("mode,cat_seg", RENDER_VARIANTS)
+def test_float64_evaluation_agrees_with_default(tiny_common, mode, cat_seg):
+    """compute_dtype=torch.float64 (the reference of the shape-sweep tests) against the default fp32 evaluation on the
+    tiny fixtures: outputs and gradients to fp32 noise; compute_dtype=None is the default bit for bit (the golden
+    reproduction above)."""
+    g = tiny_common
+    r = load_golden(render_fixture_name(mode, cat_seg))
+    c = dataclasses.replace(CFG_TINY, density_mode=mode, cat_seg=cat_seg)
+    geom = torch.nan_to_num(g["geom"], -1e3)
+    res = {}
+    for cd in (None, torch.float64):
+        vols = [g[k].clone().requires_grad_(True) for k in ("density_feature", "semantic_logits", "base", "rgb")]
+        beta = r["beta"].clone().reshape(()).requires_grad_(True) if mode == "sdf" else None
+        outs = O.render(geom, *vols, seg_bounds=SEG_BOUNDS, output_coords=GEO.output_coords,
+                        camera_mids=GEO.camera_mids, bev_mids=GEO.bev_mids, d_far=c.d_bound[1],
+                        z_step_det=c.z_bound_det[2], num_classes=c.num_classes, density_mode=mode,
+                        beta_param=beta, sdf_bias=c.sdf_bias, cat_seg=cat_seg, compute_dtype=cd)
+        assert all(o.dtype == (cd or torch.float32) for o in outs)
+        torch.autograd.backward(outs, [r["g_" + n].to(outs[0].dtype) for n in NAMES])
+        res[cd] = (outs, [v.grad for v in vols] + ([beta.grad] if beta is not None else []))
+    for name, a in zip(NAMES, res[None][0]):
+        assert torch.equal(a, r[name]), name
+    for name, a, b in zip(NAMES, res[None][0], res[torch.float64][0]):
+        b = b.detach()
+        tol = 2e-6 * float(b.abs().max()) + (3 * 1.2e-7 * c.d_bound[1] if name == "depth_preds" else 0.0)
+        err = float((a.detach().double() - b).abs().max())
+        assert err <= tol, (name, err, tol)
+        assert err > 0 or name in ("voxel_density",), f"{name}: float64 evaluation identical to fp32"
+    for i, (a, b) in enumerate(zip(res[None][1], res[torch.float64][1])):
+        err = float((a.double() - b.double()).abs().max())
+        rel = 5e-5 if i == 4 else 1e-5           # (grad_beta: one sum over every sample, of mixed signs)
+        assert err <= rel * float(b.abs().max()) + 1e-12, (i, err)
+
+
+def test_float64_lift_agrees_with_default(tiny_common):
+    """The lift in float64 against the default evaluation on the tiny fixture: forward and gradients to fp32 noise,
+    the taps (mask and grid) the same."""
+    g = tiny_common
+    c = CFG_TINY
+    res = {}
+    for cd in (None, torch.float64):
+        d = g["depth"].clone().requires_grad_(True)
+        f = g["feat"].clone().requires_grad_(True)
+        vox = O.lift(d, f, GEO.voxel_coords, None, None, None, None, c.final_dim, c.d_bound,
+                     prepared=g["lift_mats"], compute_dtype=cd)
+        assert vox.dtype == (cd or torch.float32)
+        vox.backward(g["g_lift"].to(vox.dtype))
+        res[cd] = (vox.detach(), d.grad, f.grad)
+    assert torch.equal(res[None][0], g["lift"])
+    for i, (a, b) in enumerate(zip(res[None], res[torch.float64])):
+        err = float((a.double() - b.double()).abs().max())
+        assert 0 < err <= 2e-6 * float(b.abs().max()) + 1e-12, (i, err)

@@ -63,6 +63,33 @@ def _chk(t: torch.Tensor, shape, name):
     return t.contiguous()
 
 
+def render_desc(cfg: PathConfig, B, N, dtype_code, C_=None) -> _capi.VampRenderDesc:
+    """The render descriptor of `cfg` for B samples of N cameras (C_: mid channels, default cfg.mid_channels); host
+    only, no device needed."""
+    c = cfg
+    d = _capi.VampRenderDesc()
+    d.B, d.N = B, N
+    d.D, d.fH, d.fW = c.D, c.fH, c.fW
+    d.K, d.C = c.num_classes, (c.mid_channels if C_ is None else C_)
+    d.Z, d.Y, d.X = c.vZ, c.vY, c.vX
+    d.oZ, d.oY, d.oX = c.oZ, c.oY, c.oX
+    bounds = (c.x_bound_seg, c.y_bound_seg, c.z_bound_seg)
+    for i, b in enumerate(bounds):
+        d.lo[i] = b[0]
+        d.span[i] = b[1] - b[0]
+    d.d_far = c.d_bound[1]
+    d.z_step_det = c.z_bound_det[2]
+    for i, bnd in enumerate((c.x_bound_det, c.y_bound_det, c.z_bound_det)):
+        d.det_step[i] = bnd[2]
+    d.density_mode = (_capi.VAMP_DENSITY_SDF_LAPLACE if c.density_mode == "sdf"
+                      else _capi.VAMP_DENSITY_SIGMOID)
+    d.sdf_bias = c.sdf_bias
+    d.beta_min = 1e-4
+    d.cat_seg = 1 if c.cat_seg else 0
+    d.in_dtype = dtype_code
+    return d
+
+
 class HotPath:
     """Device constants + operators for one PathConfig on one device."""
 
@@ -157,28 +184,7 @@ class HotPath:
         return d
 
     def render_desc(self, B, N, dtype_code, C_=None) -> _capi.VampRenderDesc:
-        c = self.cfg
-        d = _capi.VampRenderDesc()
-        d.B, d.N = B, N
-        d.D, d.fH, d.fW = c.D, c.fH, c.fW
-        d.K, d.C = c.num_classes, (c.mid_channels if C_ is None else C_)
-        d.Z, d.Y, d.X = c.vZ, c.vY, c.vX
-        d.oZ, d.oY, d.oX = c.oZ, c.oY, c.oX
-        bounds = (c.x_bound_seg, c.y_bound_seg, c.z_bound_seg)
-        for i, b in enumerate(bounds):
-            d.lo[i] = b[0]
-            d.span[i] = b[1] - b[0]
-        d.d_far = c.d_bound[1]
-        d.z_step_det = c.z_bound_det[2]
-        for i, bnd in enumerate((c.x_bound_det, c.y_bound_det, c.z_bound_det)):
-            d.det_step[i] = bnd[2]
-        d.density_mode = (_capi.VAMP_DENSITY_SDF_LAPLACE if c.density_mode == "sdf"
-                          else _capi.VAMP_DENSITY_SIGMOID)
-        d.sdf_bias = c.sdf_bias
-        d.beta_min = 1e-4
-        d.cat_seg = 1 if c.cat_seg else 0
-        d.in_dtype = dtype_code
-        return d
+        return render_desc(self.cfg, B, N, dtype_code, C_)
 
     def _side_stream(self):
         """Second HIP stream for the BEV branch of the renderer: it shares no kernel with the camera
@@ -724,6 +730,9 @@ class _RenderFn(torch.autograd.Function):
         dev, f32 = dens.device, torch.float32
         K = c.num_classes
         CO = C_ + (K if c.cat_seg else 0)
+        if CO == 0:
+            # (the library takes C = 0 beside cat_seg only: voxel_output would have no channels, and its forward needs one)
+            raise ValueError("mid_channels = 0 needs cat_seg: voxel_output would have no channels")
         rgb_p = torch.empty(B, N, 3, c.fH, c.fW, dtype=f32, device=dev)
         seg_p = torch.empty(B, N, K, c.fH, c.fW, dtype=f32, device=dev)
         dep_p = torch.empty(B, N, 1, c.fH, c.fW, dtype=f32, device=dev)
