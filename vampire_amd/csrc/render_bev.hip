@@ -1343,10 +1343,15 @@ bev_gather_pass_kernel(RenderParams P, const int4* __restrict__ tab, const float
 }
 
 // d beta partial sums the scan leaves in the workspace: one per workgroup of bev_scan_kernel, or -- when the
-// forward kept its samples -- of bev_qscan_saved_kernel (the workspace holds the larger count)
-static size_t bev_scan_blocks(const VampRenderDesc* d, bool saved = true) {
+// forward kept its samples -- of bev_qscan_saved_kernel
+static size_t bev_scan_blocks(const VampRenderDesc* d, bool saved) {
   if (saved) return (size_t) (((long) d->oY * d->oX + 63) / 64) * d->B;
   return (size_t) ((d->oX + 63) / 64) * ((d->oY + 3) / 4) * d->B;
+}
+// the workspace holds the larger of the two counts: either is the larger one, depending on the det grid (oX = 4,
+// oY = 200: 26 workgroups of 64 columns against 100 of 64 x 4)
+static size_t bev_scan_blocks_max(const VampRenderDesc* d) {
+  return std::max(bev_scan_blocks(d, true), bev_scan_blocks(d, false));
 }
 
 // workspace: Q, Wb, DS0 [B, oZ, oY, oX] | axis tables | beta partials | what the forward keeps for
@@ -1357,7 +1362,7 @@ static size_t bev_one(const VampRenderDesc* d) {
 }
 static size_t bev_saved_offset(const VampRenderDesc* d) {
   return 3 * bev_one(d) + 2 * align_up((size_t) 2 * (d->X + d->Y + d->Z) * sizeof(int4), 256) +
-         align_up(bev_scan_blocks(d) * sizeof(float), 256);
+         align_up(bev_scan_blocks_max(d) * sizeof(float), 256);
 }
 static size_t bev_ws_bytes(const VampRenderDesc* d) {
   return bev_saved_offset(d) + (size_t) (1 + d->K + 3) * bev_one(d);
@@ -1539,15 +1544,20 @@ int vamp_render_bev_backward_ex(const VampRenderDesc* d, const float* oxs, const
   }
   z_lo = z_lo < 0 ? 0 : z_lo;
   z_hi = z_hi > d->Z - 1 ? d->Z - 1 : z_hi;
-  if (z_lo > z_hi) {
-    // the det lattice misses the volume: only zeros to write.  A split pair zeroes each buffer in the
-    // half that owns it (ONLY_BASE is issued behind the event the camera gather waits for: zeroing the
-    // three camera tensors again there would race with, or wipe, that gather's sums)
+  const bool outside = z_lo > z_hi;
+  if (outside) {
+    // the det lattice misses the volume: only zeros to write to the volume gradients.  A split pair zeroes
+    // each buffer in the half that owns it (ONLY_BASE is issued behind the event the camera gather waits
+    // for: zeroing the three camera tensors again there would race with, or wipe, that gather's sums)
     int zf = flags;
     if (flags & VAMP_BEVBWD_ONLY_BASE) zf &= ~VAMP_BEVBWD_OVERWRITE_CAM;
     if (flags & VAMP_BEVBWD_SKIP_BASE) zf &= ~VAMP_BEVBWD_OVERWRITE_BASE;
-    return bev_zero_overwritten(d, zf, grad_density_feature, grad_semantic, grad_rgb, grad_base,
-                                static_cast<hipStream_t>(stream));
+    if (int e = bev_zero_overwritten(d, zf, grad_density_feature, grad_semantic, grad_rgb, grad_base,
+                                     static_cast<hipStream_t>(stream))) return e;
+    // ... but the sdf density of the zero-padded samples, f(0; beta), still depends on beta: the scan below
+    // forms d loss / d beta of bev_height and voxel_density, and this call (SKIP_BASE of a pair: the
+    // ONLY_BASE call returns here) adds it to grad_beta
+    if (d->density_mode != VAMP_DENSITY_SDF_LAPLACE || only_base) return VAMP_OK;
   }
 
   dim3 gq((d->oX + 63) / 64, d->oY, d->B);
@@ -1589,6 +1599,13 @@ int vamp_render_bev_backward_ex(const VampRenderDesc* d, const float* oxs, const
     if (d->in_dtype == VAMP_F32) VAMP_BEVB(float); else VAMP_BEVB(__hip_bfloat16);
   }
 #undef VAMP_BEVB
+  if (outside) {
+    // (here, in the SKIP_BASE call of a pair, the reduction sits in front of the event the camera gather waits for,
+    // where the other lattices leave it to the ONLY_BASE call behind that event: a launch more on the camera gather's
+    // path, for lattices that miss the volume only.  The add is atomic and commutes with the camera branch's.)
+    if (int e = launch_beta_reduce(beta_part, (int) bev_scan_blocks(d, saved), beta, grad_beta, s)) return e;
+    return check_launch("beta_reduce");
+  }
   // the beta partial sums of the scan are added up where nobody waits: in the second call of a split
   // pair (ONLY_BASE; the first, SKIP_BASE, leaves them in the workspace), else right here
   // ... by the first workgroup of the first column-gather launch of that call (beta_tail), or, where no

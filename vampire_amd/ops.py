@@ -63,6 +63,10 @@ def _chk(t: torch.Tensor, shape, name):
     return t.contiguous()
 
 
+# det-grid heights the BEV kernels take: their z taps and weights live in fixed LDS tables (kBevMaxOZ, render_bev.hip)
+BEV_MAX_OZ = 64
+
+
 def render_desc(cfg: PathConfig, B, N, dtype_code, C_=None) -> _capi.VampRenderDesc:
     """The render descriptor of `cfg` for B samples of N cameras (C_: mid channels, default cfg.mid_channels); host
     only, no device needed."""
@@ -94,6 +98,10 @@ class HotPath:
     """Device constants + operators for one PathConfig on one device."""
 
     def __init__(self, cfg: PathConfig, device="cuda"):
+        if cfg.oZ > BEV_MAX_OZ:
+            # (refused here, before any device work: the library would refuse every BEV call)
+            raise ValueError(f"z_bound_det gives {cfg.oZ} heights: the BEV kernels take at most {BEV_MAX_OZ} "
+                             "det-grid heights")
         self.cfg = cfg
         self.device = torch.device(device)
         self.lib = _capi.load()
