@@ -27,8 +27,8 @@
 extern "C" {
 #endif
 
-#define VAMP_ABI_VERSION 7   /* bumped whenever entry points or flags are added (round 2: 2, round 3: 3, round 4: 4, round 5: 5, round 6: 6;
-                                 7: segmentation metrics) */
+#define VAMP_ABI_VERSION 8   /* bumped whenever entry points or flags are added (round 2: 2, round 3: 3, round 4: 4, round 5: 5, round 6: 6;
+                                 7: segmentation metrics; 8: detection post-processing) */
 
 enum {
   VAMP_OK = 0,
@@ -800,6 +800,64 @@ size_t vamp_lidarseg_workspace_bytes(int64_t P, int64_t num_ref);
 int vamp_lidarseg_predict(int64_t P, int32_t K, int32_t dtype, int32_t lo, int32_t hi, const void* pts_logits,
                           const int64_t* ref_index, int64_t num_ref, int64_t* labels, int64_t* invalid,
                           void* workspace, size_t workspace_bytes, void* stream);
+
+/* --------------------------------------------------------------------------
+ * Detection post-processing: the reference head's get_bboxes (bev_depth_head.py:381-494, the decode of
+ * CenterPointBBoxCoder and the three NMS kinds of :420-475) for all T tasks of a head and all B samples, on the
+ * device, with a fixed-capacity output.  Per task t the head tensors are contiguous, all of dtype in_dtype
+ * (VAMP_F32 | VAMP_BF16 | VAMP_F16): heatmap [B, ncls[t], H, W], reg [B, 2, H, W], height [B, 1, H, W],
+ * dim [B, 3, H, W], rot [B, 2, H, W] (sin, cos), vel [B, 2, H, W] when has_vel.
+ *
+ *  score      sigmoid as aten computes it: 1 / (1 + expf(-x)) in fp32 (accurate expf), rounded to in_dtype.
+ *  candidates the top K = min(max_num, ncls[t] * H * W) of the flattened [ncls, H, W] scores, score descending,
+ *             ties by flat index ascending (a NaN ranks above every number).
+ *  decode     x = ((W-index + reg0) * out_size_factor) * voxel_size[0] + pc_range[0] (each op rounded, no FMA),
+ *             y likewise with the H-index and reg1; z = height; dim = exp(dim) when norm_bbox; rot = atan2(sin,
+ *             cos); vel.  Exp and atan2 of 16-bit heads are rounded to in_dtype, as torch computes them.
+ *  filter     score > score_threshold (when use_score_threshold; the caller passes the threshold rounded to
+ *             in_dtype, as torch compares a tensor with a Python scalar) and, when use_center_range,
+ *             post_center_range[0:3] <= (x, y, z) <= post_center_range[3:6].  Survivors keep their order.
+ *  NMS        greedy in candidate order per (sample, task), the kept list truncated to post_max_size:
+ *               VAMP_NMS_CIRCLE      suppress when dx^2 + dy^2 <= min_radius[t] (circle_nms);
+ *               VAMP_NMS_SIZE_AWARE  suppress when |dx| <= (ex_i + ex_j) * thresh_scale[t] / 2 and the same in
+ *                                    y, ex = dx |cos yaw| + dy |sin yaw|, ey = dx |sin yaw| + dy |cos yaw|;
+ *               VAMP_NMS_ROTATE      candidates truncated to pre_max_size first; suppress when the IoU of the
+ *                                    rotated BEV rectangles (x, y, dx, dy, yaw) is > nms_thr[t], IoU =
+ *                                    intersection / max(union, 1e-8) (a box with dx or dy <= 0 overlaps nothing).
+ *  output     per sample b, the tasks' kept rows in task order: boxes [B, T * P, 9 | 7] fp32 (9 with vel),
+ *             scores [B, T * P] in_dtype, labels [B, T * P] int32 = class within the task + sum of the earlier
+ *             tasks' ncls, counts [B] int32; rows at or beyond counts[b] are zero.  P = post_max_size.
+ * Limits: 1 <= T <= 8, 1 <= ncls[t] <= 4, ncls * H * W < 2^31, K <= 1024, 1 <= post_max_size <= max_num.  Every
+ * argument is checked before any device work.  Four launches on `stream`, no host synchronisation, no atomics
+ * beyond integer LDS counts: the output is a pure function of the inputs, and the call can be captured in a
+ * graph.  The workspace (vamp_det_workspace_bytes) needs no initialisation.
+ * -------------------------------------------------------------------------- */
+enum { VAMP_NMS_CIRCLE = 0, VAMP_NMS_SIZE_AWARE = 1, VAMP_NMS_ROTATE = 2 };
+typedef struct VampDetTask {
+  const void* heatmap;
+  const void* reg;
+  const void* height;
+  const void* dim;
+  const void* rot;
+  const void* vel;       /* NULL without velocity */
+} VampDetTask;
+typedef struct VampDetDesc {
+  int32_t B, T, H, W;
+  int32_t ncls[8];
+  int32_t max_num, pre_max_size, post_max_size;
+  int32_t nms_kind;               /* VAMP_NMS_CIRCLE | VAMP_NMS_SIZE_AWARE | VAMP_NMS_ROTATE */
+  int32_t in_dtype;               /* VAMP_F32 | VAMP_BF16 | VAMP_F16 */
+  int32_t has_vel, norm_bbox;
+  int32_t use_score_threshold, use_center_range;
+  float score_threshold;
+  float out_size_factor, voxel_size[2], pc_range[2];
+  float post_center_range[6];
+  float min_radius[8], thresh_scale[8], nms_thr[8];
+  int32_t reserved;               /* 0 */
+} VampDetDesc;
+size_t vamp_det_workspace_bytes(const VampDetDesc* d);
+int vamp_det_postprocess(const VampDetDesc* d, const VampDetTask* tasks, float* boxes, void* scores, int32_t* labels,
+                         int32_t* counts, void* workspace, size_t workspace_bytes, void* stream);
 
 #ifdef __cplusplus
 }

@@ -9,7 +9,7 @@ import os
 
 from .build import lib_path
 
-ABI_VERSION = 7
+ABI_VERSION = 8
 
 VAMP_F32, VAMP_BF16, VAMP_F16 = 0, 1, 2
 VAMP_DENSITY_SIGMOID, VAMP_DENSITY_SDF_LAPLACE = 0, 1
@@ -66,6 +66,24 @@ class VampConfDesc(C.Structure):
                 ("reserved", C.c_int32)]
 
 
+VAMP_NMS_CIRCLE, VAMP_NMS_SIZE_AWARE, VAMP_NMS_ROTATE = 0, 1, 2
+
+
+class VampDetTask(C.Structure):
+    _fields_ = [("heatmap", C.c_void_p), ("reg", C.c_void_p), ("height", C.c_void_p), ("dim", C.c_void_p),
+                ("rot", C.c_void_p), ("vel", C.c_void_p)]
+
+
+class VampDetDesc(C.Structure):
+    _fields_ = [("B", C.c_int32), ("T", C.c_int32), ("H", C.c_int32), ("W", C.c_int32), ("ncls", C.c_int32 * 8),
+                ("max_num", C.c_int32), ("pre_max_size", C.c_int32), ("post_max_size", C.c_int32),
+                ("nms_kind", C.c_int32), ("in_dtype", C.c_int32), ("has_vel", C.c_int32), ("norm_bbox", C.c_int32),
+                ("use_score_threshold", C.c_int32), ("use_center_range", C.c_int32),
+                ("score_threshold", C.c_float), ("out_size_factor", C.c_float), ("voxel_size", C.c_float * 2),
+                ("pc_range", C.c_float * 2), ("post_center_range", C.c_float * 6), ("min_radius", C.c_float * 8),
+                ("thresh_scale", C.c_float * 8), ("nms_thr", C.c_float * 8), ("reserved", C.c_int32)]
+
+
 # flag bits of vamp_lift_backward_ex / vamp_render_camera_backward_acc (include/vampire_hip.h)
 VAMP_LIFTFWD_EMIT_PAIRS, VAMP_LIFTFWD_CELLS_CLEAN, VAMP_LIFTFWD_FEAT_CHANNEL_LAST, VAMP_LIFTFWD_DEFER_SCAN = 1, 2, 4, 8
 VAMP_LIFTBWD_CELLS_VALID, VAMP_LIFTBWD_SPLAT = 1, 2
@@ -88,6 +106,7 @@ _RD = C.POINTER(VampRenderDesc)
 _SD = C.POINTER(VampSampleDesc)
 _CD = C.POINTER(VampConvDesc)
 _QD = C.POINTER(VampConfDesc)
+_DD = C.POINTER(VampDetDesc)
 
 # name -> (restype, argtypes); must list every symbol declared in include/vampire_hip.h
 SIGNATURES = {
@@ -175,6 +194,8 @@ SIGNATURES = {
     "vamp_lidarseg_workspace_bytes": (C.c_size_t, [C.c_int64, C.c_int64]),
     "vamp_lidarseg_predict": (C.c_int, [C.c_int64, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _P, _P, C.c_int64,
                                         _P, _P, _P, C.c_size_t, _P]),
+    "vamp_det_workspace_bytes": (C.c_size_t, [_DD]),
+    "vamp_det_postprocess": (C.c_int, [_DD, C.POINTER(VampDetTask)] + [_P] * 5 + [C.c_size_t, _P]),
 }
 
 _lib = None

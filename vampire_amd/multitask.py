@@ -315,6 +315,14 @@ class BEVDepthHead(nn.Module):
                         torch.cat(labels)])
         return out
 
+    def get_bboxes_device(self, preds_dicts, out=None):
+        """get_bboxes on the device for every nms_type of the reference ('circle', 'size_aware_circle',
+        'rotate'): one vamp_det_postprocess call, no host synchronisation.  Returns an ops.DetResult whose
+        to_list() is get_bboxes's [[bboxes, scores, labels], ...]; `out` takes preallocated buffers."""
+        from . import ops
+        return ops.det_postprocess(preds_dicts, self.bbox_coder, self.test_cfg, self.num_classes, self.norm_bbox,
+                                   out=out)
+
 
 # =============================================================================================
 # the model (src/models/vampire2.py)
@@ -339,6 +347,9 @@ class VAMPIRE2(nn.Module):
 
     def get_bboxes(self, preds_dicts, img_metas=None, img=None, rescale=False):
         return self.head.get_bboxes(preds_dicts, img_metas, img, rescale)
+
+    def get_bboxes_device(self, preds_dicts, out=None):
+        return self.head.get_bboxes_device(preds_dicts, out=out)
 
 
 # =============================================================================================

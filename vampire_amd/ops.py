@@ -12,6 +12,7 @@ All heavy work happens in hand-written HIP kernels reached through ctypes
 (`_capi`); torch supplies device memory and the current stream only.
 """
 import ctypes as C
+import dataclasses
 import math
 import os
 
@@ -1480,3 +1481,134 @@ def lidarseg_predict(pts_logits, ref_index, num_ref, class_window):
                                               _ptr(invalid), _ptr(ws), ws.numel(), _stream()),
                     "vamp_lidarseg_predict")
     return labels, invalid
+
+
+# ===========================================================================
+# detection post-processing (bev_depth_head.py:381-494)
+# ===========================================================================
+_DET_DTYPES = {torch.float32: _capi.VAMP_F32, torch.bfloat16: _capi.VAMP_BF16, torch.float16: _capi.VAMP_F16}
+_NMS_KINDS = {"circle": _capi.VAMP_NMS_CIRCLE, "size_aware_circle": _capi.VAMP_NMS_SIZE_AWARE,
+              "rotate": _capi.VAMP_NMS_ROTATE}
+
+
+@dataclasses.dataclass
+class DetResult:
+    """Fixed-capacity detections of a batch: boxes [B, T * P, 9 | 7] fp32, scores [B, T * P] (heatmap dtype),
+    labels [B, T * P] int32, counts [B] int32; rows at or beyond counts[b] are zero."""
+    boxes: torch.Tensor
+    scores: torch.Tensor
+    labels: torch.Tensor
+    counts: torch.Tensor
+
+    def to_list(self):
+        """get_bboxes's return value, [[bboxes, scores, labels], ...] per sample (one host synchronisation)."""
+        n = self.counts.tolist()
+        return [[self.boxes[b, :k], self.scores[b, :k], self.labels[b, :k]] for b, k in enumerate(n)]
+
+
+def _cfg(c, name, default=None):
+    if isinstance(c, dict):
+        return c.get(name, default)
+    return getattr(c, name, default)
+
+
+def _per_task(v, T, name):
+    if v is None:
+        return [0.0] * T
+    if isinstance(v, (int, float)):
+        return [float(v)] * T
+    if len(v) < T:
+        raise ValueError(f"test_cfg['{name}'] has {len(v)} entries for {T} tasks")
+    return [float(x) for x in v[:T]]
+
+
+def det_postprocess(task_preds, coder_cfg, test_cfg, num_classes, norm_bbox, out=None):
+    """BEVDepthHead.get_bboxes on the device (vamp_det_postprocess): sigmoid, the deterministic top-K (score
+    descending, flat index ascending), CenterPointBBoxCoder.decode, the score and centre filters and test_cfg's
+    nms_type -- 'circle', 'size_aware_circle' or 'rotate' (rotated BEV IoU > nms_thr, after pre_max_size) --
+    for every task and sample in four launches, without a host synchronisation (capturable in a graph).
+    task_preds: the head's preds_dicts ([[{'heatmap', 'reg', 'height', 'dim', 'rot'[, 'vel']}], ...]);
+    coder_cfg: the bbox_coder config (dict or CenterPointBBoxCoder); num_classes: classes per task.
+    out: a DetResult of preallocated buffers to write (graph capture).  Returns a DetResult."""
+    heads = [pd[0] for pd in task_preds]
+    T = len(heads)
+    if not 1 <= T <= 8 or len(num_classes) < T:
+        raise ValueError(f"{T} tasks with {len(num_classes)} class counts (1 to 8 tasks)")
+    keys = ["heatmap", "reg", "height", "dim", "rot"]
+    has_vel = "vel" in heads[0]
+    if has_vel:
+        keys.append("vel")
+    tensors = [[h[k] for k in keys] for h in heads]
+    if not all(x.is_cuda for ts in tensors for x in ts):
+        raise _capi.VampireHipError("det_postprocess needs device tensors (no CPU fallback)")
+    dtype = heads[0]["heatmap"].dtype
+    if dtype not in _DET_DTYPES or any(x.dtype != dtype for ts in tensors for x in ts):
+        raise TypeError(f"head tensors must all be fp32, bf16 or fp16 of one dtype, got {dtype}")
+    B, _, H, W = heads[0]["heatmap"].shape
+    chans = {"reg": 2, "height": 1, "dim": 3, "rot": 2, "vel": 2}
+    for t, h in enumerate(heads):
+        if h["heatmap"].dim() != 4 or h["heatmap"].shape[0] != B or tuple(h["heatmap"].shape[2:]) != (H, W):
+            raise ValueError(f"task {t}: heatmap {tuple(h['heatmap'].shape)} does not match [{B}, *, {H}, {W}]")
+        if h["heatmap"].shape[1] != num_classes[t]:
+            raise ValueError(f"task {t}: heatmap has {h['heatmap'].shape[1]} classes, num_classes says {num_classes[t]}")
+        for k, c in chans.items():
+            if k in keys and tuple(h[k].shape) != (B, c, H, W):
+                raise ValueError(f"task {t}: {k} {tuple(h[k].shape)} is not [{B}, {c}, {H}, {W}]")
+    tensors = [[x.contiguous() for x in ts] for ts in tensors]
+    kind = test_cfg["nms_type"]
+    if kind not in _NMS_KINDS:
+        raise ValueError(f"nms_type {kind!r} is not one of {sorted(_NMS_KINDS)}")
+    thr = _cfg(coder_cfg, "score_threshold")
+    rng = _cfg(coder_cfg, "post_center_range")
+    d = _capi.VampDetDesc()
+    d.B, d.T, d.H, d.W = B, T, H, W
+    for t in range(T):
+        d.ncls[t] = num_classes[t]
+    d.max_num = int(_cfg(coder_cfg, "max_num", 100))
+    d.pre_max_size = int(test_cfg.get("pre_max_size", d.max_num))
+    d.post_max_size = int(test_cfg["post_max_size"])
+    d.nms_kind = _NMS_KINDS[kind]
+    d.in_dtype = _DET_DTYPES[dtype]
+    d.has_vel, d.norm_bbox = int(has_vel), int(bool(norm_bbox))
+    d.use_score_threshold, d.use_center_range = int(thr is not None), int(rng is not None)
+    # torch compares a tensor with a Python scalar in the tensor's dtype
+    d.score_threshold = float(torch.tensor(float(thr), dtype=dtype)) if thr is not None else 0.0
+    d.out_size_factor = float(_cfg(coder_cfg, "out_size_factor"))
+    vs, pc = _cfg(coder_cfg, "voxel_size"), _cfg(coder_cfg, "pc_range")
+    d.voxel_size[0], d.voxel_size[1] = float(vs[0]), float(vs[1])
+    d.pc_range[0], d.pc_range[1] = float(pc[0]), float(pc[1])
+    if rng is not None:
+        for i in range(6):
+            d.post_center_range[i] = float(rng[i])
+    mr = _per_task(test_cfg.get("min_radius") if kind == "circle" else None, T, "min_radius")
+    ts = _per_task(test_cfg.get("thresh_scale") if kind == "size_aware_circle" else None, T, "thresh_scale")
+    nt = _per_task(test_cfg.get("nms_thr") if kind == "rotate" else None, T, "nms_thr")
+    for t in range(T):
+        d.min_radius[t], d.thresh_scale[t], d.nms_thr[t] = mr[t], ts[t], nt[t]
+    lib = _capi.load()
+    nbytes = lib.vamp_det_workspace_bytes(C.byref(d))
+    if nbytes == 0:
+        _capi.check(lib.vamp_det_postprocess(C.byref(d), None, None, None, None, None, None, 0, None),
+                    "vamp_det_postprocess")
+    P, cs = d.post_max_size, 9 if has_vel else 7
+    dev = heads[0]["heatmap"].device
+    if out is None:
+        out = DetResult(torch.empty(B, T * P, cs, dtype=torch.float32, device=dev),
+                        torch.empty(B, T * P, dtype=dtype, device=dev),
+                        torch.empty(B, T * P, dtype=torch.int32, device=dev),
+                        torch.empty(B, dtype=torch.int32, device=dev))
+    else:
+        want = [(out.boxes, (B, T * P, cs), torch.float32), (out.scores, (B, T * P), dtype),
+                (out.labels, (B, T * P), torch.int32), (out.counts, (B,), torch.int32)]
+        for x, shape, dt in want:
+            if tuple(x.shape) != shape or x.dtype != dt or not x.is_contiguous() or x.device != dev:
+                raise ValueError(f"out buffer {tuple(x.shape)} {x.dtype} is not a contiguous {shape} {dt} on {dev}")
+    table = (_capi.VampDetTask * T)()
+    for t, ts_ in enumerate(tensors):
+        table[t] = _capi.VampDetTask(*[x.data_ptr() for x in ts_], *([] if has_vel else [None]))
+    with torch.cuda.device(dev):
+        ws = _metric_workspace("det", dev, nbytes)
+        _capi.check(lib.vamp_det_postprocess(C.byref(d), table, _ptr(out.boxes), _ptr(out.scores), _ptr(out.labels),
+                                             _ptr(out.counts), _ptr(ws), ws.numel(), _stream()),
+                    "vamp_det_postprocess")
+    return out
