@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Benchmark of the lift + render hot path (driver contract: see the task statement).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--cfg B] [--batch 1]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--cfg B] [--batch 1] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
 
 A "step" = lift forward -> render forward (camera + BEV) -> backward of both, for
@@ -11,7 +11,13 @@ BASELINE.json configs[1] (R50 256x704 features, 200x200x16 voxel grid, bs=1 per 
 Ranks shard samples (data parallel); the only collective is the DDP all-reduce of the
 path's one parameter gradient (density beta) over RCCL.
 
-Extra objects in the JSON line:
+A plain run sets up, warms up, times the steps, writes --dump-outputs and prints the headline.
+`--full` then measures in the same process what takes runs of its own: the per-kernel, stage and
+roofline figures, the step matrix, the batch-8, layered and multi-task legs, the secondary
+configurations and the CPU baseline; --no-extra, --no-matrix and --no-cpu-baseline leave parts
+of them out.
+
+Extra objects in the JSON line of a --full run:
   roofline      dominant kernel of the step: algorithmic bytes per launch / HIP-event
                 duration, against the 8 TB/s HBM peak (in-library event timer)
   fwd_roofline  the fused forward (north_star's 70 % target) timed as ONE unit: a HIP-event pair
@@ -34,6 +40,34 @@ import time
 # the tuned numbers.
 ROOT = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, ROOT)
+
+
+def parse_args(argv=None):
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--gpus", type=int, default=1)
+    ap.add_argument("--steps", type=int, default=20)
+    ap.add_argument("--warmup", type=int, default=5)
+    ap.add_argument("--cfg", default="B", help="A | B | D (vampire_amd.config.PRESETS)")
+    ap.add_argument("--batch", type=int, default=1, help="samples per GPU per step")
+    ap.add_argument("--dtype", default="f32", choices=["f32", "bf16"])
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline, measure everything else the line can carry (per-kernel and roofline figures, "
+                         "step matrix, batch-8, layered and multi-task legs, secondary configurations, CPU baseline)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="(--full) skip the CPU baseline")
+    ap.add_argument("--no-extra", action="store_true", help="(--full) skip the secondary configurations (extra_configs)")
+    ap.add_argument("--no-matrix", action="store_true",
+                    help="(--full) skip the {eager, graph} x {early termination on, off} step matrix (profile runs: only default-path kernels)")
+    ap.add_argument("--multitask", action="store_true", help="(accepted for compatibility: --full times the multi-task step unless --no-extra)")
+    ap.add_argument("--layers", action="store_true", help="(accepted for compatibility: --full times the layered step unless --no-extra)")
+    ap.add_argument("--miopen-find", action="store_true",
+                    help="(--full) let MIOpen tune the convolutions of the layered / multi-task legs (6.5 minutes on a fresh box)")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="after the timed steps, write what the last timed step computed (outputs and gradients, "
+                         "float32, a fixed sample of the large ones) as DIR/<name>.npy, e.g. DIR=bench_outputs")
+    a = ap.parse_args(argv)
+    if a.steps < 1:
+        ap.error("--steps must be at least 1")
+    return a
 
 
 def _use_shipped_miopen_db():
@@ -105,7 +139,10 @@ def _miopen_db_matches():
         return False
 
 
-MIOPEN_DB = _use_shipped_miopen_db()
+# The arguments are read before torch is imported: only --full runs the MIOpen legs, so a plain run leaves
+# MIOpen's environment alone (a module that imports bench for those legs still gets the shipped db).
+ARGS = parse_args() if __name__ == "__main__" else None
+MIOPEN_DB = _use_shipped_miopen_db() if ARGS is None or ARGS.full else None
 
 import torch                                    # noqa: E402  (after the MIOpen environment)
 import torch.distributed as dist                # noqa: E402
@@ -615,29 +652,7 @@ def _mark(what):
     print(f"[bench] +{time.perf_counter() - _T0:6.1f} s  {what}", file=sys.stderr, flush=True)
 
 
-def main():
-    ap = argparse.ArgumentParser()
-    ap.add_argument("--gpus", type=int, default=1)
-    ap.add_argument("--steps", type=int, default=20)
-    ap.add_argument("--warmup", type=int, default=5)
-    ap.add_argument("--cfg", default="B", help="A | B | D (vampire_amd.config.PRESETS)")
-    ap.add_argument("--batch", type=int, default=1, help="samples per GPU per step")
-    ap.add_argument("--dtype", default="f32", choices=["f32", "bf16"])
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-extra", action="store_true", help="skip the secondary configurations (extra_configs)")
-    ap.add_argument("--no-matrix", action="store_true",
-                    help="skip the {eager, graph} x {early termination on, off} step matrix (profile runs: only default-path kernels)")
-    ap.add_argument("--multitask", action="store_true", help="(accepted for compatibility: the multi-task step is always timed unless --no-extra)")
-    ap.add_argument("--layers", action="store_true", help="(accepted for compatibility: the layered step is always timed unless --no-extra)")
-    ap.add_argument("--miopen-find", action="store_true",
-                    help="let MIOpen tune the convolutions of the layered / multi-task legs (6.5 minutes on a fresh box)")
-    ap.add_argument("--dump-outputs", metavar="DIR",
-                    help="after the timed steps, write what the last timed step computed (outputs and gradients, "
-                         "float32, a fixed sample of the large ones) as DIR/<name>.npy, e.g. DIR=bench_outputs")
-    a = ap.parse_args()
-    if a.steps < 1:
-        ap.error("--steps must be at least 1")
-
+def main(a):
     world = int(os.environ.get("WORLD_SIZE", "1"))
     rank = int(os.environ.get("RANK", "0"))
     local_rank = int(os.environ.get("LOCAL_RANK", "0"))
@@ -760,6 +775,41 @@ def main():
         # (before the eager profile steps below replace the gradients)
         dump_outputs(a.dump_outputs, model, batch, *(graph.step_outputs if graph is not None else last["outputs"]))
         _mark("outputs dumped")
+
+    def headline(ert_stats=None):
+        """The line of a plain run; --full adds its own measurements behind these fields."""
+        return {
+            "metric": "6-cam samples/sec (lift+render fwd+bwd)",
+            "value": a.batch * world * a.steps / elapsed,
+            "unit": "samples/s",
+            "n_gpus": world, "steps": a.steps, "warmup": a.warmup,
+            "ms_per_step": elapsed / a.steps * 1e3,
+            "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
+            "dtype": a.dtype, "data": "synthetic",
+            "config": {"workload": f"cfg-{a.cfg}: 6x{cfg.final_dim[0]}x{cfg.final_dim[1]} images, "
+                                   f"D={cfg.D} C={cfg.mid_channels} K={cfg.num_classes}, voxel grid "
+                                   f"{cfg.vX}x{cfg.vY}x{cfg.vZ}, det grid {cfg.oX}x{cfg.oY}x{cfg.oZ}, "
+                                   f"{a.batch} sample(s)/GPU/step, lift+render fwd+bwd, density_mode={cfg.density_mode} "
+                                   f"(the reference's default), camera-branch early ray termination "
+                                   f"{'on' if model.hp.impl['ert'] else 'off'} (T < 1.5e-8)"
+                                   + (f": on this synthetic density (0.5 randn - 1) {100 * ert_stats['terminated_fraction']:.0f} % of the "
+                                      f"inside samples lie behind a saturated ray and are skipped -- data-dependent, see step_matrix "
+                                      f"for the same step with termination off" if ert_stats else ""),
+                       "per_gpu_batch": a.batch, "global_batch": a.batch * world,
+                       "parallelism": f"dp{world}",
+                       "launch": ("the step replayed from a HIP graph (DDP all-reduce issued after each replay)"
+                                  + ("; kernel timings from HIP events in eager one-stream steps of the same run" if a.full else "")
+                                  if launch_mode == "hip_graph" else "eager launches")},
+            "rccl_ranks": (dist.get_world_size() if dist.is_initialized() else 1),
+        }
+
+    if not a.full:                                  # a plain run: the headline is all it prints
+        _capi.profile_select(None)
+        if rank == 0:
+            print(json.dumps(headline()), flush=True)
+        vdist.shutdown()
+        return
+
     if graph is not None:
         # the dominant kernel's launches, timed with HIP events in K eager one-stream steps
         model.hp.impl["overlap"] = False
@@ -879,29 +929,8 @@ def main():
         fwd_us = fwd_graph[0] if fwd_graph else fwd_med
         fwd_bytes = sb["fwd"] * a.batch
         fwd_gbs = fwd_bytes / (fwd_us * 1e-6) / 1e9
-        line = {
-            "metric": "6-cam samples/sec (lift+render fwd+bwd)",
-            "value": a.batch * world * a.steps / elapsed,
-            "unit": "samples/s",
-            "n_gpus": world, "steps": a.steps, "warmup": a.warmup,
-            "ms_per_step": elapsed / a.steps * 1e3,
-            "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
-            "dtype": a.dtype, "data": "synthetic",
-            "config": {"workload": f"cfg-{a.cfg}: 6x{cfg.final_dim[0]}x{cfg.final_dim[1]} images, "
-                                   f"D={cfg.D} C={cfg.mid_channels} K={cfg.num_classes}, voxel grid "
-                                   f"{cfg.vX}x{cfg.vY}x{cfg.vZ}, det grid {cfg.oX}x{cfg.oY}x{cfg.oZ}, "
-                                   f"{a.batch} sample(s)/GPU/step, lift+render fwd+bwd, density_mode={cfg.density_mode} "
-                                   f"(the reference's default), camera-branch early ray termination "
-                                   f"{'on' if model.hp.impl['ert'] else 'off'} (T < 1.5e-8)"
-                                   + (f": on this synthetic density (0.5 randn - 1) {100 * ert_stats['terminated_fraction']:.0f} % of the "
-                                      f"inside samples lie behind a saturated ray and are skipped -- data-dependent, see step_matrix "
-                                      f"for the same step with termination off" if ert_stats else ""),
-                       "per_gpu_batch": a.batch, "global_batch": a.batch * world,
-                       "parallelism": f"dp{world}",
-                       "launch": ("the step replayed from a HIP graph (DDP all-reduce issued after each replay); "
-                                  "kernel timings from HIP events in eager one-stream steps of the same run"
-                                  if launch_mode == "hip_graph" else "eager launches")},
-            "rccl_ranks": (dist.get_world_size() if dist.is_initialized() else 1),
+        line = headline(ert_stats)
+        line.update({
             "roofline": {"bound": "hbm", "kernel": dom, "achieved": dom_gbs, "peak": HBM_PEAK_GBS,
                          "unit": "GB/s", "frac": dom_gbs / HBM_PEAK_GBS,
                          "traffic": measured_traffic(a.cfg, dom, a.batch, list(kern)),
@@ -952,7 +981,7 @@ def main():
             "early_ray_termination": ert_stats,
             "kernels_avg_us": {k: round(v["avg_us"], 2) for k, v in sorted(kern.items())},
             "kernels_us_per_step": {k: round(v["us_per_step"], 2) for k, v in sorted(kern.items())},
-        }
+        })
         if world == 1 and not a.no_extra:
             # secondary configurations of BASELINE.json / SURVEY 8(d), measured in this same run
             line["extra_configs"] = [extra_config("A", 1, torch.float32), extra_config("B", 8, torch.float32),
@@ -968,4 +997,4 @@ def main():
 
 
 if __name__ == "__main__":
-    main()
+    main(ARGS)

@@ -34,7 +34,7 @@ stats train_step_replayed "cfg-$CFG, 1 sample: 20 + 3 eager steps, then 200 repl
 stats fwd_pair "cfg-$CFG, 1 sample: the no-grad forward pair, 4 eager calls then 20 + 300 + 300 replays (tools/fwd_graph.py)" $ROOT/tools/fwd_graph.py $CFG 1 300 0
 stats cfg${CFG}_b8_replayed "cfg-$CFG, 8 samples per GPU: 20 + 3 eager steps, then 60 replays of the captured step (tools/try_graph.py)" $ROOT/tools/try_graph.py $CFG 8 60
 # the bench line under the profiler (default-path kernels only)
-timeout 300 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/stats -- python3 $ROOT/bench.py --cfg $CFG --steps 20 --warmup 5 --no-cpu-baseline --no-extra --no-matrix > $OUT/bench_under_rocprof_$TAG.json 2> $OUT/bench_under_rocprof.log
+timeout 300 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/stats -- python3 $ROOT/bench.py --full --cfg $CFG --steps 20 --warmup 5 --no-cpu-baseline --no-extra --no-matrix > $OUT/bench_under_rocprof_$TAG.json 2> $OUT/bench_under_rocprof.log
 rm -rf $OUT/stats
 # HBM traffic: separate passes, no trace domains
 timeout 300 rocprofv3 --pmc FETCH_SIZE --output-format csv -d $OUT/pmc_fetch -- python3 $ROOT/tools/time_bwd.py $CFG 1 > /dev/null 2> $OUT/pmc_fetch.log
