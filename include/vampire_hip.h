@@ -27,8 +27,8 @@
 extern "C" {
 #endif
 
-#define VAMP_ABI_VERSION 8   /* bumped whenever entry points or flags are added (round 2: 2, round 3: 3, round 4: 4, round 5: 5, round 6: 6;
-                                 7: segmentation metrics; 8: detection post-processing) */
+#define VAMP_ABI_VERSION 9   /* bumped whenever entry points or flags are added (round 2: 2, round 3: 3, round 4: 4, round 5: 5, round 6: 6;
+                                 7: segmentation metrics; 8: detection post-processing; 9: detection targets) */
 
 enum {
   VAMP_OK = 0,
@@ -858,6 +858,56 @@ typedef struct VampDetDesc {
 size_t vamp_det_workspace_bytes(const VampDetDesc* d);
 int vamp_det_postprocess(const VampDetDesc* d, const VampDetTask* tasks, float* boxes, void* scores, int32_t* labels,
                          int32_t* counts, void* workspace, size_t workspace_bytes, void* stream);
+
+/* --------------------------------------------------------------------------
+ * Detection training targets: the reference head's get_targets (bev_depth_head.py:168-319, with mmdet3d's
+ * gaussian_radius and draw_heatmap_gaussian) for all T tasks of a head and all B samples, on the device.
+ * Inputs: boxes [B, M, box_cols] fp32 (x y z dx dy dz yaw [vx vy]) and labels [B, M] (label_dtype) of flat class
+ * ids; rows past a sample's count carry label -1.  Task t owns the labels flag_t .. flag_t + ncls[t] - 1, flag_t
+ * the sum of the earlier tasks' ncls; other labels (-1, >= the sum, ...) belong to no task.
+ *
+ *  slots      per (sample, task) the task's boxes class by class in class order, ascending box index within a
+ *             class (the order of torch.where); slot k is the position in that run, only k < max_objs counts.
+ *  size       w = box[3] * (1 / voxel_size[0]) * (1 / out_size_factor), l likewise with box[4] and voxel_size[1]
+ *             (aten divides by a CPU scalar as a product with its reciprocal: 1.0f / b for the fp32 voxel size,
+ *             (float) (1.0 / b) for a Python number; each op rounded, no FMA); the box is skipped unless w > 0
+ *             and l > 0 (a NaN fails).
+ *  radius     r = max(min_radius, int(gaussian_radius((l, w), gaussian_overlap))), the three roots in fp32 op by
+ *             op with the Python-float terms of the overlap rounded to fp32; a radius that is not finite or is
+ *             >= 2^30 (where the reference raises) skips the box.
+ *  centre     c = (xy - pc_range) * (1 / voxel_size) * (1 / out_size_factor) in fp32, cast to int32 as aten does
+ *             on this device (truncation, NaN -> 0); the box is skipped unless 0 <= x < fw and 0 <= y < fh.
+ *  heatmap    max-merge of the stamp exp(-(dx^2 + dy^2) / ((2 sigma) sigma)), sigma = (2 r + 1) / 6, in float64,
+ *             zeroed below DBL_EPSILON, rounded to fp32, over |dx| <= r, |dy| <= r clipped to the map.
+ *  rows       anno [k] = (cx - x, cy - y, z, dims (log when norm_bbox), sin yaw, cos yaw[, vx, vy]), ind [k] =
+ *             y * fw + x, mask [k] = 1; skipped slots and slots past the task's count are zero.
+ * Outputs: heatmaps, task-major: task t's [B, ncls[t], fh, fw] block follows the earlier tasks' (each a
+ * contiguous view); anno [T, B, max_objs, code] fp32, inds [T, B, max_objs] int64, masks [T, B, max_objs]
+ * uint8.  Every element is written.
+ * Limits: 1 <= B <= 4096, 1 <= T <= 8, 1 <= ncls[t] <= 4, 0 <= M <= 2^20, box_cols 7 | 9 with code = box_cols + 1,
+ * 1 <= max_objs <= 8192, 1 <= fh, fw <= 8192, out_size_factor >= 1, voxel_size > 0.  Every argument is checked
+ * before any device work.  Two launches on `stream`, no host synchronisation, no atomics: the output is a pure
+ * function of the inputs, and the call can be captured in a graph.  The workspace
+ * (vamp_det_targets_workspace_bytes) needs no initialisation.
+ * -------------------------------------------------------------------------- */
+typedef struct VampDetTargetDesc {
+  double gaussian_overlap;        /* train_cfg['gaussian_overlap'], the Python float */
+  int32_t B, T, M;
+  int32_t ncls[8];
+  int32_t box_cols;               /* 7 | 9 */
+  int32_t code;                   /* anno width, len(code_weights): box_cols + 1 */
+  int32_t max_objs;               /* max_objs * dense_reg */
+  int32_t fh, fw;                 /* grid_size[1] // out_size_factor, grid_size[0] // out_size_factor */
+  int32_t out_size_factor;
+  int32_t min_radius;
+  int32_t norm_bbox;
+  int32_t label_dtype;            /* VAMP_I32 | VAMP_I64 */
+  float voxel_size[2], pc_range[2];
+  int32_t reserved[2];            /* 0 */
+} VampDetTargetDesc;
+size_t vamp_det_targets_workspace_bytes(const VampDetTargetDesc* d);
+int vamp_det_targets(const VampDetTargetDesc* d, const float* boxes, const void* labels, float* heatmaps, float* anno,
+                     int64_t* inds, uint8_t* masks, void* workspace, size_t workspace_bytes, void* stream);
 
 #ifdef __cplusplus
 }

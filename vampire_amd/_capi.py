@@ -9,7 +9,7 @@ import os
 
 from .build import lib_path
 
-ABI_VERSION = 8
+ABI_VERSION = 9
 
 VAMP_F32, VAMP_BF16, VAMP_F16 = 0, 1, 2
 VAMP_DENSITY_SIGMOID, VAMP_DENSITY_SDF_LAPLACE = 0, 1
@@ -84,6 +84,14 @@ class VampDetDesc(C.Structure):
                 ("thresh_scale", C.c_float * 8), ("nms_thr", C.c_float * 8), ("reserved", C.c_int32)]
 
 
+class VampDetTargetDesc(C.Structure):
+    _fields_ = [("gaussian_overlap", C.c_double), ("B", C.c_int32), ("T", C.c_int32), ("M", C.c_int32),
+                ("ncls", C.c_int32 * 8), ("box_cols", C.c_int32), ("code", C.c_int32), ("max_objs", C.c_int32),
+                ("fh", C.c_int32), ("fw", C.c_int32), ("out_size_factor", C.c_int32), ("min_radius", C.c_int32),
+                ("norm_bbox", C.c_int32), ("label_dtype", C.c_int32), ("voxel_size", C.c_float * 2),
+                ("pc_range", C.c_float * 2), ("reserved", C.c_int32 * 2)]
+
+
 # flag bits of vamp_lift_backward_ex / vamp_render_camera_backward_acc (include/vampire_hip.h)
 VAMP_LIFTFWD_EMIT_PAIRS, VAMP_LIFTFWD_CELLS_CLEAN, VAMP_LIFTFWD_FEAT_CHANNEL_LAST, VAMP_LIFTFWD_DEFER_SCAN = 1, 2, 4, 8
 VAMP_LIFTBWD_CELLS_VALID, VAMP_LIFTBWD_SPLAT = 1, 2
@@ -107,6 +115,7 @@ _SD = C.POINTER(VampSampleDesc)
 _CD = C.POINTER(VampConvDesc)
 _QD = C.POINTER(VampConfDesc)
 _DD = C.POINTER(VampDetDesc)
+_TD = C.POINTER(VampDetTargetDesc)
 
 # name -> (restype, argtypes); must list every symbol declared in include/vampire_hip.h
 SIGNATURES = {
@@ -196,6 +205,8 @@ SIGNATURES = {
                                         _P, _P, _P, C.c_size_t, _P]),
     "vamp_det_workspace_bytes": (C.c_size_t, [_DD]),
     "vamp_det_postprocess": (C.c_int, [_DD, C.POINTER(VampDetTask)] + [_P] * 5 + [C.c_size_t, _P]),
+    "vamp_det_targets_workspace_bytes": (C.c_size_t, [_TD]),
+    "vamp_det_targets": (C.c_int, [_TD] + [_P] * 7 + [C.c_size_t, _P]),
 }
 
 _lib = None

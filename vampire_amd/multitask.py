@@ -260,6 +260,15 @@ class BEVDepthHead(nn.Module):
         anno_d, ind_d, mask_d = torch.stack(anno_boxes).to(dev), torch.stack(inds).to(dev), torch.stack(masks).to(dev)
         return list(heat_d.split(ncls, 0)), list(anno_d.unbind(0)), list(ind_d.unbind(0)), list(mask_d.unbind(0))
 
+    def get_targets_device(self, gt_bboxes_3d, gt_labels_3d, out=None):
+        """get_targets on the device: one vamp_det_targets call (two launches), no host synchronisation, the
+        reference's fp32 chain and float64 Gaussian stamps.  gt_bboxes_3d / gt_labels_3d: the
+        per-sample lists get_targets takes (packed on the device, labels padded with -1) or packed [B, M, 7 | 9]
+        fp32 / [B, M] tensors whose padding rows carry label -1 (graph capture).  Returns an ops.DetTargets whose
+        as_tuple() is get_targets's (heatmaps, anno_boxes, inds, masks); `out` takes preallocated buffers."""
+        from . import ops
+        return ops.det_targets(gt_bboxes_3d, gt_labels_3d, self.num_classes, self.train_cfg, self.norm_bbox, out=out)
+
     # ---- loss (bev_depth_head.py:318-375) ----
     def loss(self, targets, preds_dicts, **_):
         heatmaps, anno_boxes, inds, masks = targets
@@ -342,6 +351,9 @@ class VAMPIRE2(nn.Module):
     def get_targets(self, gt_boxes, gt_labels):
         return self.head.get_targets(gt_boxes, gt_labels)
 
+    def get_targets_device(self, gt_boxes, gt_labels, out=None):
+        return self.head.get_targets_device(gt_boxes, gt_labels, out=out)
+
     def loss(self, targets, preds_dicts):
         return self.head.loss(targets, preds_dicts)
 
@@ -422,8 +434,11 @@ class MultiTaskLoss:
     `task_weights` (occ, lidarseg, detection) and `loss_weights` (depth, seg, rgb, sdf, density)."""
 
     def __init__(self, model, task_weights=(1., 1., 1.), loss_weights=(1., 1., 1., 1., 1.), downsample_factor=4,
-                 upsample_factor=4, sdf_bias=-1.0):
+                 upsample_factor=4, sdf_bias=-1.0, det_targets="host"):
+        if det_targets not in ("host", "device"):
+            raise ValueError(f"det_targets must be 'host' or 'device', got {det_targets!r}")
         self.model, self.task_weights, self.loss_weights = model, task_weights, loss_weights
+        self.det_targets = det_targets
         self.down, self.up, self.sdf_bias = downsample_factor, upsample_factor, sdf_bias
         self.last = {}
 
@@ -438,9 +453,15 @@ class MultiTaskLoss:
 
     def targets(self, batch):
         """The detection targets depend on the labels only: made BEFORE the forward is launched, their host
-        round trip (boxes to the CPU, heatmaps back) does not wait for the GPU to drain the forward."""
+        round trip (boxes to the CPU, heatmaps back) does not wait for the GPU to drain the forward.  With
+        det_targets="device" they are two HIP launches on the stream instead (get_targets_device)."""
         head = self.model.module if hasattr(self.model, "module") else self.model
-        return head.get_targets(batch[4], batch[5])
+        return self._targets(head, batch[4], batch[5])
+
+    def _targets(self, head, gt_boxes, gt_labels):
+        if self.det_targets == "device":
+            return head.get_targets_device(gt_boxes, gt_labels).as_tuple()
+        return head.get_targets(gt_boxes, gt_labels)
 
     def __call__(self, outputs, batch, targets=None):
         (sweep_imgs, mats, _, _, gt_boxes, gt_labels, depth_labels, seg_labels, bev_seg, bev_height, bev_mask,
@@ -448,7 +469,7 @@ class MultiTaskLoss:
         (preds, rgb_p, seg_p, depth_p, bev_rgb_p, bev_seg_p, bev_h_p, bev_density, pts_logits, pts_sdf,
          occ_logits, occ_density) = outputs
         head = self.model.module if hasattr(self.model, "module") else self.model
-        det = head.loss(head.get_targets(gt_boxes, gt_labels) if targets is None else targets, preds)
+        det = head.loss(self._targets(head, gt_boxes, gt_labels) if targets is None else targets, preds)
         if depth_labels.dim() == 5:                      # only the key frame carries camera labels
             sweep_imgs, depth_labels, seg_labels = sweep_imgs[:, 0], depth_labels[:, 0], seg_labels[:, 0]
         depth_p = depth_p[:, :, 0]

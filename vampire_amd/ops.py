@@ -1612,3 +1612,117 @@ def det_postprocess(task_preds, coder_cfg, test_cfg, num_classes, norm_bbox, out
                                              _ptr(out.counts), _ptr(ws), ws.numel(), _stream()),
                     "vamp_det_postprocess")
     return out
+
+
+# ===========================================================================
+# detection training targets (bev_depth_head.py:168-319)
+# ===========================================================================
+_LABEL_CODES = {torch.int32: _capi.VAMP_I32, torch.int64: _capi.VAMP_I64}
+
+
+@dataclasses.dataclass
+class DetTargets:
+    """The training targets of a batch: `heat` holds the tasks' [B, ncls_t, fh, fw] heatmaps one after the other
+    (fp32), anno [T, B, max_objs, code] fp32, inds [T, B, max_objs] int64, masks [T, B, max_objs] uint8."""
+    heat: torch.Tensor
+    anno: torch.Tensor
+    inds: torch.Tensor
+    masks: torch.Tensor
+    ncls: tuple
+    fh: int
+    fw: int
+
+    def heatmaps(self):
+        B = self.anno.shape[1]
+        return [h.view(B, n, self.fh, self.fw) for h, n in
+                zip(self.heat.split([B * n * self.fh * self.fw for n in self.ncls]), self.ncls)]
+
+    def as_tuple(self):
+        """get_targets's return value: (heatmaps, anno_boxes, inds, masks), each a list over tasks of [B, ...]
+        views of the buffers."""
+        return self.heatmaps(), list(self.anno.unbind(0)), list(self.inds.unbind(0)), list(self.masks.unbind(0))
+
+
+def _pack_targets_input(boxes, labels):
+    """Per-sample lists ([n_b, 7 | 9] boxes, [n_b] labels) -> padded [B, M, 7 | 9], [B, M] (label -1) on the
+    device, without a host synchronisation; tensors pass through."""
+    if isinstance(boxes, torch.Tensor):
+        if not isinstance(labels, torch.Tensor):
+            raise ValueError("boxes is a packed tensor but labels is not")
+        return boxes, labels
+    if len(boxes) != len(labels) or len(boxes) == 0:
+        raise ValueError(f"{len(boxes)} box tensors and {len(labels)} label tensors (one per sample, at least one)")
+    if any(b.dtype != torch.float32 for b in boxes):
+        raise TypeError(f"boxes must be fp32, got {sorted({str(b.dtype) for b in boxes})}")
+    if len({l.dtype for l in labels}) != 1:
+        raise TypeError(f"labels must share one dtype, got {sorted({str(l.dtype) for l in labels})}")
+    if not all(b.is_cuda for b in boxes) or not all(l.is_cuda for l in labels):
+        raise _capi.VampireHipError("det_targets needs device tensors (no CPU fallback)")
+    pad = torch.nn.utils.rnn.pad_sequence
+    return pad(list(boxes), batch_first=True), pad(list(labels), batch_first=True, padding_value=-1)
+
+
+def det_targets(boxes, labels, tasks_ncls, train_cfg, norm_bbox, out=None):
+    """BEVDepthHead.get_targets on the device (vamp_det_targets): per task and sample the Gaussian heatmaps and
+    the anno / ind / mask rows of the first max_objs boxes in the reference's slot order, with the reference's
+    fp32 chain, in two launches and without a host synchronisation (capturable in a graph with packed inputs).
+    boxes, labels: per-sample lists ([n_b, 7 | 9] fp32, [n_b] int32 | int64; packed on the device with label -1
+    padding) or packed [B, M, 7 | 9] and [B, M] tensors whose padding rows carry label -1.  tasks_ncls: classes
+    per task, labels flat over the tasks.  out: a DetTargets of preallocated buffers to write (graph capture).
+    Returns a DetTargets; as_tuple() is get_targets's (heatmaps, anno_boxes, inds, masks)."""
+    boxes, labels = _pack_targets_input(boxes, labels)
+    if boxes.dtype != torch.float32:
+        raise TypeError(f"boxes must be fp32, got {boxes.dtype}")
+    if labels.dtype not in _LABEL_CODES:
+        raise TypeError(f"labels must be int32 or int64, got {labels.dtype}")
+    if not (boxes.is_cuda and labels.is_cuda):
+        raise _capi.VampireHipError("det_targets needs device tensors (no CPU fallback)")
+    if boxes.dim() != 3 or boxes.shape[2] not in (7, 9) or tuple(labels.shape) != tuple(boxes.shape[:2]):
+        raise ValueError(f"expected boxes [B, M, 7 | 9] and labels [B, M], got {tuple(boxes.shape)} "
+                         f"and {tuple(labels.shape)}")
+    ncls = tuple(int(n) for n in tasks_ncls)
+    T = len(ncls)
+    if not 1 <= T <= 8:
+        raise ValueError(f"{T} tasks (1 to 8)")
+    B, Mb, cols = boxes.shape
+    osf = train_cfg["out_size_factor"]
+    fw, fh = int(train_cfg["grid_size"][0]) // osf, int(train_cfg["grid_size"][1]) // osf
+    code = len(train_cfg["code_weights"])
+    max_objs = int(train_cfg["max_objs"] * train_cfg["dense_reg"])
+    d = _capi.VampDetTargetDesc()
+    d.gaussian_overlap = float(train_cfg["gaussian_overlap"])
+    d.B, d.T, d.M = B, T, Mb
+    for t in range(T):
+        d.ncls[t] = ncls[t]
+    d.box_cols, d.code, d.max_objs, d.fh, d.fw = cols, code, max_objs, fh, fw
+    d.out_size_factor, d.min_radius, d.norm_bbox = int(osf), int(train_cfg["min_radius"]), int(bool(norm_bbox))
+    d.label_dtype = _LABEL_CODES[labels.dtype]
+    vs, pc = train_cfg["voxel_size"], train_cfg["point_cloud_range"]
+    d.voxel_size[0], d.voxel_size[1] = float(vs[0]), float(vs[1])
+    d.pc_range[0], d.pc_range[1] = float(pc[0]), float(pc[1])
+    lib = _capi.load()
+    nbytes = lib.vamp_det_targets_workspace_bytes(C.byref(d))
+    if nbytes == 0:
+        _capi.check(lib.vamp_det_targets(C.byref(d), None, None, None, None, None, None, None, 0, None),
+                    "vamp_det_targets")
+    dev = boxes.device
+    boxes, labels = boxes.contiguous(), labels.contiguous()
+    if out is None:
+        out = DetTargets(torch.empty(B * sum(ncls) * fh * fw, dtype=torch.float32, device=dev),
+                         torch.empty(T, B, max_objs, code, dtype=torch.float32, device=dev),
+                         torch.empty(T, B, max_objs, dtype=torch.int64, device=dev),
+                         torch.empty(T, B, max_objs, dtype=torch.uint8, device=dev), ncls, fh, fw)
+    else:
+        want = [(out.heat, (B * sum(ncls) * fh * fw,), torch.float32), (out.anno, (T, B, max_objs, code), torch.float32),
+                (out.inds, (T, B, max_objs), torch.int64), (out.masks, (T, B, max_objs), torch.uint8)]
+        for x, shape, dt in want:
+            if tuple(x.shape) != shape or x.dtype != dt or not x.is_contiguous() or x.device != dev:
+                raise ValueError(f"out buffer {tuple(x.shape)} {x.dtype} is not a contiguous {shape} {dt} on {dev}")
+        if tuple(out.ncls) != ncls or (out.fh, out.fw) != (fh, fw):
+            raise ValueError(f"out was made for classes {out.ncls} on {out.fh} x {out.fw}, not {ncls} on {fh} x {fw}")
+    with torch.cuda.device(dev):
+        ws = _metric_workspace("det_targets", dev, nbytes)
+        _capi.check(lib.vamp_det_targets(C.byref(d), _ptr(boxes), _ptr(labels), _ptr(out.heat), _ptr(out.anno),
+                                         _ptr(out.inds), _ptr(out.masks), _ptr(ws), ws.numel(), _stream()),
+                    "vamp_det_targets")
+    return out
