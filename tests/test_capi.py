@@ -127,3 +127,118 @@ def test_render_descriptor_limits_are_rejected_without_gpu(lib, field, value, me
         assert message in lib.vamp_last_error(), (name, lib.vamp_last_error())
     assert lib.vamp_render_forward_merged_supported(C.byref(bad), heights) == 0
     assert lib.vamp_render_workspace_bytes(C.byref(ok)) > 0
+
+
+# ------------------------------------------------------------------ the binding's conversions (CPU tensors only)
+def _as_address(converted):
+    """What ctypes puts on the stack for a TensorPtr argument: None is NULL, otherwise the 64-bit value."""
+    return 0 if converted is None else (C.cast(converted, C.c_void_p).value or 0)
+
+
+def test_tensor_pointer_passes_a_full_64_bit_address():
+    """A tensor goes in as its data_ptr(), as a c_void_p: a bare int from from_param would travel as a 32-bit C int."""
+    t = torch.arange(5, dtype=torch.int64)
+    assert t.data_ptr() >= 2 ** 32, "the host heap lies above 4 GiB on every 64-bit Linux this runs on"
+    got = _capi.TensorPtr.from_param(t)
+    assert isinstance(got, C.c_void_p) and got.value == t.data_ptr()
+    high = _capi.TensorPtr.from_param(0xfedc_ba98_7654_3210)
+    assert isinstance(high, C.c_void_p) and high.value == 0xfedc_ba98_7654_3210
+    # through a real foreign call: memcpy with TensorPtr parameters copies between the two tensors
+    libc = C.CDLL(None)
+    memcpy = libc["memcpy"]
+    memcpy.restype, memcpy.argtypes = C.c_void_p, [_capi.TensorPtr, _capi.TensorPtr, C.c_size_t]
+    dst = torch.zeros(5, dtype=torch.int64)
+    assert memcpy(dst, t, 40) == dst.data_ptr()
+    assert torch.equal(dst, t)
+
+
+def test_tensor_pointer_accepts_none_parameters_and_pointers():
+    assert _as_address(_capi.TensorPtr.from_param(None)) == 0
+    p = torch.nn.Parameter(torch.ones(3))
+    assert _capi.TensorPtr.from_param(p).value == p.data_ptr()
+    assert _as_address(_capi.TensorPtr.from_param(C.c_void_p(1 << 40))) == 1 << 40
+    arr = (C.c_int32 * 2)()
+    assert _as_address(_capi.TensorPtr.from_param(arr)) == C.addressof(arr)
+
+
+def test_tensor_pointer_refuses_other_objects(lib):
+    d = _capi.VampLiftDesc()
+    for bad in ("a string", 1.5, [1, 2], object()):
+        with pytest.raises(C.ArgumentError):
+            lib.vamp_lift_indices(d, bad, None, None, None, None, None, None, None, None)
+
+
+def test_checked_call_raises_where_the_raw_call_returns_the_code(lib):
+    d = _capi.VampLiftDesc()          # all zeros, passed without byref
+    args = (d, None, None, None, None, None, None, None, None, None)
+    with pytest.raises(_capi.VampireHipError) as e:
+        _capi.checked().vamp_lift_indices(*args)
+    assert str(e.value).startswith("vamp_lift_indices failed with code -1:")
+    assert "requirement failed" in str(e.value)
+    assert lib.vamp_lift_indices(*args) == -1
+    assert lib.vamp_lift_indices is not _capi.checked().vamp_lift_indices
+
+
+def test_every_signature_is_a_status_or_a_value(lib):
+    vamp = _capi.checked()
+    for name, (ret, args) in _capi.SIGNATURES.items():
+        assert ret.is_status in (True, False), name
+        assert ret.ctype is C.c_int or not ret.is_status, f"{name}: a status is a C int"
+        fn = getattr(vamp, name)
+        assert (fn.errcheck is not None) == ret.is_status if hasattr(fn, "errcheck") else not ret.is_status, name
+        assert fn.restype is getattr(lib, name).restype and fn.argtypes == getattr(lib, name).argtypes, name
+    values = {n for n, (ret, _) in _capi.SIGNATURES.items() if not ret.is_status}
+    assert {"vamp_abi_version", "vamp_profile_slots", "vamp_last_error"} <= values
+    assert {n for n in _capi.SIGNATURES if n.endswith(("_supported", "_bytes", "_offset"))} <= values
+    # the value returns come back as they are, 0 included, without raising
+    assert vamp.vamp_abi_version() == _capi.ABI_VERSION
+    cd = _capi.VampConvDesc(1, 8, 16, 4, 4, 4)
+    assert vamp.vamp_conv3d_supported(cd) == 0 and vamp.vamp_conv3d_bf16_supported(cd) == 0
+    assert vamp.vamp_upsample_trilinear_supported(0, 0, 0, 0, 0, 0) == 0
+    assert vamp.vamp_gate_conv1x1_supported(0, 0, 0) == 0
+    assert vamp.vamp_render_forward_merged_supported(_capi.VampRenderDesc(), None) == 0
+
+
+def test_checked_set_follows_a_reload(monkeypatch):
+    first = _capi.checked()
+    assert _capi.checked() is first
+    monkeypatch.setattr(_capi, "_lib", None)
+    again = _capi.checked()
+    assert again is not first and again.vamp_abi_version() == _capi.ABI_VERSION
+
+
+def test_checked_calls_go_through_a_stand_in_library(lib):
+    """HotPath.lib can be replaced by an object that wraps the library (the sweeps' call recorders): the checked set
+    made from it calls through it, and still raises."""
+    seen = []
+
+    class Recorder:
+        def __getattr__(self, name):
+            fn = getattr(lib, name)
+            return lambda *a: (seen.append(name), fn(*a))[1]
+
+    vamp = _capi.checked(Recorder())
+    assert vamp.vamp_abi_version() == _capi.ABI_VERSION
+    with pytest.raises(_capi.VampireHipError, match="vamp_frustum_geometry failed with code -1"):
+        vamp.vamp_frustum_geometry(_capi.VampRenderDesc(), None, None, None, None, None, None)
+    assert seen == ["vamp_abi_version", "vamp_frustum_geometry"]
+    assert _capi.checked(lib) is _capi.checked()
+
+
+def test_descriptor_parameters_are_typed_pointers():
+    """Every `const VampXDesc*` (or VampDetTask*) parameter of the header is a POINTER(VampXDesc) in the table, so that
+    a bare structure instance is passed by reference -- a void* parameter would refuse it."""
+    text = open(os.path.join(ROOT, "include", "vampire_hip.h")).read()
+    text = re.sub(r"/\*.*?\*/", "", text, flags=re.S)
+    seen = 0
+    for name, params in re.findall(r"\b(vamp_[a-z_0-9]+)\s*\(([^)]*)\)\s*;", text):
+        for i, prm in enumerate(p.strip() for p in params.split(",")):
+            m = re.match(r"const\s+(Vamp\w+)\s*\*", prm)
+            if m:
+                seen += 1
+                want = C.POINTER(getattr(_capi, m.group(1)))
+                assert _capi.SIGNATURES[name][1][i] is want, f"{name}: parameter {i} should be POINTER({m.group(1)})"
+    assert seen >= 60
+    pd = _capi.VampPoolDesc(1, 4, 16, 0, 4, 1, _capi.VAMP_F32)         # an empty grid, passed without byref
+    assert _capi.checked().vamp_voxel_pooling_workspace_bytes(pd) == 0
+    assert _capi.load().vamp_voxel_pooling_workspace_bytes(C.byref(pd)) == 0

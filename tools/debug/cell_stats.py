@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """GPU box: how the camera backward's records distribute over cells and voxels (cfg-B sample of the bench; early termination on, or -- argument `noert` -- off)."""
-import os, sys, ctypes as C, torch
+import os, sys, torch
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__)))))
 from vampire_amd.config import PRESETS
 from vampire_amd.step import LiftRenderStep, SyntheticBatch
@@ -9,7 +9,7 @@ model = LiftRenderStep(cfg, dev); batch = SyntheticBatch(cfg, 1, dev); hp = mode
 with torch.no_grad():
     hp.render(*batch.vols, model.beta, render_mats=batch.render_mats)
 d = hp.render_desc(1, cfg.num_cams, 0)
-off = hp.lib.vamp_render_term_offset(C.byref(d)); n = cfg.num_cams * cfg.fH * cfg.fW
+off = hp.vamp.vamp_render_term_offset(d); n = cfg.num_cams * cfg.fH * cfg.fW
 term = hp._ws["render"][off:off + 4 * n].view(torch.int32).reshape(1, cfg.num_cams, 1, cfg.fH, cfg.fW).clone()
 inside, ix0, iy0, iz0 = hp.render_indices(render_mats=batch.render_mats)
 idx = torch.arange(cfg.D - 1, device=dev).reshape(1, 1, -1, 1, 1)

@@ -6,6 +6,12 @@ through oracle/ or any CPU implementation.
 """
 import ctypes as C
 import os
+import types
+import typing
+
+# torch must bring in ITS libamdhip64 first: a second HIP runtime (the system copy this
+# library would otherwise pull in) sees no device inside a torch process.
+import torch
 
 from .build import lib_path
 
@@ -108,108 +114,143 @@ VAMP_RENDERFWD_SAVE_SAMPLES, VAMP_RENDERFWD_BEV_SAVE, VAMP_RENDERFWD_RANK, VAMP_
 VAMP_CAMFWD_PACK_ONLY, VAMP_CAMFWD_PACKED_VALID, VAMP_CAMFWD_DIRECT, VAMP_CAMFWD_EXACT_TAPS = 8, 16, 32, 64
 VAMP_BEVBWD_ONLY_BASE, VAMP_BEVBWD_SKIP_BASE, VAMP_BEVBWD_TABLE_VALID = 8, 16, 32
 
-_P = C.c_void_p
+
+_Tensor, _void_p = torch.Tensor, C.c_void_p       # (module globals: from_param runs once per pointer argument of every call)
+
+
+class TensorPtr(C.c_void_p):
+    """`void*` parameter of the signature table: takes a torch tensor (its data_ptr()), None (NULL), an integer address
+    or anything c_void_p itself takes (a c_void_p, a ctypes array or pointer).  Contiguity, device and shape are the
+    caller's business (ops `_chk`): this type converts, it does not validate."""
+
+    @classmethod
+    def from_param(cls, obj):
+        if isinstance(obj, _Tensor):
+            # a c_void_p, never the bare integer: ctypes passes an int that from_param returns as a 32-bit C int
+            return _void_p(obj.data_ptr())
+        if obj is None:
+            return None
+        if isinstance(obj, int):
+            return _void_p(obj)
+        if isinstance(obj, (str, bytes)):         # (c_void_p would take the characters' address)
+            raise TypeError(f"expected a tensor or a pointer, got {type(obj).__name__}")
+        return _void_p.from_param(obj)
+
+
+class _Ret(typing.NamedTuple):
+    """What an entry point returns: its ctypes type, and whether that is a VampStatus code (VAMP_OK or negative), which
+    the checked set turns into an exception, or a value handed to the caller as it is."""
+    ctype: type
+    is_status: bool
+
+
+_STATUS = _Ret(C.c_int, True)
+_INT, _SIZE, _STR = _Ret(C.c_int, False), _Ret(C.c_size_t, False), _Ret(C.c_char_p, False)
+
+_P = TensorPtr
 _LD = C.POINTER(VampLiftDesc)
 _RD = C.POINTER(VampRenderDesc)
 _SD = C.POINTER(VampSampleDesc)
 _CD = C.POINTER(VampConvDesc)
+_PD = C.POINTER(VampPoolDesc)
 _QD = C.POINTER(VampConfDesc)
 _DD = C.POINTER(VampDetDesc)
 _TD = C.POINTER(VampDetTargetDesc)
 
-# name -> (restype, argtypes); must list every symbol declared in include/vampire_hip.h
+# name -> (return kind, argtypes); must list every symbol declared in include/vampire_hip.h
 SIGNATURES = {
-    "vamp_abi_version": (C.c_int, []),
-    "vamp_debug_checks": (C.c_int, [C.c_int]),
-    "vamp_last_error": (C.c_char_p, []),
-    "vamp_profile_enable": (C.c_int, [C.c_int]),
-    "vamp_profile_slots": (C.c_int, []),
-    "vamp_profile_select": (C.c_int, [C.c_int]),
-    "vamp_profile_read": (C.c_int, [C.c_int, C.POINTER(C.c_char_p), C.POINTER(C.c_int),
+    "vamp_abi_version": (_INT, []),
+    "vamp_debug_checks": (_STATUS, [C.c_int]),
+    "vamp_last_error": (_STR, []),
+    "vamp_profile_enable": (_STATUS, [C.c_int]),
+    "vamp_profile_slots": (_INT, []),
+    "vamp_profile_select": (_STATUS, [C.c_int]),
+    "vamp_profile_read": (_STATUS, [C.c_int, C.POINTER(C.c_char_p), C.POINTER(C.c_int),
                                     C.POINTER(C.c_double)]),
-    "vamp_lift_workspace_bytes": (C.c_size_t, [_LD]),
-    "vamp_lift_forward": (C.c_int, [_LD] + [_P] * 8 + [_P, C.c_size_t, _P]),
-    "vamp_lift_forward_logits": (C.c_int, [_LD] + [_P] * 5 + [C.c_int32] + [_P] * 4 + [_P, C.c_size_t, _P]),
-    "vamp_lift_forward_ex": (C.c_int, [_LD] + [_P] * 8 + [_P, C.c_size_t, C.c_int, _P]),
-    "vamp_lift_forward_logits_ex": (C.c_int, [_LD] + [_P] * 5 + [C.c_int32] + [_P] * 4 + [_P, C.c_size_t, C.c_int, _P]),
-    "vamp_lift_backward": (C.c_int, [_LD] + [_P] * 10 + [_P, C.c_size_t, _P]),
-    "vamp_lift_backward_ex": (C.c_int, [_LD] + [_P] * 10 + [_P, C.c_size_t, C.c_int, _P]),
-    "vamp_lift_prepare": (C.c_int, [_LD] + [_P] * 5 + [_P, C.c_size_t, _P]),
-    "vamp_lift_finish_cells": (C.c_int, [_LD, _P, C.c_size_t, _P]),
-    "vamp_render_camera_prepare_with_lift": (C.c_int, [_RD] + [_P] * 4 + [_P, C.c_size_t, C.c_int, _LD, _P, C.c_size_t, _P]),
-    "vamp_lift_forward_dense": (C.c_int, [_LD] + [_P] * 7 + [_P]),
-    "vamp_lift_backward_dense": (C.c_int, [_LD] + [_P] * 7 + [_P]),
-    "vamp_lift_indices": (C.c_int, [_LD] + [_P] * 8 + [_P]),
-    "vamp_lift_cull_words": (C.c_int, [_LD] + [_P] * 7 + [_P]),
-    "vamp_render_workspace_bytes": (C.c_size_t, [_RD]),
-    "vamp_render_camera_forward": (C.c_int, [_RD] + [_P] * 13 + [_P, C.c_size_t, _P]),
-    "vamp_render_samples_bytes": (C.c_size_t, [_RD]),
-    "vamp_render_term_offset": (C.c_size_t, [_RD]),
-    "vamp_render_camera_terminate": (C.c_int, [_RD] + [_P] * 6 + [_P, C.c_size_t, _P]),
-    "vamp_render_camera_prepare_ex": (C.c_int, [_RD] + [_P] * 4 + [_P, C.c_size_t, C.c_int, _P]),
-    "vamp_render_camera_forward_ex": (C.c_int, [_RD] + [_P] * 13 + [_P, C.c_size_t, C.c_int, _P]),
-    "vamp_render_camera_backward": (C.c_int, [_RD] + [_P] * 17 + [_P, C.c_size_t, _P]),
-    "vamp_render_camera_prepare": (C.c_int, [_RD] + [_P] * 4 + [_P, C.c_size_t, _P]),
-    "vamp_render_camera_backward_acc": (C.c_int, [_RD] + [_P] * 17 + [_P, C.c_size_t, C.c_int, _P, _P]),
-    "vamp_render_bev_forward": (C.c_int, [_RD] + [_P] * 14 + [_P]),
-    "vamp_render_bev_forward_ex": (C.c_int, [_RD] + [_P] * 14 + [C.POINTER(C.c_float), _P, C.c_size_t, C.c_int, _P]),
-    "vamp_render_forward_merged_supported": (C.c_int, [_RD, C.POINTER(C.c_float)]),
-    "vamp_render_forward_merged": (C.c_int, [_RD] + [_P] * 8 + [C.POINTER(C.c_float)] + [_P] * 14
+    "vamp_lift_workspace_bytes": (_SIZE, [_LD]),
+    "vamp_lift_forward": (_STATUS, [_LD] + [_P] * 8 + [_P, C.c_size_t, _P]),
+    "vamp_lift_forward_logits": (_STATUS, [_LD] + [_P] * 5 + [C.c_int32] + [_P] * 4 + [_P, C.c_size_t, _P]),
+    "vamp_lift_forward_ex": (_STATUS, [_LD] + [_P] * 8 + [_P, C.c_size_t, C.c_int, _P]),
+    "vamp_lift_forward_logits_ex": (_STATUS, [_LD] + [_P] * 5 + [C.c_int32] + [_P] * 4 + [_P, C.c_size_t, C.c_int, _P]),
+    "vamp_lift_backward": (_STATUS, [_LD] + [_P] * 10 + [_P, C.c_size_t, _P]),
+    "vamp_lift_backward_ex": (_STATUS, [_LD] + [_P] * 10 + [_P, C.c_size_t, C.c_int, _P]),
+    "vamp_lift_prepare": (_STATUS, [_LD] + [_P] * 5 + [_P, C.c_size_t, _P]),
+    "vamp_lift_finish_cells": (_STATUS, [_LD, _P, C.c_size_t, _P]),
+    "vamp_render_camera_prepare_with_lift": (_STATUS, [_RD] + [_P] * 4 + [_P, C.c_size_t, C.c_int, _LD, _P, C.c_size_t, _P]),
+    "vamp_lift_forward_dense": (_STATUS, [_LD] + [_P] * 7 + [_P]),
+    "vamp_lift_backward_dense": (_STATUS, [_LD] + [_P] * 7 + [_P]),
+    "vamp_lift_indices": (_STATUS, [_LD] + [_P] * 8 + [_P]),
+    "vamp_lift_cull_words": (_STATUS, [_LD] + [_P] * 7 + [_P]),
+    "vamp_render_workspace_bytes": (_SIZE, [_RD]),
+    "vamp_render_camera_forward": (_STATUS, [_RD] + [_P] * 13 + [_P, C.c_size_t, _P]),
+    "vamp_render_samples_bytes": (_SIZE, [_RD]),
+    "vamp_render_term_offset": (_SIZE, [_RD]),
+    "vamp_render_camera_terminate": (_STATUS, [_RD] + [_P] * 6 + [_P, C.c_size_t, _P]),
+    "vamp_render_camera_prepare_ex": (_STATUS, [_RD] + [_P] * 4 + [_P, C.c_size_t, C.c_int, _P]),
+    "vamp_render_camera_forward_ex": (_STATUS, [_RD] + [_P] * 13 + [_P, C.c_size_t, C.c_int, _P]),
+    "vamp_render_camera_backward": (_STATUS, [_RD] + [_P] * 17 + [_P, C.c_size_t, _P]),
+    "vamp_render_camera_prepare": (_STATUS, [_RD] + [_P] * 4 + [_P, C.c_size_t, _P]),
+    "vamp_render_camera_backward_acc": (_STATUS, [_RD] + [_P] * 17 + [_P, C.c_size_t, C.c_int, _P, _P]),
+    "vamp_render_bev_forward": (_STATUS, [_RD] + [_P] * 14 + [_P]),
+    "vamp_render_bev_forward_ex": (_STATUS, [_RD] + [_P] * 14 + [C.POINTER(C.c_float), _P, C.c_size_t, C.c_int, _P]),
+    "vamp_render_forward_merged_supported": (_INT, [_RD, C.POINTER(C.c_float)]),
+    "vamp_render_forward_merged": (_STATUS, [_RD] + [_P] * 8 + [C.POINTER(C.c_float)] + [_P] * 14
                                    + [_P, C.c_size_t, _P, C.c_size_t, _P, C.c_int, _P]),
-    "vamp_render_bev_workspace_bytes": (C.c_size_t, [_RD]),
-    "vamp_render_bev_backward": (C.c_int, [_RD] + [_P] * 19 + [C.POINTER(C.c_float), _P, C.c_size_t, _P]),
-    "vamp_render_bev_backward_ex": (C.c_int, [_RD] + [_P] * 19 + [C.POINTER(C.c_float), _P, C.c_size_t, C.c_int, _P]),
-    "vamp_render_indices": (C.c_int, [_RD] + [_P] * 9 + [_P]),
-    "vamp_render_camera_direct_taps": (C.c_int, [_RD] + [_P] * 9 + [_P]),
-    "vamp_frustum_geometry": (C.c_int, [_RD] + [_P] * 5 + [_P]),
-    "vamp_sample_points_forward": (C.c_int, [_SD, _P, _P, _P, C.c_int64, _P, _P]),
-    "vamp_sample_points_workspace_bytes": (C.c_size_t, [_SD, C.c_int64]),
-    "vamp_sample_points_backward": (C.c_int, [_SD, _P, _P, _P, C.c_int64, _P, _P, _P, _P, C.c_size_t, _P]),
-    "vamp_depth_softmax_forward": (C.c_int, [C.c_int64, C.c_int32, C.c_int64, _P, C.c_int32, _P, _P]),
-    "vamp_depth_softmax_backward": (C.c_int, [C.c_int64, C.c_int32, C.c_int64, _P, _P, _P, _P]),
-    "vamp_density_gate_forward": (C.c_int, [C.c_int64, C.c_int32, C.c_int64, C.c_int32, _P, _P, _P, _P]),
-    "vamp_upsample_trilinear_forward": (C.c_int, [C.c_int64] + [C.c_int32] * 6 + [_P, _P, _P]),
-    "vamp_upsample_trilinear_forward_ex": (C.c_int, [C.c_int64] + [C.c_int32] * 7 + [_P, _P, _P]),
-    "vamp_upsample_trilinear_backward_ex": (C.c_int, [C.c_int64] + [C.c_int32] * 7 + [_P, _P, _P, C.c_size_t, _P]),
-    "vamp_upsample_trilinear_workspace_bytes": (C.c_size_t, [C.c_int32] * 3),
-    "vamp_upsample_trilinear_supported": (C.c_int, [C.c_int32] * 6),
-    "vamp_upsample_trilinear_backward": (C.c_int, [C.c_int64] + [C.c_int32] * 6 + [_P, _P, _P, C.c_size_t, _P]),
-    "vamp_conv3d_supported": (C.c_int, [_CD]),
-    "vamp_conv3d_forward": (C.c_int, [_CD, _P, _P, _P, _P]),
-    "vamp_conv3d_backward_data": (C.c_int, [_CD, _P, _P, _P, _P]),
-    "vamp_conv3d_workspace_bytes": (C.c_size_t, [_CD]),
-    "vamp_conv3d_backward_weight": (C.c_int, [_CD, _P, _P, _P, _P, C.c_size_t, _P]),
-    "vamp_conv3d_bf16_supported": (C.c_int, [_CD]),
-    "vamp_conv3d_bf16_forward": (C.c_int, [_CD, _P, _P, _P, _P]),
-    "vamp_conv3d_bf16_backward_data": (C.c_int, [_CD, _P, _P, _P, _P]),
-    "vamp_conv3d_bf16_workspace_bytes": (C.c_size_t, [_CD]),
-    "vamp_conv3d_bf16_backward_weight": (C.c_int, [_CD, _P, _P, _P, _P, C.c_size_t, _P]),
-    "vamp_conv3d_half_forward": (C.c_int, [_CD, C.c_int32, _P, _P, _P, _P]),
-    "vamp_conv3d_half_backward_data": (C.c_int, [_CD, C.c_int32, _P, _P, _P, _P]),
-    "vamp_conv3d_half_backward_weight": (C.c_int, [_CD, C.c_int32, _P, _P, _P, _P, C.c_size_t, _P]),
-    "vamp_density_gate_backward": (C.c_int, [C.c_int64, C.c_int32, C.c_int64, C.c_int32, _P, _P, _P, _P, _P,
+    "vamp_render_bev_workspace_bytes": (_SIZE, [_RD]),
+    "vamp_render_bev_backward": (_STATUS, [_RD] + [_P] * 19 + [C.POINTER(C.c_float), _P, C.c_size_t, _P]),
+    "vamp_render_bev_backward_ex": (_STATUS, [_RD] + [_P] * 19 + [C.POINTER(C.c_float), _P, C.c_size_t, C.c_int, _P]),
+    "vamp_render_indices": (_STATUS, [_RD] + [_P] * 9 + [_P]),
+    "vamp_render_camera_direct_taps": (_STATUS, [_RD] + [_P] * 9 + [_P]),
+    "vamp_frustum_geometry": (_STATUS, [_RD] + [_P] * 5 + [_P]),
+    "vamp_sample_points_forward": (_STATUS, [_SD, _P, _P, _P, C.c_int64, _P, _P]),
+    "vamp_sample_points_workspace_bytes": (_SIZE, [_SD, C.c_int64]),
+    "vamp_sample_points_backward": (_STATUS, [_SD, _P, _P, _P, C.c_int64, _P, _P, _P, _P, C.c_size_t, _P]),
+    "vamp_depth_softmax_forward": (_STATUS, [C.c_int64, C.c_int32, C.c_int64, _P, C.c_int32, _P, _P]),
+    "vamp_depth_softmax_backward": (_STATUS, [C.c_int64, C.c_int32, C.c_int64, _P, _P, _P, _P]),
+    "vamp_density_gate_forward": (_STATUS, [C.c_int64, C.c_int32, C.c_int64, C.c_int32, _P, _P, _P, _P]),
+    "vamp_upsample_trilinear_forward": (_STATUS, [C.c_int64] + [C.c_int32] * 6 + [_P, _P, _P]),
+    "vamp_upsample_trilinear_forward_ex": (_STATUS, [C.c_int64] + [C.c_int32] * 7 + [_P, _P, _P]),
+    "vamp_upsample_trilinear_backward_ex": (_STATUS, [C.c_int64] + [C.c_int32] * 7 + [_P, _P, _P, C.c_size_t, _P]),
+    "vamp_upsample_trilinear_workspace_bytes": (_SIZE, [C.c_int32] * 3),
+    "vamp_upsample_trilinear_supported": (_INT, [C.c_int32] * 6),
+    "vamp_upsample_trilinear_backward": (_STATUS, [C.c_int64] + [C.c_int32] * 6 + [_P, _P, _P, C.c_size_t, _P]),
+    "vamp_conv3d_supported": (_INT, [_CD]),
+    "vamp_conv3d_forward": (_STATUS, [_CD, _P, _P, _P, _P]),
+    "vamp_conv3d_backward_data": (_STATUS, [_CD, _P, _P, _P, _P]),
+    "vamp_conv3d_workspace_bytes": (_SIZE, [_CD]),
+    "vamp_conv3d_backward_weight": (_STATUS, [_CD, _P, _P, _P, _P, C.c_size_t, _P]),
+    "vamp_conv3d_bf16_supported": (_INT, [_CD]),
+    "vamp_conv3d_bf16_forward": (_STATUS, [_CD, _P, _P, _P, _P]),
+    "vamp_conv3d_bf16_backward_data": (_STATUS, [_CD, _P, _P, _P, _P]),
+    "vamp_conv3d_bf16_workspace_bytes": (_SIZE, [_CD]),
+    "vamp_conv3d_bf16_backward_weight": (_STATUS, [_CD, _P, _P, _P, _P, C.c_size_t, _P]),
+    "vamp_conv3d_half_forward": (_STATUS, [_CD, C.c_int32, _P, _P, _P, _P]),
+    "vamp_conv3d_half_backward_data": (_STATUS, [_CD, C.c_int32, _P, _P, _P, _P]),
+    "vamp_conv3d_half_backward_weight": (_STATUS, [_CD, C.c_int32, _P, _P, _P, _P, C.c_size_t, _P]),
+    "vamp_density_gate_backward": (_STATUS, [C.c_int64, C.c_int32, C.c_int64, C.c_int32, _P, _P, _P, _P, _P,
                                              _P]),
-    "vamp_voxel_pooling_workspace_bytes": (C.c_size_t, [_P]),
-    "vamp_voxel_pooling_forward": (C.c_int, [_P] * 4 + [_P, C.c_size_t, _P]),
-    "vamp_voxel_pooling_backward": (C.c_int, [_P] * 5),
-    "vamp_gate_conv1x1_supported": (C.c_int, [C.c_int32] * 3),
-    "vamp_gate_conv1x1_workspace_bytes": (C.c_size_t, [C.c_int32] * 3),
-    "vamp_gate_conv1x1_forward": (C.c_int, [C.c_int64, C.c_int32, C.c_int32, C.c_int64, C.c_int32, C.c_int32]
+    "vamp_voxel_pooling_workspace_bytes": (_SIZE, [_PD]),
+    "vamp_voxel_pooling_forward": (_STATUS, [_PD] + [_P] * 3 + [_P, C.c_size_t, _P]),
+    "vamp_voxel_pooling_backward": (_STATUS, [_PD] + [_P] * 4),
+    "vamp_gate_conv1x1_supported": (_INT, [C.c_int32] * 3),
+    "vamp_gate_conv1x1_workspace_bytes": (_SIZE, [C.c_int32] * 3),
+    "vamp_gate_conv1x1_forward": (_STATUS, [C.c_int64, C.c_int32, C.c_int32, C.c_int64, C.c_int32, C.c_int32]
                                   + [_P] * 6),
-    "vamp_gate_conv1x1_backward": (C.c_int, [C.c_int64, C.c_int32, C.c_int32, C.c_int64, C.c_int32, C.c_int32]
+    "vamp_gate_conv1x1_backward": (_STATUS, [C.c_int64, C.c_int32, C.c_int32, C.c_int64, C.c_int32, C.c_int32]
                                    + [_P] * 9 + [C.c_size_t, _P]),
-    "vamp_confusion_workspace_bytes": (C.c_size_t, [_QD]),
-    "vamp_confusion_update": (C.c_int, [_QD] + [_P] * 5 + [_P, C.c_size_t, _P]),
-    "vamp_lidarseg_workspace_bytes": (C.c_size_t, [C.c_int64, C.c_int64]),
-    "vamp_lidarseg_predict": (C.c_int, [C.c_int64, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _P, _P, C.c_int64,
+    "vamp_confusion_workspace_bytes": (_SIZE, [_QD]),
+    "vamp_confusion_update": (_STATUS, [_QD] + [_P] * 5 + [_P, C.c_size_t, _P]),
+    "vamp_lidarseg_workspace_bytes": (_SIZE, [C.c_int64, C.c_int64]),
+    "vamp_lidarseg_predict": (_STATUS, [C.c_int64, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _P, _P, C.c_int64,
                                         _P, _P, _P, C.c_size_t, _P]),
-    "vamp_det_workspace_bytes": (C.c_size_t, [_DD]),
-    "vamp_det_postprocess": (C.c_int, [_DD, C.POINTER(VampDetTask)] + [_P] * 5 + [C.c_size_t, _P]),
-    "vamp_det_targets_workspace_bytes": (C.c_size_t, [_TD]),
-    "vamp_det_targets": (C.c_int, [_TD] + [_P] * 7 + [C.c_size_t, _P]),
+    "vamp_det_workspace_bytes": (_SIZE, [_DD]),
+    "vamp_det_postprocess": (_STATUS, [_DD, C.POINTER(VampDetTask)] + [_P] * 5 + [C.c_size_t, _P]),
+    "vamp_det_targets_workspace_bytes": (_SIZE, [_TD]),
+    "vamp_det_targets": (_STATUS, [_TD] + [_P] * 7 + [C.c_size_t, _P]),
 }
 
 _lib = None
+_checked = None     # (the library it was made from, the checked set)
 
 
 class VampireHipError(RuntimeError):
@@ -217,22 +258,20 @@ class VampireHipError(RuntimeError):
 
 
 def load():
-    """Load the library and bind every symbol; raises if anything is missing."""
+    """Load the library and bind every symbol; raises if anything is missing.  The functions of the returned library
+    hand status codes back as integers (what the C-ABI tests assert on); `checked()` is the set that raises."""
     global _lib
     if _lib is not None:
         return _lib
-    # torch must bring in ITS libamdhip64 first: a second HIP runtime (the system copy this
-    # library would otherwise pull in) sees no device inside a torch process.
-    import torch  # noqa: F401
     path = os.environ.get("VAMPIRE_HIP_LIB", lib_path())
     if not os.path.exists(path):
         raise VampireHipError(
             f"{path} not found: build it with `python -m vampire_amd.build` "
             "(hipcc --offload-arch=gfx950). There is no CPU fallback.")
     lib = C.CDLL(path)
-    for name, (res, args) in SIGNATURES.items():
+    for name, (ret, args) in SIGNATURES.items():
         fn = getattr(lib, name)           # AttributeError if the symbol is missing
-        fn.restype = res
+        fn.restype = ret.ctype
         fn.argtypes = args
     got = lib.vamp_abi_version()
     if got != ABI_VERSION:
@@ -241,38 +280,65 @@ def load():
     return lib
 
 
-def check(code: int, what: str):
-    if code != 0:
-        msg = load().vamp_last_error().decode("utf-8", "replace")
-        raise VampireHipError(f"{what} failed with code {code}: {msg}")
+def _raise_on_status(last_error, name):
+    def errcheck(code, func=None, args=None):
+        if code != 0:
+            raise VampireHipError(f"{name} failed with code {code}: {last_error().decode('utf-8', 'replace')}")
+        return code
+    return errcheck
+
+
+def checked(through=None):
+    """The entry points of `load()` once more, as attributes of one object, with every status return checked: a call
+    that fails raises VampireHipError with the library's message; the value returns (`*_bytes`, `*_supported`, ...)
+    come back as they are.  `through`: a stand-in for the library whose attributes the calls are to go through (the
+    tests' call recorders); None or the library itself gives the set bound to the library's own symbols."""
+    global _checked
+    lib = load()
+    if through is not None and through is not lib:
+        def via(name):
+            fn, check = getattr(through, name), _raise_on_status(lib.vamp_last_error, name)
+            return lambda *a: check(fn(*a))
+        return types.SimpleNamespace(**{name: via(name) if ret.is_status else getattr(through, name)
+                                        for name, (ret, _) in SIGNATURES.items()})
+    if _checked is None or _checked[0] is not lib:
+        fns = {}
+        for name, (ret, args) in SIGNATURES.items():
+            fn = lib[name]                # (a function object of its own: lib.name is the unchecked one)
+            fn.restype, fn.argtypes = ret.ctype, args
+            if ret.is_status:
+                fn.errcheck = _raise_on_status(lib.vamp_last_error, name)
+            fns[name] = fn
+        _checked = (lib, types.SimpleNamespace(**fns))
+    return _checked[1]
 
 
 def profile_enable(on: bool):
-    check(load().vamp_profile_enable(1 if on else 0), "vamp_profile_enable")
+    checked().vamp_profile_enable(1 if on else 0)
 
 
 def profile_select(name=None):
     """Restrict the event timer to one kernel slot (by name); None = all slots."""
-    lib = load()
+    vamp = checked()
     slot = -1
     if name is not None:
-        for i in range(lib.vamp_profile_slots()):
+        for i in range(vamp.vamp_profile_slots()):
             nm, n, ms = C.c_char_p(), C.c_int(), C.c_double()
-            check(lib.vamp_profile_read(i, C.byref(nm), C.byref(n), C.byref(ms)), "vamp_profile_read")
+            vamp.vamp_profile_read(i, nm, n, ms)
             if nm.value.decode() == name:
                 slot = i
         if slot < 0:
             raise KeyError(name)
-    check(lib.vamp_profile_select(slot), "vamp_profile_select")
+    vamp.vamp_profile_select(slot)
 
 
 def profile_read():
     """{kernel name: (launches, total_ms)} since the last profile_enable(True)."""
-    lib = load()
+    vamp = checked()
     out = {}
-    for slot in range(lib.vamp_profile_slots()):
+    for slot in range(vamp.vamp_profile_slots()):
         name, n, ms = C.c_char_p(), C.c_int(), C.c_double()
-        check(lib.vamp_profile_read(slot, C.byref(name), C.byref(n), C.byref(ms)), "vamp_profile_read")
+        vamp.vamp_profile_read(slot, name, n, ms)
         if n.value:
             out[name.value.decode()] = (n.value, ms.value)
     return out

@@ -1,0 +1,64 @@
+"""Tensor-side helpers every operator module shares (ops, layers, evaluation): what a kernel accepts, how a tensor is
+checked before its address goes to the library, dtype and density codes, the current stream, scratch workspaces."""
+import ctypes as C
+
+import torch
+
+from . import _capi
+
+# torch dtype -> VAMP_* code, for every dtype some entry point reads; each operator names the ones IT accepts
+DTYPE_CODES = {torch.float32: _capi.VAMP_F32, torch.bfloat16: _capi.VAMP_BF16, torch.float16: _capi.VAMP_F16,
+               torch.int64: _capi.VAMP_I64, torch.int32: _capi.VAMP_I32, torch.uint8: _capi.VAMP_U8}
+HOT_PATH_DTYPES = (torch.float32, torch.bfloat16)
+HALF_DTYPES = (torch.bfloat16, torch.float16)
+FLOAT_DTYPES = (torch.float32, torch.bfloat16, torch.float16)
+
+
+def _stream(stream=None):
+    return C.c_void_p((stream or torch.cuda.current_stream()).cuda_stream)
+
+
+def _dtype_code(t: torch.Tensor) -> int:
+    if t.dtype not in HOT_PATH_DTYPES:
+        raise TypeError(f"unsupported dtype {t.dtype}: the hot path takes fp32 or bf16 inputs")
+    return DTYPE_CODES[t.dtype]
+
+
+def _density_code(cfg) -> int:
+    return _capi.VAMP_DENSITY_SDF_LAPLACE if cfg.density_mode == "sdf" else _capi.VAMP_DENSITY_SIGMOID
+
+
+def _accept(t):
+    """The kernels read fp32 or bf16; anything else (fp16 under the reference's precision=16
+    autocast, base_cli.py:77, fp64) is promoted to fp32, as aten's autocast does for these ops."""
+    if t is None or t.dtype in HOT_PATH_DTYPES:
+        return t
+    return t.float()
+
+
+def _is_channel_last(feat: torch.Tensor) -> bool:
+    """feat [B, N, C, fH, fW] whose memory is [B, N, fH, fW, C] (a torch.channels_last producer's output, reshaped):
+    what the lift wants -- it samples a pixel's C features as one run -- and takes zero-copy."""
+    return (feat.dim() == 5 and feat.dtype == torch.float32 and feat.shape[2] > 1
+            and feat.permute(0, 1, 3, 4, 2).is_contiguous() and feat.data_ptr() % 16 == 0)
+
+
+def _chk(t: torch.Tensor, shape, name):
+    if not t.is_cuda:
+        raise _capi.VampireHipError(f"{name} must be a device tensor (no CPU fallback)")
+    if tuple(t.shape) != tuple(shape):
+        raise ValueError(f"{name}: expected shape {tuple(shape)}, got {tuple(t.shape)}")
+    return t.contiguous()
+
+
+_scratch = {}
+
+
+def _workspace(key, device, nbytes):
+    """The uint8 scratch buffer kept under `key`: reused while it is large enough, otherwise allocated anew with
+    max(nbytes, 256) bytes (uninitialised).  The key is the caller's: whatever it holds besides the device -- the
+    stream, the operator, the size -- decides who shares a buffer and whether one is ever regrown."""
+    ws = _scratch.get(key)
+    if ws is None or ws.numel() < nbytes:
+        ws = _scratch[key] = torch.empty(max(nbytes, 256), dtype=torch.uint8, device=device)
+    return ws

@@ -49,10 +49,10 @@ def _resize(x, size):
     device tensors (its backward is a gather; aten's atomic scatter is 8.8 ms of the module's
     backward at cfg-B), torch for CPU tensors like the other dense layers."""
     if x.is_cuda and x.dim() == 5:
-        from .ops import upsample_trilinear
+        from .layers import upsample_trilinear
         from . import _capi
         # scale factors beyond the backward's gather table (about 6x per axis) go to aten
-        if _capi.load().vamp_upsample_trilinear_supported(*x.shape[2:], *[int(v) for v in size]):
+        if _capi.checked().vamp_upsample_trilinear_supported(*x.shape[2:], *[int(v) for v in size]):
             return upsample_trilinear(x, size)
     return F.interpolate(x, tuple(size), mode="trilinear", align_corners=True)
 
@@ -92,7 +92,7 @@ class _Conv3(nn.Conv3d):
 
     def forward(self, x):
         if SWITCHES.conv3d and x.dim() == 5 and x.is_cuda:
-            from .ops import conv3d_3x3x3, conv3d_supported, conv3d_bf16, conv3d_bf16_supported
+            from .layers import conv3d_3x3x3, conv3d_supported, conv3d_bf16, conv3d_bf16_supported
             dt16 = _autocast_16(x)
             if dt16 is not None:
                 # the reference's mixed-precision training: 16-bit operands, as autocast would hand them to MIOpen
@@ -397,7 +397,7 @@ class BaseVAMPIRE2(nn.Module):
         launches become one each; biases and the rgb sigmoid follow.  Parameters are untouched."""
         nout = 1 + self.num_classes + 3
         if SWITCHES.conv3d and nout <= 32 and base.dim() == 5 and base.is_cuda:
-            from .ops import conv3d_3x3x3, conv3d_supported, conv3d_bf16, conv3d_bf16_supported
+            from .layers import conv3d_3x3x3, conv3d_supported, conv3d_bf16, conv3d_bf16_supported
             wd, ws, wr = self.density_conv.weight, self.seg_conv.weight, self.rgb_conv[0].weight
             w = torch.cat([wd, ws, wr, wd.new_zeros((32 - nout,) + tuple(wd.shape[1:]))], 0)
             y = None

@@ -1,0 +1,348 @@
+"""Evaluation and detection-head operators on plain tensors (Python over the C ABI): the segmentation metrics'
+confusion-matrix pass and lidar-segmentation prediction, CenterPoint post-processing (decode + NMS) and training
+targets.  All work happens in hand-written HIP kernels reached through `_capi`; there is no CPU fallback."""
+import dataclasses
+import math
+
+import torch
+
+from . import _capi
+from ._tensors import DTYPE_CODES, FLOAT_DTYPES, _accept, _dtype_code, _stream, _workspace
+
+
+# ===========================================================================
+# segmentation metrics (base_exp.py:370-382, :634-663, :835-840)
+# ===========================================================================
+_TARGET_DTYPES = (torch.int64, torch.int32, torch.uint8)
+
+
+def _scratch(kind, device, nbytes):
+    """This operator's workspace on the device's current stream (regrown when a call needs more)."""
+    return _workspace((kind, device, torch.cuda.current_stream(device).cuda_stream), device, nbytes)
+
+
+def _logit_layout(x):
+    """(layout, B, S, x) for logits [..., K]: rows when contiguous, planes when the memory is channel-first
+    ([B, K, ...] behind a permute(0, 2, .., 1) view, the backbone's occ_logits), else a contiguous copy."""
+    if x.is_contiguous():
+        return _capi.VAMP_SEG_ROWS, 1, x.numel() // max(x.shape[-1], 1), x
+    if x.dim() == 2 and x.t().is_contiguous():
+        return _capi.VAMP_SEG_PLANES, 1, x.shape[0], x
+    if x.dim() >= 3 and x.movedim(-1, 1).is_contiguous():
+        return _capi.VAMP_SEG_PLANES, x.shape[0], math.prod(x.shape[1:-1]), x
+    x = x.contiguous()
+    return _capi.VAMP_SEG_ROWS, 1, x.numel() // max(x.shape[-1], 1), x
+
+
+def confusion_update(confmat, invalid, logits_or_preds, target, mask=None, *, class_window=None, ignore_index=None):
+    """confmat[t, p] += 1 for every element with mask true and target t != ignore_index, where p =
+    lo + argmax(logits[..., lo:hi]) (torch.argmax ties and NaNs) or the integer prediction itself; targets
+    (and integer predictions) outside [0, Kc) add 1 to `invalid` instead.  confmat: int64 [Kc, Kc], invalid:
+    int64 with one element, both device tensors, accumulated.  logits [..., K] fp32 | bf16 (fp16 promoted),
+    target / mask shaped like logits[..., 0] (or like the integer predictions); target int64 | int32 | uint8.
+    One HIP pass on the current stream; no host synchronisation, capturable in a graph."""
+    x = logits_or_preds
+    if not (confmat.is_cuda and invalid.is_cuda and x.is_cuda and target.is_cuda and (mask is None or mask.is_cuda)):
+        raise _capi.VampireHipError("confusion_update needs device tensors (no CPU fallback)")
+    if confmat.dtype != torch.int64 or confmat.dim() != 2 or confmat.shape[0] != confmat.shape[1] \
+            or not confmat.is_contiguous():
+        raise ValueError("confmat must be a contiguous int64 [Kc, Kc] tensor")
+    if invalid.dtype != torch.int64 or invalid.numel() != 1:
+        raise ValueError("invalid must be a one-element int64 tensor")
+    Kc = confmat.shape[0]
+    integer = not x.is_floating_point()
+    if integer:
+        if tuple(x.shape) != tuple(target.shape):
+            raise ValueError(f"predictions {tuple(x.shape)} and target {tuple(target.shape)} differ in shape")
+        if x.dtype not in (torch.int64, torch.int32):
+            x = x.long()
+        layout, B, S, x, K = _capi.VAMP_SEG_ROWS, 1, x.numel(), x.contiguous(), 1
+        lo, hi = 0, 1
+    else:
+        x = _accept(x)
+        if tuple(x.shape[:-1]) != tuple(target.shape):
+            raise ValueError(f"logits {tuple(x.shape)} do not match target {tuple(target.shape)}")
+        K = x.shape[-1]
+        lo, hi = (0, K) if class_window is None else (int(class_window[0]), int(class_window[1]))
+        layout, B, S, x = _logit_layout(x)
+    if target.dtype not in _TARGET_DTYPES:
+        target = target.long()
+    target = target.contiguous()
+    if mask is not None:
+        if tuple(mask.shape) != tuple(target.shape):
+            raise ValueError(f"mask {tuple(mask.shape)} does not match target {tuple(target.shape)}")
+        mask = (mask if mask.dtype == torch.bool else mask != 0).contiguous()
+    d = _capi.VampConfDesc(B, S, K, layout, DTYPE_CODES[x.dtype], DTYPE_CODES[target.dtype], Kc, lo, hi,
+                           0 if ignore_index is None else int(ignore_index), 0 if ignore_index is None else 1, 0)
+    vamp = _capi.checked()
+    nbytes = vamp.vamp_confusion_workspace_bytes(d)
+    if nbytes == 0:
+        vamp.vamp_confusion_update(d, None, None, None, None, None, None, 0, None)
+    with torch.cuda.device(x.device):
+        ws = _scratch("confusion", x.device, nbytes)
+        vamp.vamp_confusion_update(d, x, target, mask, confmat, invalid, ws, ws.numel(), _stream())
+    return confmat
+
+
+def lidarseg_predict(pts_logits, ref_index, num_ref, class_window):
+    """The reference's lidar-segmentation prediction (base_exp.py:645-649, :835-838): zeros [num_ref, K],
+    index_add_(0, ref_index, pts_logits), then lo + argmax over classes [lo, hi).  Sums run in increasing
+    point order (bit-exact against a sequential CPU index_add_).  Returns (labels int64 [num_ref], invalid
+    int64 0-dim: the number of points whose index lies outside [0, num_ref)).  HIP kernels on the current
+    stream; no host synchronisation."""
+    if not (pts_logits.is_cuda and ref_index.is_cuda):
+        raise _capi.VampireHipError("lidarseg_predict needs device tensors (no CPU fallback)")
+    if pts_logits.dim() != 2 or ref_index.dim() != 1 or ref_index.shape[0] != pts_logits.shape[0]:
+        raise ValueError(f"expected pts_logits [P, K] and ref_index [P], got {tuple(pts_logits.shape)} "
+                         f"and {tuple(ref_index.shape)}")
+    x = _accept(pts_logits).contiguous()
+    idx = ref_index.long().contiguous()
+    P, K = x.shape
+    lo, hi = int(class_window[0]), int(class_window[1])
+    num_ref = int(num_ref)
+    labels = torch.empty(num_ref, dtype=torch.int64, device=x.device)
+    invalid = torch.empty((), dtype=torch.int64, device=x.device)
+    vamp = _capi.checked()
+    with torch.cuda.device(x.device):
+        ws = _scratch("lidarseg", x.device, vamp.vamp_lidarseg_workspace_bytes(P, num_ref))
+        vamp.vamp_lidarseg_predict(P, K, _dtype_code(x), lo, hi, x, idx, num_ref, labels, invalid, ws, ws.numel(),
+                                  _stream())
+    return labels, invalid
+
+
+# ===========================================================================
+# detection post-processing (bev_depth_head.py:381-494)
+# ===========================================================================
+_NMS_KINDS = {"circle": _capi.VAMP_NMS_CIRCLE, "size_aware_circle": _capi.VAMP_NMS_SIZE_AWARE,
+              "rotate": _capi.VAMP_NMS_ROTATE}
+
+
+@dataclasses.dataclass
+class DetResult:
+    """Fixed-capacity detections of a batch: boxes [B, T * P, 9 | 7] fp32, scores [B, T * P] (heatmap dtype),
+    labels [B, T * P] int32, counts [B] int32; rows at or beyond counts[b] are zero."""
+    boxes: torch.Tensor
+    scores: torch.Tensor
+    labels: torch.Tensor
+    counts: torch.Tensor
+
+    def to_list(self):
+        """get_bboxes's return value, [[bboxes, scores, labels], ...] per sample (one host synchronisation)."""
+        n = self.counts.tolist()
+        return [[self.boxes[b, :k], self.scores[b, :k], self.labels[b, :k]] for b, k in enumerate(n)]
+
+
+def _cfg(c, name, default=None):
+    if isinstance(c, dict):
+        return c.get(name, default)
+    return getattr(c, name, default)
+
+
+def _per_task(v, T, name):
+    if v is None:
+        return [0.0] * T
+    if isinstance(v, (int, float)):
+        return [float(v)] * T
+    if len(v) < T:
+        raise ValueError(f"test_cfg['{name}'] has {len(v)} entries for {T} tasks")
+    return [float(x) for x in v[:T]]
+
+
+def det_postprocess(task_preds, coder_cfg, test_cfg, num_classes, norm_bbox, out=None):
+    """BEVDepthHead.get_bboxes on the device (vamp_det_postprocess): sigmoid, the deterministic top-K (score
+    descending, flat index ascending), CenterPointBBoxCoder.decode, the score and centre filters and test_cfg's
+    nms_type -- 'circle', 'size_aware_circle' or 'rotate' (rotated BEV IoU > nms_thr, after pre_max_size) --
+    for every task and sample in four launches, without a host synchronisation (capturable in a graph).
+    task_preds: the head's preds_dicts ([[{'heatmap', 'reg', 'height', 'dim', 'rot'[, 'vel']}], ...]);
+    coder_cfg: the bbox_coder config (dict or CenterPointBBoxCoder); num_classes: classes per task.
+    out: a DetResult of preallocated buffers to write (graph capture).  Returns a DetResult."""
+    heads = [pd[0] for pd in task_preds]
+    T = len(heads)
+    if not 1 <= T <= 8 or len(num_classes) < T:
+        raise ValueError(f"{T} tasks with {len(num_classes)} class counts (1 to 8 tasks)")
+    keys = ["heatmap", "reg", "height", "dim", "rot"]
+    has_vel = "vel" in heads[0]
+    if has_vel:
+        keys.append("vel")
+    tensors = [[h[k] for k in keys] for h in heads]
+    if not all(x.is_cuda for ts in tensors for x in ts):
+        raise _capi.VampireHipError("det_postprocess needs device tensors (no CPU fallback)")
+    dtype = heads[0]["heatmap"].dtype
+    if dtype not in FLOAT_DTYPES or any(x.dtype != dtype for ts in tensors for x in ts):
+        raise TypeError(f"head tensors must all be fp32, bf16 or fp16 of one dtype, got {dtype}")
+    B, _, H, W = heads[0]["heatmap"].shape
+    chans = {"reg": 2, "height": 1, "dim": 3, "rot": 2, "vel": 2}
+    for t, h in enumerate(heads):
+        if h["heatmap"].dim() != 4 or h["heatmap"].shape[0] != B or tuple(h["heatmap"].shape[2:]) != (H, W):
+            raise ValueError(f"task {t}: heatmap {tuple(h['heatmap'].shape)} does not match [{B}, *, {H}, {W}]")
+        if h["heatmap"].shape[1] != num_classes[t]:
+            raise ValueError(f"task {t}: heatmap has {h['heatmap'].shape[1]} classes, num_classes says {num_classes[t]}")
+        for k, c in chans.items():
+            if k in keys and tuple(h[k].shape) != (B, c, H, W):
+                raise ValueError(f"task {t}: {k} {tuple(h[k].shape)} is not [{B}, {c}, {H}, {W}]")
+    tensors = [[x.contiguous() for x in ts] for ts in tensors]
+    kind = test_cfg["nms_type"]
+    if kind not in _NMS_KINDS:
+        raise ValueError(f"nms_type {kind!r} is not one of {sorted(_NMS_KINDS)}")
+    thr = _cfg(coder_cfg, "score_threshold")
+    rng = _cfg(coder_cfg, "post_center_range")
+    d = _capi.VampDetDesc()
+    d.B, d.T, d.H, d.W = B, T, H, W
+    for t in range(T):
+        d.ncls[t] = num_classes[t]
+    d.max_num = int(_cfg(coder_cfg, "max_num", 100))
+    d.pre_max_size = int(test_cfg.get("pre_max_size", d.max_num))
+    d.post_max_size = int(test_cfg["post_max_size"])
+    d.nms_kind = _NMS_KINDS[kind]
+    d.in_dtype = DTYPE_CODES[dtype]
+    d.has_vel, d.norm_bbox = int(has_vel), int(bool(norm_bbox))
+    d.use_score_threshold, d.use_center_range = int(thr is not None), int(rng is not None)
+    # torch compares a tensor with a Python scalar in the tensor's dtype
+    d.score_threshold = float(torch.tensor(float(thr), dtype=dtype)) if thr is not None else 0.0
+    d.out_size_factor = float(_cfg(coder_cfg, "out_size_factor"))
+    vs, pc = _cfg(coder_cfg, "voxel_size"), _cfg(coder_cfg, "pc_range")
+    d.voxel_size[0], d.voxel_size[1] = float(vs[0]), float(vs[1])
+    d.pc_range[0], d.pc_range[1] = float(pc[0]), float(pc[1])
+    if rng is not None:
+        for i in range(6):
+            d.post_center_range[i] = float(rng[i])
+    mr = _per_task(test_cfg.get("min_radius") if kind == "circle" else None, T, "min_radius")
+    ts = _per_task(test_cfg.get("thresh_scale") if kind == "size_aware_circle" else None, T, "thresh_scale")
+    nt = _per_task(test_cfg.get("nms_thr") if kind == "rotate" else None, T, "nms_thr")
+    for t in range(T):
+        d.min_radius[t], d.thresh_scale[t], d.nms_thr[t] = mr[t], ts[t], nt[t]
+    vamp = _capi.checked()
+    nbytes = vamp.vamp_det_workspace_bytes(d)
+    if nbytes == 0:
+        vamp.vamp_det_postprocess(d, None, None, None, None, None, None, 0, None)
+    P, cs = d.post_max_size, 9 if has_vel else 7
+    dev = heads[0]["heatmap"].device
+    if out is None:
+        out = DetResult(torch.empty(B, T * P, cs, dtype=torch.float32, device=dev),
+                        torch.empty(B, T * P, dtype=dtype, device=dev),
+                        torch.empty(B, T * P, dtype=torch.int32, device=dev),
+                        torch.empty(B, dtype=torch.int32, device=dev))
+    else:
+        want = [(out.boxes, (B, T * P, cs), torch.float32), (out.scores, (B, T * P), dtype),
+                (out.labels, (B, T * P), torch.int32), (out.counts, (B,), torch.int32)]
+        for x, shape, dt in want:
+            if tuple(x.shape) != shape or x.dtype != dt or not x.is_contiguous() or x.device != dev:
+                raise ValueError(f"out buffer {tuple(x.shape)} {x.dtype} is not a contiguous {shape} {dt} on {dev}")
+    table = (_capi.VampDetTask * T)()
+    for t, ts_ in enumerate(tensors):
+        table[t] = _capi.VampDetTask(*[x.data_ptr() for x in ts_], *([] if has_vel else [None]))
+    with torch.cuda.device(dev):
+        ws = _scratch("det", dev, nbytes)
+        vamp.vamp_det_postprocess(d, table, out.boxes, out.scores, out.labels, out.counts, ws, ws.numel(), _stream())
+    return out
+
+
+# ===========================================================================
+# detection training targets (bev_depth_head.py:168-319)
+# ===========================================================================
+_LABEL_DTYPES = (torch.int32, torch.int64)
+
+
+@dataclasses.dataclass
+class DetTargets:
+    """The training targets of a batch: `heat` holds the tasks' [B, ncls_t, fh, fw] heatmaps one after the other
+    (fp32), anno [T, B, max_objs, code] fp32, inds [T, B, max_objs] int64, masks [T, B, max_objs] uint8."""
+    heat: torch.Tensor
+    anno: torch.Tensor
+    inds: torch.Tensor
+    masks: torch.Tensor
+    ncls: tuple
+    fh: int
+    fw: int
+
+    def heatmaps(self):
+        B = self.anno.shape[1]
+        return [h.view(B, n, self.fh, self.fw) for h, n in
+                zip(self.heat.split([B * n * self.fh * self.fw for n in self.ncls]), self.ncls)]
+
+    def as_tuple(self):
+        """get_targets's return value: (heatmaps, anno_boxes, inds, masks), each a list over tasks of [B, ...]
+        views of the buffers."""
+        return self.heatmaps(), list(self.anno.unbind(0)), list(self.inds.unbind(0)), list(self.masks.unbind(0))
+
+
+def _pack_targets_input(boxes, labels):
+    """Per-sample lists ([n_b, 7 | 9] boxes, [n_b] labels) -> padded [B, M, 7 | 9], [B, M] (label -1) on the
+    device, without a host synchronisation; tensors pass through."""
+    if isinstance(boxes, torch.Tensor):
+        if not isinstance(labels, torch.Tensor):
+            raise ValueError("boxes is a packed tensor but labels is not")
+        return boxes, labels
+    if len(boxes) != len(labels) or len(boxes) == 0:
+        raise ValueError(f"{len(boxes)} box tensors and {len(labels)} label tensors (one per sample, at least one)")
+    if any(b.dtype != torch.float32 for b in boxes):
+        raise TypeError(f"boxes must be fp32, got {sorted({str(b.dtype) for b in boxes})}")
+    if len({l.dtype for l in labels}) != 1:
+        raise TypeError(f"labels must share one dtype, got {sorted({str(l.dtype) for l in labels})}")
+    if not all(b.is_cuda for b in boxes) or not all(l.is_cuda for l in labels):
+        raise _capi.VampireHipError("det_targets needs device tensors (no CPU fallback)")
+    pad = torch.nn.utils.rnn.pad_sequence
+    return pad(list(boxes), batch_first=True), pad(list(labels), batch_first=True, padding_value=-1)
+
+
+def det_targets(boxes, labels, tasks_ncls, train_cfg, norm_bbox, out=None):
+    """BEVDepthHead.get_targets on the device (vamp_det_targets): per task and sample the Gaussian heatmaps and
+    the anno / ind / mask rows of the first max_objs boxes in the reference's slot order, with the reference's
+    fp32 chain, in two launches and without a host synchronisation (capturable in a graph with packed inputs).
+    boxes, labels: per-sample lists ([n_b, 7 | 9] fp32, [n_b] int32 | int64; packed on the device with label -1
+    padding) or packed [B, M, 7 | 9] and [B, M] tensors whose padding rows carry label -1.  tasks_ncls: classes
+    per task, labels flat over the tasks.  out: a DetTargets of preallocated buffers to write (graph capture).
+    Returns a DetTargets; as_tuple() is get_targets's (heatmaps, anno_boxes, inds, masks)."""
+    boxes, labels = _pack_targets_input(boxes, labels)
+    if boxes.dtype != torch.float32:
+        raise TypeError(f"boxes must be fp32, got {boxes.dtype}")
+    if labels.dtype not in _LABEL_DTYPES:
+        raise TypeError(f"labels must be int32 or int64, got {labels.dtype}")
+    if not (boxes.is_cuda and labels.is_cuda):
+        raise _capi.VampireHipError("det_targets needs device tensors (no CPU fallback)")
+    if boxes.dim() != 3 or boxes.shape[2] not in (7, 9) or tuple(labels.shape) != tuple(boxes.shape[:2]):
+        raise ValueError(f"expected boxes [B, M, 7 | 9] and labels [B, M], got {tuple(boxes.shape)} "
+                         f"and {tuple(labels.shape)}")
+    ncls = tuple(int(n) for n in tasks_ncls)
+    T = len(ncls)
+    if not 1 <= T <= 8:
+        raise ValueError(f"{T} tasks (1 to 8)")
+    B, Mb, cols = boxes.shape
+    osf = train_cfg["out_size_factor"]
+    fw, fh = int(train_cfg["grid_size"][0]) // osf, int(train_cfg["grid_size"][1]) // osf
+    code = len(train_cfg["code_weights"])
+    max_objs = int(train_cfg["max_objs"] * train_cfg["dense_reg"])
+    d = _capi.VampDetTargetDesc()
+    d.gaussian_overlap = float(train_cfg["gaussian_overlap"])
+    d.B, d.T, d.M = B, T, Mb
+    for t in range(T):
+        d.ncls[t] = ncls[t]
+    d.box_cols, d.code, d.max_objs, d.fh, d.fw = cols, code, max_objs, fh, fw
+    d.out_size_factor, d.min_radius, d.norm_bbox = int(osf), int(train_cfg["min_radius"]), int(bool(norm_bbox))
+    d.label_dtype = DTYPE_CODES[labels.dtype]
+    vs, pc = train_cfg["voxel_size"], train_cfg["point_cloud_range"]
+    d.voxel_size[0], d.voxel_size[1] = float(vs[0]), float(vs[1])
+    d.pc_range[0], d.pc_range[1] = float(pc[0]), float(pc[1])
+    vamp = _capi.checked()
+    nbytes = vamp.vamp_det_targets_workspace_bytes(d)
+    if nbytes == 0:
+        vamp.vamp_det_targets(d, None, None, None, None, None, None, None, 0, None)
+    dev = boxes.device
+    boxes, labels = boxes.contiguous(), labels.contiguous()
+    if out is None:
+        out = DetTargets(torch.empty(B * sum(ncls) * fh * fw, dtype=torch.float32, device=dev),
+                         torch.empty(T, B, max_objs, code, dtype=torch.float32, device=dev),
+                         torch.empty(T, B, max_objs, dtype=torch.int64, device=dev),
+                         torch.empty(T, B, max_objs, dtype=torch.uint8, device=dev), ncls, fh, fw)
+    else:
+        want = [(out.heat, (B * sum(ncls) * fh * fw,), torch.float32), (out.anno, (T, B, max_objs, code), torch.float32),
+                (out.inds, (T, B, max_objs), torch.int64), (out.masks, (T, B, max_objs), torch.uint8)]
+        for x, shape, dt in want:
+            if tuple(x.shape) != shape or x.dtype != dt or not x.is_contiguous() or x.device != dev:
+                raise ValueError(f"out buffer {tuple(x.shape)} {x.dtype} is not a contiguous {shape} {dt} on {dev}")
+        if tuple(out.ncls) != ncls or (out.fh, out.fw) != (fh, fw):
+            raise ValueError(f"out was made for classes {out.ncls} on {out.fh} x {out.fw}, not {ncls} on {fh} x {fw}")
+    with torch.cuda.device(dev):
+        ws = _scratch("det_targets", dev, nbytes)
+        vamp.vamp_det_targets(d, boxes, labels, out.heat, out.anno, out.inds, out.masks, ws, ws.numel(), _stream())
+    return out

@@ -1,0 +1,208 @@
+"""Layer operators on plain tensors (Python over the C ABI): the free functions a network calls without a `HotPath`
+-- BEVDepth voxel pooling, and the trilinear resize and 3x3x3 convolutions of the 3-D UNet, with autograd support.
+All work happens in hand-written HIP kernels reached through `_capi`; there is no CPU fallback."""
+import torch
+
+from . import _capi
+from ._tensors import DTYPE_CODES, FLOAT_DTYPES, HALF_DTYPES, _accept, _chk, _dtype_code, _stream, _workspace
+
+
+# ===========================================================================
+# BEVDepth-style voxel pooling (north_star; SURVEY 8 row a11 -- not in the reference tree, parity unpinned)
+# ===========================================================================
+def voxel_pooling(geom_xyz, input_features, voxel_num):
+    """The published BEVDepth operator `voxel_pooling(geom_xyz, input_features, voxel_num)`:
+    geom_xyz [B, N, D, H, W, 3] integer voxel indices (x, y, z), input_features [B, N, D, H, W, C]
+    (fp32 | bf16), voxel_num (nx, ny, nz) -> [B, C, ny, nx] fp32, the sum of the features of the points
+    falling into each BEV cell (points outside the grid are dropped).  HIP kernels, no CPU fallback."""
+    return _VoxelPoolingFn.apply(geom_xyz, input_features, tuple(int(v) for v in voxel_num))
+
+
+class _VoxelPoolingFn(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, geom, feat, voxel_num):
+        if not (geom.is_cuda and feat.is_cuda):
+            raise _capi.VampireHipError("voxel_pooling needs device tensors (no CPU fallback)")
+        vamp = _capi.checked()
+        B, C_ = feat.shape[0], feat.shape[-1]
+        P = feat[0].numel() // C_
+        ctx.in_dtype, ctx.fshape = feat.dtype, tuple(feat.shape)
+        feat = _accept(feat).reshape(B, P, C_).contiguous()
+        geom = _chk(geom.reshape(B, P, 3).to(torch.int32), (B, P, 3), "geom_xyz")
+        d = _capi.VampPoolDesc(B, C_, P, voxel_num[0], voxel_num[1], voxel_num[2], _dtype_code(feat))
+        out = torch.empty(B, voxel_num[1], voxel_num[0], C_, dtype=torch.float32, device=feat.device)
+        nbytes = vamp.vamp_voxel_pooling_workspace_bytes(d)
+        ws = _workspace((feat.device, torch.cuda.current_stream().cuda_stream), feat.device, nbytes)
+        with torch.cuda.device(feat.device):
+            vamp.vamp_voxel_pooling_forward(d, geom, feat, out, ws, ws.numel(), _stream())
+        ctx.desc = d
+        ctx.save_for_backward(geom)
+        return out.permute(0, 3, 1, 2)
+
+    @staticmethod
+    def backward(ctx, g):
+        (geom,) = ctx.saved_tensors
+        d = ctx.desc
+        g = g.permute(0, 2, 3, 1).contiguous().float()
+        gfeat = torch.empty(d.B, d.P, d.C, dtype=torch.float32, device=g.device)
+        with torch.cuda.device(g.device):
+            _capi.checked().vamp_voxel_pooling_backward(d, geom, g, gfeat, _stream())
+        return None, gfeat.reshape(ctx.fshape).to(ctx.in_dtype), None
+
+
+# ===========================================================================
+# trilinear resize of the 3-D UNet (first piece)
+# ===========================================================================
+def upsample_trilinear(x, size):
+    """F.interpolate(x, size, mode='trilinear', align_corners=True) (bv2:66, 72) on the HIP
+    kernels: x [B,C,z,y,x] fp32 device tensor -> [B,C,*size]; the backward is a gather (aten's
+    float-atomic scatter takes 2.2 ms per call at the UNet's full-resolution level)."""
+    return _UpsampleTrilinearFn.apply(x, tuple(int(v) for v in size))
+
+
+class _UpsampleTrilinearFn(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, x, size):
+        if not x.is_cuda:
+            raise _capi.VampireHipError("x must be a device tensor (no CPU fallback)")
+        if x.dim() != 5 or len(size) != 3:
+            raise ValueError("expected a [B,C,z,y,x] tensor and a 3-tuple size")
+        vamp = _capi.checked()
+        ctx.in_dtype = x.dtype
+        if x.dtype not in FLOAT_DTYPES:
+            x = x.float()
+        x = x.contiguous()
+        ctx.code = DTYPE_CODES[x.dtype]
+        B, C_ = x.shape[:2]
+        ctx.dtype = x.dtype
+        out = torch.empty((B, C_) + size, dtype=x.dtype, device=x.device)
+        if out.numel() and x.numel():
+            vamp.vamp_upsample_trilinear_forward_ex(B * C_, *x.shape[2:], *size, ctx.code, x, out, _stream())
+        ctx.vamp, ctx.dims = vamp, (B * C_,) + tuple(x.shape[2:]) + size
+        ctx.in_shape = tuple(x.shape)
+        return out
+
+    @staticmethod
+    def backward(ctx, g):
+        dt = ctx.dtype
+        g = g.contiguous().to(dt)
+        gin = torch.empty(ctx.in_shape, dtype=dt, device=g.device)
+        if gin.numel() and g.numel():
+            vamp = ctx.vamp
+            nbytes = vamp.vamp_upsample_trilinear_workspace_bytes(*ctx.dims[1:4])
+            # (one table per stream and size: the size in the key, so a buffer is never regrown)
+            ws = _workspace((g.device, torch.cuda.current_stream().cuda_stream, nbytes), g.device, nbytes)
+            vamp.vamp_upsample_trilinear_backward_ex(*ctx.dims, ctx.code, g, gin, ws, ws.numel(), _stream())
+        else:
+            gin.zero_()
+        return gin.to(ctx.in_dtype), None
+
+
+# ===========================================================================
+# 3x3x3 convolutions of the 3-D UNet
+# ===========================================================================
+def _conv_desc(x, w) -> _capi.VampConvDesc:
+    d = _capi.VampConvDesc()
+    d.B, d.cin, d.Z, d.Y, d.X = x.shape
+    d.cout = w.shape[0]
+    return d
+
+
+def conv3d_3x3x3(x, weight):
+    """nn.Conv3d(cin, cout, 3, 1, 1, bias=False) (bv2:20, 40-60) on the fp32 matrix cores:
+    x [B,cin,Z,Y,X], weight [cout,cin,3,3,3], cin / cout in {16, 32}; fp32 device tensors."""
+    return _Conv3dFn.apply(x, weight)
+
+
+def conv3d_bf16(x, weight):
+    """The same layer in bf16 (what the reference's `precision=16` training hands it): x bf16 [B,cin,Z,Y,X],
+    weight bf16 [cout,cin,3,3,3] -> bf16 [B,cout,Z,Y,X]; fp32 accumulation on the bf16 matrix cores."""
+    return _Conv3dBf16Fn.apply(x, weight)
+
+
+def conv3d_bf16_supported(x, weight, stride, padding, bias):
+    if not (x.is_cuda and x.dtype in HALF_DTYPES and bias is None and tuple(stride) == (1, 1, 1)
+            and tuple(padding) == (1, 1, 1) and tuple(weight.shape[2:]) == (3, 3, 3) and x.dim() == 5
+            and weight.shape[1] == x.shape[1]):
+        return False
+    return bool(_capi.checked().vamp_conv3d_bf16_supported(_conv_desc(x, weight)))
+
+
+class _Conv3dBf16Fn(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, x, w):
+        if not (x.is_cuda and w.is_cuda):
+            raise _capi.VampireHipError("x / weight must be device tensors (no CPU fallback)")
+        if x.dtype not in HALF_DTYPES or w.dtype != x.dtype or x.dim() != 5 or w.dim() != 5:
+            raise TypeError("conv3d_bf16 takes bf16 (or fp16) [B,cin,Z,Y,X] and [cout,cin,3,3,3] tensors of one dtype")
+        code = DTYPE_CODES[x.dtype]
+        vamp = _capi.checked()
+        x, w = x.contiguous(), w.contiguous()
+        d = _conv_desc(x, w)
+        if w.shape[1] != d.cin:
+            raise ValueError("weight / input channel mismatch")
+        out = torch.empty((d.B, d.cout, d.Z, d.Y, d.X), dtype=x.dtype, device=x.device)
+        vamp.vamp_conv3d_half_forward(d, code, x, w, out, _stream())
+        ctx.vamp, ctx.desc, ctx.code = vamp, d, code
+        ctx.save_for_backward(x, w)
+        return out
+
+    @staticmethod
+    def backward(ctx, g):
+        x, w = ctx.saved_tensors
+        vamp, d = ctx.vamp, ctx.desc
+        g = g.contiguous().to(x.dtype)
+        gx = gw = None
+        if ctx.needs_input_grad[0]:
+            gx = torch.empty_like(x)
+            vamp.vamp_conv3d_half_backward_data(d, ctx.code, g, w, gx, _stream())
+        if ctx.needs_input_grad[1]:
+            gw32 = torch.empty(w.shape, dtype=torch.float32, device=w.device)
+            nbytes = vamp.vamp_conv3d_bf16_workspace_bytes(d)
+            ws = _workspace((g.device, torch.cuda.current_stream().cuda_stream, "conv16", nbytes), g.device, nbytes)
+            vamp.vamp_conv3d_half_backward_weight(d, ctx.code, x, g, gw32, ws, ws.numel(), _stream())
+            gw = gw32.to(w.dtype)                 # the gradient of the 16-bit copy autocast made of the fp32 parameter
+        return gx, gw
+
+
+def conv3d_supported(x, weight, stride, padding, bias):
+    if not (x.is_cuda and x.dtype == torch.float32 and weight.dtype == torch.float32 and bias is None
+            and tuple(stride) == (1, 1, 1) and tuple(padding) == (1, 1, 1) and tuple(weight.shape[2:]) == (3, 3, 3)
+            and x.dim() == 5 and weight.shape[1] == x.shape[1] and not torch.is_autocast_enabled()):
+        return False
+    return bool(_capi.checked().vamp_conv3d_supported(_conv_desc(x, weight)))
+
+
+class _Conv3dFn(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, x, w):
+        if not (x.is_cuda and w.is_cuda):
+            raise _capi.VampireHipError("x / weight must be device tensors (no CPU fallback)")
+        if x.dtype != torch.float32 or w.dtype != torch.float32 or x.dim() != 5 or w.dim() != 5:
+            raise TypeError("conv3d_3x3x3 takes fp32 [B,cin,Z,Y,X] and [cout,cin,3,3,3] tensors")
+        vamp = _capi.checked()
+        x, w = x.contiguous(), w.contiguous()
+        d = _conv_desc(x, w)
+        if w.shape[1] != d.cin:
+            raise ValueError("weight / input channel mismatch")
+        out = torch.empty((d.B, d.cout, d.Z, d.Y, d.X), dtype=torch.float32, device=x.device)
+        vamp.vamp_conv3d_forward(d, x, w, out, _stream())
+        ctx.vamp, ctx.desc = vamp, d
+        ctx.save_for_backward(x, w)
+        return out
+
+    @staticmethod
+    def backward(ctx, g):
+        x, w = ctx.saved_tensors
+        vamp, d = ctx.vamp, ctx.desc
+        g = g.contiguous().float()
+        gx = gw = None
+        if ctx.needs_input_grad[0]:
+            gx = torch.empty_like(x)
+            vamp.vamp_conv3d_backward_data(d, g, w, gx, _stream())
+        if ctx.needs_input_grad[1]:
+            gw = torch.empty_like(w)
+            nbytes = vamp.vamp_conv3d_workspace_bytes(d)
+            ws = _workspace((g.device, torch.cuda.current_stream().cuda_stream, "conv", nbytes), g.device, nbytes)
+            vamp.vamp_conv3d_backward_weight(d, x, g, gw, ws, ws.numel(), _stream())
+        return gx, gw

@@ -4,14 +4,14 @@
 
 The reference counts with torchmetrics' `JaccardIndex`, after a boolean index (`occ_logits[mask_camera]`:
 a host synchronisation and a copy of half the logits) and an argmax.  Here the counting is the HIP
-confusion-matrix pass of `ops.confusion_update` over the logits in place, and the per-reference-point
-prediction is `ops.lidarseg_predict`; nothing leaves the device until `compute()`.
+confusion-matrix pass of `evaluation.confusion_update` over the logits in place, and the per-reference-point
+prediction is `evaluation.lidarseg_predict`; nothing leaves the device until `compute()`.
 """
 import numpy as np
 import torch
 import torch.distributed as dist
 
-from . import ops
+from . import evaluation
 
 # base_exp.py:222-224 (label_17_names): the 18 classes of the lidar-seg / Occ3D label space
 CLASS_NAMES = ["other", "barrier", "bicycle", "bus", "car", "construction_vehicle", "motorcycle", "pedestrian",
@@ -39,7 +39,7 @@ class JaccardIndex:
     def update(self, logits_or_preds, target, mask=None, class_window=None):
         """Logits [..., K] (prediction lo + argmax over `class_window` = (lo, hi), default all classes) or
         integer predictions shaped like `target`; `mask` (bool, like target) selects the elements counted."""
-        ops.confusion_update(self.confmat, self.invalid, logits_or_preds, target, mask, class_window=class_window,
+        evaluation.confusion_update(self.confmat, self.invalid, logits_or_preds, target, mask, class_window=class_window,
                              ignore_index=self.ignore_index)
 
     def reset(self):
@@ -99,7 +99,7 @@ class SegEvaluator:
         ref_labels, ref_index, occ_semantics, mask_camera = batch[8], batch[9], batch[11], batch[14]
         for logits, idx, labels in zip(pts_logits, ref_index, ref_labels):
             dev = logits.device
-            pred, bad = ops.lidarseg_predict(logits, idx.to(dev, non_blocking=True), len(labels), self.window)
+            pred, bad = evaluation.lidarseg_predict(logits, idx.to(dev, non_blocking=True), len(labels), self.window)
             self.val_iou.update(pred, labels.to(dev, non_blocking=True))
             self.val_iou.invalid += bad                  # index_add_ rejects an index out of range
         self.occ_val_iou.update(occ_logits, occ_semantics, mask_camera)
@@ -140,7 +140,7 @@ class SegEvaluator:
         tensor per sample; no files are written.  Raises ValueError on a reference index out of range."""
         out = []
         for logits, idx, labels in zip(pts_logits_batch, ref_index, ref_labels):
-            pred, bad = ops.lidarseg_predict(logits, idx.to(logits.device), len(labels), self.window)
+            pred, bad = evaluation.lidarseg_predict(logits, idx.to(logits.device), len(labels), self.window)
             if int(bad):
                 raise ValueError(f"{int(bad)} points map outside the {len(labels)} reference points")
             out.append(pred.to(torch.uint8))

@@ -264,10 +264,10 @@ class BEVDepthHead(nn.Module):
         """get_targets on the device: one vamp_det_targets call (two launches), no host synchronisation, the
         reference's fp32 chain and float64 Gaussian stamps.  gt_bboxes_3d / gt_labels_3d: the
         per-sample lists get_targets takes (packed on the device, labels padded with -1) or packed [B, M, 7 | 9]
-        fp32 / [B, M] tensors whose padding rows carry label -1 (graph capture).  Returns an ops.DetTargets whose
+        fp32 / [B, M] tensors whose padding rows carry label -1 (graph capture).  Returns an evaluation.DetTargets whose
         as_tuple() is get_targets's (heatmaps, anno_boxes, inds, masks); `out` takes preallocated buffers."""
-        from . import ops
-        return ops.det_targets(gt_bboxes_3d, gt_labels_3d, self.num_classes, self.train_cfg, self.norm_bbox, out=out)
+        from . import evaluation
+        return evaluation.det_targets(gt_bboxes_3d, gt_labels_3d, self.num_classes, self.train_cfg, self.norm_bbox, out=out)
 
     # ---- loss (bev_depth_head.py:318-375) ----
     def loss(self, targets, preds_dicts, **_):
@@ -326,10 +326,10 @@ class BEVDepthHead(nn.Module):
 
     def get_bboxes_device(self, preds_dicts, out=None):
         """get_bboxes on the device for every nms_type of the reference ('circle', 'size_aware_circle',
-        'rotate'): one vamp_det_postprocess call, no host synchronisation.  Returns an ops.DetResult whose
+        'rotate'): one vamp_det_postprocess call, no host synchronisation.  Returns an evaluation.DetResult whose
         to_list() is get_bboxes's [[bboxes, scores, labels], ...]; `out` takes preallocated buffers."""
-        from . import ops
-        return ops.det_postprocess(preds_dicts, self.bbox_coder, self.test_cfg, self.num_classes, self.norm_bbox,
+        from . import evaluation
+        return evaluation.det_postprocess(preds_dicts, self.bbox_coder, self.test_cfg, self.num_classes, self.norm_bbox,
                                    out=out)
 
 

@@ -12,56 +12,20 @@ All heavy work happens in hand-written HIP kernels reached through ctypes
 (`_capi`); torch supplies device memory and the current stream only.
 """
 import ctypes as C
-import dataclasses
 import math
 import os
-
-import numpy as np
 
 import torch
 
 from . import _capi
 from .config import PathConfig
 from . import geometry as G
-
-
-def _ptr(t):
-    return None if t is None else C.c_void_p(t.data_ptr())
-
-
-def _stream(stream=None):
-    return C.c_void_p((stream or torch.cuda.current_stream()).cuda_stream)
-
-
-def _dtype_code(t: torch.Tensor) -> int:
-    if t.dtype == torch.float32:
-        return _capi.VAMP_F32
-    if t.dtype == torch.bfloat16:
-        return _capi.VAMP_BF16
-    raise TypeError(f"unsupported dtype {t.dtype}: the hot path takes fp32 or bf16 inputs")
-
-
-def _accept(t):
-    """The kernels read fp32 or bf16; anything else (fp16 under the reference's precision=16
-    autocast, base_cli.py:77, fp64) is promoted to fp32, as aten's autocast does for these ops."""
-    if t is None or t.dtype in (torch.float32, torch.bfloat16):
-        return t
-    return t.float()
-
-
-def _is_channel_last(feat: torch.Tensor) -> bool:
-    """feat [B, N, C, fH, fW] whose memory is [B, N, fH, fW, C] (a torch.channels_last producer's output, reshaped):
-    what the lift wants -- it samples a pixel's C features as one run -- and takes zero-copy."""
-    return (feat.dim() == 5 and feat.dtype == torch.float32 and feat.shape[2] > 1
-            and feat.permute(0, 1, 3, 4, 2).is_contiguous() and feat.data_ptr() % 16 == 0)
-
-
-def _chk(t: torch.Tensor, shape, name):
-    if not t.is_cuda:
-        raise _capi.VampireHipError(f"{name} must be a device tensor (no CPU fallback)")
-    if tuple(t.shape) != tuple(shape):
-        raise ValueError(f"{name}: expected shape {tuple(shape)}, got {tuple(t.shape)}")
-    return t.contiguous()
+from ._tensors import _accept, _chk, _density_code, _dtype_code, _is_channel_last, _stream
+# the operators that take no HotPath live in modules of their own; their public names stay importable from here
+from .layers import (voxel_pooling, upsample_trilinear, conv3d_3x3x3, conv3d_bf16, conv3d_supported,  # noqa: F401
+                     conv3d_bf16_supported)
+from .evaluation import (confusion_update, lidarseg_predict, det_postprocess, det_targets, DetResult,  # noqa: F401
+                         DetTargets)
 
 
 # det-grid heights the BEV kernels take: their z taps and weights live in fixed LDS tables (kBevMaxOZ, render_bev.hip)
@@ -86,8 +50,7 @@ def render_desc(cfg: PathConfig, B, N, dtype_code, C_=None) -> _capi.VampRenderD
     d.z_step_det = c.z_bound_det[2]
     for i, bnd in enumerate((c.x_bound_det, c.y_bound_det, c.z_bound_det)):
         d.det_step[i] = bnd[2]
-    d.density_mode = (_capi.VAMP_DENSITY_SDF_LAPLACE if c.density_mode == "sdf"
-                      else _capi.VAMP_DENSITY_SIGMOID)
+    d.density_mode = _density_code(c)
     d.sdf_bias = c.sdf_bias
     d.beta_min = 1e-4
     d.cat_seg = 1 if c.cat_seg else 0
@@ -105,7 +68,7 @@ class HotPath:
                              "det-grid heights")
         self.cfg = cfg
         self.device = torch.device(device)
-        self.lib = _capi.load()
+        self.lib = _capi.load()     # (sets self.vamp too: the `lib` property below)
         geo = G.PathGeometry(cfg)
         dev = self.device
         f32 = torch.float32
@@ -172,6 +135,18 @@ class HotPath:
                      "defer_lift_scan": True}
         self._lift_scan_pending = None      # (desc, workspace, stream) of a lift forward whose cell scan is still due
 
+    # ------------------------------------------------------------- the library
+    # `lib` hands status codes back as integers; `vamp` is the same entry points raising VampireHipError on a failure,
+    # which every call of this file goes through.  Assigning `lib` (a test's call recorder around the library) re-derives
+    # `vamp`, so that the calls still pass through whatever `lib` is.
+    @property
+    def lib(self):
+        return self._lib
+
+    @lib.setter
+    def lib(self, lib):
+        self._lib, self.vamp = lib, _capi.checked(lib)
+
     # ---------------------------------------------------------------- descs
     def lift_desc(self, B, N, C_, dtype_code, use_depth=True, fhw=None) -> _capi.VampLiftDesc:
         """`fhw`: size of the image feature map when it is not final_dim / downsample_factor -- the lift
@@ -213,8 +188,7 @@ class HotPath:
         cur = torch.cuda.current_stream()
         if cur != st:
             cur.wait_stream(st)
-        _capi.check(self.lib.vamp_lift_finish_cells(C.byref(d), _ptr(ws), ws.numel(), _stream(cur)),
-                    "vamp_lift_finish_cells")
+        self.vamp.vamp_lift_finish_cells(d, ws, ws.numel(), _stream(cur))
         self._dirty.discard("lift")         # scanned: the counters are back at zero
 
     def _cam_clean_flag(self):
@@ -286,10 +260,9 @@ class HotPath:
         c = self.cfg
         if not ert:
             mats, beta, dens = tensors
-            _capi.check(self.lib.vamp_render_camera_terminate(
-                C.byref(d), _ptr(mats), _ptr(self.us), _ptr(self.vs), _ptr(self.ds), _ptr(beta), _ptr(dens), _ptr(ws),
-                ws.numel(), _stream(stream)), "vamp_render_camera_terminate")
-        off = self.lib.vamp_render_term_offset(C.byref(d))
+            self.vamp.vamp_render_camera_terminate(d, mats, self.us, self.vs, self.ds, beta, dens, ws, ws.numel(),
+                                                  _stream(stream))
+        off = self.vamp.vamp_render_term_offset(d)
         n = d.B * d.N * c.fH * c.fW
         term = ws[off:off + 4 * n].view(torch.int32).view(d.B * d.N, 1, c.fH, c.fW)
         tile_max = torch.nn.functional.max_pool2d(term.float(), 8, ceil_mode=True)
@@ -334,9 +307,7 @@ class HotPath:
         valid = torch.empty(shp, dtype=torch.uint8, device=self.device)
         ix0, iy0, iz0 = (torch.empty(shp, dtype=torch.int16, device=self.device) for _ in range(3))
         mats = _chk(lift_mats.float(), (B, N, 3, 4, 4), "lift_mats")
-        _capi.check(self.lib.vamp_lift_indices(C.byref(d), _ptr(mats), _ptr(self.xs), _ptr(self.ys),
-                                               _ptr(self.zs), _ptr(valid), _ptr(ix0), _ptr(iy0),
-                                               _ptr(iz0), _stream()), "vamp_lift_indices")
+        self.vamp.vamp_lift_indices(d, mats, self.xs, self.ys, self.zs, valid, ix0, iy0, iz0, _stream())
         return valid, ix0, iy0, iz0
 
     def lift_cull_words(self, lift_mats, use_depth=True):
@@ -347,12 +318,9 @@ class HotPath:
         d = self.lift_desc(B, N, 4, _capi.VAMP_F32, use_depth)
         patch, grid = (C.c_int32 * 2)(), (C.c_int32 * 2)()
         mats = _chk(lift_mats.float(), (B, N, 3, 4, 4), "lift_mats")
-        _capi.check(self.lib.vamp_lift_cull_words(C.byref(d), None, None, None, None, None, patch, grid, None),
-                    "vamp_lift_cull_words")
+        self.vamp.vamp_lift_cull_words(d, None, None, None, None, None, patch, grid, None)
         words = torch.empty(B, c.vZ, grid[1], grid[0], dtype=torch.int32, device=self.device)
-        _capi.check(self.lib.vamp_lift_cull_words(C.byref(d), _ptr(mats), _ptr(self.xs), _ptr(self.ys),
-                                                  _ptr(self.zs), _ptr(words), patch, grid, _stream()),
-                    "vamp_lift_cull_words")
+        self.vamp.vamp_lift_cull_words(d, mats, self.xs, self.ys, self.zs, words, patch, grid, _stream())
         return words.long() & 0xffffffff, (patch[0], patch[1])
 
     # --------------------------------------------------------------- render
@@ -362,9 +330,7 @@ class HotPath:
         d = self.render_desc(B, N, _capi.VAMP_F32)
         mats = _chk(render_mats.float(), (B, N, 3, 4, 4), "render_mats")
         geom = torch.empty(B, N, c.D, c.fH, c.fW, 3, dtype=torch.float32, device=self.device)
-        _capi.check(self.lib.vamp_frustum_geometry(C.byref(d), _ptr(mats), _ptr(self.us), _ptr(self.vs),
-                                                   _ptr(self.ds), _ptr(geom), _stream()),
-                    "vamp_frustum_geometry")
+        self.vamp.vamp_frustum_geometry(d, mats, self.us, self.vs, self.ds, geom, _stream())
         return geom
 
     def render_indices(self, geom=None, render_mats=None):
@@ -377,9 +343,7 @@ class HotPath:
         ix0, iy0, iz0 = (torch.empty(shp, dtype=torch.int16, device=self.device) for _ in range(3))
         g = None if geom is None else _chk(geom.float(), (B, N, c.D, c.fH, c.fW, 3), "geom")
         m = None if render_mats is None else _chk(render_mats.float(), (B, N, 3, 4, 4), "render_mats")
-        _capi.check(self.lib.vamp_render_indices(C.byref(d), _ptr(g), _ptr(m), _ptr(self.us),
-                                                 _ptr(self.vs), _ptr(self.ds), _ptr(inside), _ptr(ix0),
-                                                 _ptr(iy0), _ptr(iz0), _stream()), "vamp_render_indices")
+        self.vamp.vamp_render_indices(d, g, m, self.us, self.vs, self.ds, inside, ix0, iy0, iz0, _stream())
         return inside, ix0, iy0, iz0
 
     def render_direct_taps(self, render_mats, coords=False):
@@ -393,10 +357,7 @@ class HotPath:
         ix0, iy0, iz0 = (torch.empty(shp, dtype=torch.int16, device=self.device) for _ in range(3))
         fxyz = torch.empty(shp + (3,), dtype=torch.float32, device=self.device) if coords else None
         m = _chk(render_mats.float(), (B, N, 3, 4, 4), "render_mats")
-        _capi.check(self.lib.vamp_render_camera_direct_taps(C.byref(d), _ptr(m), _ptr(self.us), _ptr(self.vs),
-                                                            _ptr(self.ds), _ptr(inside), _ptr(ix0), _ptr(iy0),
-                                                            _ptr(iz0), _ptr(fxyz), _stream()),
-                    "vamp_render_camera_direct_taps")
+        self.vamp.vamp_render_camera_direct_taps(d, m, self.us, self.vs, self.ds, inside, ix0, iy0, iz0, fxyz, _stream())
         return (inside, ix0, iy0, iz0) + ((fxyz,) if coords else ())
 
     def render(self, density_feature, semantic_logits, base, rgb, beta=None, *, geom=None,
@@ -423,12 +384,11 @@ class HotPath:
         d = self.render_desc(B, N, _dtype_code(dens))
         mats = _chk(render_mats.float(), (B, N, 3, 4, 4), "render_mats")
         beta = (torch.zeros(1, device=self.device) if beta is None else beta.detach().reshape(1).float().contiguous())
-        ws = self._workspace("render", self.lib.vamp_render_workspace_bytes(C.byref(d)))
+        ws = self._workspace("render", self.vamp.vamp_render_workspace_bytes(d))
         with torch.cuda.device(self.device):
-            _capi.check(self.lib.vamp_render_camera_terminate(
-                C.byref(d), _ptr(mats), _ptr(self.us), _ptr(self.vs), _ptr(self.ds), _ptr(beta), _ptr(dens),
-                _ptr(ws), ws.numel(), _stream()), "vamp_render_camera_terminate")
-            off = self.lib.vamp_render_term_offset(C.byref(d))
+            self.vamp.vamp_render_camera_terminate(d, mats, self.us, self.vs, self.ds, beta, dens, ws, ws.numel(),
+                                                  _stream())
+            off = self.vamp.vamp_render_term_offset(d)
             term = ws[off:off + 4 * B * N * c.fH * c.fW].view(torch.int32).reshape(B, N, 1, c.fH, c.fW).clone()
             inside = self.render_indices(render_mats=mats)[0].bool()
         idx = torch.arange(c.D - 1, device=self.device).reshape(1, 1, -1, 1, 1)
@@ -480,7 +440,7 @@ class HotPath:
 
 
     def gate_conv1x1_supported(self, C_, oZ, cout):
-        return bool(self.lib.vamp_gate_conv1x1_supported(int(C_), int(oZ), int(cout)))
+        return bool(self.vamp.vamp_gate_conv1x1_supported(int(C_), int(oZ), int(cout)))
 
     def gate_conv1x1(self, voxel_output, voxel_density, weight, bias=None):
         """The density gate and the `voxel_output` 1x1 conv in one kernel (bv2:627-632; SURVEY 8f N2, consumer
@@ -533,7 +493,7 @@ class _LiftFn(torch.autograd.Function):
         nchunk = (C_ + 15) // 16
         hits = (torch.empty(B, c.vZ, c.vY, c.vX, nchunk, dtype=torch.int64, device=feat.device)
                 if need_grad else None)
-        nbytes = hp.lib.vamp_lift_workspace_bytes(C.byref(d))
+        nbytes = hp.vamp.vamp_lift_workspace_bytes(d)
         ws = hp._workspace("lift", nbytes)
         cur = torch.cuda.current_stream()
         hp._lift_gen = getattr(hp, "_lift_gen", 0) + 1
@@ -553,15 +513,11 @@ class _LiftFn(torch.autograd.Function):
             hp._dirty.add("lift")           # (until this call has been issued in full)
             ctx.cells_key = (hp._lift_gen, ws.data_ptr())
         if logits:
-            _capi.check(hp.lib.vamp_lift_forward_logits_ex(C.byref(d), _ptr(mats), _ptr(hp.xs), _ptr(hp.ys), _ptr(hp.zs),
-                                                           _ptr(lg), _dtype_code(lg), _ptr(feat), _ptr(depth), _ptr(out),
-                                                           _ptr(hits), _ptr(ws), ws.numel(), flags, _stream(cur)),
-                        "vamp_lift_forward_logits_ex")
+            hp.vamp.vamp_lift_forward_logits_ex(d, mats, hp.xs, hp.ys, hp.zs, lg, _dtype_code(lg), feat, depth, out,
+                                               hits, ws, ws.numel(), flags, _stream(cur))
         else:
-            _capi.check(hp.lib.vamp_lift_forward_ex(C.byref(d), _ptr(mats), _ptr(hp.xs), _ptr(hp.ys), _ptr(hp.zs),
-                                                    _ptr(depth if use_depth else None), _ptr(feat), _ptr(out),
-                                                    _ptr(hits), _ptr(ws), ws.numel(), flags, _stream(cur)),
-                        "vamp_lift_forward_ex")
+            hp.vamp.vamp_lift_forward_ex(d, mats, hp.xs, hp.ys, hp.zs, depth if use_depth else None, feat, out, hits, ws,
+                                        ws.numel(), flags, _stream(cur))
         if flags & _capi.VAMP_LIFTFWD_DEFER_SCAN:
             hp._lift_scan_pending = (d, ws, cur)      # (the counters stay in flight until the scan)
         else:
@@ -583,7 +539,7 @@ class _LiftFn(torch.autograd.Function):
             gfeat = torch.empty(feat.shape, dtype=torch.float32, device=feat.device)
         gdepth = (torch.empty(depth.shape, dtype=torch.float32, device=feat.device)
                   if use_depth else None)
-        nbytes = hp.lib.vamp_lift_workspace_bytes(C.byref(d))
+        nbytes = hp.vamp.vamp_lift_workspace_bytes(d)
         ws = hp._workspace("lift", nbytes)
         hp._finish_lift_scan()              # (nobody has run the forward's deferred scan: a lift without a render forward)
         valid = 1 if ctx.cells_key == (getattr(hp, "_lift_gen", 0), ws.data_ptr()) else 0
@@ -599,10 +555,8 @@ class _LiftFn(torch.autograd.Function):
         hp._dirty.add("lift")
 
         def call(flags, stream):
-            _capi.check(hp.lib.vamp_lift_backward_ex(C.byref(d), _ptr(mats), _ptr(hp.xs), _ptr(hp.ys), _ptr(hp.zs),
-                                                     _ptr(depth if use_depth else None), _ptr(feat), _ptr(g),
-                                                     _ptr(hits), _ptr(gdepth), _ptr(gfeat), _ptr(ws),
-                                                     ws.numel(), flags, _stream(stream)), "vamp_lift_backward_ex")
+            hp.vamp.vamp_lift_backward_ex(d, mats, hp.xs, hp.ys, hp.zs, depth if use_depth else None, feat, g, hits,
+                                         gdepth, gfeat, ws, ws.numel(), flags, _stream(stream))
 
         call(valid, None)
         if hp.impl["lift_bwd"] == "cell":
@@ -628,9 +582,7 @@ class _LiftDenseFn(torch.autograd.Function):
         nchunk = (C_ + 15) // 16
         hits = (torch.empty(B, c.vZ, c.vY, c.vX, nchunk, dtype=torch.int64, device=ff.device)
                 if ctx.needs_input_grad[1] else None)
-        _capi.check(hp.lib.vamp_lift_forward_dense(C.byref(d), _ptr(mats), _ptr(hp.xs), _ptr(hp.ys),
-                                                   _ptr(hp.zs), _ptr(ff), _ptr(out), _ptr(hits),
-                                                   _stream()), "vamp_lift_forward_dense")
+        hp.vamp.vamp_lift_forward_dense(d, mats, hp.xs, hp.ys, hp.zs, ff, out, hits, _stream())
         if ctx.needs_input_grad[1]:
             ctx.hp, ctx.desc, ctx.shape = hp, d, ff.shape
             ctx.save_for_backward(mats, hits)
@@ -642,9 +594,7 @@ class _LiftDenseFn(torch.autograd.Function):
         mats, hits = ctx.saved_tensors
         g = g.contiguous().float()
         gff = torch.zeros(ctx.shape, dtype=torch.float32, device=g.device)
-        _capi.check(hp.lib.vamp_lift_backward_dense(C.byref(d), _ptr(mats), _ptr(hp.xs), _ptr(hp.ys),
-                                                    _ptr(hp.zs), _ptr(g), _ptr(hits), _ptr(gff),
-                                                    _stream()), "vamp_lift_backward_dense")
+        hp.vamp.vamp_lift_backward_dense(d, mats, hp.xs, hp.ys, hp.zs, g, hits, gff, _stream())
         return None, gff, None
 
 
@@ -750,13 +700,13 @@ class _RenderFn(torch.autograd.Function):
         bev_h = torch.empty(B, 1, c.oY, c.oX, dtype=f32, device=dev)
         vdens = torch.empty(B, 1, c.oZ, c.oY, c.oX, dtype=f32, device=dev)
         vout = torch.empty(B, CO, c.oZ, c.oY, c.oX, dtype=f32, device=dev)
-        nbytes = hp.lib.vamp_render_workspace_bytes(C.byref(d))
+        nbytes = hp.vamp.vamp_render_workspace_bytes(d)
         # training: the camera forward also keeps every inside sample's gathered values (tile-major rows, 256
         # contiguous bytes per tile, depth index and channel), and the backward's per-ray pass reads them back
         # instead of repeating the 8-tap gathers
         save = bool(train and geom is None and hp.impl["save_rows"] and hp.impl["cam_bwd"] != "v1" and (c.D - 1) <= 128)
         if save:
-            nbytes += hp.lib.vamp_render_samples_bytes(C.byref(d))
+            nbytes += hp.vamp.vamp_render_samples_bytes(d)
         ws = hp._workspace("render", nbytes)
         # which camera forward: the one kernel with early termination, or copy + planned march (with the
         # termination pre-pass or without) -- from the switches, or ("auto") from what the rays did lately
@@ -769,7 +719,7 @@ class _RenderFn(torch.autograd.Function):
         # camera tiles + BEV column blocks in one launch where the library takes the shapes (it checks the heights
         # hp.ozs_host against the BEV kernel's plane slabs itself)
         merged = bool(direct and ert and hp.impl["fwd_merged"] and hp.impl["bev_fused"] and
-                      hp.lib.vamp_render_forward_merged_supported(C.byref(d), hp.ozs_host))
+                      hp.vamp.vamp_render_forward_merged_supported(d, hp.ozs_host))
         # training calls take the one launch (camera tiles + rank pass + BEV blocks) while the camera tiles are at most
         # four rounds of the chip's workgroup slots: cfg-B, replayed step, merged against the three launches on two
         # streams -- 1 / 2 / 3 samples per GPU 0.395 / 0.710 / 1.03 against 0.410 / 0.723 / 1.05 ms, 4 samples equal,
@@ -780,7 +730,7 @@ class _RenderFn(torch.autograd.Function):
         plan = render_forward_plan(train, side is not None, prep_ok, direct, ert, merged)
         bev_flags = 0 if hp.impl["bev_fused"] else _capi.VAMP_BEVFWD_TWO_KERNELS
         bev_save = train and hp.impl["bev_bwd"] != "v1"
-        ws_bev = hp._workspace("bev", hp.lib.vamp_render_bev_workspace_bytes(C.byref(d))) if bev_save else None
+        ws_bev = hp._workspace("bev", hp.vamp.vamp_render_bev_workspace_bytes(d)) if bev_save else None
         cam_base = 0 if ert else _capi.VAMP_CAMFWD_NO_ERT
         streams, events = {"cur": cur, "side": side}, {}
         ctx.cells, ctx.ert, ctx.bev_key = False, ert, None
@@ -808,16 +758,13 @@ class _RenderFn(torch.autograd.Function):
             for w in waits:
                 st.wait_event(events[w])
             if op == "term":
-                _capi.check(hp.lib.vamp_render_camera_terminate(
-                    C.byref(d), _ptr(mats), _ptr(hp.us), _ptr(hp.vs), _ptr(hp.ds), _ptr(beta), _ptr(dens), _ptr(ws),
-                    ws.numel(), _stream(st)), "vamp_render_camera_terminate")
+                hp.vamp.vamp_render_camera_terminate(d, mats, hp.us, hp.vs, hp.ds, beta, dens, ws, ws.numel(),
+                                                    _stream(st))
             elif op in ("cam", "pack"):
                 keep = _capi.VAMP_CAMFWD_SAVE_SAMPLES if (save and op == "cam") else 0
-                _capi.check(hp.lib.vamp_render_camera_forward_ex(
-                    C.byref(d), _ptr(geom), _ptr(mats), _ptr(hp.us), _ptr(hp.vs), _ptr(hp.ds),
-                    _ptr(hp.camera_mids), _ptr(beta), _ptr(dens), _ptr(sem), _ptr(rgb), _ptr(rgb_p),
-                    _ptr(seg_p), _ptr(dep_p), _ptr(ws), ws.numel(), cam_base | flags | keep, _stream(st)),
-                    "vamp_render_camera_forward_ex")
+                hp.vamp.vamp_render_camera_forward_ex(d, geom, mats, hp.us, hp.vs, hp.ds, hp.camera_mids, beta, dens,
+                                                     sem, rgb, rgb_p, seg_p, dep_p, ws, ws.numel(),
+                                                     cam_base | flags | keep, _stream(st))
             elif op == "prep":
                 ranked = bool(flags & _capi.VAMP_CAMPREP_RANKED)       # (the forward drew the ranks: scan + work lists only)
                 pend = hp._lift_scan_pending
@@ -827,34 +774,29 @@ class _RenderFn(torch.autograd.Function):
                     # op's stream is `cur` or the side stream, which has waited for `cur` above and which `cur` waits
                     # for below: the lift backward is ordered behind the scan either way.)
                     hp._lift_scan_pending = None
-                    _capi.check(hp.lib.vamp_render_camera_prepare_with_lift(
-                        C.byref(d), _ptr(mats), _ptr(hp.us), _ptr(hp.vs), _ptr(hp.ds), _ptr(ws), ws.numel(), pflags,
-                        C.byref(pend[0]), _ptr(pend[1]), pend[1].numel(), _stream(st)),
-                        "vamp_render_camera_prepare_with_lift")
+                    hp.vamp.vamp_render_camera_prepare_with_lift(
+                        d, mats, hp.us, hp.vs, hp.ds, ws, ws.numel(), pflags, pend[0], pend[1], pend[1].numel(),
+                        _stream(st))
                     hp._dirty.discard("lift")
                 else:
-                    _capi.check(hp.lib.vamp_render_camera_prepare_ex(
-                        C.byref(d), _ptr(mats), _ptr(hp.us), _ptr(hp.vs), _ptr(hp.ds), _ptr(ws), ws.numel(),
-                        pflags, _stream(st)), "vamp_render_camera_prepare_ex")
+                    hp.vamp.vamp_render_camera_prepare_ex(d, mats, hp.us, hp.vs, hp.ds, ws, ws.numel(), pflags,
+                                                         _stream(st))
                 hp._dirty.discard("render")
                 ctx.cells = True
             elif op == "render":
-                _capi.check(hp.lib.vamp_render_forward_merged(
-                    C.byref(d), _ptr(mats), _ptr(hp.us), _ptr(hp.vs), _ptr(hp.ds), _ptr(hp.camera_mids),
-                    _ptr(hp.oxs), _ptr(hp.oys), _ptr(hp.ozs), hp.ozs_host, _ptr(hp.bev_mids), _ptr(beta),
-                    _ptr(dens), _ptr(sem), _ptr(rgb), _ptr(base), _ptr(rgb_p), _ptr(seg_p), _ptr(dep_p),
-                    _ptr(bev_rgb), _ptr(bev_seg), _ptr(bev_h), _ptr(vdens), _ptr(vout), _ptr(ws), ws.numel(),
-                    _ptr(ws_bev), ws_bev.numel() if bev_save else 0, _ptr(ctx.gbeta0) if train else None,
+                hp.vamp.vamp_render_forward_merged(
+                    d, mats, hp.us, hp.vs, hp.ds, hp.camera_mids, hp.oxs, hp.oys, hp.ozs, hp.ozs_host, hp.bev_mids, beta,
+                    dens, sem, rgb, base, rgb_p, seg_p, dep_p, bev_rgb, bev_seg, bev_h, vdens, vout, ws, ws.numel(),
+                    ws_bev, ws_bev.numel() if bev_save else 0, ctx.gbeta0 if train else None,
                     (_capi.VAMP_RENDERFWD_SAVE_SAMPLES if save else 0) | (_capi.VAMP_RENDERFWD_BEV_SAVE if bev_save else 0)
                     | flags | (_capi.VAMP_RENDERFWD_COUNTERS_CLEAN if (flags & _capi.VAMP_RENDERFWD_RANK) and hp._cam_clean_flag() else 0),
-                    _stream(st)), "vamp_render_forward_merged")
+                    _stream(st))
                 # (with VAMP_RENDERFWD_RANK the counters stay "in flight" until the "prep" op behind has scanned them)
             else:
-                _capi.check(hp.lib.vamp_render_bev_forward_ex(
-                    C.byref(d), _ptr(hp.oxs), _ptr(hp.oys), _ptr(hp.ozs), _ptr(hp.bev_mids), _ptr(beta),
-                    _ptr(dens), _ptr(sem), _ptr(rgb), _ptr(base), _ptr(bev_rgb), _ptr(bev_seg), _ptr(bev_h),
-                    _ptr(vdens), _ptr(vout), hp.ozs_host, _ptr(ws_bev), ws_bev.numel() if bev_save else 0,
-                    (_capi.VAMP_BEVFWD_SAVE if bev_save else 0) | bev_flags, _stream(st)), "vamp_render_bev_forward_ex")
+                hp.vamp.vamp_render_bev_forward_ex(d, hp.oxs, hp.oys, hp.ozs, hp.bev_mids, beta, dens, sem, rgb, base,
+                                                  bev_rgb, bev_seg, bev_h, vdens, vout, hp.ozs_host, ws_bev,
+                                                  ws_bev.numel() if bev_save else 0,
+                                                  (_capi.VAMP_BEVFWD_SAVE if bev_save else 0) | bev_flags, _stream(st))
             if op in ("render", "bev"):
                 hp._bev_gen = getattr(hp, "_bev_gen", 0) + 1
                 ctx.bev_key = (hp._bev_gen, ws_bev.data_ptr()) if bev_save else None
@@ -885,11 +827,11 @@ class _RenderFn(torch.autograd.Function):
         cont = lambda t: None if t is None else t.contiguous().float()
         g_rgb, g_seg, g_dep, g_brgb, g_bseg, g_bh, g_vd, g_vo = map(
             cont, (g_rgb, g_seg, g_dep, g_brgb, g_bseg, g_bh, g_vd, g_vo))
-        nbytes = hp.lib.vamp_render_workspace_bytes(C.byref(d))
+        nbytes = hp.vamp.vamp_render_workspace_bytes(d)
         if ctx.samples:
-            nbytes += hp.lib.vamp_render_samples_bytes(C.byref(d))
+            nbytes += hp.vamp.vamp_render_samples_bytes(d)
         ws = hp._workspace("render", nbytes)
-        ws_bev = hp._workspace("bev", hp.lib.vamp_render_bev_workspace_bytes(C.byref(d)))
+        ws_bev = hp._workspace("bev", hp.vamp.vamp_render_bev_workspace_bytes(d))
         # every gradient buffer is written in full by the calls below (the BEV branch overwrites,
         # the camera branch adds, or the other way round): no zero fills
         gb = torch.empty(base.shape, dtype=f32, device=dens.device)
@@ -914,16 +856,12 @@ class _RenderFn(torch.autograd.Function):
                 flags |= _capi.VAMP_BEVBWD_TABLE_VALID
             if bev_saved:
                 flags |= _capi.VAMP_BEVBWD_SAVED_VALID
-            _capi.check(hp.lib.vamp_render_bev_backward_ex(
-                C.byref(d), _ptr(hp.oxs), _ptr(hp.oys), _ptr(hp.ozs), _ptr(hp.bev_mids), _ptr(beta),
-                _ptr(dens), _ptr(sem), _ptr(rgb), _ptr(base), _ptr(g_brgb), _ptr(g_bseg), _ptr(g_bh),
-                _ptr(g_vd), _ptr(g_vo), _ptr(gd), _ptr(gs), _ptr(gr), _ptr(gb), _ptr(gbeta),
-                None if hp.impl["bev_bwd"] == "v1" else hp.ozs_host, _ptr(ws_bev), ws_bev.numel(),
-                flags, _stream(stream)), "vamp_render_bev_backward_ex")
+            hp.vamp.vamp_render_bev_backward_ex(d, hp.oxs, hp.oys, hp.ozs, hp.bev_mids, beta, dens, sem, rgb, base,
+                                               g_brgb, g_bseg, g_bh, g_vd, g_vo, gd, gs, gr, gb, gbeta,
+                                               None if hp.impl["bev_bwd"] == "v1" else hp.ozs_host, ws_bev,
+                                               ws_bev.numel(), flags, _stream(stream))
 
-        cam_args = (C.byref(d), _ptr(geom), _ptr(mats), _ptr(hp.us), _ptr(hp.vs), _ptr(hp.ds),
-                    _ptr(hp.camera_mids), _ptr(beta), _ptr(dens), _ptr(sem), _ptr(rgb), _ptr(g_rgb),
-                    _ptr(g_seg), _ptr(g_dep))
+        cam_args = (d, geom, mats, hp.us, hp.vs, hp.ds, hp.camera_mids, beta, dens, sem, rgb, g_rgb, g_seg, g_dep)
         cur, side = torch.cuda.current_stream(), hp._side_stream()
         default_impl = hp.impl["cam_bwd"] != "v1"
         if not default_impl or geom is not None or not ctx.cells:
@@ -961,9 +899,8 @@ class _RenderFn(torch.autograd.Function):
             cam_flags = 1 | packed_valid
 
             def cam_part(part, stream, event=None):
-                _capi.check(hp.lib.vamp_render_camera_backward_acc(
-                    *cam_args, _ptr(gd), _ptr(gs), _ptr(gr), _ptr(gbeta), _ptr(ws), ws.numel(), cam_flags | part,
-                    event, _stream(stream)), "vamp_render_camera_backward_acc")
+                hp.vamp.vamp_render_camera_backward_acc(*cam_args, gd, gs, gr, gbeta, ws, ws.numel(), cam_flags | part,
+                                                       event, _stream(stream))
 
             # (cfg-B replayed: 0.3625 - 0.370 ms/step against 0.3735 with the BEV chain issued first.)
             cam_part(_capi.VAMP_CAMBWD_PART_RAY | _capi.VAMP_CAMBWD_PART_HEAVY, s_cam)
@@ -976,14 +913,12 @@ class _RenderFn(torch.autograd.Function):
             cur.wait_stream(side)
         elif geom is None and default_impl:
             bev_backward(cur, True)
-            _capi.check(hp.lib.vamp_render_camera_backward_acc(
-                *cam_args, _ptr(gd), _ptr(gs), _ptr(gr), _ptr(gbeta), _ptr(ws), ws.numel(), 1 | packed_valid,
-                None, _stream(cur)), "vamp_render_camera_backward_acc")
+            hp.vamp.vamp_render_camera_backward_acc(*cam_args, gd, gs, gr, gbeta, ws, ws.numel(), 1 | packed_valid, None,
+                                                   _stream(cur))
         else:
-            _capi.check(hp.lib.vamp_render_camera_backward_acc(
-                *cam_args, _ptr(gd), _ptr(gs), _ptr(gr), _ptr(gbeta), _ptr(ws), ws.numel(),
-                packed_valid | (0 if default_impl else _capi.VAMP_CAMBWD_SPLAT), None, _stream(cur)),
-                "vamp_render_camera_backward_acc")
+            hp.vamp.vamp_render_camera_backward_acc(*cam_args, gd, gs, gr, gbeta, ws, ws.numel(),
+                                                   packed_valid | (0 if default_impl else _capi.VAMP_CAMBWD_SPLAT),
+                                                   None, _stream(cur))
             bev_backward(cur, False)
         grad_beta = gbeta.reshape(ctx.beta_shape) if hp.cfg.density_mode == "sdf" else None
         dt = ctx.in_dtypes
@@ -1010,8 +945,7 @@ class _SamplePointsFn(torch.autograd.Function):
         d.padding = _capi.VAMP_PAD_BORDER if padding == "border" else _capi.VAMP_PAD_ZEROS
         d.mask_outside = 1 if mask_outside else 0
         d.activation = 1 if activation else 0
-        d.density_mode = (_capi.VAMP_DENSITY_SDF_LAPLACE if c.density_mode == "sdf"
-                          else _capi.VAMP_DENSITY_SIGMOID)
+        d.density_mode = _density_code(c)
         d.sdf_bias, d.beta_min = c.sdf_bias, 1e-4
         d.channel_last_out = 1 if channel_last else 0
         d.in_dtype = _dtype_code(volume)
@@ -1021,9 +955,7 @@ class _SamplePointsFn(torch.autograd.Function):
         beta = beta.reshape(1).float().contiguous()
         out = torch.empty((B, P, C_) if channel_last else (B, C_, P), dtype=torch.float32,
                           device=volume.device)
-        _capi.check(hp.lib.vamp_sample_points_forward(C.byref(d), _ptr(volume), _ptr(beta), _ptr(points),
-                                                      P, _ptr(out), _stream()),
-                    "vamp_sample_points_forward")
+        hp.vamp.vamp_sample_points_forward(d, volume, beta, points, P, out, _stream())
         ctx.hp, ctx.desc, ctx.P, ctx.activation = hp, d, P, activation
         ctx.save_for_backward(volume, points, beta)
         return out
@@ -1035,10 +967,8 @@ class _SamplePointsFn(torch.autograd.Function):
         g = g.contiguous().float()
         gvol = torch.empty(volume.shape, dtype=torch.float32, device=volume.device)
         gbeta = torch.zeros(1, dtype=torch.float32, device=volume.device)
-        ws = hp._workspace("sample", hp.lib.vamp_sample_points_workspace_bytes(C.byref(d), P))
-        _capi.check(hp.lib.vamp_sample_points_backward(
-            C.byref(d), _ptr(volume), _ptr(beta), _ptr(points), P, _ptr(g), _ptr(gvol), _ptr(gbeta),
-            _ptr(ws), ws.numel(), _stream()), "vamp_sample_points_backward")
+        ws = hp._workspace("sample", hp.vamp.vamp_sample_points_workspace_bytes(d, P))
+        hp.vamp.vamp_sample_points_backward(d, volume, beta, points, P, g, gvol, gbeta, ws, ws.numel(), _stream())
         grad_beta = (gbeta.reshape(ctx.beta_shape)
                      if (ctx.activation and hp.cfg.density_mode == "sdf") else None)
         return None, gvol.to(ctx.in_dtype), None, grad_beta, None, None, None, None, None
@@ -1057,8 +987,7 @@ class _DepthSoftmaxFn(torch.autograd.Function):
         HW = logits[0, 0].numel()
         out = torch.empty(logits.shape, dtype=torch.float32, device=logits.device)
         if logits.numel():
-            _capi.check(hp.lib.vamp_depth_softmax_forward(images, D, HW, _ptr(logits), _dtype_code(logits),
-                                                          _ptr(out), _stream()), "vamp_depth_softmax_forward")
+            hp.vamp.vamp_depth_softmax_forward(images, D, HW, logits, _dtype_code(logits), out, _stream())
         ctx.hp, ctx.dims = hp, (images, D, HW)
         ctx.save_for_backward(out)
         return out
@@ -1069,8 +998,7 @@ class _DepthSoftmaxFn(torch.autograd.Function):
         g = g.contiguous().float()
         gx = torch.empty_like(p)
         if p.numel():
-            _capi.check(ctx.hp.lib.vamp_depth_softmax_backward(*ctx.dims, _ptr(p), _ptr(g), _ptr(gx), _stream()),
-                        "vamp_depth_softmax_backward")
+            ctx.hp.vamp.vamp_depth_softmax_backward(*ctx.dims, p, g, gx, _stream())
         return None, gx.to(ctx.in_dtype)
 
 
@@ -1083,11 +1011,10 @@ class _DensityGateFn(torch.autograd.Function):
         vd = _chk(vd.float(), (B, 1) + tuple(vo.shape[2:]), "voxel_density")
         vo = vo.float().contiguous()
         cells = vd[0].numel()
-        mode = (_capi.VAMP_DENSITY_SDF_LAPLACE if hp.cfg.density_mode == "sdf" else _capi.VAMP_DENSITY_SIGMOID)
+        mode = _density_code(hp.cfg)
         out = torch.empty_like(vo)
         if vo.numel():
-            _capi.check(hp.lib.vamp_density_gate_forward(B, C_, cells, mode, _ptr(vo), _ptr(vd), _ptr(out),
-                                                         _stream()), "vamp_density_gate_forward")
+            hp.vamp.vamp_density_gate_forward(B, C_, cells, mode, vo, vd, out, _stream())
         ctx.hp, ctx.dims = hp, (B, C_, cells, mode)
         ctx.save_for_backward(vo, vd)
         return out
@@ -1098,8 +1025,7 @@ class _DensityGateFn(torch.autograd.Function):
         g = g.contiguous().float()
         gvo, gvd = torch.empty_like(vo), torch.empty_like(vd)
         if vo.numel():
-            _capi.check(ctx.hp.lib.vamp_density_gate_backward(*ctx.dims, _ptr(g), _ptr(vo), _ptr(vd), _ptr(gvo),
-                                                              _ptr(gvd), _stream()), "vamp_density_gate_backward")
+            ctx.hp.vamp.vamp_density_gate_backward(*ctx.dims, g, vo, vd, gvo, gvd, _stream())
         return None, gvo, gvd
 
 
@@ -1116,11 +1042,10 @@ class _GateConvFn(torch.autograd.Function):
         vo = vo.float().contiguous()
         w = _chk(weight.float().reshape(cout, -1), (cout, C_ * oZ), "weight")
         bs = None if bias is None else _chk(bias.float(), (cout,), "bias")
-        mode = (_capi.VAMP_DENSITY_SDF_LAPLACE if hp.cfg.density_mode == "sdf" else _capi.VAMP_DENSITY_SIGMOID)
+        mode = _density_code(hp.cfg)
         out = torch.empty((B, cout) + plane, dtype=torch.float32, device=vo.device)
         dims = (B, C_, oZ, cells, cout, mode)
-        _capi.check(hp.lib.vamp_gate_conv1x1_forward(*dims, _ptr(vo), _ptr(vd), _ptr(w), _ptr(bs), _ptr(out),
-                                                     _stream()), "vamp_gate_conv1x1_forward")
+        hp.vamp.vamp_gate_conv1x1_forward(*dims, vo, vd, w, bs, out, _stream())
         ctx.hp, ctx.dims, ctx.wshape, ctx.has_bias = hp, dims, tuple(weight.shape), bias is not None
         ctx.dtypes = (weight.dtype, None if bias is None else bias.dtype)
         ctx.save_for_backward(vo, vd, w)
@@ -1134,595 +1059,7 @@ class _GateConvFn(torch.autograd.Function):
         gvo, gvd, gw = torch.empty_like(vo), torch.empty_like(vd), torch.empty_like(w)
         gb = torch.empty(w.shape[0], dtype=torch.float32, device=w.device) if ctx.has_bias else None
         B, C_, oZ, cells, cout, mode = ctx.dims
-        ws = hp._workspace("gate_conv", hp.lib.vamp_gate_conv1x1_workspace_bytes(C_, oZ, cout))
-        _capi.check(hp.lib.vamp_gate_conv1x1_backward(*ctx.dims, _ptr(g), _ptr(vo), _ptr(vd), _ptr(w), _ptr(gvo),
-                                                      _ptr(gvd), _ptr(gw), _ptr(gb), _ptr(ws), ws.numel(), _stream()),
-                    "vamp_gate_conv1x1_backward")
+        ws = hp._workspace("gate_conv", hp.vamp.vamp_gate_conv1x1_workspace_bytes(C_, oZ, cout))
+        hp.vamp.vamp_gate_conv1x1_backward(*ctx.dims, g, vo, vd, w, gvo, gvd, gw, gb, ws, ws.numel(), _stream())
         return (None, gvo, gvd, gw.reshape(ctx.wshape).to(ctx.dtypes[0]),
                 None if gb is None else gb.to(ctx.dtypes[1]))
-
-
-# ===========================================================================
-# BEVDepth-style voxel pooling (north_star; SURVEY 8 row a11 -- not in the reference tree, parity unpinned)
-# ===========================================================================
-_pool_ws = {}
-
-
-def voxel_pooling(geom_xyz, input_features, voxel_num):
-    """The published BEVDepth operator `voxel_pooling(geom_xyz, input_features, voxel_num)`:
-    geom_xyz [B, N, D, H, W, 3] integer voxel indices (x, y, z), input_features [B, N, D, H, W, C]
-    (fp32 | bf16), voxel_num (nx, ny, nz) -> [B, C, ny, nx] fp32, the sum of the features of the points
-    falling into each BEV cell (points outside the grid are dropped).  HIP kernels, no CPU fallback."""
-    return _VoxelPoolingFn.apply(geom_xyz, input_features, tuple(int(v) for v in voxel_num))
-
-
-class _VoxelPoolingFn(torch.autograd.Function):
-    @staticmethod
-    def forward(ctx, geom, feat, voxel_num):
-        if not (geom.is_cuda and feat.is_cuda):
-            raise _capi.VampireHipError("voxel_pooling needs device tensors (no CPU fallback)")
-        lib = _capi.load()
-        B, C_ = feat.shape[0], feat.shape[-1]
-        P = feat[0].numel() // C_
-        ctx.in_dtype, ctx.fshape = feat.dtype, tuple(feat.shape)
-        feat = _accept(feat).reshape(B, P, C_).contiguous()
-        geom = _chk(geom.reshape(B, P, 3).to(torch.int32), (B, P, 3), "geom_xyz")
-        d = _capi.VampPoolDesc(B, C_, P, voxel_num[0], voxel_num[1], voxel_num[2], _dtype_code(feat))
-        out = torch.empty(B, voxel_num[1], voxel_num[0], C_, dtype=torch.float32, device=feat.device)
-        nbytes = lib.vamp_voxel_pooling_workspace_bytes(C.byref(d))
-        key = (feat.device, torch.cuda.current_stream().cuda_stream)
-        ws = _pool_ws.get(key)
-        if ws is None or ws.numel() < nbytes:
-            ws = _pool_ws[key] = torch.empty(max(nbytes, 256), dtype=torch.uint8, device=feat.device)
-        with torch.cuda.device(feat.device):
-            _capi.check(lib.vamp_voxel_pooling_forward(C.byref(d), _ptr(geom), _ptr(feat), _ptr(out), _ptr(ws),
-                                                       ws.numel(), _stream()), "vamp_voxel_pooling_forward")
-        ctx.desc = d
-        ctx.save_for_backward(geom)
-        return out.permute(0, 3, 1, 2)
-
-    @staticmethod
-    def backward(ctx, g):
-        (geom,) = ctx.saved_tensors
-        d = ctx.desc
-        g = g.permute(0, 2, 3, 1).contiguous().float()
-        gfeat = torch.empty(d.B, d.P, d.C, dtype=torch.float32, device=g.device)
-        with torch.cuda.device(g.device):
-            _capi.check(_capi.load().vamp_voxel_pooling_backward(C.byref(d), _ptr(geom), _ptr(g), _ptr(gfeat), _stream()),
-                        "vamp_voxel_pooling_backward")
-        return None, gfeat.reshape(ctx.fshape).to(ctx.in_dtype), None
-
-
-# ===========================================================================
-# trilinear resize of the 3-D UNet (SURVEY 8f N3, first piece)
-# ===========================================================================
-_resize_ws = {}
-
-
-def upsample_trilinear(x, size):
-    """F.interpolate(x, size, mode='trilinear', align_corners=True) (bv2:66, 72) on the HIP
-    kernels: x [B,C,z,y,x] fp32 device tensor -> [B,C,*size]; the backward is a gather (aten's
-    float-atomic scatter takes 2.2 ms per call at the UNet's full-resolution level)."""
-    return _UpsampleTrilinearFn.apply(x, tuple(int(v) for v in size))
-
-
-class _UpsampleTrilinearFn(torch.autograd.Function):
-    @staticmethod
-    def forward(ctx, x, size):
-        if not x.is_cuda:
-            raise _capi.VampireHipError("x must be a device tensor (no CPU fallback)")
-        if x.dim() != 5 or len(size) != 3:
-            raise ValueError("expected a [B,C,z,y,x] tensor and a 3-tuple size")
-        lib = _capi.load()
-        ctx.in_dtype = x.dtype
-        codes = {torch.float32: _capi.VAMP_F32, torch.bfloat16: _capi.VAMP_BF16, torch.float16: _capi.VAMP_F16}
-        if x.dtype not in codes:
-            x = x.float()
-        x = x.contiguous()
-        ctx.code = codes[x.dtype]
-        B, C_ = x.shape[:2]
-        out = torch.empty((B, C_) + size, dtype=x.dtype, device=x.device)
-        if out.numel() and x.numel():
-            _capi.check(lib.vamp_upsample_trilinear_forward_ex(B * C_, *x.shape[2:], *size, ctx.code, _ptr(x), _ptr(out),
-                                                               _stream()), "vamp_upsample_trilinear_forward_ex")
-        ctx.lib, ctx.dims = lib, (B * C_,) + tuple(x.shape[2:]) + size
-        ctx.in_shape = tuple(x.shape)
-        return out
-
-    @staticmethod
-    def backward(ctx, g):
-        dt = {_capi.VAMP_F32: torch.float32, _capi.VAMP_BF16: torch.bfloat16, _capi.VAMP_F16: torch.float16}[ctx.code]
-        g = g.contiguous().to(dt)
-        gin = torch.empty(ctx.in_shape, dtype=dt, device=g.device)
-        if gin.numel() and g.numel():
-            lib = ctx.lib
-            nbytes = lib.vamp_upsample_trilinear_workspace_bytes(*ctx.dims[1:4])
-            key = (g.device, torch.cuda.current_stream().cuda_stream, nbytes)   # one table per stream
-            ws = _resize_ws.get(key)
-            if ws is None:
-                ws = _resize_ws[key] = torch.empty(nbytes, dtype=torch.uint8, device=g.device)
-            _capi.check(lib.vamp_upsample_trilinear_backward_ex(*ctx.dims, ctx.code, _ptr(g), _ptr(gin), _ptr(ws), ws.numel(),
-                                                                _stream()), "vamp_upsample_trilinear_backward_ex")
-        else:
-            gin.zero_()
-        return gin.to(ctx.in_dtype), None
-
-
-# ===========================================================================
-# 3x3x3 convolutions of the 3-D UNet (SURVEY 8f N3)
-# ===========================================================================
-def conv3d_3x3x3(x, weight):
-    """nn.Conv3d(cin, cout, 3, 1, 1, bias=False) (bv2:20, 40-60) on the fp32 matrix cores:
-    x [B,cin,Z,Y,X], weight [cout,cin,3,3,3], cin / cout in {16, 32}; fp32 device tensors."""
-    return _Conv3dFn.apply(x, weight)
-
-
-def conv3d_bf16(x, weight):
-    """The same layer in bf16 (what the reference's `precision=16` training hands it): x bf16 [B,cin,Z,Y,X],
-    weight bf16 [cout,cin,3,3,3] -> bf16 [B,cout,Z,Y,X]; fp32 accumulation on the bf16 matrix cores."""
-    return _Conv3dBf16Fn.apply(x, weight)
-
-
-def conv3d_bf16_supported(x, weight, stride, padding, bias):
-    if not (x.is_cuda and x.dtype in (torch.bfloat16, torch.float16) and bias is None and tuple(stride) == (1, 1, 1)
-            and tuple(padding) == (1, 1, 1) and tuple(weight.shape[2:]) == (3, 3, 3) and x.dim() == 5
-            and weight.shape[1] == x.shape[1]):
-        return False
-    d = _capi.VampConvDesc()
-    d.B, d.cin, d.Z, d.Y, d.X = x.shape
-    d.cout = weight.shape[0]
-    return bool(_capi.load().vamp_conv3d_bf16_supported(C.byref(d)))
-
-
-class _Conv3dBf16Fn(torch.autograd.Function):
-    @staticmethod
-    def forward(ctx, x, w):
-        if not (x.is_cuda and w.is_cuda):
-            raise _capi.VampireHipError("x / weight must be device tensors (no CPU fallback)")
-        if x.dtype not in (torch.bfloat16, torch.float16) or w.dtype != x.dtype or x.dim() != 5 or w.dim() != 5:
-            raise TypeError("conv3d_bf16 takes bf16 (or fp16) [B,cin,Z,Y,X] and [cout,cin,3,3,3] tensors of one dtype")
-        code = _capi.VAMP_BF16 if x.dtype == torch.bfloat16 else _capi.VAMP_F16
-        lib = _capi.load()
-        x, w = x.contiguous(), w.contiguous()
-        d = _capi.VampConvDesc()
-        d.B, d.cin, d.Z, d.Y, d.X = x.shape
-        d.cout = w.shape[0]
-        if w.shape[1] != d.cin:
-            raise ValueError("weight / input channel mismatch")
-        out = torch.empty((d.B, d.cout, d.Z, d.Y, d.X), dtype=x.dtype, device=x.device)
-        _capi.check(lib.vamp_conv3d_half_forward(C.byref(d), code, _ptr(x), _ptr(w), _ptr(out), _stream()),
-                    "vamp_conv3d_half_forward")
-        ctx.lib, ctx.desc, ctx.code = lib, d, code
-        ctx.save_for_backward(x, w)
-        return out
-
-    @staticmethod
-    def backward(ctx, g):
-        x, w = ctx.saved_tensors
-        lib, d = ctx.lib, ctx.desc
-        g = g.contiguous().to(x.dtype)
-        gx = gw = None
-        if ctx.needs_input_grad[0]:
-            gx = torch.empty_like(x)
-            _capi.check(lib.vamp_conv3d_half_backward_data(C.byref(d), ctx.code, _ptr(g), _ptr(w), _ptr(gx), _stream()),
-                        "vamp_conv3d_half_backward_data")
-        if ctx.needs_input_grad[1]:
-            gw32 = torch.empty(w.shape, dtype=torch.float32, device=w.device)
-            nbytes = lib.vamp_conv3d_bf16_workspace_bytes(C.byref(d))
-            key = (g.device, torch.cuda.current_stream().cuda_stream, "conv16", nbytes)
-            ws = _resize_ws.get(key)
-            if ws is None:
-                ws = _resize_ws[key] = torch.empty(nbytes, dtype=torch.uint8, device=g.device)
-            _capi.check(lib.vamp_conv3d_half_backward_weight(C.byref(d), ctx.code, _ptr(x), _ptr(g), _ptr(gw32), _ptr(ws),
-                                                             ws.numel(), _stream()), "vamp_conv3d_half_backward_weight")
-            gw = gw32.to(w.dtype)                 # the gradient of the 16-bit copy autocast made of the fp32 parameter
-        return gx, gw
-
-
-def conv3d_supported(x, weight, stride, padding, bias):
-    if not (x.is_cuda and x.dtype == torch.float32 and weight.dtype == torch.float32 and bias is None
-            and tuple(stride) == (1, 1, 1) and tuple(padding) == (1, 1, 1) and tuple(weight.shape[2:]) == (3, 3, 3)
-            and x.dim() == 5 and weight.shape[1] == x.shape[1] and not torch.is_autocast_enabled()):
-        return False
-    d = _capi.VampConvDesc()
-    d.B, d.cin, d.Z, d.Y, d.X = x.shape
-    d.cout = weight.shape[0]
-    return bool(_capi.load().vamp_conv3d_supported(C.byref(d)))
-
-
-class _Conv3dFn(torch.autograd.Function):
-    @staticmethod
-    def forward(ctx, x, w):
-        if not (x.is_cuda and w.is_cuda):
-            raise _capi.VampireHipError("x / weight must be device tensors (no CPU fallback)")
-        if x.dtype != torch.float32 or w.dtype != torch.float32 or x.dim() != 5 or w.dim() != 5:
-            raise TypeError("conv3d_3x3x3 takes fp32 [B,cin,Z,Y,X] and [cout,cin,3,3,3] tensors")
-        lib = _capi.load()
-        x, w = x.contiguous(), w.contiguous()
-        d = _capi.VampConvDesc()
-        d.B, d.cin, d.Z, d.Y, d.X = x.shape
-        d.cout = w.shape[0]
-        if w.shape[1] != d.cin:
-            raise ValueError("weight / input channel mismatch")
-        out = torch.empty((d.B, d.cout, d.Z, d.Y, d.X), dtype=torch.float32, device=x.device)
-        _capi.check(lib.vamp_conv3d_forward(C.byref(d), _ptr(x), _ptr(w), _ptr(out), _stream()),
-                    "vamp_conv3d_forward")
-        ctx.lib, ctx.desc = lib, d
-        ctx.save_for_backward(x, w)
-        return out
-
-    @staticmethod
-    def backward(ctx, g):
-        x, w = ctx.saved_tensors
-        lib, d = ctx.lib, ctx.desc
-        g = g.contiguous().float()
-        gx = gw = None
-        if ctx.needs_input_grad[0]:
-            gx = torch.empty_like(x)
-            _capi.check(lib.vamp_conv3d_backward_data(C.byref(d), _ptr(g), _ptr(w), _ptr(gx), _stream()),
-                        "vamp_conv3d_backward_data")
-        if ctx.needs_input_grad[1]:
-            gw = torch.empty_like(w)
-            nbytes = lib.vamp_conv3d_workspace_bytes(C.byref(d))
-            key = (g.device, torch.cuda.current_stream().cuda_stream, "conv", nbytes)
-            ws = _resize_ws.get(key)
-            if ws is None:
-                ws = _resize_ws[key] = torch.empty(nbytes, dtype=torch.uint8, device=g.device)
-            _capi.check(lib.vamp_conv3d_backward_weight(C.byref(d), _ptr(x), _ptr(g), _ptr(gw), _ptr(ws),
-                                                        ws.numel(), _stream()), "vamp_conv3d_backward_weight")
-        return gx, gw
-
-
-# ===========================================================================
-# segmentation metrics (base_exp.py:370-382, :634-663, :835-840)
-# ===========================================================================
-_metric_ws = {}
-_TARGET_CODES = {torch.int64: _capi.VAMP_I64, torch.int32: _capi.VAMP_I32, torch.uint8: _capi.VAMP_U8}
-_PRED_CODES = {torch.float32: _capi.VAMP_F32, torch.bfloat16: _capi.VAMP_BF16,
-               torch.int64: _capi.VAMP_I64, torch.int32: _capi.VAMP_I32}
-
-
-def _metric_workspace(kind, device, nbytes):
-    key = (kind, device, torch.cuda.current_stream(device).cuda_stream)
-    ws = _metric_ws.get(key)
-    if ws is None or ws.numel() < nbytes:
-        ws = _metric_ws[key] = torch.empty(max(nbytes, 256), dtype=torch.uint8, device=device)
-    return ws
-
-
-def _logit_layout(x):
-    """(layout, B, S, x) for logits [..., K]: rows when contiguous, planes when the memory is channel-first
-    ([B, K, ...] behind a permute(0, 2, .., 1) view, the backbone's occ_logits), else a contiguous copy."""
-    if x.is_contiguous():
-        return _capi.VAMP_SEG_ROWS, 1, x.numel() // max(x.shape[-1], 1), x
-    if x.dim() == 2 and x.t().is_contiguous():
-        return _capi.VAMP_SEG_PLANES, 1, x.shape[0], x
-    if x.dim() >= 3 and x.movedim(-1, 1).is_contiguous():
-        return _capi.VAMP_SEG_PLANES, x.shape[0], math.prod(x.shape[1:-1]), x
-    x = x.contiguous()
-    return _capi.VAMP_SEG_ROWS, 1, x.numel() // max(x.shape[-1], 1), x
-
-
-def confusion_update(confmat, invalid, logits_or_preds, target, mask=None, *, class_window=None, ignore_index=None):
-    """confmat[t, p] += 1 for every element with mask true and target t != ignore_index, where p =
-    lo + argmax(logits[..., lo:hi]) (torch.argmax ties and NaNs) or the integer prediction itself; targets
-    (and integer predictions) outside [0, Kc) add 1 to `invalid` instead.  confmat: int64 [Kc, Kc], invalid:
-    int64 with one element, both device tensors, accumulated.  logits [..., K] fp32 | bf16 (fp16 promoted),
-    target / mask shaped like logits[..., 0] (or like the integer predictions); target int64 | int32 | uint8.
-    One HIP pass on the current stream; no host synchronisation, capturable in a graph."""
-    x = logits_or_preds
-    if not (confmat.is_cuda and invalid.is_cuda and x.is_cuda and target.is_cuda and (mask is None or mask.is_cuda)):
-        raise _capi.VampireHipError("confusion_update needs device tensors (no CPU fallback)")
-    if confmat.dtype != torch.int64 or confmat.dim() != 2 or confmat.shape[0] != confmat.shape[1] \
-            or not confmat.is_contiguous():
-        raise ValueError("confmat must be a contiguous int64 [Kc, Kc] tensor")
-    if invalid.dtype != torch.int64 or invalid.numel() != 1:
-        raise ValueError("invalid must be a one-element int64 tensor")
-    Kc = confmat.shape[0]
-    integer = not x.is_floating_point()
-    if integer:
-        if tuple(x.shape) != tuple(target.shape):
-            raise ValueError(f"predictions {tuple(x.shape)} and target {tuple(target.shape)} differ in shape")
-        if x.dtype not in (torch.int64, torch.int32):
-            x = x.long()
-        layout, B, S, x, K = _capi.VAMP_SEG_ROWS, 1, x.numel(), x.contiguous(), 1
-        lo, hi = 0, 1
-    else:
-        x = _accept(x)
-        if tuple(x.shape[:-1]) != tuple(target.shape):
-            raise ValueError(f"logits {tuple(x.shape)} do not match target {tuple(target.shape)}")
-        K = x.shape[-1]
-        lo, hi = (0, K) if class_window is None else (int(class_window[0]), int(class_window[1]))
-        layout, B, S, x = _logit_layout(x)
-    if target.dtype not in _TARGET_CODES:
-        target = target.long()
-    target = target.contiguous()
-    if mask is not None:
-        if tuple(mask.shape) != tuple(target.shape):
-            raise ValueError(f"mask {tuple(mask.shape)} does not match target {tuple(target.shape)}")
-        mask = (mask if mask.dtype == torch.bool else mask != 0).contiguous()
-    d = _capi.VampConfDesc(B, S, K, layout, _PRED_CODES[x.dtype], _TARGET_CODES[target.dtype], Kc, lo, hi,
-                           0 if ignore_index is None else int(ignore_index), 0 if ignore_index is None else 1, 0)
-    lib = _capi.load()
-    nbytes = lib.vamp_confusion_workspace_bytes(C.byref(d))
-    if nbytes == 0:
-        _capi.check(lib.vamp_confusion_update(C.byref(d), None, None, None, None, None, None, 0, None),
-                    "vamp_confusion_update")
-    with torch.cuda.device(x.device):
-        ws = _metric_workspace("confusion", x.device, nbytes)
-        _capi.check(lib.vamp_confusion_update(C.byref(d), _ptr(x), _ptr(target), _ptr(mask), _ptr(confmat),
-                                              _ptr(invalid), _ptr(ws), ws.numel(), _stream()),
-                    "vamp_confusion_update")
-    return confmat
-
-
-def lidarseg_predict(pts_logits, ref_index, num_ref, class_window):
-    """The reference's lidar-segmentation prediction (base_exp.py:645-649, :835-838): zeros [num_ref, K],
-    index_add_(0, ref_index, pts_logits), then lo + argmax over classes [lo, hi).  Sums run in increasing
-    point order (bit-exact against a sequential CPU index_add_).  Returns (labels int64 [num_ref], invalid
-    int64 0-dim: the number of points whose index lies outside [0, num_ref)).  HIP kernels on the current
-    stream; no host synchronisation."""
-    if not (pts_logits.is_cuda and ref_index.is_cuda):
-        raise _capi.VampireHipError("lidarseg_predict needs device tensors (no CPU fallback)")
-    if pts_logits.dim() != 2 or ref_index.dim() != 1 or ref_index.shape[0] != pts_logits.shape[0]:
-        raise ValueError(f"expected pts_logits [P, K] and ref_index [P], got {tuple(pts_logits.shape)} "
-                         f"and {tuple(ref_index.shape)}")
-    x = _accept(pts_logits).contiguous()
-    idx = ref_index.long().contiguous()
-    P, K = x.shape
-    lo, hi = int(class_window[0]), int(class_window[1])
-    num_ref = int(num_ref)
-    labels = torch.empty(num_ref, dtype=torch.int64, device=x.device)
-    invalid = torch.empty((), dtype=torch.int64, device=x.device)
-    lib = _capi.load()
-    with torch.cuda.device(x.device):
-        ws = _metric_workspace("lidarseg", x.device, lib.vamp_lidarseg_workspace_bytes(P, num_ref))
-        _capi.check(lib.vamp_lidarseg_predict(P, K, _dtype_code(x), lo, hi, _ptr(x), _ptr(idx), num_ref, _ptr(labels),
-                                              _ptr(invalid), _ptr(ws), ws.numel(), _stream()),
-                    "vamp_lidarseg_predict")
-    return labels, invalid
-
-
-# ===========================================================================
-# detection post-processing (bev_depth_head.py:381-494)
-# ===========================================================================
-_DET_DTYPES = {torch.float32: _capi.VAMP_F32, torch.bfloat16: _capi.VAMP_BF16, torch.float16: _capi.VAMP_F16}
-_NMS_KINDS = {"circle": _capi.VAMP_NMS_CIRCLE, "size_aware_circle": _capi.VAMP_NMS_SIZE_AWARE,
-              "rotate": _capi.VAMP_NMS_ROTATE}
-
-
-@dataclasses.dataclass
-class DetResult:
-    """Fixed-capacity detections of a batch: boxes [B, T * P, 9 | 7] fp32, scores [B, T * P] (heatmap dtype),
-    labels [B, T * P] int32, counts [B] int32; rows at or beyond counts[b] are zero."""
-    boxes: torch.Tensor
-    scores: torch.Tensor
-    labels: torch.Tensor
-    counts: torch.Tensor
-
-    def to_list(self):
-        """get_bboxes's return value, [[bboxes, scores, labels], ...] per sample (one host synchronisation)."""
-        n = self.counts.tolist()
-        return [[self.boxes[b, :k], self.scores[b, :k], self.labels[b, :k]] for b, k in enumerate(n)]
-
-
-def _cfg(c, name, default=None):
-    if isinstance(c, dict):
-        return c.get(name, default)
-    return getattr(c, name, default)
-
-
-def _per_task(v, T, name):
-    if v is None:
-        return [0.0] * T
-    if isinstance(v, (int, float)):
-        return [float(v)] * T
-    if len(v) < T:
-        raise ValueError(f"test_cfg['{name}'] has {len(v)} entries for {T} tasks")
-    return [float(x) for x in v[:T]]
-
-
-def det_postprocess(task_preds, coder_cfg, test_cfg, num_classes, norm_bbox, out=None):
-    """BEVDepthHead.get_bboxes on the device (vamp_det_postprocess): sigmoid, the deterministic top-K (score
-    descending, flat index ascending), CenterPointBBoxCoder.decode, the score and centre filters and test_cfg's
-    nms_type -- 'circle', 'size_aware_circle' or 'rotate' (rotated BEV IoU > nms_thr, after pre_max_size) --
-    for every task and sample in four launches, without a host synchronisation (capturable in a graph).
-    task_preds: the head's preds_dicts ([[{'heatmap', 'reg', 'height', 'dim', 'rot'[, 'vel']}], ...]);
-    coder_cfg: the bbox_coder config (dict or CenterPointBBoxCoder); num_classes: classes per task.
-    out: a DetResult of preallocated buffers to write (graph capture).  Returns a DetResult."""
-    heads = [pd[0] for pd in task_preds]
-    T = len(heads)
-    if not 1 <= T <= 8 or len(num_classes) < T:
-        raise ValueError(f"{T} tasks with {len(num_classes)} class counts (1 to 8 tasks)")
-    keys = ["heatmap", "reg", "height", "dim", "rot"]
-    has_vel = "vel" in heads[0]
-    if has_vel:
-        keys.append("vel")
-    tensors = [[h[k] for k in keys] for h in heads]
-    if not all(x.is_cuda for ts in tensors for x in ts):
-        raise _capi.VampireHipError("det_postprocess needs device tensors (no CPU fallback)")
-    dtype = heads[0]["heatmap"].dtype
-    if dtype not in _DET_DTYPES or any(x.dtype != dtype for ts in tensors for x in ts):
-        raise TypeError(f"head tensors must all be fp32, bf16 or fp16 of one dtype, got {dtype}")
-    B, _, H, W = heads[0]["heatmap"].shape
-    chans = {"reg": 2, "height": 1, "dim": 3, "rot": 2, "vel": 2}
-    for t, h in enumerate(heads):
-        if h["heatmap"].dim() != 4 or h["heatmap"].shape[0] != B or tuple(h["heatmap"].shape[2:]) != (H, W):
-            raise ValueError(f"task {t}: heatmap {tuple(h['heatmap'].shape)} does not match [{B}, *, {H}, {W}]")
-        if h["heatmap"].shape[1] != num_classes[t]:
-            raise ValueError(f"task {t}: heatmap has {h['heatmap'].shape[1]} classes, num_classes says {num_classes[t]}")
-        for k, c in chans.items():
-            if k in keys and tuple(h[k].shape) != (B, c, H, W):
-                raise ValueError(f"task {t}: {k} {tuple(h[k].shape)} is not [{B}, {c}, {H}, {W}]")
-    tensors = [[x.contiguous() for x in ts] for ts in tensors]
-    kind = test_cfg["nms_type"]
-    if kind not in _NMS_KINDS:
-        raise ValueError(f"nms_type {kind!r} is not one of {sorted(_NMS_KINDS)}")
-    thr = _cfg(coder_cfg, "score_threshold")
-    rng = _cfg(coder_cfg, "post_center_range")
-    d = _capi.VampDetDesc()
-    d.B, d.T, d.H, d.W = B, T, H, W
-    for t in range(T):
-        d.ncls[t] = num_classes[t]
-    d.max_num = int(_cfg(coder_cfg, "max_num", 100))
-    d.pre_max_size = int(test_cfg.get("pre_max_size", d.max_num))
-    d.post_max_size = int(test_cfg["post_max_size"])
-    d.nms_kind = _NMS_KINDS[kind]
-    d.in_dtype = _DET_DTYPES[dtype]
-    d.has_vel, d.norm_bbox = int(has_vel), int(bool(norm_bbox))
-    d.use_score_threshold, d.use_center_range = int(thr is not None), int(rng is not None)
-    # torch compares a tensor with a Python scalar in the tensor's dtype
-    d.score_threshold = float(torch.tensor(float(thr), dtype=dtype)) if thr is not None else 0.0
-    d.out_size_factor = float(_cfg(coder_cfg, "out_size_factor"))
-    vs, pc = _cfg(coder_cfg, "voxel_size"), _cfg(coder_cfg, "pc_range")
-    d.voxel_size[0], d.voxel_size[1] = float(vs[0]), float(vs[1])
-    d.pc_range[0], d.pc_range[1] = float(pc[0]), float(pc[1])
-    if rng is not None:
-        for i in range(6):
-            d.post_center_range[i] = float(rng[i])
-    mr = _per_task(test_cfg.get("min_radius") if kind == "circle" else None, T, "min_radius")
-    ts = _per_task(test_cfg.get("thresh_scale") if kind == "size_aware_circle" else None, T, "thresh_scale")
-    nt = _per_task(test_cfg.get("nms_thr") if kind == "rotate" else None, T, "nms_thr")
-    for t in range(T):
-        d.min_radius[t], d.thresh_scale[t], d.nms_thr[t] = mr[t], ts[t], nt[t]
-    lib = _capi.load()
-    nbytes = lib.vamp_det_workspace_bytes(C.byref(d))
-    if nbytes == 0:
-        _capi.check(lib.vamp_det_postprocess(C.byref(d), None, None, None, None, None, None, 0, None),
-                    "vamp_det_postprocess")
-    P, cs = d.post_max_size, 9 if has_vel else 7
-    dev = heads[0]["heatmap"].device
-    if out is None:
-        out = DetResult(torch.empty(B, T * P, cs, dtype=torch.float32, device=dev),
-                        torch.empty(B, T * P, dtype=dtype, device=dev),
-                        torch.empty(B, T * P, dtype=torch.int32, device=dev),
-                        torch.empty(B, dtype=torch.int32, device=dev))
-    else:
-        want = [(out.boxes, (B, T * P, cs), torch.float32), (out.scores, (B, T * P), dtype),
-                (out.labels, (B, T * P), torch.int32), (out.counts, (B,), torch.int32)]
-        for x, shape, dt in want:
-            if tuple(x.shape) != shape or x.dtype != dt or not x.is_contiguous() or x.device != dev:
-                raise ValueError(f"out buffer {tuple(x.shape)} {x.dtype} is not a contiguous {shape} {dt} on {dev}")
-    table = (_capi.VampDetTask * T)()
-    for t, ts_ in enumerate(tensors):
-        table[t] = _capi.VampDetTask(*[x.data_ptr() for x in ts_], *([] if has_vel else [None]))
-    with torch.cuda.device(dev):
-        ws = _metric_workspace("det", dev, nbytes)
-        _capi.check(lib.vamp_det_postprocess(C.byref(d), table, _ptr(out.boxes), _ptr(out.scores), _ptr(out.labels),
-                                             _ptr(out.counts), _ptr(ws), ws.numel(), _stream()),
-                    "vamp_det_postprocess")
-    return out
-
-
-# ===========================================================================
-# detection training targets (bev_depth_head.py:168-319)
-# ===========================================================================
-_LABEL_CODES = {torch.int32: _capi.VAMP_I32, torch.int64: _capi.VAMP_I64}
-
-
-@dataclasses.dataclass
-class DetTargets:
-    """The training targets of a batch: `heat` holds the tasks' [B, ncls_t, fh, fw] heatmaps one after the other
-    (fp32), anno [T, B, max_objs, code] fp32, inds [T, B, max_objs] int64, masks [T, B, max_objs] uint8."""
-    heat: torch.Tensor
-    anno: torch.Tensor
-    inds: torch.Tensor
-    masks: torch.Tensor
-    ncls: tuple
-    fh: int
-    fw: int
-
-    def heatmaps(self):
-        B = self.anno.shape[1]
-        return [h.view(B, n, self.fh, self.fw) for h, n in
-                zip(self.heat.split([B * n * self.fh * self.fw for n in self.ncls]), self.ncls)]
-
-    def as_tuple(self):
-        """get_targets's return value: (heatmaps, anno_boxes, inds, masks), each a list over tasks of [B, ...]
-        views of the buffers."""
-        return self.heatmaps(), list(self.anno.unbind(0)), list(self.inds.unbind(0)), list(self.masks.unbind(0))
-
-
-def _pack_targets_input(boxes, labels):
-    """Per-sample lists ([n_b, 7 | 9] boxes, [n_b] labels) -> padded [B, M, 7 | 9], [B, M] (label -1) on the
-    device, without a host synchronisation; tensors pass through."""
-    if isinstance(boxes, torch.Tensor):
-        if not isinstance(labels, torch.Tensor):
-            raise ValueError("boxes is a packed tensor but labels is not")
-        return boxes, labels
-    if len(boxes) != len(labels) or len(boxes) == 0:
-        raise ValueError(f"{len(boxes)} box tensors and {len(labels)} label tensors (one per sample, at least one)")
-    if any(b.dtype != torch.float32 for b in boxes):
-        raise TypeError(f"boxes must be fp32, got {sorted({str(b.dtype) for b in boxes})}")
-    if len({l.dtype for l in labels}) != 1:
-        raise TypeError(f"labels must share one dtype, got {sorted({str(l.dtype) for l in labels})}")
-    if not all(b.is_cuda for b in boxes) or not all(l.is_cuda for l in labels):
-        raise _capi.VampireHipError("det_targets needs device tensors (no CPU fallback)")
-    pad = torch.nn.utils.rnn.pad_sequence
-    return pad(list(boxes), batch_first=True), pad(list(labels), batch_first=True, padding_value=-1)
-
-
-def det_targets(boxes, labels, tasks_ncls, train_cfg, norm_bbox, out=None):
-    """BEVDepthHead.get_targets on the device (vamp_det_targets): per task and sample the Gaussian heatmaps and
-    the anno / ind / mask rows of the first max_objs boxes in the reference's slot order, with the reference's
-    fp32 chain, in two launches and without a host synchronisation (capturable in a graph with packed inputs).
-    boxes, labels: per-sample lists ([n_b, 7 | 9] fp32, [n_b] int32 | int64; packed on the device with label -1
-    padding) or packed [B, M, 7 | 9] and [B, M] tensors whose padding rows carry label -1.  tasks_ncls: classes
-    per task, labels flat over the tasks.  out: a DetTargets of preallocated buffers to write (graph capture).
-    Returns a DetTargets; as_tuple() is get_targets's (heatmaps, anno_boxes, inds, masks)."""
-    boxes, labels = _pack_targets_input(boxes, labels)
-    if boxes.dtype != torch.float32:
-        raise TypeError(f"boxes must be fp32, got {boxes.dtype}")
-    if labels.dtype not in _LABEL_CODES:
-        raise TypeError(f"labels must be int32 or int64, got {labels.dtype}")
-    if not (boxes.is_cuda and labels.is_cuda):
-        raise _capi.VampireHipError("det_targets needs device tensors (no CPU fallback)")
-    if boxes.dim() != 3 or boxes.shape[2] not in (7, 9) or tuple(labels.shape) != tuple(boxes.shape[:2]):
-        raise ValueError(f"expected boxes [B, M, 7 | 9] and labels [B, M], got {tuple(boxes.shape)} "
-                         f"and {tuple(labels.shape)}")
-    ncls = tuple(int(n) for n in tasks_ncls)
-    T = len(ncls)
-    if not 1 <= T <= 8:
-        raise ValueError(f"{T} tasks (1 to 8)")
-    B, Mb, cols = boxes.shape
-    osf = train_cfg["out_size_factor"]
-    fw, fh = int(train_cfg["grid_size"][0]) // osf, int(train_cfg["grid_size"][1]) // osf
-    code = len(train_cfg["code_weights"])
-    max_objs = int(train_cfg["max_objs"] * train_cfg["dense_reg"])
-    d = _capi.VampDetTargetDesc()
-    d.gaussian_overlap = float(train_cfg["gaussian_overlap"])
-    d.B, d.T, d.M = B, T, Mb
-    for t in range(T):
-        d.ncls[t] = ncls[t]
-    d.box_cols, d.code, d.max_objs, d.fh, d.fw = cols, code, max_objs, fh, fw
-    d.out_size_factor, d.min_radius, d.norm_bbox = int(osf), int(train_cfg["min_radius"]), int(bool(norm_bbox))
-    d.label_dtype = _LABEL_CODES[labels.dtype]
-    vs, pc = train_cfg["voxel_size"], train_cfg["point_cloud_range"]
-    d.voxel_size[0], d.voxel_size[1] = float(vs[0]), float(vs[1])
-    d.pc_range[0], d.pc_range[1] = float(pc[0]), float(pc[1])
-    lib = _capi.load()
-    nbytes = lib.vamp_det_targets_workspace_bytes(C.byref(d))
-    if nbytes == 0:
-        _capi.check(lib.vamp_det_targets(C.byref(d), None, None, None, None, None, None, None, 0, None),
-                    "vamp_det_targets")
-    dev = boxes.device
-    boxes, labels = boxes.contiguous(), labels.contiguous()
-    if out is None:
-        out = DetTargets(torch.empty(B * sum(ncls) * fh * fw, dtype=torch.float32, device=dev),
-                         torch.empty(T, B, max_objs, code, dtype=torch.float32, device=dev),
-                         torch.empty(T, B, max_objs, dtype=torch.int64, device=dev),
-                         torch.empty(T, B, max_objs, dtype=torch.uint8, device=dev), ncls, fh, fw)
-    else:
-        want = [(out.heat, (B * sum(ncls) * fh * fw,), torch.float32), (out.anno, (T, B, max_objs, code), torch.float32),
-                (out.inds, (T, B, max_objs), torch.int64), (out.masks, (T, B, max_objs), torch.uint8)]
-        for x, shape, dt in want:
-            if tuple(x.shape) != shape or x.dtype != dt or not x.is_contiguous() or x.device != dev:
-                raise ValueError(f"out buffer {tuple(x.shape)} {x.dtype} is not a contiguous {shape} {dt} on {dev}")
-        if tuple(out.ncls) != ncls or (out.fh, out.fw) != (fh, fw):
-            raise ValueError(f"out was made for classes {out.ncls} on {out.fh} x {out.fw}, not {ncls} on {fh} x {fw}")
-    with torch.cuda.device(dev):
-        ws = _metric_workspace("det_targets", dev, nbytes)
-        _capi.check(lib.vamp_det_targets(C.byref(d), _ptr(boxes), _ptr(labels), _ptr(out.heat), _ptr(out.anno),
-                                         _ptr(out.inds), _ptr(out.masks), _ptr(ws), ws.numel(), _stream()),
-                    "vamp_det_targets")
-    return out
