@@ -27,8 +27,9 @@
 extern "C" {
 #endif
 
-#define VAMP_ABI_VERSION 9   /* bumped whenever entry points or flags are added (round 2: 2, round 3: 3, round 4: 4, round 5: 5, round 6: 6;
-                                 7: segmentation metrics; 8: detection post-processing; 9: detection targets) */
+#define VAMP_ABI_VERSION 10  /* bumped whenever entry points or flags are added (round 2: 2, round 3: 3, round 4: 4, round 5: 5, round 6: 6;
+                                 7: segmentation metrics; 8: detection post-processing; 9: detection targets;
+                                 10: the BEV backward's plan) */
 
 enum {
   VAMP_OK = 0,
@@ -543,6 +544,62 @@ int vamp_render_bev_backward_ex(const VampRenderDesc* d, const float* oxs, const
                              float* grad_rgb, float* grad_base, float* grad_beta,
                              const float* ozs_host, void* workspace, size_t workspace_bytes,
                              int flags, void* stream);
+
+/*
+ * What vamp_render_bev_backward_ex(d, .., ozs_host, .., flags, ..) will launch (ABI 10): every choice the call makes
+ * from the descriptor, the host heights and the flags, as numbers.  A pure host function -- no HIP call, no GPU --
+ * and the very function the backward asks before it launches.  Returns VAMP_OK, or the code (and vamp_last_error
+ * message) with which the backward refuses the same arguments: more than 64 heights, ONLY_BASE with SKIP_BASE,
+ * tensors beyond the column gather's 32-bit offsets.  Fields a path does not use are 0.
+ * The one input the plan does not see is whether g_voxel_output is NULL: seg_gather, base_body and beta_reduce say
+ * what a call WITH g_voxel_output does; without it the seg_gather launch is dropped and base_body / beta_reduce
+ * take the *_no_vo values.
+ */
+enum { VAMP_BEVPLAN_PATH_V1 = 0,      /* ozs_host == NULL: the float-atomic splat (zero_* fills in front of it) */
+       VAMP_BEVPLAN_PATH_NOOP = 1,    /* ozs_host == NULL with ONLY_BASE: the SKIP_BASE call of the pair did it all */
+       VAMP_BEVPLAN_PATH_CELL = 2 };  /* scan + gathers */
+enum { VAMP_BEVPLAN_SCAN_NONE = 0, VAMP_BEVPLAN_SCAN_QSCAN21 = 1,   /* bev_qscan_saved_kernel<21> */
+       VAMP_BEVPLAN_SCAN_QSCAN0 = 2,                                /* bev_qscan_saved_kernel<0> */
+       VAMP_BEVPLAN_SCAN_Q_SCAN = 3 };                              /* bev_q_kernel, then bev_scan_kernel */
+enum { VAMP_BEVPLAN_BODY_NONE = 0, VAMP_BEVPLAN_BODY_COMP = 1,      /* bev_gather_comp_kernel */
+       VAMP_BEVPLAN_BODY_PASS = 2,                                  /* bev_gather_pass_kernel */
+       VAMP_BEVPLAN_BODY_COL = 3,                                   /* bev_gather_col_kernel */
+       VAMP_BEVPLAN_BODY_ZERO = 4 };                                /* a zero fill of grad_base */
+enum { VAMP_BEVPLAN_BETA_NONE = 0,
+       VAMP_BEVPLAN_BETA_TAIL_COMP = 1,   /* first workgroup of the composited gather (comp_body) */
+       VAMP_BEVPLAN_BETA_TAIL_BASE = 2,   /* first workgroup of the base gather (base_body PASS or COL) */
+       VAMP_BEVPLAN_BETA_LAUNCH = 3,      /* a launch of its own behind the gathers */
+       VAMP_BEVPLAN_BETA_EARLY = 4 };     /* outside: a launch of its own right behind the scan */
+typedef struct VampBevBackwardPlan {
+  int64_t scan_lds;            /* dynamic LDS bytes of the scan body (Q_SCAN: of bev_q_kernel; bev_scan_kernel has none) */
+  int32_t path;                /* VAMP_BEVPLAN_PATH_* */
+  int32_t z_lo, z_hi;          /* volume planes the lattice touches, clamped to the volume */
+  int32_t outside;             /* z_lo > z_hi: only zeros (and, sdf density, d beta) to write */
+  int32_t zero_cam, zero_base; /* zero fills in front of a body that adds (v1 splat, generic gather) or of nothing (outside):
+                                  grad_density_feature / grad_semantic / grad_rgb, and grad_base where it is not NULL */
+  int32_t scan;                /* VAMP_BEVPLAN_SCAN_* */
+  int32_t scan_grid[3];        /* grid of bev_qscan_saved_kernel, or of bev_scan_kernel */
+  int32_t q_grid[3];           /* grid of bev_q_kernel (Q_SCAN) */
+  int32_t scan_waves;          /* waves per workgroup of the scan body */
+  int32_t raise_lds;           /* the dynamic-LDS limit is raised first (bev_q_kernel above 60 KB) */
+  int32_t beta_parts;          /* d beta partial sums the scan leaves, and the reduction adds up */
+  int32_t fits;                /* the column gathers apply (else the generic gather) */
+  int32_t nseg, zseg;          /* z segments of the column gather, and planes per segment */
+  int32_t comp_ok, pass_ok;    /* tensors within the byte offsets of the composited / pass-through body */
+  int32_t build_table;         /* bev_axis_table_kernel runs (fits, no TABLE_VALID) */
+  int32_t table;               /* which of the workspace's two axis tables: 1 for ONLY_BASE */
+  int32_t comp_body;           /* semantic + rgb + density: NONE, COMP or COL */
+  int32_t comp_overwrite;      /* its <.., true> variant (OVERWRITE_CAM) */
+  int32_t seg_gather;          /* the cat_seg column launch of voxel_output's semantic part */
+  int32_t base_body;           /* grad_base: NONE, PASS, COL or ZERO */
+  int32_t base_overwrite;      /* its <.., true> variant (OVERWRITE_BASE) */
+  int32_t base_body_no_vo;     /* g_voxel_output == NULL: NONE or ZERO */
+  int32_t generic;             /* bev_gather_generic_kernel over planes z_lo .. z_hi, behind the zero_* fills */
+  int32_t beta_reduce;         /* VAMP_BEVPLAN_BETA_* */
+  int32_t beta_reduce_no_vo;   /* g_voxel_output == NULL */
+  int32_t reserved[6];         /* 0 */
+} VampBevBackwardPlan;
+int vamp_render_bev_backward_plan(const VampRenderDesc* d, const float* ozs_host, int flags, VampBevBackwardPlan* out);
 
 /*
  * Diagnostics: inside-mask (bv2:405-407) and floor taps of the camera branch's

@@ -5,10 +5,10 @@ float64 (oracle/aten_oracle.py, compute_dtype): every output and every gradient,
 
 One axis moves at a time from CFG_TINY (B = 2, six cameras); where the det lattice grows in z the seg grid's z bound
 grows with it, except in the cases that are about leaving the volume.  Scene, upstream gradients and bars are those of
-tests/test_render_shape_sweep.py.  The CPU tests at the end map the cases through mirrors of the BEV launchers' dispatch
-(pinned to their C++ lines), fail if a forward body, a backward gather body, the zero path or an LDS regime is reached
-by no case, and compare the library's own host-side answers (merged launch supported, BEV workspace bytes) with the
-mirrors."""
+tests/test_render_shape_sweep.py.  The CPU tests at the end map the cases through mirrors of the BEV launchers' dispatch,
+fail if a forward body, a backward gather body, the zero path or an LDS regime is reached by no case, and compare the
+library's own host-side answers (merged launch supported, BEV workspace bytes, the backward's plan field by field) with
+the mirrors -- the plan also on descriptors above 2 GB, which no GPU test can allocate."""
 import ctypes as C
 import dataclasses
 import functools
@@ -198,7 +198,7 @@ def merged_supported(d, ozs):
 
 
 def scan_blocks(d, saved):
-    """render_bev.hip: bev_scan_blocks -- the d beta partials of bev_qscan_saved_kernel / bev_scan_kernel."""
+    """render_common.hpp: bev_scan_blocks -- the d beta partials of bev_qscan_saved_kernel / bev_scan_kernel."""
     if saved:
         return (d.oY * d.oX + 63) // 64 * d.B
     return (d.oX + 63) // 64 * ((d.oY + 3) // 4) * d.B
@@ -209,7 +209,7 @@ def align_up(n, a=256):
 
 
 def ws_needed(d):
-    """The BEV workspace both scans need: Q, Wb, DS0 | two axis tables | the larger count of beta partials | density
+    """render_common.hpp: bev_workspace -- the BEV workspace both scans need: Q, Wb, DS0 | two axis tables | the larger count of beta partials | density
     samples and composited channels' samples the forward keeps."""
     one = align_up(d.B * d.oZ * d.oY * d.oX * 4)
     tab = align_up(2 * (d.X + d.Y + d.Z) * 16)
@@ -217,10 +217,10 @@ def ws_needed(d):
 
 
 def bwd_plan(d, ozs):
-    """render_bev.hip: vamp_render_bev_backward_ex's choices for the cell backward."""
+    """render_bev.hip: bev_backward_plan's numbers for the cell backward (flags aside: lib_plan)."""
     taps = [tap0(d, pos)[1] for pos in ozs]
     z_lo, z_hi = max(0, min(taps)), min(d.Z - 1, max(taps) + 1)
-    p = dict(zero=z_lo > z_hi, q_lds=d.oZ * 4 * 64 * 4, qs_lds=4 * d.oZ * 64 * 4,
+    p = dict(z_lo=z_lo, z_hi=z_hi, zero=z_lo > z_hi, q_lds=d.oZ * 4 * 64 * 4, qs_lds=4 * d.oZ * 64 * 4,
              qscan=21 if d.K + 3 == 21 and d.B * 21 * d.oZ * d.oY * d.oX * 4 < I32 else 0)
     fits = True
     for a, n in enumerate((d.X, d.Y, d.Z)):
@@ -238,6 +238,102 @@ def bwd_plan(d, ozs):
     zseg = (d.Z + nseg - 1) // nseg
     p["nseg"], p["zseg"] = (d.Z + zseg - 1) // zseg, zseg
     return p
+
+
+PLAN_FIELDS = [n for n, _ in _capi.VampBevBackwardPlan._fields_]
+ERR_HEIGHTS = "at most 64 det-grid heights"
+ERR_HALVES = "ONLY_BASE and SKIP_BASE exclude each other"
+ERR_OFFSETS = "tensor too large for the 32-bit offsets of the BEV gather"
+
+
+def lib_plan(d, ozs, flags):
+    """render_bev.hip: bev_backward_plan -- what vamp_render_bev_backward_plan is to answer for (d, ozs, flags): every
+    field of VampBevBackwardPlan (grids and reserved words as lists), or the message of the refusal.  ozs None: the
+    caller gave no host heights."""
+    A = _capi
+    only, skip = bool(flags & A.VAMP_BEVBWD_ONLY_BASE), bool(flags & A.VAMP_BEVBWD_SKIP_BASE)
+    ow_base, ow_cam = bool(flags & A.VAMP_BEVBWD_OVERWRITE_BASE), bool(flags & A.VAMP_BEVBWD_OVERWRITE_CAM)
+    saved, sdf = bool(flags & A.VAMP_BEVBWD_SAVED_VALID), d.density_mode == A.VAMP_DENSITY_SDF_LAPLACE
+    p = {n: [0] * 3 if n.endswith("_grid") else [0] * 6 if n == "reserved" else 0 for n in PLAN_FIELDS}
+    if ozs is None:
+        # the float-atomic splat behind its zero fills; of a split pair the SKIP_BASE call does it all
+        p.update(path=A.VAMP_BEVPLAN_PATH_NOOP if only else A.VAMP_BEVPLAN_PATH_V1,
+                 zero_cam=int(ow_cam and not only), zero_base=int(ow_base and not only))
+        return p
+    p["path"] = A.VAMP_BEVPLAN_PATH_CELL
+    if d.oZ > BEV_MAX_OZ:
+        return ERR_HEIGHTS
+    if only and skip:
+        return ERR_HALVES
+    b = bwd_plan(d, ozs)
+    p.update(z_lo=b["z_lo"], z_hi=b["z_hi"], outside=int(b["zero"]), beta_parts=scan_blocks(d, saved))
+    # the scan: not in the ONLY_BASE half; outside the volume only for the sdf density's d beta
+    if not only and (sdf or not b["zero"]):
+        gx = (d.oX + 63) // 64
+        if saved:
+            p.update(scan=A.VAMP_BEVPLAN_SCAN_QSCAN21 if b["qscan"] == 21 else A.VAMP_BEVPLAN_SCAN_QSCAN0,
+                     scan_grid=[(d.oY * d.oX + 63) // 64, d.B, 1], scan_waves=min(d.oZ, QS_MAX_WAVES),
+                     scan_lds=b["qs_lds"])
+        else:
+            p.update(scan=A.VAMP_BEVPLAN_SCAN_Q_SCAN, q_grid=[gx, d.oY, d.B], scan_grid=[gx, (d.oY + 3) // 4, d.B],
+                     scan_waves=4, scan_lds=b["q_lds"], raise_lds=int(b["q_lds"] > LDS_RAISE))
+    if b["zero"]:
+        # each half of a pair zeroes what it owns; the d beta partials are added up right behind the scan
+        early = A.VAMP_BEVPLAN_BETA_EARLY if p["scan"] else A.VAMP_BEVPLAN_BETA_NONE
+        p.update(zero_cam=int(ow_cam and not only), zero_base=int(ow_base and not skip), beta_reduce=early,
+                 beta_reduce_no_vo=early)
+        return p
+    p["fits"] = int(b["fits"])
+    beta_due = sdf and not skip                 # (the SKIP_BASE half leaves the partials to the ONLY_BASE half)
+    if not b["fits"]:
+        # the generic gather adds to all four tensors at once: the ONLY_BASE half has nothing to launch but the reduction
+        launch = A.VAMP_BEVPLAN_BETA_LAUNCH if beta_due else A.VAMP_BEVPLAN_BETA_NONE
+        p.update(generic=int(not only), zero_cam=int(ow_cam and not only), zero_base=int(ow_base and not only),
+                 beta_reduce=launch, beta_reduce_no_vo=launch)
+        return p
+    if d.B * max(d.K, d.C) * d.Z * d.Y * d.X >= I32 or d.B * (d.C + d.K) * d.oZ * d.oY * d.oX >= I32:
+        return ERR_OFFSETS
+    p.update(build_table=int(not flags & A.VAMP_BEVBWD_TABLE_VALID), table=int(only), nseg=b["nseg"], zseg=b["zseg"],
+             comp_ok=int(b["comp_ok"]), pass_ok=int(b["pass_ok"]))
+    launches = []                               # the column-gather launches that can carry the beta tail, in order
+    if not only:
+        p.update(comp_body=A.VAMP_BEVPLAN_BODY_COMP if b["comp_ok"] else A.VAMP_BEVPLAN_BODY_COL,
+                 comp_overwrite=int(ow_cam), seg_gather=int(bool(d.cat_seg)))
+        launches.append((A.VAMP_BEVPLAN_BETA_TAIL_COMP, False))
+    if not skip and d.C > 0:
+        p.update(base_body=A.VAMP_BEVPLAN_BODY_PASS if b["pass_ok"] else A.VAMP_BEVPLAN_BODY_COL,
+                 base_overwrite=int(ow_base),
+                 base_body_no_vo=A.VAMP_BEVPLAN_BODY_ZERO if ow_base else A.VAMP_BEVPLAN_BODY_NONE)
+        launches.append((A.VAMP_BEVPLAN_BETA_TAIL_BASE, True))       # (runs only with g_voxel_output)
+    if beta_due:
+        p["beta_reduce"] = launches[0][0] if launches else A.VAMP_BEVPLAN_BETA_LAUNCH
+        no_vo = [where for where, needs_vo in launches if not needs_vo]
+        p["beta_reduce_no_vo"] = no_vo[0] if no_vo else A.VAMP_BEVPLAN_BETA_LAUNCH
+    return p
+
+
+def big_descriptors():
+    """Descriptors no GPU test can allocate (pure numbers here): [(name, d, ozs, flags)].  The seg grid grows to
+    20 x 2000 x 2000 inside CFG_TINY's bounds (finer voxels: the lattice still fits the column gathers), or the det
+    grid to 2000 x 2000 columns."""
+    def make(K=5, C=4, B=2, seg=None, det=None, oZ=None):
+        d = desc(Case("big", K=K, C=C), B=B)
+        if seg:
+            d.Z, d.Y, d.X = seg
+        if det:
+            d.oY, d.oX = det
+        ozs = ozs_host(Case("big"))
+        if oZ:
+            d.oZ, ozs = oZ, [f32(-1.9 + 0.05 * k) for k in range(oZ)]
+        return d, ozs
+    SEG = (20, 2000, 2000)
+    both = _capi.VAMP_BEVBWD_OVERWRITE_BASE | _capi.VAMP_BEVBWD_OVERWRITE_CAM
+    return [("comp-col", *make(K=5, C=1, seg=SEG), both),                    # B K Z Y X 4 = 3.2e9, B C Z Y X 4 = 6.4e8
+            ("pass-col", *make(K=1, C=4, seg=SEG), both),                    # B K Z Y X 4 = 6.4e8, B C Z Y X 4 = 2.6e9
+            ("qscan0-21ch", *make(K=18, B=4, det=(2000, 2000)), both | _capi.VAMP_BEVBWD_SAVED_VALID),
+            ("offsets", *make(K=18, B=4, seg=SEG), both),                    # B K Z Y X = 5.8e9 elements
+            ("both-halves", *make(), both | _capi.VAMP_BEVBWD_ONLY_BASE | _capi.VAMP_BEVBWD_SKIP_BASE),
+            ("oZ65", *make(oZ=65), both)]
 
 
 def plan(case, path="merged"):
@@ -602,8 +698,9 @@ def test_sweep_reaches_every_bev_body():
     """Every BEV forward body (merged launch, one kernel, two kernels -- forced and on geometry), every backward body
     the shapes can reach (saved q-scan <21> / <0>, q kernel + scan, composited gather overwriting / accumulating, the
     cat_seg column gather with one and with several z segments, the pass-through gather, the generic gather, the zero
-    path, the v1 splat) and both LDS regimes of both scans are reached by at least one case.  (The composited column
-    gather and the pass-through column gather run above 2 GB tensors only.)"""
+    path, the v1 splat) and both LDS regimes of both scans are reached by at least one case.  The composited column
+    gather, the pass-through column gather and the <0> q-scan on 21 channels run above 2 GB tensors only: those are
+    reached by big_descriptors(), whose plans test_library_plan_is_the_mirrors compares with the library's."""
     fwd, bodies, lds = set(), set(), set()
     for c in CASES:
         for path in PATHS:
@@ -621,6 +718,11 @@ def test_sweep_reaches_every_bev_body():
     ozs = {c.cfg.oZ for c in CASES}
     assert {1, QS_MAX_WAVES, QS_MAX_WAVES + 1, BEV_MAX_OZ} <= ozs
     assert any(plan(c)["qscan"] == 21 and plan(c)["qs_lds"] > LDS_RAISE for c in CASES)
+    big = {name: lib_plan(d, ozs, flags) for name, d, ozs, flags in big_descriptors()}
+    assert big["comp-col"]["comp_body"] == _capi.VAMP_BEVPLAN_BODY_COL and big["comp-col"]["pass_ok"]
+    assert big["pass-col"]["base_body"] == _capi.VAMP_BEVPLAN_BODY_COL and big["pass-col"]["comp_ok"]
+    assert big["qscan0-21ch"]["scan"] == _capi.VAMP_BEVPLAN_SCAN_QSCAN0 and big["qscan0-21ch"]["fits"]
+    assert (big["offsets"], big["both-halves"], big["oZ65"]) == (ERR_OFFSETS, ERR_HALVES, ERR_HEIGHTS)
 
 
 def test_library_agrees_with_the_mirrors():
@@ -640,6 +742,80 @@ def test_library_agrees_with_the_mirrors():
             assert got == ws_needed(d), (c.name, got, ws_needed(d), scan_blocks(d, True), scan_blocks(d, False))
 
 
+def library_plan(lib, d, ozs, flags):
+    """vamp_render_bev_backward_plan's answer in lib_plan's form: the fields, or the refusal's message."""
+    out = _capi.VampBevBackwardPlan()
+    arr = None if ozs is None else (C.c_float * len(ozs))(*[float(v) for v in ozs])
+    rc = lib.vamp_render_bev_backward_plan(C.byref(d), arr, flags, C.byref(out))
+    if rc != 0:
+        assert rc == -1, rc                       # VAMP_EINVAL
+        msg = lib.vamp_last_error().decode()
+        for known in (ERR_HEIGHTS, ERR_HALVES, ERR_OFFSETS):
+            if msg.endswith("requirement failed: " + known):
+                return known
+        return msg
+    return {n: list(getattr(out, n)) if isinstance(getattr(out, n), C.Array) else getattr(out, n) for n in PLAN_FIELDS}
+
+
+def test_library_plan_is_the_mirrors():
+    """vamp_render_bev_backward_plan -- the function vamp_render_bev_backward_ex asks before it launches -- answers
+    what lib_plan predicts, field by field: every case x f32 / bf16 x SAVED_VALID x (OVERWRITE_BASE with and without
+    OVERWRITE_CAM, no flags) x (whole call, SKIP_BASE, ONLY_BASE) x TABLE_VALID x host heights given / NULL; and on
+    big_descriptors(): the column bodies of tensors above 2 GB, the <0> q-scan on 21 channels, and the three refusals.
+    Every enumerator of the plan is met at least once."""
+    from vampire_amd.build import build_library
+    build_library(verbose=False)
+    lib = _capi.load()
+    A = _capi
+    seen = {k: set() for k in ("path", "scan", "comp_body", "base_body", "base_body_no_vo", "beta_reduce",
+                               "beta_reduce_no_vo", "table", "raise_lds", "outside", "generic", "seg_gather")}
+    n = 0
+
+    def check(what, d, ozs, flags):
+        nonlocal n
+        got, want = library_plan(lib, d, ozs, flags), lib_plan(d, ozs, flags)
+        assert type(got) is type(want), (what, flags, got, want)
+        if isinstance(want, dict):
+            diff = {k: (got[k], want[k]) for k in PLAN_FIELDS if got[k] != want[k]}
+            assert not diff, (what, flags, ozs is None, diff)
+            for k in seen:
+                seen[k].add(got[k])
+        else:
+            assert got == want, (what, flags, got, want)
+        n += 1
+        return got
+
+    for c in CASES:
+        for bf16 in (False, True):
+            case = dataclasses.replace(c, bf16=bf16)
+            d, ozs = desc(case), ozs_host(case)
+            for saved in (0, A.VAMP_BEVBWD_SAVED_VALID):
+                for ow in (A.VAMP_BEVBWD_OVERWRITE_BASE, A.VAMP_BEVBWD_OVERWRITE_BASE | A.VAMP_BEVBWD_OVERWRITE_CAM, 0):
+                    for part in (0, A.VAMP_BEVBWD_SKIP_BASE, A.VAMP_BEVBWD_ONLY_BASE):
+                        for tab in (0, A.VAMP_BEVBWD_TABLE_VALID):
+                            for heights_given in (True, False):
+                                check(c.name, d, ozs if heights_given else None, saved | ow | part | tab)
+    assert n == len(CASES) * 2 * 2 * 3 * 3 * 2 * 2
+    big = {name: check(name, d, ozs, flags) for name, d, ozs, flags in big_descriptors()}
+    assert big["comp-col"]["comp_body"] == A.VAMP_BEVPLAN_BODY_COL and big["comp-col"]["comp_overwrite"] == 1
+    assert big["pass-col"]["base_body"] == A.VAMP_BEVPLAN_BODY_COL and big["pass-col"]["base_overwrite"] == 1
+    assert big["qscan0-21ch"]["scan"] == A.VAMP_BEVPLAN_SCAN_QSCAN0
+    assert (big["offsets"], big["both-halves"], big["oZ65"]) == (ERR_OFFSETS, ERR_HALVES, ERR_HEIGHTS)
+    assert seen["path"] == {A.VAMP_BEVPLAN_PATH_V1, A.VAMP_BEVPLAN_PATH_NOOP, A.VAMP_BEVPLAN_PATH_CELL}
+    assert seen["scan"] == {A.VAMP_BEVPLAN_SCAN_NONE, A.VAMP_BEVPLAN_SCAN_QSCAN21, A.VAMP_BEVPLAN_SCAN_QSCAN0,
+                            A.VAMP_BEVPLAN_SCAN_Q_SCAN}
+    assert seen["comp_body"] == {A.VAMP_BEVPLAN_BODY_NONE, A.VAMP_BEVPLAN_BODY_COMP, A.VAMP_BEVPLAN_BODY_COL}
+    assert seen["base_body"] == {A.VAMP_BEVPLAN_BODY_NONE, A.VAMP_BEVPLAN_BODY_PASS, A.VAMP_BEVPLAN_BODY_COL}
+    assert seen["base_body_no_vo"] == {A.VAMP_BEVPLAN_BODY_NONE, A.VAMP_BEVPLAN_BODY_ZERO}
+    assert seen["beta_reduce"] == {A.VAMP_BEVPLAN_BETA_NONE, A.VAMP_BEVPLAN_BETA_TAIL_COMP, A.VAMP_BEVPLAN_BETA_TAIL_BASE,
+                                   A.VAMP_BEVPLAN_BETA_LAUNCH, A.VAMP_BEVPLAN_BETA_EARLY}
+    assert seen["beta_reduce_no_vo"] == seen["beta_reduce"] - {A.VAMP_BEVPLAN_BETA_TAIL_BASE}
+    assert all(seen[k] == {0, 1} for k in ("table", "raise_lds", "outside", "generic", "seg_gather"))
+    # a NULL descriptor or plan is refused, not read
+    assert lib.vamp_render_bev_backward_plan(None, None, 0, C.byref(_capi.VampBevBackwardPlan())) == -1
+    assert lib.vamp_render_bev_backward_plan(C.byref(desc(Case("tiny"))), None, 0, None) == -1
+
+
 # the C++ the mirrors above copy: if one of these lines changes, the mirror (and the reach table) needs a look
 DISPATCH_SOURCE = {
     "render_common.hpp": [
@@ -654,40 +830,18 @@ DISPATCH_SOURCE = {
     "render_bev_fused_dev.hpp": ["constexpr int kFusedMaxOZ = 64;", "constexpr int kFusedMaxNP = 40;"],
     "render_fwd_merged.hip": [
         "return d->D - 1 <= kPlanMax && bev_fwd_fused_supported(d) && d->oZ > 0 && d->oY > 0 && d->oX > 0;"],
-    "render_bev.hip": [
-        "constexpr int kBevMaxOZ = 64;", "constexpr int kQsMaxWaves = 16;", "constexpr int kMaxT = 3;",
-        "#define VAMP_COLG 4",
-        "if (saved) return (size_t) (((long) d->oY * d->oX + 63) / 64) * d->B;",
-        "return (size_t) ((d->oX + 63) / 64) * ((d->oY + 3) / 4) * d->B;",
-        "return std::max(bev_scan_blocks(d, true), bev_scan_blocks(d, false));",
-        "align_up(bev_scan_blocks_max(d) * sizeof(float), 256);",
-        "if (!(flags & VAMP_BEVFWD_TWO_KERNELS) && bev_fwd_fused_supported(d) && bev_fused_heights_fit(d, ozs_host))",
-        "return render_fwd_merged_supported(d) && bev_fused_heights_fit(d, ozs_host) ? 1 : 0;",
-        "z_lo = z_lo < 0 ? 0 : z_lo;", "z_hi = z_hi > d->Z - 1 ? d->Z - 1 : z_hi;", "const bool outside = z_lo > z_hi;",
-        "if (d->density_mode != VAMP_DENSITY_SDF_LAPLACE || only_base) return VAMP_OK;",
-        "const size_t q_lds = (size_t) d->oZ * 4 * 64 * sizeof(float);",
-        "const size_t qlds = (size_t) 4 * d->oZ * 64 * sizeof(float);",
-        "if (d->K + 3 == 21 && (size_t) d->B * 21 * d->oZ * d->oY * d->oX * 4 < 0x7fffffffull)",
-        "if (q_lds > 60 * 1024 &&",
-        "const float e = d->span[a] / (float) (nvox[a] - 1);",
-        "if (!(d->det_step[a] > 0.f) || (int) floorf(2.0f * e / d->det_step[a]) + 1 > kMaxT) fits = false;",
-        "if (d->oZ > kBevMaxOZ) fits = false;",
-        "if (!(ozs_host[k] > ozs_host[k - 1])) fits = false;",
-        "const long wgs = (((long) d->Y * d->X + 255) / 256) * d->B * ((d->C + kColG - 1) / kColG);",
-        "int nseg = (int) std::min<long>(std::max<long>(1, (1250 + wgs - 1) / std::max<long>(1, wgs)), "
-        "std::max(1, d->Z / 4));",
-        "const int zseg = (d->Z + nseg - 1) / nseg;", "nseg = (d->Z + zseg - 1) / zseg;",
-        "const bool comp_ok = (size_t) d->B * d->K * d->Z * d->Y * d->X * 4 < lim && "
-        "(size_t) d->B * d->oZ * d->oY * d->oX * 4 < lim;",
-        "const bool pass_ok = (size_t) d->B * (d->C + (d->cat_seg ? d->K : 0)) * d->oZ * d->oY * d->oX * 4 < lim &&",
-        "(size_t) d->B * d->C * d->Z * d->Y * d->X * 4 < lim;",
-        "const bool vo_sem = g_voxel_output && d->cat_seg;"],
+    # (the backward's decisions are compared by value: test_library_plan_is_the_mirrors)
+    "render_bev_dev.hpp": ["constexpr int kBevMaxOZ = 64;"],
+    "render_bev.hip": ["constexpr int kQsMaxWaves = 16;", "constexpr int kMaxT = 3;", "#define VAMP_COLG 4"],
+    "render_bev_fwd.hip": [
+        "if (!(flags & VAMP_BEVFWD_TWO_KERNELS) && bev_fwd_fused_supported(d) && bev_fused_heights_fit(d, ozs_host))"],
 }
 
 
 def test_dispatch_mirrors():
     """The launcher lines the mirrors copy are still those of the source (DISPATCH_SOURCE): a change to the BEV dispatch
-    fails here until the mirrors are brought along.  The mirrors at CFG_TINY: the one-kernel forward, the merged launch,
+    fails here until the mirrors are brought along (the backward's dispatch is compared by value instead:
+    test_library_plan_is_the_mirrors).  The mirrors at CFG_TINY: the one-kernel forward, the merged launch,
     three taps per axis, one z segment, the saved q-scan's <0> body."""
     from conftest import ROOT
     for fname, lines in DISPATCH_SOURCE.items():

@@ -41,6 +41,7 @@ def test_struct_layout_matches_header(lib):
     assert C.sizeof(_capi.VampRenderDesc) == 29 * 4
     assert C.sizeof(_capi.VampSampleDesc) == 22 * 4
     assert C.sizeof(_capi.VampConvDesc) == 6 * 4
+    assert C.sizeof(_capi.VampBevBackwardPlan) == 40 * 4
 
 
 def test_bad_descriptor_is_rejected_without_gpu(lib):

@@ -9,7 +9,7 @@
 //                      composited without evaluating the frustum chain
 //  render_cam_fwd      (caller-supplied geom tensor) every lane gathers its own 8 taps of CP
 //                      contiguous floats from global memory
-//  (the BEV branch lives in render_bev.hip)
+//  (the BEV branch lives in render_bev_fwd.hip, render_bev_fused.hip and render_bev.hip)
 // HBM/L2-bound gathers and a short scan: no MFMA.
 #include "render_common.hpp"
 #include "brick.hpp"

@@ -15,7 +15,7 @@ import torch
 
 from .build import lib_path
 
-ABI_VERSION = 9
+ABI_VERSION = 10
 
 VAMP_F32, VAMP_BF16, VAMP_F16 = 0, 1, 2
 VAMP_DENSITY_SIGMOID, VAMP_DENSITY_SDF_LAPLACE = 0, 1
@@ -97,6 +97,26 @@ class VampDetTargetDesc(C.Structure):
                 ("norm_bbox", C.c_int32), ("label_dtype", C.c_int32), ("voxel_size", C.c_float * 2),
                 ("pc_range", C.c_float * 2), ("reserved", C.c_int32 * 2)]
 
+
+class VampBevBackwardPlan(C.Structure):
+    """What vamp_render_bev_backward_ex will launch (vamp_render_bev_backward_plan; include/vampire_hip.h)."""
+    _fields_ = [("scan_lds", C.c_int64), ("path", C.c_int32), ("z_lo", C.c_int32), ("z_hi", C.c_int32),
+                ("outside", C.c_int32), ("zero_cam", C.c_int32), ("zero_base", C.c_int32), ("scan", C.c_int32),
+                ("scan_grid", C.c_int32 * 3), ("q_grid", C.c_int32 * 3), ("scan_waves", C.c_int32),
+                ("raise_lds", C.c_int32), ("beta_parts", C.c_int32), ("fits", C.c_int32), ("nseg", C.c_int32),
+                ("zseg", C.c_int32), ("comp_ok", C.c_int32), ("pass_ok", C.c_int32), ("build_table", C.c_int32),
+                ("table", C.c_int32), ("comp_body", C.c_int32), ("comp_overwrite", C.c_int32),
+                ("seg_gather", C.c_int32), ("base_body", C.c_int32), ("base_overwrite", C.c_int32),
+                ("base_body_no_vo", C.c_int32), ("generic", C.c_int32), ("beta_reduce", C.c_int32),
+                ("beta_reduce_no_vo", C.c_int32), ("reserved", C.c_int32 * 6)]
+
+
+VAMP_BEVPLAN_PATH_V1, VAMP_BEVPLAN_PATH_NOOP, VAMP_BEVPLAN_PATH_CELL = 0, 1, 2
+VAMP_BEVPLAN_SCAN_NONE, VAMP_BEVPLAN_SCAN_QSCAN21, VAMP_BEVPLAN_SCAN_QSCAN0, VAMP_BEVPLAN_SCAN_Q_SCAN = 0, 1, 2, 3
+(VAMP_BEVPLAN_BODY_NONE, VAMP_BEVPLAN_BODY_COMP, VAMP_BEVPLAN_BODY_PASS, VAMP_BEVPLAN_BODY_COL,
+ VAMP_BEVPLAN_BODY_ZERO) = 0, 1, 2, 3, 4
+(VAMP_BEVPLAN_BETA_NONE, VAMP_BEVPLAN_BETA_TAIL_COMP, VAMP_BEVPLAN_BETA_TAIL_BASE, VAMP_BEVPLAN_BETA_LAUNCH,
+ VAMP_BEVPLAN_BETA_EARLY) = 0, 1, 2, 3, 4
 
 # flag bits of vamp_lift_backward_ex / vamp_render_camera_backward_acc (include/vampire_hip.h)
 VAMP_LIFTFWD_EMIT_PAIRS, VAMP_LIFTFWD_CELLS_CLEAN, VAMP_LIFTFWD_FEAT_CHANNEL_LAST, VAMP_LIFTFWD_DEFER_SCAN = 1, 2, 4, 8
@@ -199,6 +219,7 @@ SIGNATURES = {
     "vamp_render_bev_workspace_bytes": (_SIZE, [_RD]),
     "vamp_render_bev_backward": (_STATUS, [_RD] + [_P] * 19 + [C.POINTER(C.c_float), _P, C.c_size_t, _P]),
     "vamp_render_bev_backward_ex": (_STATUS, [_RD] + [_P] * 19 + [C.POINTER(C.c_float), _P, C.c_size_t, C.c_int, _P]),
+    "vamp_render_bev_backward_plan": (_STATUS, [_RD, C.POINTER(C.c_float), C.c_int, C.POINTER(VampBevBackwardPlan)]),
     "vamp_render_indices": (_STATUS, [_RD] + [_P] * 9 + [_P]),
     "vamp_render_camera_direct_taps": (_STATUS, [_RD] + [_P] * 9 + [_P]),
     "vamp_frustum_geometry": (_STATUS, [_RD] + [_P] * 5 + [_P]),

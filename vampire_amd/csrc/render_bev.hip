@@ -1,21 +1,23 @@
-// BEV (top-down) branch of the renderer for gfx950: base_vampire2.py:408-418, 442-461.
+// BEV (top-down) branch of the renderer for gfx950, the backward: base_vampire2.py:408-418, 442-461.
+// (The forward is render_bev_fwd.hip -- two kernels -- and render_bev_fused.hip -- one.)
 //
 // The det-grid sample lattice is regular, so every access pattern here is coalesced
 // (lanes along x) and the work splits per channel:
 //
-//  forward   bev_density   thread per column: density samples -> sigma_j (= voxel_density)
-//                          and the height expectation
-//            bev_channels  thread per (channel, column): trilinear samples of one channel at
-//                          the oZ heights; composite (sem / rgb) with weights rebuilt from
-//                          voxel_density, or pass through (base -> voxel_output)
-//  backward  bev_q         thread per (channel-lane, column): q_j = sum_c G_c s_j[c]
-//            bev_scan      thread per column: weights, dL/dtau_j, dL/ds_j[0], d beta
-//            bev_gather    thread per (voxel column, 4 channels): walks the lattice heights
-//                          upwards, one (y, x)-weighted plane sum per height, the two voxel
-//                          planes it feeds kept in registers -- no atomics; overwrites (the
-//                          camera gather then adds) or adds onto what the buffers hold
-#include "render_common.hpp"
+//  bev_q         thread per (channel-lane, column): q_j = sum_c G_c s_j[c]
+//  bev_scan      thread per column: weights, dL/dtau_j, dL/ds_j[0], d beta
+//  bev_gather    thread per (voxel column, 4 channels): walks the lattice heights
+//                upwards, one (y, x)-weighted plane sum per height, the two voxel
+//                planes it feeds kept in registers -- no atomics; overwrites (the
+//                camera gather then adds) or adds onto what the buffers hold
+//
+// Host side: bev_backward_plan decides (a pure function of the descriptor, the host heights and the
+// flags: vamp_render_bev_backward_plan), vamp_render_bev_backward_ex launches what the plan says.
+#include "render_bev_dev.hpp"
 #include "pair_gather.hpp"
+
+#include <algorithm>
+#include <type_traits>
 
 namespace vamp {
 
@@ -27,239 +29,6 @@ int launch_bev_bwd_v1(const VampRenderDesc* d, const float* oxs, const float* oy
                       const float* g_voxel_output, float* grad_density_feature,
                       float* grad_semantic, float* grad_rgb, float* grad_base, float* grad_beta,
                       void* stream);
-
-// x/y part of a column's taps (shared by all heights) and the z part per height
-struct AxisTap {
-  int i0;
-  float w0, w1;
-};
-
-__device__ __forceinline__ AxisTap axis_tap(float pos, float lo, float span, int n) {
-  const float g = ((pos - lo) / span) * 2.0f - 1.0f;
-  const float f = ((g + 1.0f) / 2.0f) * (float) (n - 1);
-  const float fl = floorf(f);
-  AxisTap t;
-  t.i0 = (int) fl;
-  t.w1 = f - fl;
-  t.w0 = (fl + 1.0f) - f;
-  return t;
-}
-
-template <typename T>
-__device__ __forceinline__ float sample8(const RenderParams& P, const T* __restrict__ vol, long cb,
-                                         const AxisTap& tx, const AxisTap& ty, const AxisTap& tz) {
-  // aten tap order: x fastest, then y, then z; zero padding outside the volume
-  // branch-free: out-of-volume taps are clamped to a legal address and given zero weight, so
-  // the eight loads are independent (a bounds branch per tap serialises the round trips)
-  float s = 0.f;
-#pragma unroll
-  for (int k = 0; k < 8; ++k) {
-    const int iz = tz.i0 + (k >> 2), iy = ty.i0 + ((k >> 1) & 1), ix = tx.i0 + (k & 1);
-    const bool in = iz >= 0 && iz < P.Z && iy >= 0 && iy < P.Y && ix >= 0 && ix < P.X;
-    const float wt = in ? ((k & 1) ? tx.w1 : tx.w0) * ((k & 2) ? ty.w1 : ty.w0) * ((k & 4) ? tz.w1 : tz.w0) : 0.f;
-    const long at = ((long) min(max(iz, 0), P.Z - 1) * P.Y + min(max(iy, 0), P.Y - 1)) * P.X + min(max(ix, 0), P.X - 1);
-    s = __builtin_fmaf(wt, ldf(vol, cb + at), s);
-  }
-  return s;
-}
-
-// bilinear (x, y) sample of one volume plane, zero padding (also for a plane outside the volume)
-template <typename T>
-__device__ __forceinline__ float bilinear_plane(const RenderParams& P, const T* __restrict__ vol,
-                                                long cb, const AxisTap& tx, const AxisTap& ty, int iz) {
-  const bool zin = iz >= 0 && iz < P.Z;
-  const int izc = min(max(iz, 0), P.Z - 1);
-  float s = 0.f;
-#pragma unroll
-  for (int k = 0; k < 4; ++k) {
-    const int iy = ty.i0 + (k >> 1), ix = tx.i0 + (k & 1);
-    const bool in = zin && iy >= 0 && iy < P.Y && ix >= 0 && ix < P.X;
-    const float wt = in ? ((k & 1) ? tx.w1 : tx.w0) * ((k & 2) ? ty.w1 : ty.w0) : 0.f;
-    s = __builtin_fmaf(wt, ldf(vol, cb + ((long) izc * P.Y + min(max(iy, 0), P.Y - 1)) * P.X + min(max(ix, 0), P.X - 1)), s);
-  }
-  return s;
-}
-
-// ---------------------------------------------------------------------------
-// forward
-// ---------------------------------------------------------------------------
-// Heights are taken kHChunk at a time: a column is one thread and the grid is only oY * oX / 64
-// waves, so the loads of one height cannot hide behind other waves -- the taps of a whole chunk
-// are issued together instead of one round trip per height.
-constexpr int kHChunk = 5;
-
-template <typename T>
-__global__ void __launch_bounds__(256)
-bev_density_kernel(RenderParams P, const float* __restrict__ oxs, const float* __restrict__ oys,
-                   const float* __restrict__ ozs, const float* __restrict__ bev_mids,
-                   const float* __restrict__ beta_raw, const T* __restrict__ dens,
-                   float* __restrict__ voxel_density, float* __restrict__ bev_height,
-                   float* __restrict__ s0_save) {
-  const int x = blockIdx.x * 64 + (threadIdx.x & 63);
-  const int y = blockIdx.y * 4 + (threadIdx.x >> 6);
-  const int b = blockIdx.z;
-  if (x >= P.oX || y >= P.oY) return;
-  const DensityParams dp = load_density(P.density_mode, beta_raw, P.beta_min, P.sdf_bias);
-  const long V = (long) P.Z * P.Y * P.X, OYX = (long) P.oY * P.oX, col = (long) y * P.oX + x;
-  const AxisTap tx = axis_tap(oxs[x], P.lo[0], P.span[0], P.X);
-  const AxisTap ty = axis_tap(oys[y], P.lo[1], P.span[1], P.Y);
-  float cum = 0.f, height = 0.f;
-  for (int j0 = 0; j0 < P.oZ; j0 += kHChunk) {
-    float s0[kHChunk];
-#pragma unroll
-    for (int u = 0; u < kHChunk; ++u) {
-      const int j = min(j0 + u, P.oZ - 1);
-      const AxisTap tz = axis_tap(ozs[P.oZ - 1 - j], P.lo[2], P.span[2], P.Z);     // flip (bv2:443)
-      s0[u] = sample8(P, dens, (long) b * V, tx, ty, tz);
-    }
-#pragma unroll
-    for (int u = 0; u < kHChunk; ++u) {
-      const int j = j0 + u;
-      if (j >= P.oZ) break;
-      const float sigma = density_fwd(dp, s0[u]);
-      voxel_density[((long) b * P.oZ + j) * OYX + col] = sigma;
-      if (s0_save) s0_save[((long) b * P.oZ + j) * OYX + col] = s0[u];           // for the backward's scan
-      const float tau = sigma * (1.0f * P.z_step);                                  // bv2:451-453
-      height = __builtin_fmaf((1.0f - expf(-tau)) * expf(-cum), bev_mids[j], height);
-      cum += tau;
-    }
-  }
-  bev_height[(long) b * OYX + col] = height;
-}
-
-// channel index space of bev_channels: [0, K) semantic, [K, K+3) rgb, [K+3, K+3+C) base.
-// A thread owns one BEV column and NC consecutive channels: the column's compositing weights
-// (two exps per height) and the height taps are worked out once and shared by its channels --
-// with a thread per (channel, column) this kernel spent 80 % of its time in the vector ALU
-// redoing them 38 times -- and the 8 * NC plane loads of a height go out together.
-// cfg-B, us per launch: one thread per (channel, column) 55; NC = 1 / 2 / 4 / 8: 46 / 41.5 / 50 / 48
-// (fewer waves per CU hide less latency past NC = 2).
-#ifndef VAMP_BEV_NC
-#define VAMP_BEV_NC 2
-#endif
-constexpr int kBevNC = VAMP_BEV_NC;   // channels per thread
-constexpr int kBevMaxOZ = 64;         // heights whose taps fit the LDS table
-
-template <typename T, int NC>
-__global__ void __launch_bounds__(256)
-bev_channels_kernel(RenderParams P, const float* __restrict__ oxs, const float* __restrict__ oys,
-                    const float* __restrict__ ozs, const T* __restrict__ sem,
-                    const T* __restrict__ rgb, const T* __restrict__ base,
-                    const float* __restrict__ voxel_density, float* __restrict__ bev_rgb,
-                    float* __restrict__ bev_seg, float* __restrict__ voxel_output,
-                    float* __restrict__ ss_save) {
-  __shared__ int tz_i0[kBevMaxOZ];
-  __shared__ float tz_w0[kBevMaxOZ], tz_w1[kBevMaxOZ];
-  if ((int) threadIdx.x < P.oZ) {
-    const AxisTap tz = axis_tap(ozs[P.oZ - 1 - threadIdx.x], P.lo[2], P.span[2], P.Z);   // flip (bv2:443)
-    tz_i0[threadIdx.x] = tz.i0; tz_w0[threadIdx.x] = tz.w0; tz_w1[threadIdx.x] = tz.w1;
-  }
-  __syncthreads();
-  const int x = blockIdx.x * 64 + (threadIdx.x & 63);
-  const int y = blockIdx.y * 4 + (threadIdx.x >> 6);
-  const int nch = P.K + 3 + P.C;
-  const int ngrp = (nch + NC - 1) / NC;
-  const int b = blockIdx.z / ngrp, c0 = (blockIdx.z % ngrp) * NC;
-  if (x >= P.oX || y >= P.oY) return;
-  const long V = (long) P.Z * P.Y * P.X, OYX = (long) P.oY * P.oX, col = (long) y * P.oX + x;
-  const int CO = P.C + (P.cat_seg ? P.K : 0);
-  const AxisTap tx = axis_tap(oxs[x], P.lo[0], P.span[0], P.X);
-  const AxisTap ty = axis_tap(oys[y], P.lo[1], P.span[1], P.Y);
-  // the four (y, x) taps of the column: clamped offsets and weights (zero outside the volume)
-  long off4[4];
-  float w4[4];
-#pragma unroll
-  for (int k = 0; k < 4; ++k) {
-    const int iy = ty.i0 + (k >> 1), ix = tx.i0 + (k & 1);
-    const bool in = iy >= 0 && iy < P.Y && ix >= 0 && ix < P.X;
-    w4[k] = in ? ((k & 1) ? tx.w1 : tx.w0) * ((k & 2) ? ty.w1 : ty.w0) : 0.f;
-    off4[k] = (long) min(max(iy, 0), P.Y - 1) * P.X + min(max(ix, 0), P.X - 1);
-  }
-  const T* vol[NC];
-  long cb[NC];
-  bool on[NC];
-#pragma unroll
-  for (int u = 0; u < NC; ++u) {
-    const int ch = min(c0 + u, nch - 1);
-    on[u] = c0 + u < nch;
-    if (ch < P.K) { vol[u] = sem; cb[u] = ((long) b * P.K + ch) * V; }
-    else if (ch < P.K + 3) { vol[u] = rgb; cb[u] = ((long) b * 3 + (ch - P.K)) * V; }
-    else { vol[u] = base; cb[u] = ((long) b * P.C + (ch - P.K - 3)) * V; }
-  }
-  auto plane = [&](int u, int iz) -> float {
-    const bool zin = iz >= 0 && iz < P.Z;
-    const long zo = cb[u] + (long) min(max(iz, 0), P.Z - 1) * P.Y * P.X;
-    float s = 0.f;
-#pragma unroll
-    for (int k = 0; k < 4; ++k) s = __builtin_fmaf(zin ? w4[k] : 0.f, ldf(vol[u], zo + off4[k]), s);
-    return s;
-  };
-  float cum = 0.f, acc[NC];
-#pragma unroll
-  for (int u = 0; u < NC; ++u) acc[u] = 0.f;
-  const bool any_comp = c0 < P.K + 3;
-  // Heights kHChunk at a time.  A wave's life is (heights) x (memory round trip) -- 2.3 us per
-  // height under load -- so the volume planes of a whole chunk are fetched in one go: the chunk's
-  // heights step down the volume by at most one plane each (det and seg grids have about the same
-  // spacing), so its kHChunk + 1 planes below the first height's upper plane cover it; a height
-  // outside that window (other spacings) fetches its two planes itself.
-  for (int j0 = 0; j0 < P.oZ; j0 += kHChunk) {
-    const int top = tz_i0[j0] + 1;
-    float pl[NC][kHChunk + 1], tau[kHChunk];
-#pragma unroll
-    for (int t = 0; t <= kHChunk; ++t)
-#pragma unroll
-      for (int u = 0; u < NC; ++u) pl[u][t] = plane(u, top - t);
-#pragma unroll
-    for (int h = 0; h < kHChunk; ++h)
-      tau[h] = any_comp ? voxel_density[((long) b * P.oZ + min(j0 + h, P.oZ - 1)) * OYX + col] * (1.0f * P.z_step) : 0.f;   // bv2:451-458
-#pragma unroll
-    for (int h = 0; h < kHChunk; ++h) {
-      const int j = j0 + h;
-      if (j >= P.oZ) break;
-      const int i0 = tz_i0[j];
-      const float wz0 = tz_w0[j], wz1 = tz_w1[j];
-      const int d = top - 1 - i0;                  // planes below the chunk's first height (uniform)
-      float n_lo[NC], n_hi[NC];
-      bool found = false;
-#pragma unroll
-      for (int t = 0; t < kHChunk; ++t)
-        if (d == t) {
-#pragma unroll
-          for (int u = 0; u < NC; ++u) { n_hi[u] = pl[u][t]; n_lo[u] = pl[u][t + 1]; }
-          found = true;
-        }
-      if (!found) {
-#pragma unroll
-        for (int u = 0; u < NC; ++u) { n_hi[u] = plane(u, i0 + 1); n_lo[u] = plane(u, i0); }
-      }
-      const float wj = (1.0f - expf(-tau[h])) * expf(-cum);
-      cum += tau[h];
-#pragma unroll
-      for (int u = 0; u < NC; ++u) {
-        const float sv = __builtin_fmaf(wz1, n_hi[u], wz0 * n_lo[u]);
-        const int ch = c0 + u;
-        if (!on[u]) continue;
-        if (ch < P.K + 3) {
-          acc[u] = __builtin_fmaf(wj, sv, acc[u]);
-          // training: the backward's q_j = sum_c G_c s_j[c] reads the samples back
-          if (ss_save) ss_save[(((long) b * (P.K + 3) + ch) * P.oZ + j) * OYX + col] = sv;
-          if (ch < P.K && P.cat_seg)
-            voxel_output[(((long) b * CO + P.C + ch) * P.oZ + j) * OYX + col] = sv;     // bv2:449-450
-        } else {
-          voxel_output[(((long) b * CO + (ch - P.K - 3)) * P.oZ + j) * OYX + col] = sv;
-        }
-      }
-    }
-  }
-#pragma unroll
-  for (int u = 0; u < NC; ++u) {
-    const int ch = c0 + u;
-    if (!on[u]) continue;
-    if (ch < P.K) bev_seg[((long) b * P.K + ch) * OYX + col] = acc[u];
-    else if (ch < P.K + 3) bev_rgb[((long) b * 3 + (ch - P.K)) * OYX + col] = acc[u];
-  }
-}
 
 // ---------------------------------------------------------------------------
 // backward
@@ -1342,30 +1111,290 @@ bev_gather_pass_kernel(RenderParams P, const int4* __restrict__ tab, const float
   for (int z = max(cur + 2, 0); z < P.Z; ++z) store_plane(z, 0.f, false);
 }
 
-// d beta partial sums the scan leaves in the workspace: one per workgroup of bev_scan_kernel, or -- when the
-// forward kept its samples -- of bev_qscan_saved_kernel
-static size_t bev_scan_blocks(const VampRenderDesc* d, bool saved) {
-  if (saved) return (size_t) (((long) d->oY * d->oX + 63) / 64) * d->B;
-  return (size_t) ((d->oX + 63) / 64) * ((d->oY + 3) / 4) * d->B;
+// ---------------------------------------------------------------------------
+// host side: launch what the plan says (the plan itself: vamp_render_bev_backward_plan below)
+// ---------------------------------------------------------------------------
+using BevPlan = VampBevBackwardPlan;
+
+// the arguments of one backward call
+struct BevBwdCall {
+  const VampRenderDesc* d;
+  RenderParams P;
+  const float *oxs, *oys, *ozs, *bev_mids, *beta;
+  const void *dens, *sem, *rgb, *base;
+  const float *g_brgb, *g_bseg, *g_bh, *g_vd, *g_vo;
+  float *gd, *gs, *gr, *gb, *gbeta;
+  hipStream_t s;
+};
+
+// f(TypeTag<T>{}) with the volumes' element type; f(std::true_type / std::false_type) for a runtime bool
+template <typename T>
+struct TypeTag { using type = T; };
+template <typename F>
+static int with_dtype(int in_dtype, F&& f) {
+  return in_dtype == VAMP_F32 ? f(TypeTag<float>{}) : f(TypeTag<__hip_bfloat16>{});
 }
-// the workspace holds the larger of the two counts: either is the larger one, depending on the det grid (oX = 4,
-// oY = 200: 26 workgroups of 64 columns against 100 of 64 x 4)
-static size_t bev_scan_blocks_max(const VampRenderDesc* d) {
-  return std::max(bev_scan_blocks(d, true), bev_scan_blocks(d, false));
+template <typename F>
+static int with_bool(bool b, F&& f) { return b ? f(std::true_type{}) : f(std::false_type{}); }
+
+// zero fills in front of a body that adds (the float-atomic splat, the generic gather) or of nothing (a lattice that
+// misses the volume)
+static int bev_bwd_zero(const BevBwdCall& c, const BevPlan& p) {
+  const VampRenderDesc* d = c.d;
+  const size_t vb = (size_t) d->B * d->Z * d->Y * d->X * sizeof(float);
+  if (p.zero_base && c.gb)
+    if (int e = launch_zero(c.gb, vb * d->C, c.s)) return e;
+  if (p.zero_cam) {
+    if (int e = launch_zero(c.gd, vb, c.s)) return e;
+    if (int e = launch_zero(c.gs, vb * d->K, c.s)) return e;
+    if (int e = launch_zero(c.gr, vb * 3, c.s)) return e;
+  }
+  return VAMP_OK;
 }
 
-// workspace: Q, Wb, DS0 [B, oZ, oY, oX] | axis tables | beta partials | what the forward keeps for
-// the backward (VAMP_BEVFWD_SAVE): density samples [B, oZ, oY, oX], composited channels' samples
-// [B, K + 3, oZ, oY, oX]
-static size_t bev_one(const VampRenderDesc* d) {
-  return align_up((size_t) d->B * d->oZ * d->oY * d->oX * sizeof(float), 256);
+// q_j = G . s_j and the per-column scan: Wb, DS0 and the d beta partials into the workspace
+static int bev_bwd_scan(const BevBwdCall& c, const BevPlan& p, const BevWorkspace& w) {
+  const dim3 grid(p.scan_grid[0], p.scan_grid[1], p.scan_grid[2]);
+  const unsigned threads = p.scan_waves * 64;
+  const size_t lds = (size_t) p.scan_lds;
+  if (p.scan == VAMP_BEVPLAN_SCAN_Q_SCAN)
+    return with_dtype(c.d->in_dtype, [&](auto tag) {
+      using T = typename decltype(tag)::type;
+      if (p.raise_lds && hipFuncSetAttribute(reinterpret_cast<const void*>(&bev_q_kernel<T>),
+                                             hipFuncAttributeMaxDynamicSharedMemorySize, (int) lds) != hipSuccess)
+        return fail(VAMP_EHIP, "%s: cannot raise dynamic LDS", "vamp_render_bev_backward_ex");
+      const dim3 qgrid(p.q_grid[0], p.q_grid[1], p.q_grid[2]);
+      VAMP_TIMED(kProfBevBwdQ, c.s, (bev_q_kernel<T><<<qgrid, threads, lds, c.s>>>(
+          c.P, c.oxs, c.oys, c.ozs, (const T*) c.sem, (const T*) c.rgb, c.g_brgb, c.g_bseg, w.Q)));
+      if (int e = check_launch("bev_q_kernel")) return e;
+      VAMP_TIMED(kProfBevBwd, c.s, (bev_scan_kernel<T><<<grid, threads, 0, c.s>>>(
+          c.P, c.oxs, c.oys, c.ozs, c.bev_mids, c.beta, (const T*) c.dens, nullptr, c.g_bh, c.g_vd, w.Q, w.Wb, w.DS0,
+          w.beta_part)));
+      return check_launch("bev_scan_kernel");
+    });
+  auto qscan = [&](auto nch) {
+    VAMP_TIMED(kProfBevBwd, c.s, (bev_qscan_saved_kernel<decltype(nch)::value><<<grid, threads, lds, c.s>>>(
+        c.P, c.bev_mids, c.beta, w.s0_saved, w.ss_saved, c.g_brgb, c.g_bseg, c.g_bh, c.g_vd, w.Wb, w.DS0, w.beta_part)));
+    return check_launch("bev_qscan_saved_kernel");
+  };
+  return p.scan == VAMP_BEVPLAN_SCAN_QSCAN21 ? qscan(std::integral_constant<int, 21>{})
+                                             : qscan(std::integral_constant<int, 0>{});
 }
-static size_t bev_saved_offset(const VampRenderDesc* d) {
-  return 3 * bev_one(d) + 2 * align_up((size_t) 2 * (d->X + d->Y + d->Z) * sizeof(int4), 256) +
-         align_up(bev_scan_blocks_max(d) * sizeof(float), 256);
+
+static int bev_bwd_beta_reduce(const BevBwdCall& c, const BevPlan& p, const BevWorkspace& w) {
+  if (int e = launch_beta_reduce(w.beta_part, p.beta_parts, c.beta, c.gbeta, c.s)) return e;
+  return check_launch("beta_reduce");
 }
-static size_t bev_ws_bytes(const VampRenderDesc* d) {
-  return bev_saved_offset(d) + (size_t) (1 + d->K + 3) * bev_one(d);
+
+// the volume gradients from Wb, DS0 and the upstream gradients: column gathers, or the generic gather
+static int bev_bwd_gathers(const BevBwdCall& c, const BevPlan& p, const BevWorkspace& w) {
+  const VampRenderDesc* d = c.d;
+  const RenderParams& P = c.P;
+  hipStream_t s = c.s;
+  const bool has_vo = c.g_vo != nullptr;
+  const int base_body = has_vo ? p.base_body : p.base_body_no_vo;
+  const int beta_at = has_vo ? p.beta_reduce : p.beta_reduce_no_vo;
+  // the scan's d beta partials ride with the first workgroup of one column-gather launch
+  const BetaTail no_tail{nullptr, 0, nullptr, nullptr}, tail{w.beta_part, p.beta_parts, c.beta, c.gbeta};
+  const int4* tab = w.tab[p.table];
+  if (p.build_table) {
+    VAMP_TIMED(kProfAux, s, (bev_axis_table_kernel<<<(d->X + d->Y + d->Z + 255) / 256, 256, 0, s>>>(
+        P, c.oxs, c.oys, c.ozs, w.tab[p.table])));
+    if (int e = check_launch("bev_axis_table_kernel")) return e;
+  }
+  const unsigned col_wgs = (unsigned) (((long) d->Y * d->X + 255) / 256);
+  auto col_grid = [&](int nchan, int g) { return dim3(col_wgs, d->B * p.nseg * ((nchan + g - 1) / g)); };
+  // semantic + rgb + density in one launch (they share the Wb taps of a height)
+  if (p.comp_body == VAMP_BEVPLAN_BODY_COMP) {
+    const int ngrp = (d->K + 3 + kCompG - 1) / kCompG + 1;
+    const int nwv = ngrp < kCompMaxW ? ngrp : kCompMaxW;
+    const dim3 grid((unsigned) ((((long) d->Y * d->X + 63) / 64 + 7) / 8 * 8), d->B);
+    if (int e = with_bool(p.comp_overwrite != 0, [&](auto ow) {
+          VAMP_TIMED(kProfBevBwdGather, s, (bev_gather_comp_kernel<kCompG, kCompHC, decltype(ow)::value><<<grid, nwv * 64, 0, s>>>(
+              P, tab, c.ozs, c.g_bseg, c.g_brgb, w.Wb, w.DS0, c.gd, c.gs, c.gr, d->K, 3,
+              beta_at == VAMP_BEVPLAN_BETA_TAIL_COMP ? tail : no_tail)));
+          return check_launch("bev_gather_comp_kernel");
+        })) return e;
+  } else if (p.comp_body == VAMP_BEVPLAN_BODY_COL) {
+    if (int e = with_bool(p.comp_overwrite != 0, [&](auto ow) {
+          VAMP_TIMED(kProfBevBwdGather, s, (bev_gather_col_kernel<kColGC, true, false, decltype(ow)::value><<<col_grid(d->K + 3, kColGC), 256, 0, s>>>(
+              P, tab, c.ozs, c.g_bseg, c.g_brgb, nullptr, -1, w.Wb, w.DS0, c.gd, c.gs, c.gr, d->K, 3, p.zseg, 1, 0,
+              beta_at == VAMP_BEVPLAN_BETA_TAIL_COMP ? tail : no_tail)));
+          return check_launch("bev_gather_col_kernel");
+        })) return e;
+  }
+  // pass-through gradients (voxel_output): the semantic part (cat_seg) adds, base is its own tensor
+  if (p.seg_gather && has_vo) {
+    VAMP_TIMED(kProfBevBwdGather, s, (bev_gather_col_kernel<kColG, false, true, false><<<col_grid(d->K, kColG), 256, 0, s>>>(
+        P, tab, c.ozs, nullptr, nullptr, c.g_vo, d->C, w.Wb, w.DS0, c.gd, c.gs, nullptr, d->K, 0, p.zseg, 0, 0, no_tail)));
+    if (int e = check_launch("bev_gather_col_kernel")) return e;
+  }
+  const BetaTail base_tail = beta_at == VAMP_BEVPLAN_BETA_TAIL_BASE ? tail : no_tail;
+  if (base_body == VAMP_BEVPLAN_BODY_PASS) {
+    const dim3 grid(col_wgs, (unsigned) (d->B * d->C));
+    if (int e = with_bool(p.base_overwrite != 0, [&](auto ow) {
+          VAMP_TIMED(kProfBevBwdGather, s, (bev_gather_pass_kernel<kCompHC, decltype(ow)::value><<<grid, 256, 0, s>>>(
+              P, tab, c.ozs, c.g_vo, 0, c.gb, d->C, base_tail)));
+          return check_launch("bev_gather_pass_kernel");
+        })) return e;
+  } else if (base_body == VAMP_BEVPLAN_BODY_COL) {
+    if (int e = with_bool(p.base_overwrite != 0, [&](auto ow) {
+          VAMP_TIMED(kProfBevBwdGather, s, (bev_gather_col_kernel<kColG, false, true, decltype(ow)::value><<<col_grid(d->C, kColG), 256, 0, s>>>(
+              P, tab, c.ozs, nullptr, nullptr, c.g_vo, 0, w.Wb, w.DS0, c.gd, c.gb, nullptr, d->C, 0, p.zseg, 0, 0,
+              base_tail)));
+          return check_launch("bev_gather_col_kernel");
+        })) return e;
+  } else if (base_body == VAMP_BEVPLAN_BODY_ZERO) {
+    if (int e = launch_zero(c.gb, (size_t) d->B * d->C * d->Z * d->Y * d->X * sizeof(float), s)) return e;
+  }
+  if (p.generic) {
+    // (the generic kernel does all four tensors at once, and adds: of a split pair of calls the SKIP_BASE one does
+    // the whole job behind the zero fills and the ONLY_BASE one nothing)
+    if (int e = bev_bwd_zero(c, p)) return e;
+    const dim3 grid((d->X + 63) / 64, (d->Y + 3) / 4, d->B * (p.z_hi - p.z_lo + 1));
+    VAMP_TIMED(kProfBevBwdGather, s, (bev_gather_generic_kernel<<<grid, 256, 0, s>>>(
+        P, c.oxs, c.oys, c.ozs, c.g_brgb, c.g_bseg, c.g_vo, w.Wb, w.DS0, c.gd, c.gs, c.gr, c.gb, p.z_lo, p.z_hi)));
+    if (int e = check_launch("bev_gather_generic_kernel")) return e;
+  }
+  return VAMP_OK;
+}
+
+// The plan for `who` (the entry point whose name a refusal carries).
+static int bev_backward_plan(const char* who, const VampRenderDesc* d, const float* ozs_host, int flags, BevPlan* out) {
+#define VAMP_PLAN_REQUIRE(cond, msg)                                                        \
+  do {                                                                                      \
+    if (!(cond)) return fail(VAMP_EINVAL, "%s: requirement failed: " msg, who);             \
+  } while (0)
+  VAMP_PLAN_REQUIRE(out != nullptr, "plan is NULL");
+  memset(out, 0, sizeof(*out));
+  if (int e = validate(d)) return e;
+  VAMP_PLAN_REQUIRE(d->oZ > 0 && d->oY > 0 && d->oX > 0, "det grid must be non-empty");
+  BevPlan& p = *out;
+  // VAMP_BEVBWD_ONLY_BASE / _SKIP_BASE: the pass-through (base) gather needs neither q nor the
+  // scan and nobody waits for grad_base, so a caller may issue it as a call of its own -- behind
+  // the event the camera gather waits for, or on another stream; that call has its own axis table
+  const bool only_base = (flags & VAMP_BEVBWD_ONLY_BASE) != 0, skip_base = (flags & VAMP_BEVBWD_SKIP_BASE) != 0;
+  const bool ow_base = (flags & VAMP_BEVBWD_OVERWRITE_BASE) != 0, ow_cam = (flags & VAMP_BEVBWD_OVERWRITE_CAM) != 0;
+  const bool saved = (flags & VAMP_BEVBWD_SAVED_VALID) != 0;
+  const bool sdf = d->density_mode == VAMP_DENSITY_SDF_LAPLACE;
+  if (!ozs_host) {
+    // the float-atomic formulation adds, so zero what the caller asked to have overwritten; of a split pair the
+    // SKIP_BASE call does it all
+    p.path = only_base ? VAMP_BEVPLAN_PATH_NOOP : VAMP_BEVPLAN_PATH_V1;
+    p.zero_cam = ow_cam && !only_base;
+    p.zero_base = ow_base && !only_base;
+    return VAMP_OK;
+  }
+  p.path = VAMP_BEVPLAN_PATH_CELL;
+  VAMP_PLAN_REQUIRE(d->oZ <= kBevMaxOZ, "at most 64 det-grid heights");
+  VAMP_PLAN_REQUIRE(!(only_base && skip_base), "ONLY_BASE and SKIP_BASE exclude each other");
+
+  // z-range of volume planes the lattice touches (host copy of the det-grid heights)
+  int z_lo = d->Z, z_hi = -1;
+  for (int k = 0; k < d->oZ; ++k) {
+    const float g = ((ozs_host[k] - d->lo[2]) / d->span[2]) * 2.0f - 1.0f;
+    const float f = ((g + 1.0f) / 2.0f) * (float) (d->Z - 1);
+    const int i0 = (int) floorf(f);
+    z_lo = i0 < z_lo ? i0 : z_lo;
+    z_hi = i0 + 1 > z_hi ? i0 + 1 : z_hi;
+  }
+  p.z_lo = z_lo < 0 ? 0 : z_lo;
+  p.z_hi = z_hi > d->Z - 1 ? d->Z - 1 : z_hi;
+  p.outside = p.z_lo > p.z_hi;
+  p.beta_parts = (int) bev_scan_blocks(d, saved);
+
+  // The scan.  A lattice that misses the volume (outside) has only zeros to write to the volume gradients, but the
+  // sdf density of the zero-padded samples, f(0; beta), still depends on beta: the scan then runs for d loss / d beta
+  // of bev_height and voxel_density alone.
+  if (!only_base && (!p.outside || sdf)) {
+    if (saved) {
+      // (the <21> body's buffer descriptors address bytes: 2 GB per tensor)
+      const bool k21 = d->K + 3 == 21 && (size_t) d->B * 21 * d->oZ * d->oY * d->oX * 4 < 0x7fffffffull;
+      p.scan = k21 ? VAMP_BEVPLAN_SCAN_QSCAN21 : VAMP_BEVPLAN_SCAN_QSCAN0;
+      p.scan_grid[0] = (int) (((long) d->oY * d->oX + 63) / 64); p.scan_grid[1] = d->B; p.scan_grid[2] = 1;
+      p.scan_waves = d->oZ < kQsMaxWaves ? d->oZ : kQsMaxWaves;      // a wave per height
+      p.scan_lds = (int64_t) 4 * d->oZ * 64 * sizeof(float);
+    } else {
+      p.scan = VAMP_BEVPLAN_SCAN_Q_SCAN;
+      p.q_grid[0] = (d->oX + 63) / 64; p.q_grid[1] = d->oY; p.q_grid[2] = d->B;
+      p.scan_grid[0] = (d->oX + 63) / 64; p.scan_grid[1] = (d->oY + 3) / 4; p.scan_grid[2] = d->B;
+      p.scan_waves = 4;
+      p.scan_lds = (int64_t) d->oZ * 4 * 64 * sizeof(float);
+      p.raise_lds = p.scan_lds > 60 * 1024;
+    }
+  }
+  if (p.outside) {
+    // A split pair zeroes each buffer in the half that owns it (ONLY_BASE is issued behind the event the camera
+    // gather waits for: zeroing the three camera tensors again there would race with, or wipe, that gather's sums).
+    p.zero_cam = ow_cam && !only_base;
+    p.zero_base = ow_base && !skip_base;
+    // (in the SKIP_BASE call of a pair the reduction sits in front of the event the camera gather waits for, where
+    // the other lattices leave it to the ONLY_BASE call behind that event: a launch more on the camera gather's
+    // path, for lattices that miss the volume only.  The add is atomic and commutes with the camera branch's.)
+    if (p.scan) p.beta_reduce = p.beta_reduce_no_vo = VAMP_BEVPLAN_BETA_EARLY;
+    return VAMP_OK;
+  }
+
+  // lattice points within one voxel's trilinear support, per axis
+  bool fits = true;
+  const int nvox[3] = {d->X, d->Y, d->Z};
+  for (int a = 0; a < 3; ++a) {
+    const float e = d->span[a] / (float) (nvox[a] - 1);
+    if (!(d->det_step[a] > 0.f) || (int) floorf(2.0f * e / d->det_step[a]) + 1 > kMaxT) fits = false;
+  }
+  // the column gather walks the heights upwards and keeps their z taps in an LDS table
+  if (d->oZ > kBevMaxOZ) fits = false;
+  for (int k = 1; k < d->oZ; ++k)
+    if (!(ozs_host[k] > ozs_host[k - 1])) fits = false;
+  p.fits = fits;
+  // the beta partial sums of the scan are added up where nobody waits: in the second call of a split pair
+  // (ONLY_BASE; the first, SKIP_BASE, leaves them in the workspace), else in this one
+  const bool beta_due = !skip_base && sdf;
+  if (!fits) {
+    p.generic = !only_base;
+    p.zero_cam = ow_cam && !only_base;
+    p.zero_base = ow_base && !only_base;
+    if (beta_due) p.beta_reduce = p.beta_reduce_no_vo = VAMP_BEVPLAN_BETA_LAUNCH;
+    return VAMP_OK;
+  }
+  // 32-bit element offsets inside the gather
+  const size_t lim = 0x7fffffffu;
+  VAMP_PLAN_REQUIRE((size_t) d->B * (d->K > d->C ? d->K : d->C) * d->Z * d->Y * d->X < lim &&
+                    (size_t) d->B * (d->C + d->K) * d->oZ * d->oY * d->oX < lim,
+                    "tensor too large for the 32-bit offsets of the BEV gather");
+  // the axis table depends on the grids only: a caller that kept the workspace says so
+  p.build_table = !(flags & VAMP_BEVBWD_TABLE_VALID);
+  p.table = only_base;
+  // z-segments: a segment redoes the plane sums of the one or two heights that straddle its
+  // lower edge, so as few as fill the chip (cfg-B, composited + pass-through launch, us:
+  // 1 segment 40 + 29, 2 segments 40 + 25, 4 segments 43 + 25, 8 segments 73 + 29)
+  const long wgs = (((long) d->Y * d->X + 255) / 256) * d->B * ((d->C + kColG - 1) / kColG);
+  const int nseg = (int) std::min<long>(std::max<long>(1, (1250 + wgs - 1) / std::max<long>(1, wgs)), std::max(1, d->Z / 4));
+  p.zseg = (d->Z + nseg - 1) / nseg;
+  p.nseg = (d->Z + p.zseg - 1) / p.zseg;
+  // (the descriptors of the composited and the pass-through body address bytes: 2 GB per tensor)
+  p.comp_ok = (size_t) d->B * d->K * d->Z * d->Y * d->X * 4 < lim && (size_t) d->B * d->oZ * d->oY * d->oX * 4 < lim;
+  p.pass_ok = (size_t) d->B * (d->C + (d->cat_seg ? d->K : 0)) * d->oZ * d->oY * d->oX * 4 < lim &&
+              (size_t) d->B * d->C * d->Z * d->Y * d->X * 4 < lim;
+  if (!only_base) {
+    p.comp_body = p.comp_ok ? VAMP_BEVPLAN_BODY_COMP : VAMP_BEVPLAN_BODY_COL;
+    p.comp_overwrite = ow_cam;
+    p.seg_gather = d->cat_seg != 0;
+  }
+  if (!skip_base && d->C > 0) {
+    p.base_body = p.pass_ok ? VAMP_BEVPLAN_BODY_PASS : VAMP_BEVPLAN_BODY_COL;
+    p.base_overwrite = ow_base;
+    p.base_body_no_vo = ow_base ? VAMP_BEVPLAN_BODY_ZERO : VAMP_BEVPLAN_BODY_NONE;
+  }
+  // ... by the first workgroup of the first column-gather launch of the call, or, where none follows, by a launch
+  // of its own
+  if (beta_due) {
+    p.beta_reduce_no_vo = p.comp_body ? VAMP_BEVPLAN_BETA_TAIL_COMP : VAMP_BEVPLAN_BETA_LAUNCH;
+    p.beta_reduce = p.comp_body ? VAMP_BEVPLAN_BETA_TAIL_COMP
+                                : (p.base_body ? VAMP_BEVPLAN_BETA_TAIL_BASE : VAMP_BEVPLAN_BETA_LAUNCH);
+  }
+  return VAMP_OK;
+#undef VAMP_PLAN_REQUIRE
 }
 
 }  // namespace vamp
@@ -1374,118 +1403,10 @@ using namespace vamp;
 
 extern "C" {
 
-size_t vamp_render_bev_workspace_bytes(const VampRenderDesc* d) { return d ? bev_ws_bytes(d) : 0; }
+size_t vamp_render_bev_workspace_bytes(const VampRenderDesc* d) { return d ? bev_workspace(d, nullptr).bytes : 0; }
 
-int vamp_render_bev_forward_ex(const VampRenderDesc* d, const float* oxs, const float* oys,
-                               const float* ozs, const float* bev_mids, const float* beta,
-                               const void* density_feature, const void* semantic, const void* rgb,
-                               const void* base, float* bev_rgb, float* bev_seg, float* bev_height,
-                               float* voxel_density, float* voxel_output, const float* ozs_host,
-                               void* workspace, size_t workspace_bytes, int flags, void* stream) {
-  if (int e = validate(d)) return e;
-  float *s0_save = nullptr, *ss_save = nullptr;
-  if (flags & VAMP_BEVFWD_SAVE) {
-    if (!workspace || workspace_bytes < bev_ws_bytes(d))
-      return fail(VAMP_ENOSPC, "%s: workspace %ld < %ld bytes", __func__, (long) workspace_bytes, (long) bev_ws_bytes(d));
-    s0_save = reinterpret_cast<float*>(static_cast<char*>(workspace) + bev_saved_offset(d));
-    ss_save = reinterpret_cast<float*>(static_cast<char*>(workspace) + bev_saved_offset(d) + bev_one(d));
-  }
-  VAMP_REQUIRE(d->oZ > 0 && d->oY > 0 && d->oX > 0, "det grid must be non-empty");
-  VAMP_REQUIRE(oxs && oys && ozs && bev_mids && density_feature && semantic && rgb, "null pointer");
-  VAMP_REQUIRE(base || d->C == 0, "base is NULL");
-  VAMP_REQUIRE(bev_rgb && bev_seg && bev_height && voxel_density && voxel_output, "null output");
-  VAMP_REQUIRE(beta || d->density_mode == VAMP_DENSITY_SIGMOID, "beta is NULL");
-  const RenderParams P = to_params(d);
-  hipStream_t s = static_cast<hipStream_t>(stream);
-  // the one-kernel forward only for heights the library has checked against its plane slabs (bev_fused_heights_fit)
-  if (!(flags & VAMP_BEVFWD_TWO_KERNELS) && bev_fwd_fused_supported(d) && bev_fused_heights_fit(d, ozs_host))
-    return launch_bev_fwd_fused(d, P, oxs, oys, ozs, bev_mids, beta, density_feature, semantic, rgb, base, bev_rgb,
-                                bev_seg, bev_height, voxel_density, voxel_output, s0_save, ss_save, s);
-  dim3 g1((d->oX + 63) / 64, (d->oY + 3) / 4, d->B);
-  VAMP_REQUIRE(d->oZ <= kBevMaxOZ, "at most 64 det-grid heights");
-  dim3 g2((d->oX + 63) / 64, (d->oY + 3) / 4, d->B * ((d->K + 3 + d->C + kBevNC - 1) / kBevNC));
-#define VAMP_BEVF(T)                                                                              \
-  do {                                                                                            \
-    VAMP_TIMED(kProfBevFwd, s, (bev_density_kernel<T><<<g1, 256, 0, s>>>(                         \
-        P, oxs, oys, ozs, bev_mids, beta, (const T*) density_feature, voxel_density, bev_height, s0_save))); \
-    if (int e = check_launch("bev_density_kernel")) return e;                                     \
-    VAMP_TIMED(kProfBevFwdCh, s, (bev_channels_kernel<T, kBevNC><<<g2, 256, 0, s>>>(              \
-        P, oxs, oys, ozs, (const T*) semantic, (const T*) rgb, (const T*) base, voxel_density,    \
-        bev_rgb, bev_seg, voxel_output, ss_save)));                                               \
-  } while (0)
-  if (d->in_dtype == VAMP_F32) VAMP_BEVF(float); else VAMP_BEVF(__hip_bfloat16);
-#undef VAMP_BEVF
-  return check_launch("bev_channels_kernel");
-}
-
-int vamp_render_forward_merged_supported(const VampRenderDesc* d, const float* ozs_host) {
-  if (!d || validate(d)) return 0;
-  return render_fwd_merged_supported(d) && bev_fused_heights_fit(d, ozs_host) ? 1 : 0;
-}
-
-int vamp_render_forward_merged(const VampRenderDesc* d, const float* mats, const float* us, const float* vs,
-                               const float* ds, const float* mids, const float* oxs, const float* oys,
-                               const float* ozs, const float* ozs_host, const float* bev_mids, const float* beta,
-                               const void* density_feature, const void* semantic, const void* rgb,
-                               const void* base, float* rgb_out, float* seg_out, float* depth_out,
-                               float* bev_rgb, float* bev_seg, float* bev_height, float* voxel_density,
-                               float* voxel_output, void* workspace, size_t workspace_bytes,
-                               void* bev_workspace, size_t bev_workspace_bytes, float* grad_beta_zero, int flags,
-                               void* stream) {
-  if (int e = validate(d)) return e;
-  VAMP_REQUIRE(mats && us && vs && ds && mids && oxs && oys && ozs && bev_mids, "null pointer");
-  VAMP_REQUIRE(density_feature && semantic && rgb && (base || d->C == 0), "null input volume");
-  VAMP_REQUIRE(rgb_out && seg_out && depth_out && bev_rgb && bev_seg && bev_height && voxel_density && voxel_output,
-               "null output");
-  VAMP_REQUIRE(beta || d->density_mode == VAMP_DENSITY_SIGMOID, "beta is NULL");
-  VAMP_REQUIRE(render_fwd_merged_supported(d), "shapes outside the merged launch's limits (vamp_render_forward_merged_supported)");
-  VAMP_REQUIRE(bev_fused_heights_fit(d, ozs_host), "ozs_host is NULL or the heights do not fit the BEV plane slabs (vamp_render_forward_merged_supported)");
-  const size_t base_bytes = vamp_render_workspace_bytes(d);
-  int* term = (workspace && workspace_bytes >= base_bytes) ? cam_term_ptr(d, workspace) : nullptr;
-  float* rows = nullptr;
-  if (flags & VAMP_RENDERFWD_SAVE_SAMPLES) {
-    const size_t need = base_bytes + vamp_render_samples_bytes(d);
-    if (!workspace || workspace_bytes < need)
-      return fail(VAMP_ENOSPC, "%s: workspace %ld < %ld bytes", __func__, (long) workspace_bytes, (long) need);
-    rows = reinterpret_cast<float*>(static_cast<char*>(workspace) + base_bytes);
-  }
-  float *s0_save = nullptr, *ss_save = nullptr;
-  if (flags & VAMP_RENDERFWD_BEV_SAVE) {
-    if (!bev_workspace || bev_workspace_bytes < bev_ws_bytes(d))
-      return fail(VAMP_ENOSPC, "%s: bev_workspace %ld < %ld bytes", __func__, (long) bev_workspace_bytes, (long) bev_ws_bytes(d));
-    s0_save = reinterpret_cast<float*>(static_cast<char*>(bev_workspace) + bev_saved_offset(d));
-    ss_save = reinterpret_cast<float*>(static_cast<char*>(bev_workspace) + bev_saved_offset(d) + bev_one(d));
-  }
-  // VAMP_RENDERFWD_RANK: the camera tiles draw the backward's cell ranks; the caller finishes the prepare step with
-  // vamp_render_camera_prepare_ex(VAMP_CAMPREP_RANKED) -- on this stream or another
-  CamRankRefs rank{nullptr, nullptr, nullptr, 0, nullptr};
-  hipStream_t s = static_cast<hipStream_t>(stream);
-  if (flags & VAMP_RENDERFWD_RANK) {
-    VAMP_REQUIRE(term != nullptr, "VAMP_RENDERFWD_RANK needs the render workspace");
-    rank = cam_rank_refs(d, workspace);
-    if (flags & VAMP_RENDERFWD_COUNTERS_CLEAN) {
-      if (int e = debug_expect_range(rank.cnt, 64, 0, 0, s, "VAMP_RENDERFWD_COUNTERS_CLEAN: the render workspace's cell counters are zero")) return e;
-    } else if (int e = launch_cam_counters_zero(d, workspace, s)) {
-      return e;
-    }
-  }
-  rank.zero_word = grad_beta_zero;
-  return launch_render_fwd_merged(d, to_params(d), mats, us, vs, ds, mids, oxs, oys, ozs, bev_mids, beta, density_feature,
-                                  semantic, rgb, base, rgb_out, seg_out, depth_out, term, rows, bev_rgb, bev_seg, bev_height,
-                                  voxel_density, voxel_output, s0_save, ss_save, rank, s);
-}
-
-static int bev_zero_overwritten(const VampRenderDesc* d, int flags, float* gd, float* gs, float* gr,
-                                float* gb, hipStream_t s) {
-  const size_t vb = (size_t) d->B * d->Z * d->Y * d->X * sizeof(float);
-  if ((flags & VAMP_BEVBWD_OVERWRITE_BASE) && gb)
-    if (int ze = launch_zero(gb, vb * d->C, s)) return ze;
-  if (flags & VAMP_BEVBWD_OVERWRITE_CAM) {
-    if (int ze = launch_zero(gd, vb, s)) return ze;
-    if (int ze = launch_zero(gs, vb * d->K, s)) return ze;
-    if (int ze = launch_zero(gr, vb * 3, s)) return ze;
-  }
-  return VAMP_OK;
+int vamp_render_bev_backward_plan(const VampRenderDesc* d, const float* ozs_host, int flags, VampBevBackwardPlan* out) {
+  return bev_backward_plan(__func__, d, ozs_host, flags, out);
 }
 
 int vamp_render_bev_backward_ex(const VampRenderDesc* d, const float* oxs, const float* oys,
@@ -1503,210 +1424,30 @@ int vamp_render_bev_backward_ex(const VampRenderDesc* d, const float* oxs, const
   VAMP_REQUIRE(grad_density_feature && grad_semantic && grad_rgb, "null output");
   VAMP_REQUIRE(grad_base || d->C == 0 || !g_voxel_output, "grad_base is NULL");
   VAMP_REQUIRE((beta && grad_beta) || d->density_mode == VAMP_DENSITY_SIGMOID, "beta / grad_beta is NULL");
-  if (!ozs_host && (flags & VAMP_BEVBWD_ONLY_BASE)) return VAMP_OK;   // the SKIP_BASE call of the pair does it all
-  if (!ozs_host) {
-    // float-atomic formulation: adds, so zero what the caller asked to have overwritten
-    if (int e = bev_zero_overwritten(d, flags, grad_density_feature, grad_semantic, grad_rgb, grad_base,
-                                     static_cast<hipStream_t>(stream))) return e;
+  BevPlan p;
+  if (int e = bev_backward_plan(__func__, d, ozs_host, flags, &p)) return e;
+  if (p.path == VAMP_BEVPLAN_PATH_NOOP) return VAMP_OK;
+  const BevBwdCall c{d, to_params(d), oxs, oys, ozs, bev_mids, beta, density_feature, semantic, rgb, base,
+                     g_bev_rgb, g_bev_seg, g_bev_height, g_voxel_density, g_voxel_output, grad_density_feature,
+                     grad_semantic, grad_rgb, grad_base, grad_beta, static_cast<hipStream_t>(stream)};
+  if (p.path == VAMP_BEVPLAN_PATH_V1) {
+    if (int e = bev_bwd_zero(c, p)) return e;
     return launch_bev_bwd_v1(d, oxs, oys, ozs, bev_mids, beta, density_feature, semantic, rgb, base,
                              g_bev_rgb, g_bev_seg, g_bev_height, g_voxel_density, g_voxel_output,
-                             grad_density_feature, grad_semantic, grad_rgb, grad_base, grad_beta,
-                             stream);
+                             grad_density_feature, grad_semantic, grad_rgb, grad_base, grad_beta, stream);
   }
-  VAMP_REQUIRE(d->oZ <= kBevMaxOZ, "at most 64 det-grid heights");
-  const size_t need = bev_ws_bytes(d);
-  if (!workspace || workspace_bytes < need)
-    return fail(VAMP_ENOSPC, "%s: workspace %ld < %ld bytes", __func__, (long) workspace_bytes, (long) need);
-  const RenderParams P = to_params(d);
-  hipStream_t s = static_cast<hipStream_t>(stream);
-  const size_t one = align_up((size_t) d->B * d->oZ * d->oY * d->oX * sizeof(float), 256);
-  const int tot_ax = d->X + d->Y + d->Z;
-  // VAMP_BEVBWD_ONLY_BASE / _SKIP_BASE: the pass-through (base) gather needs neither q nor the
-  // scan and nobody waits for grad_base, so a caller may issue it as a call of its own -- behind
-  // the event the camera gather waits for, or on another stream; that call has its own axis table
-  const bool only_base = (flags & VAMP_BEVBWD_ONLY_BASE) != 0, skip_base = (flags & VAMP_BEVBWD_SKIP_BASE) != 0;
-  VAMP_REQUIRE(!(only_base && skip_base), "ONLY_BASE and SKIP_BASE exclude each other");
-  const size_t tab_bytes = align_up((size_t) 2 * (d->X + d->Y + d->Z) * sizeof(int4), 256);
-  int4* tab = reinterpret_cast<int4*>(static_cast<char*>(workspace) + 3 * one + (only_base ? tab_bytes : 0));
-  float* Q = static_cast<float*>(workspace);
-  float* Wb = reinterpret_cast<float*>(static_cast<char*>(workspace) + one);
-  float* DS0 = reinterpret_cast<float*>(static_cast<char*>(workspace) + 2 * one);
-  float* beta_part = reinterpret_cast<float*>(static_cast<char*>(workspace) + 3 * one + 2 * tab_bytes);
-
-  // z-range of volume planes the lattice touches (host copy of the det-grid heights)
-  int z_lo = d->Z, z_hi = -1;
-  for (int k = 0; k < d->oZ; ++k) {
-    const float g = ((ozs_host[k] - d->lo[2]) / d->span[2]) * 2.0f - 1.0f;
-    const float f = ((g + 1.0f) / 2.0f) * (float) (d->Z - 1);
-    const int i0 = (int) floorf(f);
-    z_lo = i0 < z_lo ? i0 : z_lo;
-    z_hi = i0 + 1 > z_hi ? i0 + 1 : z_hi;
-  }
-  z_lo = z_lo < 0 ? 0 : z_lo;
-  z_hi = z_hi > d->Z - 1 ? d->Z - 1 : z_hi;
-  const bool outside = z_lo > z_hi;
-  if (outside) {
-    // the det lattice misses the volume: only zeros to write to the volume gradients.  A split pair zeroes
-    // each buffer in the half that owns it (ONLY_BASE is issued behind the event the camera gather waits
-    // for: zeroing the three camera tensors again there would race with, or wipe, that gather's sums)
-    int zf = flags;
-    if (flags & VAMP_BEVBWD_ONLY_BASE) zf &= ~VAMP_BEVBWD_OVERWRITE_CAM;
-    if (flags & VAMP_BEVBWD_SKIP_BASE) zf &= ~VAMP_BEVBWD_OVERWRITE_BASE;
-    if (int e = bev_zero_overwritten(d, zf, grad_density_feature, grad_semantic, grad_rgb, grad_base,
-                                     static_cast<hipStream_t>(stream))) return e;
-    // ... but the sdf density of the zero-padded samples, f(0; beta), still depends on beta: the scan below
-    // forms d loss / d beta of bev_height and voxel_density, and this call (SKIP_BASE of a pair: the
-    // ONLY_BASE call returns here) adds it to grad_beta
-    if (d->density_mode != VAMP_DENSITY_SDF_LAPLACE || only_base) return VAMP_OK;
-  }
-
-  dim3 gq((d->oX + 63) / 64, d->oY, d->B);
-  const size_t q_lds = (size_t) d->oZ * 4 * 64 * sizeof(float);
-  dim3 gs((d->oX + 63) / 64, (d->oY + 3) / 4, d->B);
-  dim3 gg((d->X + 63) / 64, (d->Y + 3) / 4, d->B * (z_hi - z_lo + 1));
-  const bool saved = (flags & VAMP_BEVBWD_SAVED_VALID) != 0;
-  const float* s0_saved = saved ? reinterpret_cast<const float*>(static_cast<char*>(workspace) + bev_saved_offset(d)) : nullptr;
-  const float* ss_saved = saved ? reinterpret_cast<const float*>(static_cast<char*>(workspace) + bev_saved_offset(d) + bev_one(d)) : nullptr;
-#define VAMP_BEVB(T)                                                                              \
-  do {                                                                                            \
-    if (saved) {                                                                                  \
-      const int nwj = d->oZ < kQsMaxWaves ? d->oZ : kQsMaxWaves;   /* a wave per height */             \
-      const dim3 gqf((unsigned) (((long) d->oY * d->oX + 63) / 64), d->B);                           \
-      const size_t qlds = (size_t) 4 * d->oZ * 64 * sizeof(float);                                    \
-      if (d->K + 3 == 21 && (size_t) d->B * 21 * d->oZ * d->oY * d->oX * 4 < 0x7fffffffull)           \
-        VAMP_TIMED(kProfBevBwd, s, (bev_qscan_saved_kernel<21><<<gqf, nwj * 64, qlds, s>>>(            \
-            P, bev_mids, beta, s0_saved, ss_saved, g_bev_rgb, g_bev_seg, g_bev_height, g_voxel_density, Wb, DS0, beta_part))); \
-      else                                                                                            \
-        VAMP_TIMED(kProfBevBwd, s, (bev_qscan_saved_kernel<0><<<gqf, nwj * 64, qlds, s>>>(             \
-            P, bev_mids, beta, s0_saved, ss_saved, g_bev_rgb, g_bev_seg, g_bev_height, g_voxel_density, Wb, DS0, beta_part))); \
-      if (int e = check_launch("bev_qscan_saved_kernel")) return e;                               \
-      break;                                                                                      \
-    } else {                                                                                      \
-    if (q_lds > 60 * 1024 &&                                                                      \
-        hipFuncSetAttribute(reinterpret_cast<const void*>(&bev_q_kernel<T>),                     \
-                            hipFuncAttributeMaxDynamicSharedMemorySize, (int) q_lds) != hipSuccess) \
-      return fail(VAMP_EHIP, "%s: cannot raise dynamic LDS", __func__);                           \
-    VAMP_TIMED(kProfBevBwdQ, s, (bev_q_kernel<T><<<gq, 256, q_lds, s>>>(                              \
-        P, oxs, oys, ozs, (const T*) semantic, (const T*) rgb, g_bev_rgb, g_bev_seg, Q)));        \
-    if (int e = check_launch("bev_q_kernel")) return e;                                           \
-    }                                                                                             \
-    VAMP_TIMED(kProfBevBwd, s, (bev_scan_kernel<T><<<gs, 256, 0, s>>>(                            \
-        P, oxs, oys, ozs, bev_mids, beta, (const T*) density_feature, s0_saved, g_bev_height,     \
-        g_voxel_density, Q, Wb, DS0, beta_part)));                                                \
-    if (int e = check_launch("bev_scan_kernel")) return e;                                        \
-  } while (0)
-  if (!only_base) {
-    if (d->in_dtype == VAMP_F32) VAMP_BEVB(float); else VAMP_BEVB(__hip_bfloat16);
-  }
-#undef VAMP_BEVB
-  if (outside) {
-    // (here, in the SKIP_BASE call of a pair, the reduction sits in front of the event the camera gather waits for,
-    // where the other lattices leave it to the ONLY_BASE call behind that event: a launch more on the camera gather's
-    // path, for lattices that miss the volume only.  The add is atomic and commutes with the camera branch's.)
-    if (int e = launch_beta_reduce(beta_part, (int) bev_scan_blocks(d, saved), beta, grad_beta, s)) return e;
-    return check_launch("beta_reduce");
-  }
-  // the beta partial sums of the scan are added up where nobody waits: in the second call of a split
-  // pair (ONLY_BASE; the first, SKIP_BASE, leaves them in the workspace), else right here
-  // ... by the first workgroup of the first column-gather launch of that call (beta_tail), or, where no
-  // such launch follows, by a launch of its own
-  BetaTail btail{nullptr, 0, nullptr, nullptr};
-  if (!skip_base && d->density_mode == VAMP_DENSITY_SDF_LAPLACE)
-    btail = BetaTail{beta_part, (int) bev_scan_blocks(d, saved), beta, grad_beta};
-  const BetaTail no_tail{nullptr, 0, nullptr, nullptr};
-  auto take_tail = [&]() { const BetaTail t = btail; btail = no_tail; return t; };
-  // lattice points within one voxel's trilinear support, per axis
-  bool fits = true;
-  const int nvox[3] = {d->X, d->Y, d->Z};
-  for (int a = 0; a < 3; ++a) {
-    const float e = d->span[a] / (float) (nvox[a] - 1);
-    if (!(d->det_step[a] > 0.f) || (int) floorf(2.0f * e / d->det_step[a]) + 1 > kMaxT) fits = false;
-  }
-  // the column gather walks the heights upwards and keeps their z taps in an LDS table
-  if (d->oZ > kBevMaxOZ) fits = false;
-  for (int k = 1; k < d->oZ; ++k)
-    if (!(ozs_host[k] > ozs_host[k - 1])) fits = false;
-  if (fits) {
-    // 32-bit element offsets inside the gather
-    const size_t lim = 0x7fffffffu;
-    VAMP_REQUIRE((size_t) d->B * (d->K > d->C ? d->K : d->C) * d->Z * d->Y * d->X < lim &&
-                 (size_t) d->B * (d->C + d->K) * d->oZ * d->oY * d->oX < lim,
-                 "tensor too large for the 32-bit offsets of the BEV gather");
-    // the axis table depends on the grids only: a caller that kept the workspace says so
-    if (!(flags & VAMP_BEVBWD_TABLE_VALID)) {
-      VAMP_TIMED(kProfAux, s, (bev_axis_table_kernel<<<(tot_ax + 255) / 256, 256, 0, s>>>(P, oxs, oys, ozs, tab)));
-      if (int e = check_launch("bev_axis_table_kernel")) return e;
-    }
-    const bool vo_sem = g_voxel_output && d->cat_seg;
-    const int ow = (flags & VAMP_BEVBWD_OVERWRITE_BASE) ? 1 : 0;
-    const int owc = (flags & VAMP_BEVBWD_OVERWRITE_CAM) ? 3 : 0;
-    // z-segments: a segment redoes the plane sums of the one or two heights that straddle its
-    // lower edge, so as few as fill the chip (cfg-B, composited + pass-through launch, us:
-    // 1 segment 40 + 29, 2 segments 40 + 25, 4 segments 43 + 25, 8 segments 73 + 29)
-    const long wgs = (((long) d->Y * d->X + 255) / 256) * d->B * ((d->C + kColG - 1) / kColG);
-    int nseg = (int) std::min<long>(std::max<long>(1, (1250 + wgs - 1) / std::max<long>(1, wgs)), std::max(1, d->Z / 4));
-    const int zseg = (d->Z + nseg - 1) / nseg;
-    nseg = (d->Z + zseg - 1) / zseg;
-    auto grid = [&](int nchan, int g = kColG) {
-      return dim3((unsigned) (((long) d->Y * d->X + 255) / 256), d->B * nseg * ((nchan + g - 1) / g));
-    };
-    // semantic + rgb + density in one launch (they share the Wb taps of a height)
-    // (the descriptors of the round-4 kernel address bytes: 2 GB per tensor)
-    const bool comp_ok = (size_t) d->B * d->K * d->Z * d->Y * d->X * 4 < lim && (size_t) d->B * d->oZ * d->oY * d->oX * 4 < lim;
-    const int ngrp_c = (d->K + 3 + kCompG - 1) / kCompG + 1;
-    const int nwv_c = ngrp_c < kCompMaxW ? ngrp_c : kCompMaxW;
-    const dim3 grid_comp((unsigned) ((((long) d->Y * d->X + 63) / 64 + 7) / 8 * 8), d->B);
-    if (only_base) {}
-    else if (comp_ok && owc) VAMP_TIMED(kProfBevBwdGather, s, (bev_gather_comp_kernel<kCompG, kCompHC, true><<<grid_comp, nwv_c * 64, 0, s>>>(
-        P, tab, ozs, g_bev_seg, g_bev_rgb, Wb, DS0, grad_density_feature, grad_semantic, grad_rgb, d->K, 3, take_tail())));
-    else if (comp_ok) VAMP_TIMED(kProfBevBwdGather, s, (bev_gather_comp_kernel<kCompG, kCompHC, false><<<grid_comp, nwv_c * 64, 0, s>>>(
-        P, tab, ozs, g_bev_seg, g_bev_rgb, Wb, DS0, grad_density_feature, grad_semantic, grad_rgb, d->K, 3, take_tail())));
-    else if (owc) VAMP_TIMED(kProfBevBwdGather, s, (bev_gather_col_kernel<kColGC, true, false, true><<<grid(d->K + 3, kColGC), 256, 0, s>>>(
-        P, tab, ozs, g_bev_seg, g_bev_rgb, nullptr, -1, Wb, DS0, grad_density_feature, grad_semantic, grad_rgb,
-        d->K, 3, zseg, 1, 0, take_tail())));
-    else VAMP_TIMED(kProfBevBwdGather, s, (bev_gather_col_kernel<kColGC, true, false, false><<<grid(d->K + 3, kColGC), 256, 0, s>>>(
-        P, tab, ozs, g_bev_seg, g_bev_rgb, nullptr, -1, Wb, DS0, grad_density_feature, grad_semantic, grad_rgb,
-        d->K, 3, zseg, 1, 0, take_tail())));
-    if (int e = check_launch("bev_gather_col_kernel")) return e;
-    // pass-through gradients (voxel_output): the semantic part (cat_seg) adds, base is its own tensor
-    if (vo_sem && !only_base)
-      VAMP_TIMED(kProfBevBwdGather, s, (bev_gather_col_kernel<kColG, false, true, false><<<grid(d->K), 256, 0, s>>>(
-          P, tab, ozs, nullptr, nullptr, g_voxel_output, d->C, Wb, DS0, grad_density_feature, grad_semantic,
-          nullptr, d->K, 0, zseg, 0, 0, take_tail())));
-    const bool pass_ok = (size_t) d->B * (d->C + (d->cat_seg ? d->K : 0)) * d->oZ * d->oY * d->oX * 4 < lim &&
-                         (size_t) d->B * d->C * d->Z * d->Y * d->X * 4 < lim;
-    const dim3 grid_pass((unsigned) (((long) d->Y * d->X + 255) / 256), (unsigned) (d->B * d->C));
-    if (skip_base) {}
-    else if (d->C > 0 && g_voxel_output && pass_ok && ow)
-      VAMP_TIMED(kProfBevBwdGather, s, (bev_gather_pass_kernel<kCompHC, true><<<grid_pass, 256, 0, s>>>(
-          P, tab, ozs, g_voxel_output, 0, grad_base, d->C, take_tail())));
-    else if (d->C > 0 && g_voxel_output && pass_ok)
-      VAMP_TIMED(kProfBevBwdGather, s, (bev_gather_pass_kernel<kCompHC, false><<<grid_pass, 256, 0, s>>>(
-          P, tab, ozs, g_voxel_output, 0, grad_base, d->C, take_tail())));
-    else if (d->C > 0 && g_voxel_output && ow)
-      VAMP_TIMED(kProfBevBwdGather, s, (bev_gather_col_kernel<kColG, false, true, true><<<grid(d->C), 256, 0, s>>>(
-          P, tab, ozs, nullptr, nullptr, g_voxel_output, 0, Wb, DS0, grad_density_feature, grad_base, nullptr,
-          d->C, 0, zseg, 0, 0, take_tail())));
-    else if (d->C > 0 && g_voxel_output)
-      VAMP_TIMED(kProfBevBwdGather, s, (bev_gather_col_kernel<kColG, false, true, false><<<grid(d->C), 256, 0, s>>>(
-          P, tab, ozs, nullptr, nullptr, g_voxel_output, 0, Wb, DS0, grad_density_feature, grad_base, nullptr,
-          d->C, 0, zseg, 0, 0, take_tail())));
-    else if (d->C > 0 && ow)
-      if (int ze = launch_zero(grad_base, (size_t) d->B * d->C * d->Z * d->Y * d->X * sizeof(float), s)) return ze;
-  }
-  else if (!only_base) {
-    // (the generic kernel does all four tensors at once: of a split pair of calls the SKIP_BASE one
-    // does the whole job and the ONLY_BASE one nothing)
-    // the generic kernel adds: zero what the caller asked to have overwritten
-    if (int e = bev_zero_overwritten(d, flags, grad_density_feature, grad_semantic, grad_rgb, grad_base, s))
-      return e;
-    VAMP_TIMED(kProfBevBwdGather, s, (bev_gather_generic_kernel<<<gg, 256, 0, s>>>(
-        P, oxs, oys, ozs, g_bev_rgb, g_bev_seg, g_voxel_output, Wb, DS0, grad_density_feature,
-        grad_semantic, grad_rgb, grad_base, z_lo, z_hi)));
-  }
-  if (btail.part)          // no column-gather launch took the partial sums over
-    if (int e = launch_beta_reduce(btail.part, btail.n, btail.beta_raw, btail.grad_beta, s)) return e;
-  return check_launch("bev_gather_kernel");
+  const BevWorkspace w = bev_workspace(d, workspace);
+  if (!workspace || workspace_bytes < w.bytes)
+    return fail(VAMP_ENOSPC, "%s: workspace %ld < %ld bytes", __func__, (long) workspace_bytes, (long) w.bytes);
+  if (p.outside)
+    if (int e = bev_bwd_zero(c, p)) return e;
+  if (p.scan)
+    if (int e = bev_bwd_scan(c, p, w)) return e;
+  if (p.beta_reduce == VAMP_BEVPLAN_BETA_EARLY) return bev_bwd_beta_reduce(c, p, w);
+  if (int e = bev_bwd_gathers(c, p, w)) return e;
+  if ((g_voxel_output ? p.beta_reduce : p.beta_reduce_no_vo) == VAMP_BEVPLAN_BETA_LAUNCH)
+    return bev_bwd_beta_reduce(c, p, w);
+  return VAMP_OK;
 }
 
 int vamp_render_bev_backward(const VampRenderDesc* d, const float* oxs, const float* oys,
@@ -1722,16 +1463,6 @@ int vamp_render_bev_backward(const VampRenderDesc* d, const float* oxs, const fl
                                      g_bev_rgb, g_bev_seg, g_bev_height, g_voxel_density, g_voxel_output,
                                      grad_density_feature, grad_semantic, grad_rgb, grad_base, grad_beta,
                                      ozs_host, workspace, workspace_bytes, 0, stream);
-}
-
-int vamp_render_bev_forward(const VampRenderDesc* d, const float* oxs, const float* oys,
-                            const float* ozs, const float* bev_mids, const float* beta,
-                            const void* density_feature, const void* semantic, const void* rgb,
-                            const void* base, float* bev_rgb, float* bev_seg, float* bev_height,
-                            float* voxel_density, float* voxel_output, void* stream) {
-  return vamp_render_bev_forward_ex(d, oxs, oys, ozs, bev_mids, beta, density_feature, semantic, rgb, base,
-                                    bev_rgb, bev_seg, bev_height, voxel_density, voxel_output, nullptr, nullptr, 0, 0,
-                                    stream);
 }
 
 }  // extern "C"

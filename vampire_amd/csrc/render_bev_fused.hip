@@ -1,6 +1,6 @@
 // BEV (top-down) branch of the renderer, forward, as ONE kernel: base_vampire2.py:408-418, 442-461.
 //
-// render_bev.hip's forward is two launches -- bev_density (a thread per column: 625 waves on 1024
+// render_bev_fwd.hip's forward is two launches -- bev_density (a thread per column: 625 waves on 1024
 // SIMDs, pure latency) and bev_channels (a thread per column and channel pair, which reads
 // voxel_density back and redoes the weights per pair).  Here a workgroup owns 64 consecutive
 // columns of the flattened (y, x) det lattice and NWV waves:

@@ -288,6 +288,50 @@ int launch_cam_counters_zero(const VampRenderDesc* d, void* workspace, hipStream
 // (`also`: another cell list scanned by the same launch -- the lift's, vamp_render_camera_prepare_with_lift)
 int launch_cam_prepare_ranked(const VampRenderDesc* d, void* workspace, hipStream_t s, const ScanJob* also = nullptr);
 
+// d beta partial sums the BEV backward's scan leaves in the BEV workspace: one per workgroup of bev_scan_kernel, or
+// -- when the forward kept its samples -- of bev_qscan_saved_kernel.  Either count is the larger one, depending on
+// the det grid (oX = 4, oY = 200: 26 workgroups of 64 columns against 100 of 64 x 4).
+inline size_t bev_scan_blocks(const VampRenderDesc* d, bool saved) {
+  if (saved) return (size_t) (((long) d->oY * d->oX + 63) / 64) * d->B;
+  return (size_t) ((d->oX + 63) / 64) * ((d->oY + 3) / 4) * d->B;
+}
+
+// The BEV workspace (vamp_render_bev_workspace_bytes), in this order, every region 256-byte aligned:
+//   Q, Wb, DS0 [B, oZ, oY, oX] | two axis tables [2 (X + Y + Z)] int4 | beta partials (the larger count of the two
+//   scans) | what a forward keeps for the backward (VAMP_BEVFWD_SAVE / VAMP_RENDERFWD_BEV_SAVE): density samples
+//   [B, oZ, oY, oX], composited channels' samples [B, K + 3, oZ, oY, oX]
+struct BevWorkspace {
+  float *Q, *Wb, *DS0;
+  int4* tab[2];          // [0]: a whole call's or the SKIP_BASE half's axis table, [1]: the ONLY_BASE half's
+  float* beta_part;
+  float *s0_saved, *ss_saved;
+  size_t bytes;
+};
+// `workspace` may be nullptr (only `bytes` is of use then)
+inline BevWorkspace bev_workspace(const VampRenderDesc* d, void* workspace) {
+  const size_t one = align_up((size_t) d->B * d->oZ * d->oY * d->oX * sizeof(float), 256);
+  const size_t tab = align_up((size_t) 2 * (d->X + d->Y + d->Z) * sizeof(int4), 256);
+  const size_t nsaved = bev_scan_blocks(d, true), nscan = bev_scan_blocks(d, false);
+  const size_t nbeta = nsaved > nscan ? nsaved : nscan;
+  size_t off = 0;
+  auto take = [&](size_t n) {
+    char* p = workspace ? static_cast<char*>(workspace) + off : nullptr;
+    off += n;
+    return p;
+  };
+  BevWorkspace w;
+  w.Q = reinterpret_cast<float*>(take(one));
+  w.Wb = reinterpret_cast<float*>(take(one));
+  w.DS0 = reinterpret_cast<float*>(take(one));
+  w.tab[0] = reinterpret_cast<int4*>(take(tab));
+  w.tab[1] = reinterpret_cast<int4*>(take(tab));
+  w.beta_part = reinterpret_cast<float*>(take(align_up(nbeta * sizeof(float), 256)));
+  w.s0_saved = reinterpret_cast<float*>(take(one));
+  w.ss_saved = reinterpret_cast<float*>(take((size_t) (d->K + 3) * one));
+  w.bytes = off;
+  return w;
+}
+
 // render_cam_direct.hip: plan + density march + scan + channel gather in one kernel, on the
 // channel-first volumes; term_out (may be NULL) receives the per-ray table
 int launch_cam_fwd_direct(const VampRenderDesc* d, const RenderParams& P, const float* mats, const float* us,

@@ -174,3 +174,67 @@ int launch_render_fwd_merged(const VampRenderDesc* d, const RenderParams& P, con
 }
 
 }  // namespace vamp
+
+using namespace vamp;
+
+extern "C" {
+
+int vamp_render_forward_merged_supported(const VampRenderDesc* d, const float* ozs_host) {
+  if (!d || validate(d)) return 0;
+  return render_fwd_merged_supported(d) && bev_fused_heights_fit(d, ozs_host) ? 1 : 0;
+}
+
+int vamp_render_forward_merged(const VampRenderDesc* d, const float* mats, const float* us, const float* vs,
+                               const float* ds, const float* mids, const float* oxs, const float* oys,
+                               const float* ozs, const float* ozs_host, const float* bev_mids, const float* beta,
+                               const void* density_feature, const void* semantic, const void* rgb,
+                               const void* base, float* rgb_out, float* seg_out, float* depth_out,
+                               float* bev_rgb, float* bev_seg, float* bev_height, float* voxel_density,
+                               float* voxel_output, void* workspace, size_t workspace_bytes,
+                               void* bev_workspace, size_t bev_workspace_bytes, float* grad_beta_zero, int flags,
+                               void* stream) {
+  if (int e = validate(d)) return e;
+  VAMP_REQUIRE(mats && us && vs && ds && mids && oxs && oys && ozs && bev_mids, "null pointer");
+  VAMP_REQUIRE(density_feature && semantic && rgb && (base || d->C == 0), "null input volume");
+  VAMP_REQUIRE(rgb_out && seg_out && depth_out && bev_rgb && bev_seg && bev_height && voxel_density && voxel_output,
+               "null output");
+  VAMP_REQUIRE(beta || d->density_mode == VAMP_DENSITY_SIGMOID, "beta is NULL");
+  VAMP_REQUIRE(render_fwd_merged_supported(d), "shapes outside the merged launch's limits (vamp_render_forward_merged_supported)");
+  VAMP_REQUIRE(bev_fused_heights_fit(d, ozs_host), "ozs_host is NULL or the heights do not fit the BEV plane slabs (vamp_render_forward_merged_supported)");
+  const size_t base_bytes = vamp_render_workspace_bytes(d);
+  int* term = (workspace && workspace_bytes >= base_bytes) ? cam_term_ptr(d, workspace) : nullptr;
+  float* rows = nullptr;
+  if (flags & VAMP_RENDERFWD_SAVE_SAMPLES) {
+    const size_t need = base_bytes + vamp_render_samples_bytes(d);
+    if (!workspace || workspace_bytes < need)
+      return fail(VAMP_ENOSPC, "%s: workspace %ld < %ld bytes", __func__, (long) workspace_bytes, (long) need);
+    rows = reinterpret_cast<float*>(static_cast<char*>(workspace) + base_bytes);
+  }
+  float *s0_save = nullptr, *ss_save = nullptr;
+  if (flags & VAMP_RENDERFWD_BEV_SAVE) {
+    const BevWorkspace w = vamp::bev_workspace(d, bev_workspace);
+    if (!bev_workspace || bev_workspace_bytes < w.bytes)
+      return fail(VAMP_ENOSPC, "%s: bev_workspace %ld < %ld bytes", __func__, (long) bev_workspace_bytes, (long) w.bytes);
+    s0_save = w.s0_saved;
+    ss_save = w.ss_saved;
+  }
+  // VAMP_RENDERFWD_RANK: the camera tiles draw the backward's cell ranks; the caller finishes the prepare step with
+  // vamp_render_camera_prepare_ex(VAMP_CAMPREP_RANKED) -- on this stream or another
+  CamRankRefs rank{nullptr, nullptr, nullptr, 0, nullptr};
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  if (flags & VAMP_RENDERFWD_RANK) {
+    VAMP_REQUIRE(term != nullptr, "VAMP_RENDERFWD_RANK needs the render workspace");
+    rank = cam_rank_refs(d, workspace);
+    if (flags & VAMP_RENDERFWD_COUNTERS_CLEAN) {
+      if (int e = debug_expect_range(rank.cnt, 64, 0, 0, s, "VAMP_RENDERFWD_COUNTERS_CLEAN: the render workspace's cell counters are zero")) return e;
+    } else if (int e = launch_cam_counters_zero(d, workspace, s)) {
+      return e;
+    }
+  }
+  rank.zero_word = grad_beta_zero;
+  return launch_render_fwd_merged(d, to_params(d), mats, us, vs, ds, mids, oxs, oys, ozs, bev_mids, beta, density_feature,
+                                  semantic, rgb, base, rgb_out, seg_out, depth_out, term, rows, bev_rgb, bev_seg, bev_height,
+                                  voxel_density, voxel_output, s0_save, ss_save, rank, s);
+}
+
+}  // extern "C"

@@ -28,7 +28,7 @@ from .evaluation import (confusion_update, lidarseg_predict, det_postprocess, de
                          DetTargets)
 
 
-# det-grid heights the BEV kernels take: their z taps and weights live in fixed LDS tables (kBevMaxOZ, render_bev.hip)
+# det-grid heights the BEV kernels take: their z taps and weights live in fixed LDS tables (kBevMaxOZ, render_bev_dev.hpp)
 BEV_MAX_OZ = 64
 
 
