@@ -117,10 +117,12 @@ sample_points_fwd_kernel(SampleParams P, const T* __restrict__ vol, const float*
                       fabsf(t.fx) < 1e9f && fabsf(t.fy) < 1e9f && fabsf(t.fz) < 1e9f;
   float wt[8];
   long at[8];
+  unsigned inm = 0;                   // taps that are voxels: the others are skipped, not multiplied by 0 (aten)
 #pragma unroll
   for (int k = 0; k < 8; ++k) {
     const int iz = iz0 + (k >> 2), iy = iy0 + ((k >> 1) & 1), ix = ix0 + (k & 1);
     const bool in = finite && iz >= 0 && iz < P.Z && iy >= 0 && iy < P.Y && ix >= 0 && ix < P.X;
+    inm |= (unsigned) in << k;
     wt[k] = in ? ((k & 1) ? wx1 : wx0) * ((k & 2) ? wy1 : wy0) * ((k & 4) ? wz1 : wz0) : 0.f;
     at[k] = ((long) min(max(iz, 0), P.Z - 1) * P.Y + min(max(iy, 0), P.Y - 1)) * P.X + min(max(ix, 0), P.X - 1);
   }
@@ -134,6 +136,7 @@ sample_points_fwd_kernel(SampleParams P, const T* __restrict__ vol, const float*
     for (int k = 0; k < 8; ++k) {
       float v = ldf(vol, cb + at[k]);
       if (P.activation) v = density_fwd(dp, v);
+      if (!((inm >> k) & 1u)) v = 0.f;          // the clamped address may hold a non-finite value: 0 * v is NaN
       s = __builtin_fmaf(wt[k], v, s);
     }
     s *= mask;
@@ -167,7 +170,10 @@ sample_points_rank_kernel(SampleParams P, const float* __restrict__ pts, int* __
   if (r.head) base = atomicAdd(cnt + cell, r.len);
   base = __shfl(base, act ? r.start : lane, 64);
   if (gid < total) {
-    KEY[gid] = key;
+    // KEY's "no contribution" is -1, not pack_cell_key's 0: floors (-1, -1, -1) -- a point less than one voxel
+    // outside the low corner on all three axes, counted into cell 0 above -- pack to 0 as well.  (A packed key
+    // never has bit 31 set: Z < 511.)
+    KEY[gid] = act ? key : -1;
     if (act) {
       RANK[gid] = base + (lane - r.start);
       F[gid] = make_float4(t.fx, t.fy, t.fz, 0.f);
@@ -182,7 +188,7 @@ sample_points_fill_kernel(SampleParams P, const int* __restrict__ KEY, const int
   const long gid = (long) blockIdx.x * 256 + threadIdx.x;
   if (gid >= (long) P.B * P.Pb) return;
   const int key = KEY[gid];
-  if (key == 0) return;
+  if (key < 0) return;                // inactive (sample_points_rank_kernel); 0 is the low-corner cell
   const long cell = key_to_cell(key, P.Y, P.X, (unsigned) (gid / P.Pb), ncell_b);
   const long slot = (long) boff[cell / kScanTile] + off[cell] + RANK[gid];
   const float4 f = F[gid];
