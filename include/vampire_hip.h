@@ -27,9 +27,9 @@
 extern "C" {
 #endif
 
-#define VAMP_ABI_VERSION 10  /* bumped whenever entry points or flags are added (round 2: 2, round 3: 3, round 4: 4, round 5: 5, round 6: 6;
+#define VAMP_ABI_VERSION 11  /* bumped whenever entry points or flags are added (round 2: 2, round 3: 3, round 4: 4, round 5: 5, round 6: 6;
                                  7: segmentation metrics; 8: detection post-processing; 9: detection targets;
-                                 10: the BEV backward's plan) */
+                                 10: the BEV backward's plan; 11: detection loss) */
 
 enum {
   VAMP_OK = 0,
@@ -965,6 +965,62 @@ typedef struct VampDetTargetDesc {
 size_t vamp_det_targets_workspace_bytes(const VampDetTargetDesc* d);
 int vamp_det_targets(const VampDetTargetDesc* d, const float* boxes, const void* labels, float* heatmaps, float* anno,
                      int64_t* inds, uint8_t* masks, void* workspace, size_t workspace_bytes, void* stream);
+
+/* --------------------------------------------------------------------------
+ * Detection loss: the reference head's loss (bev_depth_head.py:321-379 -- clip_sigmoid and GaussianFocalLoss on
+ * the heatmaps, code-weighted L1 on the box rows gathered at the targets' cells) for all T tasks of a head, forward
+ * and gradient, on the device.  fp32 predictions only (the head runs under autocast(False), bev_depth_head.py:140).
+ * Inputs: per task a VampDetTask of contiguous fp32 tensors (heatmap [B, ncls[t], H, W], reg [B, 2, H, W], height
+ * [B, 1, H, W], dim [B, 3, H, W], rot [B, 2, H, W], vel [B, 2, H, W] or NULL) and the packed targets of
+ * vamp_det_targets: heat (task t's [B, ncls[t], H, W] block after the earlier tasks'), anno [T, B, max_objs, code]
+ * fp32, inds [T, B, max_objs] int64, masks [T, B, max_objs] uint8.  code is 10 with vel and 8 without; its columns
+ * map to reg, height, dim, rot, vel in that order.
+ *
+ *  counts     counts[t] = (number of heat elements equal to 1, sum of masks) as fp32, unclamped (a caller may
+ *             average them over ranks).  Where they are used: f_pos = max(counts[t][0], 1), f_num =
+ *             max(counts[t][1], 1e-4).
+ *  heatmap    s = sigmoid(x), p = clamp(s, 1e-4, 1 - 1e-4), pos = -log(p + 1e-12) (1 - p)^2 [h == 1], neg =
+ *             -log(1 - p + 1e-12) p^2 (1 - h)^4, every step one fp32 operation in torch's order; L_heat[t] =
+ *             sum(pos + neg) / f_pos, the sum taken in float64.
+ *  boxes      slot (b, k) is live when masks[t, b, k] != 0 and 0 <= inds[t, b, k] < H W; a masked slot whose index
+ *             is out of range is skipped and never dereferenced (torch's gather would assert there).  Column c is
+ *             live when anno[t, b, k, c] is not NaN.  L_box[t] = loss_bbox_weight * sum over live slots and
+ *             columns of code_weights[c] |pred[b, c, ind] - anno| / f_num, the sum in float64.
+ *  loss       loss[0] = sum over t of (L_heat[t] + L_box[t]); terms [T, 2] = (L_heat, L_box) per task.
+ *  gradient   scaled by the device scalar grad_loss[0].  Heatmap: grad_loss / f_pos [1e-4 <= s <= 1 - 1e-4]
+ *             s (1 - s) ([h == 1] (-(1 - p)^2 / (p + 1e-12) + 2 (1 - p) log(p + 1e-12)) + (1 - h)^4 (p^2 /
+ *             (1 - p + 1e-12) - 2 p log(1 - p + 1e-12))), s and p recomputed from the logits.  Boxes: grad_loss
+ *             loss_bbox_weight code_weights[c] sign(pred - anno) / f_num (sign(0) = 0) at (b, c, ind) for every
+ *             live slot and column; live slots of one (t, b) that share a cell are summed in ascending slot
+ *             order by one writer.  Every other element of every gradient map is written as zero: the call owns
+ *             the whole buffers.  `grads` is a VampDetTask table of the outputs; a NULL entry is not computed.
+ * Sums run in a fixed order (float64 partials per workgroup in the workspace, added by one workgroup of a second
+ * launch): results are bitwise repeatable.  No float atomics, no host synchronisation; vamp_det_loss_counts is one
+ * launch, forward and backward two each, all capturable in a graph.  Limits: 1 <= B <= 4096, 1 <= T <= 8,
+ * 1 <= ncls[t] <= 4, 1 <= H, W <= 8192, 1 <= max_objs <= 4096 (the backward looks for shared cells in time
+ * quadratic in the live slots of a sample and task), code 8 | 10 agreeing with has_vel.  A bad descriptor returns VAMP_EINVAL (and a
+ * workspace size of 0), a NULL pointer or a workspace that is too small VAMP_ENOSPC, both before any launch.  The
+ * workspace (vamp_det_loss_workspace_bytes, one size for forward and backward) needs no initialisation.
+ * -------------------------------------------------------------------------- */
+typedef struct VampDetLossDesc {
+  int32_t B, T, H, W;
+  int32_t ncls[8];
+  int32_t code;                   /* 10 with vel, 8 without */
+  int32_t max_objs;               /* slots per (task, sample) */
+  int32_t has_vel;
+  float code_weights[10];         /* train_cfg['code_weights'] */
+  float loss_bbox_weight;
+  int32_t reserved[2];            /* 0 */
+} VampDetLossDesc;
+size_t vamp_det_loss_workspace_bytes(const VampDetLossDesc* d);
+int vamp_det_loss_counts(const VampDetLossDesc* d, const float* heat, const uint8_t* masks, float* counts,
+                         void* stream);
+int vamp_det_loss_forward(const VampDetLossDesc* d, const VampDetTask* preds, const float* heat, const float* anno,
+                          const int64_t* inds, const uint8_t* masks, const float* counts, float* loss, float* terms,
+                          void* workspace, size_t workspace_bytes, void* stream);
+int vamp_det_loss_backward(const VampDetLossDesc* d, const VampDetTask* preds, const float* heat, const float* anno,
+                           const int64_t* inds, const uint8_t* masks, const float* counts, const float* grad_loss,
+                           const VampDetTask* grads, void* workspace, size_t workspace_bytes, void* stream);
 
 #ifdef __cplusplus
 }

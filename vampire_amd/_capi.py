@@ -15,7 +15,7 @@ import torch
 
 from .build import lib_path
 
-ABI_VERSION = 10
+ABI_VERSION = 11
 
 VAMP_F32, VAMP_BF16, VAMP_F16 = 0, 1, 2
 VAMP_DENSITY_SIGMOID, VAMP_DENSITY_SDF_LAPLACE = 0, 1
@@ -98,6 +98,12 @@ class VampDetTargetDesc(C.Structure):
                 ("pc_range", C.c_float * 2), ("reserved", C.c_int32 * 2)]
 
 
+class VampDetLossDesc(C.Structure):
+    _fields_ = [("B", C.c_int32), ("T", C.c_int32), ("H", C.c_int32), ("W", C.c_int32), ("ncls", C.c_int32 * 8),
+                ("code", C.c_int32), ("max_objs", C.c_int32), ("has_vel", C.c_int32), ("code_weights", C.c_float * 10),
+                ("loss_bbox_weight", C.c_float), ("reserved", C.c_int32 * 2)]
+
+
 class VampBevBackwardPlan(C.Structure):
     """What vamp_render_bev_backward_ex will launch (vamp_render_bev_backward_plan; include/vampire_hip.h)."""
     _fields_ = [("scan_lds", C.c_int64), ("path", C.c_int32), ("z_lo", C.c_int32), ("z_hi", C.c_int32),
@@ -176,6 +182,8 @@ _PD = C.POINTER(VampPoolDesc)
 _QD = C.POINTER(VampConfDesc)
 _DD = C.POINTER(VampDetDesc)
 _TD = C.POINTER(VampDetTargetDesc)
+_ED = C.POINTER(VampDetLossDesc)
+_TT = C.POINTER(VampDetTask)
 
 # name -> (return kind, argtypes); must list every symbol declared in include/vampire_hip.h
 SIGNATURES = {
@@ -268,6 +276,10 @@ SIGNATURES = {
     "vamp_det_postprocess": (_STATUS, [_DD, C.POINTER(VampDetTask)] + [_P] * 5 + [C.c_size_t, _P]),
     "vamp_det_targets_workspace_bytes": (_SIZE, [_TD]),
     "vamp_det_targets": (_STATUS, [_TD] + [_P] * 7 + [C.c_size_t, _P]),
+    "vamp_det_loss_workspace_bytes": (_SIZE, [_ED]),
+    "vamp_det_loss_counts": (_STATUS, [_ED, _P, _P, _P, _P]),
+    "vamp_det_loss_forward": (_STATUS, [_ED, _TT] + [_P] * 7 + [_P, C.c_size_t, _P]),
+    "vamp_det_loss_backward": (_STATUS, [_ED, _TT] + [_P] * 6 + [_TT, _P, C.c_size_t, _P]),
 }
 
 _lib = None

@@ -1,6 +1,6 @@
 """Evaluation and detection-head operators on plain tensors (Python over the C ABI): the segmentation metrics'
-confusion-matrix pass and lidar-segmentation prediction, CenterPoint post-processing (decode + NMS) and training
-targets.  All work happens in hand-written HIP kernels reached through `_capi`; there is no CPU fallback."""
+confusion-matrix pass and lidar-segmentation prediction, CenterPoint post-processing (decode + NMS), training
+targets and the detection loss.  All work happens in hand-written HIP kernels reached through `_capi`; there is no CPU fallback."""
 import dataclasses
 import math
 
@@ -346,3 +346,168 @@ def det_targets(boxes, labels, tasks_ncls, train_cfg, norm_bbox, out=None):
         ws = _scratch("det_targets", dev, nbytes)
         vamp.vamp_det_targets(d, boxes, labels, out.heat, out.anno, out.inds, out.masks, ws, ws.numel(), _stream())
     return out
+
+
+# ===========================================================================
+# detection loss (bev_depth_head.py:321-379)
+# ===========================================================================
+_LOSS_KEYS = ("heatmap", "reg", "height", "dim", "rot", "vel")
+_LOSS_CHANS = {"reg": 2, "height": 1, "dim": 3, "rot": 2, "vel": 2}
+
+
+def _pack_loss_targets(targets, dev):
+    """A DetTargets passes through; get_targets's 4-tuple of per-task lists is stacked into one on the device
+    (cat / stack: no host synchronisation)."""
+    if isinstance(targets, DetTargets):
+        return targets
+    heat, anno, inds, masks = targets
+    if not (len(heat) == len(anno) == len(inds) == len(masks)) or len(heat) == 0:
+        raise ValueError("targets must be a DetTargets or (heatmaps, anno_boxes, inds, masks) lists of one length")
+    if not all(x.is_cuda for lst in (heat, anno, inds, masks) for x in lst):
+        raise _capi.VampireHipError("det_loss needs device tensors (no CPU fallback)")
+    if any(h.dim() != 4 for h in heat):
+        raise ValueError("every target heatmap must be [B, ncls, H, W]")
+    return DetTargets(torch.cat([h.reshape(-1) for h in heat]), torch.stack(list(anno)), torch.stack(list(inds)),
+                      torch.stack(list(masks)), tuple(h.shape[1] for h in heat), heat[0].shape[2], heat[0].shape[3])
+
+
+def _det_task_table(T, rows):
+    table = (_capi.VampDetTask * T)()
+    for t, row in enumerate(rows):
+        table[t] = _capi.VampDetTask(*[None if x is None else x.data_ptr() for x in row])
+    return table
+
+
+class _DetLoss(torch.autograd.Function):
+    """loss, terms = apply(desc, nk, heat, anno, inds, masks, counts, *predictions): the predictions task by task
+    in the order of _LOSS_KEYS (nk = 6 with vel, 5 without)."""
+
+    @staticmethod
+    def forward(ctx, desc, nk, heat, anno, inds, masks, counts, *preds):
+        dev = heat.device
+        T = desc.T
+        rows = [list(preds[t * nk:(t + 1) * nk]) + [None] * (6 - nk) for t in range(T)]
+        loss = torch.empty((), dtype=torch.float32, device=dev)
+        terms = torch.empty(T, 2, dtype=torch.float32, device=dev)
+        vamp = _capi.checked()
+        with torch.cuda.device(dev):
+            ws = _scratch("det_loss", dev, vamp.vamp_det_loss_workspace_bytes(desc))
+            vamp.vamp_det_loss_forward(desc, _det_task_table(T, rows), heat, anno, inds, masks, counts, loss, terms, ws,
+                                       ws.numel(), _stream())
+        ctx.desc, ctx.nk = desc, nk
+        ctx.save_for_backward(heat, anno, inds, masks, counts, *preds)
+        ctx.mark_non_differentiable(terms)
+        return loss, terms
+
+    @staticmethod
+    def backward(ctx, grad_loss, _grad_terms):
+        heat, anno, inds, masks, counts, *preds = ctx.saved_tensors
+        desc, nk, T = ctx.desc, ctx.nk, ctx.desc.T
+        dev = heat.device
+        want = ctx.needs_input_grad[7:]
+        grads = [torch.empty_like(x) if w else None for x, w in zip(preds, want)]
+        if any(want):
+            rows = [list(preds[t * nk:(t + 1) * nk]) + [None] * (6 - nk) for t in range(T)]
+            grows = [grads[t * nk:(t + 1) * nk] + [None] * (6 - nk) for t in range(T)]
+            gl = grad_loss.to(torch.float32).contiguous()
+            vamp = _capi.checked()
+            with torch.cuda.device(dev):
+                ws = _scratch("det_loss", dev, vamp.vamp_det_loss_workspace_bytes(desc))
+                vamp.vamp_det_loss_backward(desc, _det_task_table(T, rows), heat, anno, inds, masks, counts, gl,
+                                            _det_task_table(T, grows), ws, ws.numel(), _stream())
+        return (None,) * 7 + tuple(grads)
+
+
+def det_loss_counts(desc, heat, masks):
+    """counts [T, 2] fp32 = (number of heat == 1, sum of masks) per task (vamp_det_loss_counts, one launch)."""
+    counts = torch.empty(desc.T, 2, dtype=torch.float32, device=heat.device)
+    with torch.cuda.device(heat.device):
+        _capi.checked().vamp_det_loss_counts(desc, heat, masks, counts, _stream())
+    return counts
+
+
+def det_loss(task_preds, targets, code_weights, loss_bbox_weight=0.25, *, counts=None):
+    """BEVDepthHead.loss on the device (vamp_det_loss_*): the Gaussian focal loss of the clipped sigmoid heatmaps
+    plus the code-weighted L1 loss of the box rows gathered at the targets' cells, summed over the tasks, in three
+    launches (the counts and two for the loss; two more for the gradient, through autograd), without a host synchronisation, without float atomics
+    and bitwise repeatable; capturable in a graph.  Returns the 0-dim fp32 loss; its attribute `terms` is the
+    detached [T, 2] tensor of (heatmap, box) terms per task.
+    task_preds: the head's preds_dicts ([[{'heatmap', 'reg', 'height', 'dim', 'rot'[, 'vel']}], ...]), fp32.
+    Unlike the host loss, which replaces p['heatmap'] by its clipped sigmoid and adds p['anno_box'], this function
+    leaves the dicts as they are.  targets: a DetTargets (det_targets) or get_targets's (heatmaps, anno_boxes,
+    inds, masks) lists.  counts: None computes the averaging factors on the device and, when a process group is
+    initialised, means the [T, 2] tensor over the ranks in one collective; a given [T, 2] fp32 device tensor of
+    (positives, mask sum) per task is used as it is (the clamps to 1 and 1e-4 are applied by the kernels).
+    Gradients go to the predictions that require them; a masked slot whose index lies outside the map is skipped
+    (torch's gather would assert)."""
+    heads = [pd[0] for pd in task_preds]
+    T = len(heads)
+    if not 1 <= T <= 8:
+        raise ValueError(f"{T} tasks (1 to 8)")
+    has_vel = "vel" in heads[0]
+    keys = _LOSS_KEYS if has_vel else _LOSS_KEYS[:5]
+    for t, h in enumerate(heads):
+        if any(k not in h for k in keys) or ("vel" in h) != has_vel:
+            raise ValueError(f"task {t}: heads {sorted(h)} do not match task 0's {list(keys)}")
+    tensors = [[h[k] for k in keys] for h in heads]
+    if any(x.dtype != torch.float32 for ts in tensors for x in ts):
+        raise TypeError(f"head tensors must be fp32, got {sorted({str(x.dtype) for ts in tensors for x in ts})}")
+    if not all(x.is_cuda for ts in tensors for x in ts):
+        raise _capi.VampireHipError("det_loss needs device tensors (no CPU fallback)")
+    dev = tensors[0][0].device
+    tg = _pack_loss_targets(targets, dev)
+    if not (tg.heat.is_cuda and tg.anno.is_cuda and tg.inds.is_cuda and tg.masks.is_cuda):
+        raise _capi.VampireHipError("det_loss needs device tensors (no CPU fallback)")
+    if (tg.heat.dtype, tg.anno.dtype, tg.inds.dtype, tg.masks.dtype) != (torch.float32, torch.float32, torch.int64,
+                                                                         torch.uint8):
+        raise TypeError("targets must be fp32 heat and anno, int64 inds, uint8 masks")
+    if heads[0]["heatmap"].dim() != 4:
+        raise ValueError(f"heatmap {tuple(heads[0]['heatmap'].shape)} is not [B, ncls, H, W]")
+    B, _, H, W = heads[0]["heatmap"].shape
+    code = len(code_weights)
+    if code != (10 if has_vel else 8):
+        raise ValueError(f"{code} code weights for heads {'with' if has_vel else 'without'} vel (10 with, 8 without)")
+    if len(tg.ncls) != T or (tg.fh, tg.fw) != (H, W):
+        raise ValueError(f"targets of {len(tg.ncls)} tasks on {tg.fh} x {tg.fw}, predictions of {T} on {H} x {W}")
+    if tg.anno.dim() != 4 or tuple(tg.anno.shape[:2]) != (T, B) or tg.anno.shape[3] != code:
+        raise ValueError(f"anno {tuple(tg.anno.shape)} is not [{T}, {B}, max_objs, {code}]")
+    K = tg.anno.shape[2]
+    if tuple(tg.inds.shape) != (T, B, K) or tuple(tg.masks.shape) != (T, B, K):
+        raise ValueError(f"inds {tuple(tg.inds.shape)} / masks {tuple(tg.masks.shape)} are not [{T}, {B}, {K}]")
+    if tg.heat.numel() != B * sum(tg.ncls) * H * W:
+        raise ValueError(f"heat holds {tg.heat.numel()} elements, not {B} x {sum(tg.ncls)} x {H} x {W}")
+    for t, h in enumerate(heads):
+        if tuple(h["heatmap"].shape) != (B, tg.ncls[t], H, W):
+            raise ValueError(f"task {t}: heatmap {tuple(h['heatmap'].shape)} is not [{B}, {tg.ncls[t]}, {H}, {W}]")
+        for k in keys[1:]:
+            if tuple(h[k].shape) != (B, _LOSS_CHANS[k], H, W):
+                raise ValueError(f"task {t}: {k} {tuple(h[k].shape)} is not [{B}, {_LOSS_CHANS[k]}, {H}, {W}]")
+    d = _capi.VampDetLossDesc()
+    d.B, d.T, d.H, d.W = B, T, H, W
+    for t in range(T):
+        d.ncls[t] = int(tg.ncls[t])
+    d.code, d.max_objs, d.has_vel = code, K, int(has_vel)
+    for c in range(code):
+        d.code_weights[c] = float(code_weights[c])
+    d.loss_bbox_weight = float(loss_bbox_weight)
+    vamp = _capi.checked()
+    if vamp.vamp_det_loss_workspace_bytes(d) == 0:
+        raise _capi.VampireHipError(f"det_loss: {vamp.vamp_last_error().decode('utf-8', 'replace')}")
+    heat, anno, inds, masks = tg.heat.contiguous(), tg.anno.contiguous(), tg.inds.contiguous(), tg.masks.contiguous()
+    if counts is None:
+        counts = det_loss_counts(d, heat, masks)
+        if torch.distributed.is_available() and torch.distributed.is_initialized():
+            from .multitask import reduce_mean
+            counts = reduce_mean(counts)
+    else:
+        if not counts.is_cuda:
+            raise _capi.VampireHipError("det_loss needs device tensors (no CPU fallback)")
+        if counts.dtype != torch.float32:
+            raise TypeError(f"counts must be fp32, got {counts.dtype}")
+        if tuple(counts.shape) != (T, 2):
+            raise ValueError(f"counts {tuple(counts.shape)} is not [{T}, 2]")
+        counts = counts.detach().contiguous()
+    flat = [x.contiguous() for ts in tensors for x in ts]
+    loss, terms = _DetLoss.apply(d, len(keys), heat, anno, inds, masks, counts, *flat)
+    loss.terms = terms
+    return loss

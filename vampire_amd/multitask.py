@@ -292,6 +292,15 @@ class BEVDepthHead(nn.Module):
             total = total + self.loss_bbox_weight * ((pred - torch.nan_to_num(tgt)).abs() * w).sum() / num
         return total
 
+    def loss_device(self, targets, preds_dicts, counts=None):
+        """loss on the device: one evaluation.det_loss call (three launches forward -- the counts and two for the loss
+        -- and two backward through autograd, no host synchronisation, bitwise repeatable).  targets: the DetTargets of get_targets_device or
+        get_targets's tuple.  Unlike loss, it leaves preds_dicts untouched (no clipped 'heatmap', no 'anno_box').
+        The returned 0-dim tensor carries `terms`, the [T, 2] (heatmap, box) terms per task."""
+        from . import evaluation
+        return evaluation.det_loss(preds_dicts, targets, self.train_cfg["code_weights"], self.loss_bbox_weight,
+                                   counts=counts)
+
     # ---- decoding (bev_depth_head.py:377-494) ----
     def get_bboxes(self, preds_dicts, img_metas=None, img=None, rescale=False):
         rets = []
@@ -356,6 +365,9 @@ class VAMPIRE2(nn.Module):
 
     def loss(self, targets, preds_dicts):
         return self.head.loss(targets, preds_dicts)
+
+    def loss_device(self, targets, preds_dicts, counts=None):
+        return self.head.loss_device(targets, preds_dicts, counts=counts)
 
     def get_bboxes(self, preds_dicts, img_metas=None, img=None, rescale=False):
         return self.head.get_bboxes(preds_dicts, img_metas, img, rescale)
@@ -434,11 +446,13 @@ class MultiTaskLoss:
     `task_weights` (occ, lidarseg, detection) and `loss_weights` (depth, seg, rgb, sdf, density)."""
 
     def __init__(self, model, task_weights=(1., 1., 1.), loss_weights=(1., 1., 1., 1., 1.), downsample_factor=4,
-                 upsample_factor=4, sdf_bias=-1.0, det_targets="host"):
+                 upsample_factor=4, sdf_bias=-1.0, det_targets="host", det_loss="host"):
         if det_targets not in ("host", "device"):
             raise ValueError(f"det_targets must be 'host' or 'device', got {det_targets!r}")
+        if det_loss not in ("host", "device"):
+            raise ValueError(f"det_loss must be 'host' or 'device', got {det_loss!r}")
         self.model, self.task_weights, self.loss_weights = model, task_weights, loss_weights
-        self.det_targets = det_targets
+        self.det_targets, self.det_loss = det_targets, det_loss
         self.down, self.up, self.sdf_bias = downsample_factor, upsample_factor, sdf_bias
         self.last = {}
 
@@ -454,13 +468,15 @@ class MultiTaskLoss:
     def targets(self, batch):
         """The detection targets depend on the labels only: made BEFORE the forward is launched, their host
         round trip (boxes to the CPU, heatmaps back) does not wait for the GPU to drain the forward.  With
-        det_targets="device" they are two HIP launches on the stream instead (get_targets_device)."""
+        det_targets="device" they are two HIP launches on the stream instead (get_targets_device); det_loss="device"
+        (loss_device) then takes the packed DetTargets as it is."""
         head = self.model.module if hasattr(self.model, "module") else self.model
         return self._targets(head, batch[4], batch[5])
 
     def _targets(self, head, gt_boxes, gt_labels):
         if self.det_targets == "device":
-            return head.get_targets_device(gt_boxes, gt_labels).as_tuple()
+            tg = head.get_targets_device(gt_boxes, gt_labels)
+            return tg if self.det_loss == "device" else tg.as_tuple()
         return head.get_targets(gt_boxes, gt_labels)
 
     def __call__(self, outputs, batch, targets=None):
@@ -469,7 +485,8 @@ class MultiTaskLoss:
         (preds, rgb_p, seg_p, depth_p, bev_rgb_p, bev_seg_p, bev_h_p, bev_density, pts_logits, pts_sdf,
          occ_logits, occ_density) = outputs
         head = self.model.module if hasattr(self.model, "module") else self.model
-        det = head.loss(self._targets(head, gt_boxes, gt_labels) if targets is None else targets, preds)
+        det_fn = head.loss_device if self.det_loss == "device" else head.loss
+        det = det_fn(self._targets(head, gt_boxes, gt_labels) if targets is None else targets, preds)
         if depth_labels.dim() == 5:                      # only the key frame carries camera labels
             sweep_imgs, depth_labels, seg_labels = sweep_imgs[:, 0], depth_labels[:, 0], seg_labels[:, 0]
         depth_p = depth_p[:, :, 0]

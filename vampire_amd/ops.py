@@ -24,8 +24,8 @@ from ._tensors import _accept, _chk, _density_code, _dtype_code, _is_channel_las
 # the operators that take no HotPath live in modules of their own; their public names stay importable from here
 from .layers import (voxel_pooling, upsample_trilinear, conv3d_3x3x3, conv3d_bf16, conv3d_supported,  # noqa: F401
                      conv3d_bf16_supported)
-from .evaluation import (confusion_update, lidarseg_predict, det_postprocess, det_targets, DetResult,  # noqa: F401
-                         DetTargets)
+from .evaluation import (confusion_update, lidarseg_predict, det_postprocess, det_targets, det_loss,  # noqa: F401
+                         DetResult, DetTargets)
 
 
 # det-grid heights the BEV kernels take: their z taps and weights live in fixed LDS tables (kBevMaxOZ, render_bev_dev.hpp)
