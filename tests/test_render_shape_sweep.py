@@ -329,6 +329,46 @@ def test_depth_sweep_scene_exercises_the_scan(dev, case):
 
 
 @pytest.mark.gpu
+@pytest.mark.parametrize("path", ["merged", "planned-ert"])
+def test_backward_of_a_render_workspace_that_is_no_longer_fresh(dev, path):
+    """A backward whose forward's leavings in the render workspace are gone promises the library none of them -- no
+    PACKED / CELLS / TERM / SAMPLES_VALID on its camera calls -- and still gives every gradient within the sweep's bars:
+    (a) ert_statistics between forward and backward (it overwrites the termination table), (b) the second backward of a
+    retained graph (the first one scribbled over the cell lists)."""
+    case = Case("tiny")
+    cfg, rm, vols, beta_v = scene(case)
+    _, ref_grads, ref_gbeta, gbeta_scale = oracle_render(case)
+    promises = (_capi.VAMP_CAMBWD_PACKED_VALID | _capi.VAMP_CAMBWD_CELLS_VALID | _capi.VAMP_CAMBWD_TERM_VALID
+                | _capi.VAMP_CAMBWD_SAMPLES_VALID)
+    bad = []
+    for route in ("ert-statistics", "second-backward"):
+        hp = hot(cfg, dev)
+        hp.impl.update(PATHS[path])
+        calls = hp.lib = _Calls(hp.lib)
+        lv = [v.to(dev).requires_grad_(True) for v in vols]
+        beta = torch.tensor(beta_v, device=dev, requires_grad=True)
+        rmd = rm.to(dev)
+        outs = hp.render(*lv, beta, render_mats=rmd)
+        ups = _upstream([o.shape for o in outs], 4545, dev)
+        if route == "ert-statistics":
+            hp.ert_statistics(lv[0].detach(), beta, rmd)
+        else:
+            torch.autograd.backward(outs, ups, retain_graph=True)
+            fresh = calls.flags("vamp_render_camera_backward_acc", -3)
+            assert fresh and all(f & promises for f in fresh), fresh        # (the first backward did find them)
+            for t in lv + [beta]:
+                t.grad = None
+        n = len(calls.log)
+        torch.autograd.backward(outs, ups)
+        flags = [a[-3] for name, a in calls.log[n:] if name == "vamp_render_camera_backward_acc"]
+        assert flags and all(not (f & promises) for f in flags), (route, flags)
+        errs = {f"grad_{k}": (rel_err(v.grad, r), GRAD_BAR) for k, v, r in zip(VOLS, lv, ref_grads)}
+        errs["grad_beta"] = (abs(float(beta.grad) - ref_gbeta) / gbeta_scale, BETA_BAR)
+        bad += [f"{route} {what}: {e:.3e} > {b:.1e}" for what, (e, b) in errs.items() if not e <= b]
+    assert not bad, f"{path}:\n" + "\n".join(bad)
+
+
+@pytest.mark.gpu
 def test_zero_mid_channels_need_cat_seg(dev):
     """C = 0 renders beside cat_seg (the sweep's C0-catseg case); without it voxel_output would have no channels and
     HotPath refuses the call before any device work."""

@@ -134,6 +134,13 @@ class HotPath:
                      # (vamp_lift_finish_cells).  False = the scan inside the lift forward's call (no environment switch)
                      "defer_lift_scan": True}
         self._lift_scan_pending = None      # (desc, workspace, stream) of a lift forward whose cell scan is still due
+        # What the workspaces hold, as generation counters (a forward keeps (counter, buffer address) and its backward
+        # compares) -- each with what makes an earlier forward's leavings stale:
+        self._lift_gen = 0          # lift pair cells: any later lift forward or lift backward
+        self._bev_gen = 0           # BEV forward's samples: any later BEV forward (alone or inside the merged launch)
+        self._pack_gen = 0          # render workspace: any later render forward, render backward or ert_statistics
+        self._bev_tab_key = None    # (BEV workspace address, B) of a split BEV backward's axis tables: a new buffer or B
+        self._side = None           # the side stream, made on first use: a caller resets it to None to get a fresh one
 
     # ------------------------------------------------------------- the library
     # `lib` hands status codes back as integers; `vamp` is the same entry points raising VampireHipError on a failure,
@@ -175,7 +182,7 @@ class HotPath:
         branch, and at batch 1 neither fills the 256 CUs alone (VAMP_OVERLAP=0 disables)."""
         if not self.impl["overlap"]:
             return None
-        if getattr(self, "_side", None) is None:
+        if self._side is None:
             self._side = torch.cuda.Stream(device=self.device)
         return self._side
 
@@ -392,7 +399,7 @@ class HotPath:
             term = ws[off:off + 4 * B * N * c.fH * c.fW].view(torch.int32).reshape(B, N, 1, c.fH, c.fW).clone()
             inside = self.render_indices(render_mats=mats)[0].bool()
         idx = torch.arange(c.D - 1, device=self.device).reshape(1, 1, -1, 1, 1)
-        self._pack_gen = getattr(self, "_pack_gen", 0) + 1      # the workspace no longer matches a saved forward
+        self._pack_gen += 1         # the workspace no longer matches a saved forward
         return int(inside.sum()), int((inside & (idx < term)).sum())
 
     # ------------------------------------------------------ point resampling
@@ -496,7 +503,7 @@ class _LiftFn(torch.autograd.Function):
         nbytes = hp.vamp.vamp_lift_workspace_bytes(d)
         ws = hp._workspace("lift", nbytes)
         cur = torch.cuda.current_stream()
-        hp._lift_gen = getattr(hp, "_lift_gen", 0) + 1
+        hp._lift_gen += 1
         ctx.cells_key = None
         flags = _capi.VAMP_LIFTFWD_FEAT_CHANNEL_LAST if fcl else 0
         if need_grad and hp.impl["lift_bwd"] == "cell":
@@ -542,23 +549,20 @@ class _LiftFn(torch.autograd.Function):
         nbytes = hp.vamp.vamp_lift_workspace_bytes(d)
         ws = hp._workspace("lift", nbytes)
         hp._finish_lift_scan()              # (nobody has run the forward's deferred scan: a lift without a render forward)
-        valid = 1 if ctx.cells_key == (getattr(hp, "_lift_gen", 0), ws.data_ptr()) else 0
-        hp._lift_gen = getattr(hp, "_lift_gen", 0) + 1       # the backward consumes the prepared counters
+        fresh = ctx.cells_key == (hp._lift_gen, ws.data_ptr())       # the forward's pair cells are still in the workspace
+        hp._lift_gen += 1                                              # the backward consumes the prepared counters
         if hp.impl["lift_bwd"] == "v1":
-            valid = _capi.VAMP_LIFTBWD_SPLAT
-        elif ctx.logits:
-            valid |= _capi.VAMP_LIFTBWD_LOGITS
+            flags = _capi.VAMP_LIFTBWD_SPLAT                           # (takes neither the cells nor the logits)
+        else:
+            flags = ((_capi.VAMP_LIFTBWD_CELLS_VALID if fresh else 0)
+                     | (_capi.VAMP_LIFTBWD_LOGITS if ctx.logits else 0))
         if ctx.feat_cl:
-            valid |= _capi.VAMP_LIFTBWD_FEAT_CHANNEL_LAST
-        valid |= {1: _capi.VAMP_LIFTBWD_WPP1, 4: _capi.VAMP_LIFTBWD_WPP4,
+            flags |= _capi.VAMP_LIFTBWD_FEAT_CHANNEL_LAST
+        flags |= {1: _capi.VAMP_LIFTBWD_WPP1, 4: _capi.VAMP_LIFTBWD_WPP4,
                   16: _capi.VAMP_LIFTBWD_WPP16}.get(hp.impl["lift_wpp"], 0)
         hp._dirty.add("lift")
-
-        def call(flags, stream):
-            hp.vamp.vamp_lift_backward_ex(d, mats, hp.xs, hp.ys, hp.zs, depth if use_depth else None, feat, g, hits,
-                                         gdepth, gfeat, ws, ws.numel(), flags, _stream(stream))
-
-        call(valid, None)
+        hp.vamp.vamp_lift_backward_ex(d, mats, hp.xs, hp.ys, hp.zs, depth if use_depth else None, feat, g, hits,
+                                     gdepth, gfeat, ws, ws.numel(), flags, _stream())
         if hp.impl["lift_bwd"] == "cell":
             hp._dirty.discard("lift")       # the gather has re-zeroed the fill's cursors
         if ctx.logits and hp.impl["lift_bwd"] == "v1":
@@ -658,6 +662,53 @@ def render_forward_plan(train, two, prep_ok, direct, ert, merged=False):
         steps.append(("bev", "side", 0, (), ()))
     steps.append(("cam", "cur", camf, (), ()))
     return steps
+
+
+def render_backward_plan(two, matrices, cell_impl, fresh, cells, samples, ert, packed, bev_cell, bev_saved, tab_valid):
+    """The C calls of one render backward in issue order: [(op, stream, flags, waits, records)].
+
+    op: "cam" (vamp_render_camera_backward_acc) | "bev" (vamp_render_bev_backward_ex); stream: "cur" | "side";
+    flags: the call's COMPLETE flag word; waits / records: names of events.  Only a "cam" op waits, and its wait is not a
+    stream wait: the event goes into the call as its wait_event argument and the library places the wait itself (in
+    front of the gather).
+    `two`: a side stream is available; `matrices`: no explicit geometry; `cell_impl` / `bev_cell`: the cell-list camera /
+    BEV backward (not the v1 splats).  `fresh`: the render workspace is untouched since this forward -- what the
+    forward left there (`cells`: cell lists, `samples`: sample rows, `ert`: it ran with early termination and left the
+    table, `packed`: channel-last copy) is promised to the library only then.  `bev_saved` / `tab_valid`: the BEV
+    workspace still holds this forward's samples / a split pair's axis tables (cell-list BEV backward only).
+    The camera and the BEV branch add into the same three gradient buffers: the first writer overwrites (a BEV call
+    with OVERWRITE_CAM, or a camera call without ACCUMULATE), the second accumulates.  Three schedules: two streams
+    with both backwards split in parts, one stream BEV first, and -- v1 splat or explicit geometry, whose camera
+    backward only overwrites -- camera first."""
+    F = _capi
+    valid = 0 if ert else F.VAMP_CAMBWD_NO_ERT          # (how the forward marched, whatever has become of its leavings)
+    if fresh:
+        valid |= ((F.VAMP_CAMBWD_PACKED_VALID if packed else 0) | (F.VAMP_CAMBWD_CELLS_VALID if cells else 0)
+                  | (F.VAMP_CAMBWD_SAMPLES_VALID if samples and cell_impl else 0)
+                  | (F.VAMP_CAMBWD_TERM_VALID if ert else 0))
+    bev = F.VAMP_BEVBWD_OVERWRITE_BASE | (F.VAMP_BEVBWD_SAVED_VALID if bev_saved and bev_cell else 0)
+    if not (matrices and cell_impl):
+        return [("cam", "cur", valid | (0 if cell_impl else F.VAMP_CAMBWD_SPLAT), (), ()),
+                ("bev", "cur", bev, (), ())]
+    cam, bev = valid | F.VAMP_CAMBWD_ACCUMULATE, bev | F.VAMP_BEVBWD_OVERWRITE_CAM
+    if not two:
+        # (TABLE_VALID is sent beside a part flag only: `tab_valid` speaks of the two tables of a split pair)
+        return [("bev", "cur", bev, (), ()), ("cam", "cur", cam, (), ())]
+    # Two streams: the BEV branch writes the buffers on the side stream while the camera branch marches its rays and
+    # sorts its samples on this one (ray pass and the heavy cells' per-corner sums: neither touches the gradient
+    # buffers); the camera gather then waits for the BEV event and adds on top.  The pass-through (grad_base) gather of
+    # the BEV branch is issued behind the event: nobody waits for grad_base, so it runs beside the camera gather
+    # instead of in front of it.
+    # Issue order: the camera chain FIRST.  It is the longer chain and the lift backward follows it, and a replayed
+    # graph keeps the branch whose first node was created first on the queue of the nodes around the fork -- the other
+    # branch pays the cross-queue hand-over (5 - 13 us at its start, and again where it joins).
+    # (cfg-B replayed: 0.3625 - 0.370 ms/step against 0.3735 with the BEV chain issued first.)
+    if tab_valid and bev_cell:
+        bev |= F.VAMP_BEVBWD_TABLE_VALID
+    return [("cam", "cur", cam | F.VAMP_CAMBWD_PART_RAY | F.VAMP_CAMBWD_PART_HEAVY, (), ()),
+            ("bev", "side", bev | F.VAMP_BEVBWD_SKIP_BASE, (), ("bev",)),
+            ("bev", "side", bev | F.VAMP_BEVBWD_ONLY_BASE, (), ()),
+            ("cam", "cur", cam | F.VAMP_CAMBWD_PART_GATHER, ("bev",), ())]
 
 
 class _RenderFn(torch.autograd.Function):
@@ -798,7 +849,7 @@ class _RenderFn(torch.autograd.Function):
                                                   ws_bev.numel() if bev_save else 0,
                                                   (_capi.VAMP_BEVFWD_SAVE if bev_save else 0) | bev_flags, _stream(st))
             if op in ("render", "bev"):
-                hp._bev_gen = getattr(hp, "_bev_gen", 0) + 1
+                hp._bev_gen += 1
                 ctx.bev_key = (hp._bev_gen, ws_bev.data_ptr()) if bev_save else None
             for r in records:
                 events[r] = torch.cuda.Event()
@@ -811,7 +862,7 @@ class _RenderFn(torch.autograd.Function):
         # the workspace now holds the termination table, the channel-last copy of (dens, sem, rgb) unless the
         # one kernel ran, and the cell lists if a prepare pass did; the backward reuses them if no other render
         # call has touched the workspace in between
-        hp._pack_gen = getattr(hp, "_pack_gen", 0) + 1
+        hp._pack_gen += 1
         ctx.pack_key = None if (direct and not train) else (hp._pack_gen, ws.data_ptr())
         ctx.packed = not direct                 # (the one-kernel forward makes no channel-last copy)
         ctx.has_geom = geom is not None
@@ -842,84 +893,46 @@ class _RenderFn(torch.autograd.Function):
         if gbeta is None:
             gbeta = torch.zeros(1, dtype=f32, device=dens.device)
 
-        bev_saved = (ctx.bev_key is not None and hp.impl["bev_bwd"] != "v1"
-                     and ctx.bev_key == (getattr(hp, "_bev_gen", 0), ws_bev.data_ptr()))
-
         # the axis tables in the BEV workspace depend on the grids only (constants of this object):
         # valid once both halves of a split pair have written theirs into this very buffer
         tab_key = (ws_bev.data_ptr(), d.B)
-        tab_valid = hp.impl["bev_bwd"] != "v1" and getattr(hp, "_bev_tab_key", None) == tab_key
-
-        def bev_backward(stream, overwrite_cam, part=0):
-            flags = _capi.VAMP_BEVBWD_OVERWRITE_BASE | (_capi.VAMP_BEVBWD_OVERWRITE_CAM if overwrite_cam else 0) | part
-            if tab_valid and part:
-                flags |= _capi.VAMP_BEVBWD_TABLE_VALID
-            if bev_saved:
-                flags |= _capi.VAMP_BEVBWD_SAVED_VALID
-            hp.vamp.vamp_render_bev_backward_ex(d, hp.oxs, hp.oys, hp.ozs, hp.bev_mids, beta, dens, sem, rgb, base,
-                                               g_brgb, g_bseg, g_bh, g_vd, g_vo, gd, gs, gr, gb, gbeta,
-                                               None if hp.impl["bev_bwd"] == "v1" else hp.ozs_host, ws_bev,
-                                               ws_bev.numel(), flags, _stream(stream))
-
-        cam_args = (d, geom, mats, hp.us, hp.vs, hp.ds, hp.camera_mids, beta, dens, sem, rgb, g_rgb, g_seg, g_dep)
         cur, side = torch.cuda.current_stream(), hp._side_stream()
-        default_impl = hp.impl["cam_bwd"] != "v1"
-        if not default_impl or geom is not None or not ctx.cells:
+        cell_impl, bev_cell = hp.impl["cam_bwd"] != "v1", hp.impl["bev_bwd"] != "v1"
+        plan = render_backward_plan(
+            two=side is not None, matrices=geom is None, cell_impl=cell_impl,
+            fresh=ctx.pack_key == (hp._pack_gen, ws.data_ptr()), cells=ctx.cells, samples=ctx.samples, ert=ctx.ert,
+            packed=ctx.packed, bev_cell=bev_cell, bev_saved=ctx.bev_key == (hp._bev_gen, ws_bev.data_ptr()),
+            tab_valid=hp._bev_tab_key == tab_key)
+        if not cell_impl or geom is not None or not ctx.cells:
             # the v1 splat keeps a packed gradient copy where the cell lists live, and a backward that builds
             # its own cell lists may stop half way: either way the counters there are no longer known zero
             hp._dirty.add("render")
-        packed_valid = 2 if ctx.pack_key == (getattr(hp, "_pack_gen", 0), ws.data_ptr()) else 0
-        if packed_valid and ctx.cells:
-            packed_valid |= 4                                    # VAMP_CAMBWD_CELLS_VALID
-        if packed_valid and ctx.samples and default_impl:
-            packed_valid |= _capi.VAMP_CAMBWD_SAMPLES_VALID
-        if not ctx.ert:
-            packed_valid |= _capi.VAMP_CAMBWD_NO_ERT
-        elif packed_valid:
-            packed_valid |= _capi.VAMP_CAMBWD_TERM_VALID           # same validity as the packed copy
-        else:
-            packed_valid &= ~4                                   # no table: the cells are rebuilt with a fresh one
-        if not ctx.packed:
-            packed_valid &= ~2                                   # table / cells are there, a packed copy (v1 splat only) is not
-        hp._pack_gen = getattr(hp, "_pack_gen", 0) + 1          # the backward scribbles after the copy only,
+        hp._pack_gen += 1                                       # the backward scribbles after the copy only,
         ctx.pack_key = None                                     # but a second backward must not assume so
-        if side is not None and geom is None and default_impl:
-            # Two streams: the BEV branch writes the buffers on the side stream while the camera
-            # branch marches its rays and sorts its samples on this one; the camera gather then
-            # waits for the BEV event and adds on top.
-            # The pass-through (grad_base) gather of the BEV branch is issued behind the event: nobody
-            # waits for grad_base, so it runs beside the camera gather instead of in front of it.
-            s_bev, s_cam = side, cur
+        streams, events = {"cur": cur, "side": side}, {}
+        forked = any(where == "side" for _, where, *_ in plan)
+        if forked:
             side.wait_stream(cur)
-            # The camera backward in two calls on its own stream: the ray pass and the heavy cells' per-corner sums
-            # (neither touches the gradient buffers), then -- behind the BEV event -- the gather, which adds both on top.
-            # Issue order: the camera chain FIRST.  It is the longer chain and the lift backward follows it, and a
-            # replayed graph keeps the branch whose first node was created first on the queue of the nodes around the
-            # fork -- the other branch pays the cross-queue hand-over (5 - 13 us at its start, and again where it joins).
-            cam_flags = 1 | packed_valid
-
-            def cam_part(part, stream, event=None):
-                hp.vamp.vamp_render_camera_backward_acc(*cam_args, gd, gs, gr, gbeta, ws, ws.numel(), cam_flags | part,
-                                                       event, _stream(stream))
-
-            # (cfg-B replayed: 0.3625 - 0.370 ms/step against 0.3735 with the BEV chain issued first.)
-            cam_part(_capi.VAMP_CAMBWD_PART_RAY | _capi.VAMP_CAMBWD_PART_HEAVY, s_cam)
-            bev_backward(s_bev, True, _capi.VAMP_BEVBWD_SKIP_BASE)
-            done = torch.cuda.Event()
-            done.record(s_bev)
-            bev_backward(s_bev, True, _capi.VAMP_BEVBWD_ONLY_BASE)
-            hp._bev_tab_key = tab_key
-            cam_part(_capi.VAMP_CAMBWD_PART_GATHER, s_cam, C.c_void_p(done.cuda_event))
+        for op, where, flags, waits, records in plan:
+            st = streams[where]
+            if op == "cam":
+                # (the event is the call's own argument: the library waits for it in front of its gather)
+                wait = C.c_void_p(events[waits[0]].cuda_event) if waits else None
+                hp.vamp.vamp_render_camera_backward_acc(d, geom, mats, hp.us, hp.vs, hp.ds, hp.camera_mids, beta, dens,
+                                                       sem, rgb, g_rgb, g_seg, g_dep, gd, gs, gr, gbeta, ws, ws.numel(),
+                                                       flags, wait, _stream(st))
+            else:
+                hp.vamp.vamp_render_bev_backward_ex(d, hp.oxs, hp.oys, hp.ozs, hp.bev_mids, beta, dens, sem, rgb, base,
+                                                   g_brgb, g_bseg, g_bh, g_vd, g_vo, gd, gs, gr, gb, gbeta,
+                                                   hp.ozs_host if bev_cell else None, ws_bev, ws_bev.numel(), flags,
+                                                   _stream(st))
+                if flags & _capi.VAMP_BEVBWD_ONLY_BASE:
+                    hp._bev_tab_key = tab_key                   # (both halves of the split pair have been issued)
+            for r in records:
+                events[r] = torch.cuda.Event()
+                events[r].record(st)
+        if forked:
             cur.wait_stream(side)
-        elif geom is None and default_impl:
-            bev_backward(cur, True)
-            hp.vamp.vamp_render_camera_backward_acc(*cam_args, gd, gs, gr, gbeta, ws, ws.numel(), 1 | packed_valid, None,
-                                                   _stream(cur))
-        else:
-            hp.vamp.vamp_render_camera_backward_acc(*cam_args, gd, gs, gr, gbeta, ws, ws.numel(),
-                                                   packed_valid | (0 if default_impl else _capi.VAMP_CAMBWD_SPLAT),
-                                                   None, _stream(cur))
-            bev_backward(cur, False)
         grad_beta = gbeta.reshape(ctx.beta_shape) if hp.cfg.density_mode == "sdf" else None
         dt = ctx.in_dtypes
         return (None, gd.to(dt[0]), gs.to(dt[1]), gb.to(dt[2]), gr.to(dt[3]), grad_beta, None, None, None)
