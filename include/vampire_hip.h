@@ -27,9 +27,9 @@
 extern "C" {
 #endif
 
-#define VAMP_ABI_VERSION 11  /* bumped whenever entry points or flags are added (round 2: 2, round 3: 3, round 4: 4, round 5: 5, round 6: 6;
+#define VAMP_ABI_VERSION 12  /* bumped whenever entry points or flags are added (round 2: 2, round 3: 3, round 4: 4, round 5: 5, round 6: 6;
                                  7: segmentation metrics; 8: detection post-processing; 9: detection targets;
-                                 10: the BEV backward's plan; 11: detection loss) */
+                                 10: the BEV backward's plan; 11: detection loss; 12: rgb loss) */
 
 enum {
   VAMP_OK = 0,
@@ -1021,6 +1021,45 @@ int vamp_det_loss_forward(const VampDetLossDesc* d, const VampDetTask* preds, co
 int vamp_det_loss_backward(const VampDetLossDesc* d, const VampDetTask* preds, const float* heat, const float* anno,
                            const int64_t* inds, const uint8_t* masks, const float* counts, const float* grad_loss,
                            const VampDetTask* grads, void* workspace, size_t workspace_bytes, void* stream);
+
+/* --------------------------------------------------------------------------
+ * Rgb loss (base_exp.py:286, 539-549): mean smooth-L1 (beta 1) + 1 - MS-SSIM of the rendered image `pred` against
+ * the label `target`, both [N, C, H, W] fp32 and contiguous (N = batch x cameras), and its gradient with respect to
+ * pred.  MS-SSIM is MultiScaleStructuralSimilarityIndexMeasure(data_range) with its defaults: a Gaussian window of
+ * 11 taps, sigma 1.5, normalised, applied as a valid correlation (separably: it is the outer product of the 1-D
+ * window); five scales with betas 0.0448, 0.2856, 0.3001, 0.2363, 0.1333; c1 = (k1 data_range)^2, c2 = (k2
+ * data_range)^2.
+ *
+ *  per scale  mux, muy, sxx = E[xx] - mux^2, syy, sxy = E[xy] - mux muy (window sums and differences in float64),
+ *             cs = (2 sxy + c2) / (sxx + syy + c2); on the last scale cs is multiplied by l = (2 mux muy + c1) /
+ *             (mux^2 + muy^2 + c1).  v[n, i] = relu(mean over C and the valid region), the sum in float64.  Between
+ *             scales x and y are 2x2 average-pooled with floor: an odd last row or column is dropped.
+ *  loss       ms_ssim = mean over n of PROD_i v[n, i]^beta_i; terms = (mean smooth-L1, ms_ssim); loss[0] = terms[0]
+ *             + 1 - terms[1]; vals [N, 5] = v.
+ *  gradient   grad_pred = grad_loss[0] (a device scalar) times d loss / d pred, every element written once.
+ *             Where some v[n, i] is 0 after the relu (an anti-correlated prediction), image n contributes 0 to
+ *             ms_ssim and its MS-SSIM gradient is DEFINED as exactly 0; its smooth-L1 gradient is unaffected.  This
+ *             is the one difference from the torch expression, which yields NaN there (relu(v) ** beta has the
+ *             gradient inf * 0; a relu backward that selects instead of multiplying may drop the NaN again).
+ * Forward: one launch per scale (float64 partials per workgroup into the workspace, the pooled images of the next
+ * scale, the per-pixel unit adjoints the backward applies the transposed window to) and one finishing workgroup
+ * that adds the partials in a fixed order.  Backward: one launch per scale, coarse to fine; it takes the workspace
+ * as the forward of the same inputs left it.  No float atomics, no host synchronisation, bitwise repeatable,
+ * capturable in a graph.  The workspace (8-byte aligned, vamp_rgb_loss_workspace_bytes: about 16 bytes per valid
+ * pixel and 4 per pixel over all scales) needs no initialisation.  Limits: N >= 1, 1 <= C <= 4, 176 <= H, W <= 16384
+ * (the fifth scale still holds one window), N C H W < 2^31.  A bad descriptor returns VAMP_EINVAL (and a workspace
+ * size of 0), a NULL pointer or a workspace that is too small VAMP_ENOSPC, both before any launch.
+ * -------------------------------------------------------------------------- */
+typedef struct VampRgbLossDesc {
+  int32_t N, C, H, W;
+  float data_range;               /* 1.0 */
+  float k1, k2;                   /* 0.01, 0.03 */
+} VampRgbLossDesc;
+size_t vamp_rgb_loss_workspace_bytes(const VampRgbLossDesc* d);
+int vamp_rgb_loss_forward(const VampRgbLossDesc* d, const float* pred, const float* target, float* loss, float* terms,
+                          float* vals, void* workspace, size_t workspace_bytes, void* stream);
+int vamp_rgb_loss_backward(const VampRgbLossDesc* d, const float* pred, const float* target, const float* grad_loss,
+                           float* grad_pred, void* workspace, size_t workspace_bytes, void* stream);
 
 #ifdef __cplusplus
 }

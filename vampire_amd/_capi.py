@@ -15,7 +15,7 @@ import torch
 
 from .build import lib_path
 
-ABI_VERSION = 11
+ABI_VERSION = 12
 
 VAMP_F32, VAMP_BF16, VAMP_F16 = 0, 1, 2
 VAMP_DENSITY_SIGMOID, VAMP_DENSITY_SDF_LAPLACE = 0, 1
@@ -104,6 +104,11 @@ class VampDetLossDesc(C.Structure):
                 ("loss_bbox_weight", C.c_float), ("reserved", C.c_int32 * 2)]
 
 
+class VampRgbLossDesc(C.Structure):
+    _fields_ = [("N", C.c_int32), ("C", C.c_int32), ("H", C.c_int32), ("W", C.c_int32),
+                ("data_range", C.c_float), ("k1", C.c_float), ("k2", C.c_float)]
+
+
 class VampBevBackwardPlan(C.Structure):
     """What vamp_render_bev_backward_ex will launch (vamp_render_bev_backward_plan; include/vampire_hip.h)."""
     _fields_ = [("scan_lds", C.c_int64), ("path", C.c_int32), ("z_lo", C.c_int32), ("z_hi", C.c_int32),
@@ -184,6 +189,7 @@ _DD = C.POINTER(VampDetDesc)
 _TD = C.POINTER(VampDetTargetDesc)
 _ED = C.POINTER(VampDetLossDesc)
 _TT = C.POINTER(VampDetTask)
+_GD = C.POINTER(VampRgbLossDesc)
 
 # name -> (return kind, argtypes); must list every symbol declared in include/vampire_hip.h
 SIGNATURES = {
@@ -280,6 +286,9 @@ SIGNATURES = {
     "vamp_det_loss_counts": (_STATUS, [_ED, _P, _P, _P, _P]),
     "vamp_det_loss_forward": (_STATUS, [_ED, _TT] + [_P] * 7 + [_P, C.c_size_t, _P]),
     "vamp_det_loss_backward": (_STATUS, [_ED, _TT] + [_P] * 6 + [_TT, _P, C.c_size_t, _P]),
+    "vamp_rgb_loss_workspace_bytes": (_SIZE, [_GD]),
+    "vamp_rgb_loss_forward": (_STATUS, [_GD] + [_P] * 5 + [_P, C.c_size_t, _P]),
+    "vamp_rgb_loss_backward": (_STATUS, [_GD] + [_P] * 4 + [_P, C.c_size_t, _P]),
 }
 
 _lib = None

@@ -446,13 +446,15 @@ class MultiTaskLoss:
     `task_weights` (occ, lidarseg, detection) and `loss_weights` (depth, seg, rgb, sdf, density)."""
 
     def __init__(self, model, task_weights=(1., 1., 1.), loss_weights=(1., 1., 1., 1., 1.), downsample_factor=4,
-                 upsample_factor=4, sdf_bias=-1.0, det_targets="host", det_loss="host"):
+                 upsample_factor=4, sdf_bias=-1.0, det_targets="host", det_loss="host", rgb_loss="host"):
         if det_targets not in ("host", "device"):
             raise ValueError(f"det_targets must be 'host' or 'device', got {det_targets!r}")
         if det_loss not in ("host", "device"):
             raise ValueError(f"det_loss must be 'host' or 'device', got {det_loss!r}")
+        if rgb_loss not in ("host", "device"):
+            raise ValueError(f"rgb_loss must be 'host' or 'device', got {rgb_loss!r}")
         self.model, self.task_weights, self.loss_weights = model, task_weights, loss_weights
-        self.det_targets, self.det_loss = det_targets, det_loss
+        self.det_targets, self.det_loss, self.rgb_loss = det_targets, det_loss, rgb_loss
         self.down, self.up, self.sdf_bias = downsample_factor, upsample_factor, sdf_bias
         self.last = {}
 
@@ -495,7 +497,11 @@ class MultiTaskLoss:
         cam_depth = F.smooth_l1_loss(f32(depth_p)[fg], depth_l[fg])
         h, w = rgb_l.shape[-2:]
         rp, rl = f32(rgb_p).reshape(-1, 3, h, w), rgb_l.reshape(-1, 3, h, w)
-        rgb = (F.smooth_l1_loss(rp, rl, reduction="none") + 1 - ms_ssim(rp, rl)).mean()
+        if self.rgb_loss == "device":                    # the same expression in HIP kernels (ops.rgb_loss)
+            from . import ops
+            rgb = ops.rgb_loss(rp, rl)
+        else:
+            rgb = (F.smooth_l1_loss(rp, rl, reduction="none") + 1 - ms_ssim(rp, rl)).mean()
         cam_seg = _ce_lovasz(seg_p.permute(0, 1, 3, 4, 2)[fg], seg_l[fg])
         bev_height_l = F.smooth_l1_loss(bev_height[bev_mask], f32(bev_h_p).unsqueeze(1)[bev_mask])
         bev_seg_l = _ce_lovasz(bev_seg_p[:, None, None].permute(0, 1, 2, 4, 5, 3)[bev_mask], bev_seg[bev_mask])
