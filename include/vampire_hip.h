@@ -27,9 +27,9 @@
 extern "C" {
 #endif
 
-#define VAMP_ABI_VERSION 12  /* bumped whenever entry points or flags are added (round 2: 2, round 3: 3, round 4: 4, round 5: 5, round 6: 6;
+#define VAMP_ABI_VERSION 13  /* bumped whenever entry points or flags are added (round 2: 2, round 3: 3, round 4: 4, round 5: 5, round 6: 6;
                                  7: segmentation metrics; 8: detection post-processing; 9: detection targets;
-                                 10: the BEV backward's plan; 11: detection loss; 12: rgb loss) */
+                                 10: the BEV backward's plan; 11: detection loss; 12: rgb loss; 13: segmentation loss) */
 
 enum {
   VAMP_OK = 0,
@@ -1060,6 +1060,56 @@ int vamp_rgb_loss_forward(const VampRgbLossDesc* d, const float* pred, const flo
                           float* vals, void* workspace, size_t workspace_bytes, void* stream);
 int vamp_rgb_loss_backward(const VampRgbLossDesc* d, const float* pred, const float* target, const float* grad_loss,
                            float* grad_pred, void* workspace, size_t workspace_bytes, void* stream);
+
+/* --------------------------------------------------------------------------
+ * Segmentation loss (base_exp.py:519-575: the camera, BEV, lidar-point and occupancy segmentation terms of the
+ * training step, each F.cross_entropy(x[mask], y[mask]) + lovasz_softmax(F.softmax(x[mask], 1), y[mask]);
+ * lovasz_losses.py:171-199, lovasz_softmax_flat with classes='present'): loss = w_ce CE + w_lv LV over the VALID
+ * elements -- mask byte set (mask may be NULL: all) and label in [0, C) -- and its gradient with respect to the
+ * logits, without compacting the inputs.  Logits are fp32 in the layouts of vamp_confusion_update (VAMP_SEG_ROWS
+ * [n, C], VAMP_SEG_PLANES [B, C, S], element i = b * S + s), labels [n] of label_dtype, mask [n] bool bytes.
+ *
+ *  CE         -(1 / n) sum over valid i of log softmax(logits[i])[labels[i]]; n = number of valid elements.
+ *  LV         p = softmax in fp32, err[i, c] = |[labels[i] == c] - p[i, c]| in fp32.  For every class with a valid
+ *             foreground element: the valid elements sorted by err descending, bit-equal errors by ascending element
+ *             index (a total order: the permutation is unique), and sum_k err_k delta_k with the Jaccard step from
+ *             integer counts in float64 -- G foreground elements, cum_k of them among the first k, I = G - cum_k,
+ *             U = G + k - cum_k: delta_k = 1 / U at a foreground element, I / ((U - 1) U) at a background one.
+ *             LV = mean over those classes.
+ *  outputs    loss [1], terms [2] = (CE, LV), counts [2] int32 = (n, classes present).  sorted_err / perm (each
+ *             NULL or [C, B S] fp32 / int32, class-major) receive, for EVERY class, the sorted errors and element
+ *             indices of the valid elements in a row's first n entries; the rest of a row is unspecified.
+ *  gradient   grad_logits (the logits' layout, every element written once) = grad_loss[0] (a device scalar, the
+ *             last factor) times w_ce (p - fg) / n + w_lv p (u - sum_k p_k u_k) / present, u[i, c] = -sign(fg - p)
+ *             delta_rank(i, c) for present classes (sign(0) = 0), else 0.  Invalid elements get exactly 0.
+ *  n = 0      loss, terms and the whole gradient are DEFINED as exactly 0: the one difference from the torch
+ *             expression, whose cross_entropy of an empty selection is NaN.
+ * Forward: one pass over the rows, a per-class LSD radix sort (four 8-bit passes of histogram, scan, stable
+ * scatter), a foreground scan of the sorted order, and one finishing workgroup that adds the float64 partials in a
+ * fixed order -- sixteen launches whose grids depend on the shapes only.  Backward: one launch; it reads `kept`
+ * (vamp_seg_loss_kept_bytes: 4 bytes per element and class, the unit gradients u) as the forward of the same
+ * inputs left it.  The workspace (vamp_seg_loss_workspace_bytes, about 17 bytes per element and class) is needed
+ * by the forward only.  Neither needs initialisation; both must be 8-byte aligned.  No float atomics, no host
+ * synchronisation, bitwise repeatable, capturable in a graph.  Limits: 2 <= C <= 32, B S >= 1, B S C < 2^31.
+ * A bad descriptor returns VAMP_EINVAL (and a size of 0), a NULL required pointer or a buffer that is too small
+ * VAMP_ENOSPC, both before any launch.
+ * -------------------------------------------------------------------------- */
+typedef struct VampSegLossDesc {
+  int64_t B, S;                   /* n = B * S elements (ROWS: B = 1) */
+  int32_t C;                      /* classes */
+  int32_t layout;                 /* VAMP_SEG_ROWS | VAMP_SEG_PLANES */
+  int32_t label_dtype;            /* VAMP_I64 | VAMP_I32 | VAMP_U8 */
+  int32_t reserved;               /* 0 */
+  float w_ce, w_lv;
+} VampSegLossDesc;
+size_t vamp_seg_loss_workspace_bytes(const VampSegLossDesc* d);
+size_t vamp_seg_loss_kept_bytes(const VampSegLossDesc* d);
+int vamp_seg_loss_forward(const VampSegLossDesc* d, const float* logits, const void* labels, const uint8_t* mask,
+                          float* loss, float* terms, int32_t* counts, float* sorted_err, int32_t* perm, void* kept,
+                          size_t kept_bytes, void* workspace, size_t workspace_bytes, void* stream);
+int vamp_seg_loss_backward(const VampSegLossDesc* d, const float* logits, const void* labels, const uint8_t* mask,
+                           const float* grad_loss, float* grad_logits, const void* kept, size_t kept_bytes,
+                           void* stream);
 
 #ifdef __cplusplus
 }

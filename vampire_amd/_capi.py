@@ -15,7 +15,7 @@ import torch
 
 from .build import lib_path
 
-ABI_VERSION = 12
+ABI_VERSION = 13
 
 VAMP_F32, VAMP_BF16, VAMP_F16 = 0, 1, 2
 VAMP_DENSITY_SIGMOID, VAMP_DENSITY_SDF_LAPLACE = 0, 1
@@ -109,6 +109,11 @@ class VampRgbLossDesc(C.Structure):
                 ("data_range", C.c_float), ("k1", C.c_float), ("k2", C.c_float)]
 
 
+class VampSegLossDesc(C.Structure):
+    _fields_ = [("B", C.c_int64), ("S", C.c_int64), ("C", C.c_int32), ("layout", C.c_int32),
+                ("label_dtype", C.c_int32), ("reserved", C.c_int32), ("w_ce", C.c_float), ("w_lv", C.c_float)]
+
+
 class VampBevBackwardPlan(C.Structure):
     """What vamp_render_bev_backward_ex will launch (vamp_render_bev_backward_plan; include/vampire_hip.h)."""
     _fields_ = [("scan_lds", C.c_int64), ("path", C.c_int32), ("z_lo", C.c_int32), ("z_hi", C.c_int32),
@@ -190,6 +195,7 @@ _TD = C.POINTER(VampDetTargetDesc)
 _ED = C.POINTER(VampDetLossDesc)
 _TT = C.POINTER(VampDetTask)
 _GD = C.POINTER(VampRgbLossDesc)
+_SLD = C.POINTER(VampSegLossDesc)
 
 # name -> (return kind, argtypes); must list every symbol declared in include/vampire_hip.h
 SIGNATURES = {
@@ -289,6 +295,10 @@ SIGNATURES = {
     "vamp_rgb_loss_workspace_bytes": (_SIZE, [_GD]),
     "vamp_rgb_loss_forward": (_STATUS, [_GD] + [_P] * 5 + [_P, C.c_size_t, _P]),
     "vamp_rgb_loss_backward": (_STATUS, [_GD] + [_P] * 4 + [_P, C.c_size_t, _P]),
+    "vamp_seg_loss_workspace_bytes": (_SIZE, [_SLD]),
+    "vamp_seg_loss_kept_bytes": (_SIZE, [_SLD]),
+    "vamp_seg_loss_forward": (_STATUS, [_SLD] + [_P] * 8 + [_P, C.c_size_t, _P, C.c_size_t, _P]),
+    "vamp_seg_loss_backward": (_STATUS, [_SLD] + [_P] * 5 + [_P, C.c_size_t, _P]),
 }
 
 _lib = None

@@ -1,6 +1,7 @@
 """Tensor-side helpers every operator module shares (ops, layers, evaluation): what a kernel accepts, how a tensor is
 checked before its address goes to the library, dtype and density codes, the current stream, scratch workspaces."""
 import ctypes as C
+import math
 
 import torch
 
@@ -41,6 +42,21 @@ def _is_channel_last(feat: torch.Tensor) -> bool:
     what the lift wants -- it samples a pixel's C features as one run -- and takes zero-copy."""
     return (feat.dim() == 5 and feat.dtype == torch.float32 and feat.shape[2] > 1
             and feat.permute(0, 1, 3, 4, 2).is_contiguous() and feat.data_ptr() % 16 == 0)
+
+
+def _logit_layout(x):
+    """(layout, B, S, x) for logits [..., K]: rows when contiguous, planes when the memory is channel-first
+    ([B, K, ...] behind a permute(0, 2, .., 1) view, the backbone's occ_logits; leading dimensions in front of the
+    channel axis, as in the camera branch's [B, N, K, h, w], count into B), else a contiguous copy."""
+    if x.is_contiguous():
+        return _capi.VAMP_SEG_ROWS, 1, x.numel() // max(x.shape[-1], 1), x
+    if x.dim() == 2 and x.t().is_contiguous():
+        return _capi.VAMP_SEG_PLANES, 1, x.shape[0], x
+    for k in range(1, x.dim() - 1):
+        if x.movedim(-1, k).is_contiguous():
+            return _capi.VAMP_SEG_PLANES, math.prod(x.shape[:k]), math.prod(x.shape[k:-1]), x
+    x = x.contiguous()
+    return _capi.VAMP_SEG_ROWS, 1, x.numel() // max(x.shape[-1], 1), x
 
 
 def _chk(t: torch.Tensor, shape, name):

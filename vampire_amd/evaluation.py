@@ -2,12 +2,11 @@
 confusion-matrix pass and lidar-segmentation prediction, CenterPoint post-processing (decode + NMS), training
 targets and the detection loss.  All work happens in hand-written HIP kernels reached through `_capi`; there is no CPU fallback."""
 import dataclasses
-import math
 
 import torch
 
 from . import _capi
-from ._tensors import DTYPE_CODES, FLOAT_DTYPES, _accept, _dtype_code, _stream, _workspace
+from ._tensors import DTYPE_CODES, FLOAT_DTYPES, _accept, _dtype_code, _logit_layout, _stream, _workspace
 
 
 # ===========================================================================
@@ -19,19 +18,6 @@ _TARGET_DTYPES = (torch.int64, torch.int32, torch.uint8)
 def _scratch(kind, device, nbytes):
     """This operator's workspace on the device's current stream (regrown when a call needs more)."""
     return _workspace((kind, device, torch.cuda.current_stream(device).cuda_stream), device, nbytes)
-
-
-def _logit_layout(x):
-    """(layout, B, S, x) for logits [..., K]: rows when contiguous, planes when the memory is channel-first
-    ([B, K, ...] behind a permute(0, 2, .., 1) view, the backbone's occ_logits), else a contiguous copy."""
-    if x.is_contiguous():
-        return _capi.VAMP_SEG_ROWS, 1, x.numel() // max(x.shape[-1], 1), x
-    if x.dim() == 2 and x.t().is_contiguous():
-        return _capi.VAMP_SEG_PLANES, 1, x.shape[0], x
-    if x.dim() >= 3 and x.movedim(-1, 1).is_contiguous():
-        return _capi.VAMP_SEG_PLANES, x.shape[0], math.prod(x.shape[1:-1]), x
-    x = x.contiguous()
-    return _capi.VAMP_SEG_ROWS, 1, x.numel() // max(x.shape[-1], 1), x
 
 
 def confusion_update(confmat, invalid, logits_or_preds, target, mask=None, *, class_window=None, ignore_index=None):

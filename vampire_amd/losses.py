@@ -3,9 +3,11 @@ through `_capi`; there is no CPU fallback."""
 import torch
 
 from . import _capi
-from ._tensors import _stream
+from ._tensors import DTYPE_CODES, _logit_layout, _stream
 
 RGB_MIN_SIDE, RGB_MAX_CHANNELS, RGB_SCALES = 176, 4, 5
+SEG_MIN_CLASSES, SEG_MAX_CLASSES = 2, 32
+_SEG_LABEL_DTYPES = (torch.int64, torch.int32, torch.uint8)
 
 
 class _RgbLoss(torch.autograd.Function):
@@ -66,4 +68,95 @@ def rgb_loss(pred, target, data_range=1.0):
         raise _capi.VampireHipError("rgb_loss needs device tensors (no CPU fallback)")
     loss, terms, vals = _RgbLoss.apply(d, pred.contiguous(), target.contiguous())
     loss.terms, loss.vals = terms, vals
+    return loss
+
+
+def _seg_forward(desc, logits, labels, mask, window=False):
+    """One vamp_seg_loss_forward: (loss, terms, counts, kept, sorted_err, perm).  `window`: also export the sort --
+    sorted_err [C, P] fp32 and perm [C, P] int32, a row's first counts[0] entries (the tests' view of the order)."""
+    dev = logits.device
+    loss = torch.empty((), dtype=torch.float32, device=dev)
+    terms = torch.empty(2, dtype=torch.float32, device=dev)
+    counts = torch.empty(2, dtype=torch.int32, device=dev)
+    sorted_err = perm = None
+    vamp = _capi.checked()
+    with torch.cuda.device(dev):
+        if window:
+            sorted_err = torch.empty(desc.C, desc.B * desc.S, dtype=torch.float32, device=dev)
+            perm = torch.empty(desc.C, desc.B * desc.S, dtype=torch.int32, device=dev)
+        kept = torch.empty(vamp.vamp_seg_loss_kept_bytes(desc), dtype=torch.uint8, device=dev)
+        ws = torch.empty(vamp.vamp_seg_loss_workspace_bytes(desc), dtype=torch.uint8, device=dev)
+        vamp.vamp_seg_loss_forward(desc, logits, labels, mask, loss, terms, counts, sorted_err, perm, kept,
+                                   kept.numel(), ws, ws.numel(), _stream())
+    return loss, terms, counts, kept, sorted_err, perm
+
+
+class _SegLoss(torch.autograd.Function):
+    """loss, terms, counts = apply(desc, logits, labels, mask).  The forward's sort buffers are scratch of this call,
+    handed back to the allocator on return; what the backward reads -- the unit gradients, 4 bytes per element and
+    class, behind the two counts -- is a tensor of this call's own, kept in ctx."""
+
+    @staticmethod
+    def forward(ctx, desc, logits, labels, mask):
+        loss, terms, counts, kept, _, _ = _seg_forward(desc, logits, labels, mask)
+        ctx.desc = desc
+        ctx.save_for_backward(logits, labels, mask, kept)
+        ctx.mark_non_differentiable(terms, counts)
+        return loss, terms, counts
+
+    @staticmethod
+    def backward(ctx, grad_loss, _grad_terms, _grad_counts):
+        logits, labels, mask, kept = ctx.saved_tensors
+        grad = None
+        if ctx.needs_input_grad[1]:
+            grad = torch.empty_like(logits)              # (the logits' own strides: rows or channel-first planes)
+            gl = grad_loss.to(torch.float32).contiguous()
+            with torch.cuda.device(logits.device):
+                _capi.checked().vamp_seg_loss_backward(ctx.desc, logits, labels, mask, gl, grad, kept, kept.numel(),
+                                                       _stream())
+        return None, grad, None, None
+
+
+def _seg_inputs(logits, labels, mask, ce_weight, lovasz_weight, name="seg_loss"):
+    """Checks and the descriptor of seg_loss: (desc, logits, labels, mask) as the entry points take them."""
+    if logits.dim() < 1 or tuple(labels.shape) != tuple(logits.shape[:-1]):
+        raise ValueError(f"{name}: labels {tuple(labels.shape)} do not match logits {tuple(logits.shape)}")
+    if mask is not None and tuple(mask.shape) != tuple(labels.shape):
+        raise ValueError(f"{name}: mask {tuple(mask.shape)} does not match labels {tuple(labels.shape)}")
+    C = logits.shape[-1]
+    if not SEG_MIN_CLASSES <= C <= SEG_MAX_CLASSES:
+        raise ValueError(f"{name}: {C} classes are outside {SEG_MIN_CLASSES} <= C <= {SEG_MAX_CLASSES}")
+    if labels.is_floating_point() or labels.requires_grad:
+        raise TypeError(f"{name}: labels must be integers, got {labels.dtype}")
+    if not (logits.is_cuda and labels.is_cuda and (mask is None or mask.is_cuda)):
+        raise _capi.VampireHipError(f"{name} needs device tensors (no CPU fallback)")
+    if logits.dtype != torch.float32:
+        logits = logits.float()                          # (keeps a permuted view's channel-first memory)
+    layout, B, S, logits = _logit_layout(logits)
+    if labels.dtype not in _SEG_LABEL_DTYPES:
+        labels = labels.long()
+    labels = labels.contiguous()
+    if mask is not None:
+        mask = (mask if mask.dtype == torch.bool else mask != 0).contiguous()
+    d = _capi.VampSegLossDesc(B, S, C, layout, DTYPE_CODES[labels.dtype], 0, float(ce_weight), float(lovasz_weight))
+    vamp = _capi.checked()
+    if vamp.vamp_seg_loss_workspace_bytes(d) == 0:
+        raise ValueError(f"{name}: {vamp.vamp_last_error().decode('utf-8', 'replace')}")
+    return d, logits, labels, mask
+
+
+def seg_loss(logits, labels, mask=None, ce_weight=1.0, lovasz_weight=1.0):
+    """The segmentation loss of base_exp.py:519-575 on the device (vamp_seg_loss_*): ce_weight * F.cross_entropy(x, y)
+    + lovasz_weight * lovasz_softmax(F.softmax(x, 1), y) ('present' classes; multitask.lovasz_softmax) over x =
+    logits[mask], y = labels[mask] -- without the boolean-mask compaction, so without a host synchronisation; no float
+    atomics, bitwise repeatable, capturable in a graph.  logits [..., C], 2 <= C <= 32, read in place when contiguous
+    or when they are the permute(.., 1)-style view of channel-first memory (the backbone's occ_logits, seg_p.permute(0,
+    1, 3, 4, 2)); other dtypes than fp32 are cast.  labels (int64 | int32 | uint8, other integers cast) and mask (bool)
+    are shaped like logits[..., 0].  Elements whose label lies outside [0, C) count as masked out.  Equal errors sort
+    by ascending element index.  Returns the 0-dim fp32 loss; its attributes `terms` ([2]: CE, Lovasz), `n_valid` and
+    `n_present` (0-dim int32) are detached device tensors.  The gradient goes to the logits only.  With no valid
+    element the loss, both terms and the gradient are exactly 0 (F.cross_entropy of an empty selection is NaN)."""
+    d, x, y, m = _seg_inputs(logits, labels, mask, ce_weight, lovasz_weight)
+    loss, terms, counts = _SegLoss.apply(d, x, y, m)
+    loss.terms, loss.n_valid, loss.n_present = terms, counts[0], counts[1]
     return loss

@@ -443,18 +443,25 @@ def _ce_lovasz(logits, labels):
 class MultiTaskLoss:
     """base_exp.py:315-434 `training_step` from the model's outputs on: detection + camera depth / seg /
     rgb + BEV height / seg + lidar-point seg + sdf + occupancy seg / density, weighted by
-    `task_weights` (occ, lidarseg, detection) and `loss_weights` (depth, seg, rgb, sdf, density)."""
+    `task_weights` (occ, lidarseg, detection) and `loss_weights` (depth, seg, rgb, sdf, density).
+    `seg_loss="device"` computes the four cross-entropy + Lovasz terms (camera, BEV, lidar-point and occupancy
+    segmentation) with ops.seg_loss: the logits are read in place under their masks, without the boolean-mask
+    compaction and its host synchronisation; the default "host" keeps the torch expression `_ce_lovasz`."""
 
     def __init__(self, model, task_weights=(1., 1., 1.), loss_weights=(1., 1., 1., 1., 1.), downsample_factor=4,
-                 upsample_factor=4, sdf_bias=-1.0, det_targets="host", det_loss="host", rgb_loss="host"):
+                 upsample_factor=4, sdf_bias=-1.0, det_targets="host", det_loss="host", rgb_loss="host",
+                 seg_loss="host"):
         if det_targets not in ("host", "device"):
             raise ValueError(f"det_targets must be 'host' or 'device', got {det_targets!r}")
         if det_loss not in ("host", "device"):
             raise ValueError(f"det_loss must be 'host' or 'device', got {det_loss!r}")
         if rgb_loss not in ("host", "device"):
             raise ValueError(f"rgb_loss must be 'host' or 'device', got {rgb_loss!r}")
+        if seg_loss not in ("host", "device"):
+            raise ValueError(f"seg_loss must be 'host' or 'device', got {seg_loss!r}")
         self.model, self.task_weights, self.loss_weights = model, task_weights, loss_weights
         self.det_targets, self.det_loss, self.rgb_loss = det_targets, det_loss, rgb_loss
+        self.seg_loss = seg_loss
         self.down, self.up, self.sdf_bias = downsample_factor, upsample_factor, sdf_bias
         self.last = {}
 
@@ -502,15 +509,28 @@ class MultiTaskLoss:
             rgb = ops.rgb_loss(rp, rl)
         else:
             rgb = (F.smooth_l1_loss(rp, rl, reduction="none") + 1 - ms_ssim(rp, rl)).mean()
-        cam_seg = _ce_lovasz(seg_p.permute(0, 1, 3, 4, 2)[fg], seg_l[fg])
+        seg_dev = self.seg_loss == "device"              # the same expression in HIP kernels, the mask passed along
+        if seg_dev:
+            from . import ops
+            cam_seg = ops.seg_loss(seg_p.permute(0, 1, 3, 4, 2), seg_l, fg)
+        else:
+            cam_seg = _ce_lovasz(seg_p.permute(0, 1, 3, 4, 2)[fg], seg_l[fg])
         bev_height_l = F.smooth_l1_loss(bev_height[bev_mask], f32(bev_h_p).unsqueeze(1)[bev_mask])
-        bev_seg_l = _ce_lovasz(bev_seg_p[:, None, None].permute(0, 1, 2, 4, 5, 3)[bev_mask], bev_seg[bev_mask])
+        if seg_dev:
+            bev_seg_l = ops.seg_loss(bev_seg_p[:, None, None].permute(0, 1, 2, 4, 5, 3), bev_seg, bev_mask)
+        else:
+            bev_seg_l = _ce_lovasz(bev_seg_p[:, None, None].permute(0, 1, 2, 4, 5, 3)[bev_mask], bev_seg[bev_mask])
         lidarseg = sdf = 0.0
-        if len(pts_logits):
+        if len(pts_logits) and seg_dev:
+            lidarseg = ops.seg_loss(torch.cat(pts_logits, 0), torch.cat(inrange_labels, 0))
+        elif len(pts_logits):
             lidarseg = _ce_lovasz(torch.cat(pts_logits, 0), torch.cat(inrange_labels, 0))
         if len(pts_sdf):
             sdf = ((f32(torch.cat(pts_sdf, 0)) - self.sdf_bias) ** 2).mean()
-        occ = _ce_lovasz(occ_logits[mask_camera], occ_sem[mask_camera])
+        if seg_dev:
+            occ = ops.seg_loss(occ_logits, occ_sem, mask_camera)
+        else:
+            occ = _ce_lovasz(occ_logits[mask_camera], occ_sem[mask_camera])
         mse = lambda a, b: ((a.reshape(-1) - f32(b).reshape(-1)) ** 2).mean()
         density = mse(occ_dens_lab[mask_camera], occ_density[mask_camera]) + \
             mse(occ_dens_lab[~mask_camera], occ_density[~mask_camera])
