@@ -27,9 +27,10 @@
 extern "C" {
 #endif
 
-#define VAMP_ABI_VERSION 13  /* bumped whenever entry points or flags are added (round 2: 2, round 3: 3, round 4: 4, round 5: 5, round 6: 6;
+#define VAMP_ABI_VERSION 14  /* bumped whenever entry points or flags are added (round 2: 2, round 3: 3, round 4: 4, round 5: 5, round 6: 6;
                                  7: segmentation metrics; 8: detection post-processing; 9: detection targets;
-                                 10: the BEV backward's plan; 11: detection loss; 12: rgb loss; 13: segmentation loss) */
+                                 10: the BEV backward's plan; 11: detection loss; 12: rgb loss; 13: segmentation loss;
+                                 14: masked regression losses) */
 
 enum {
   VAMP_OK = 0,
@@ -1110,6 +1111,68 @@ int vamp_seg_loss_forward(const VampSegLossDesc* d, const float* logits, const v
 int vamp_seg_loss_backward(const VampSegLossDesc* d, const float* logits, const void* labels, const uint8_t* mask,
                            const float* grad_loss, float* grad_logits, const void* kept, size_t kept_bytes,
                            void* stream);
+
+/* --------------------------------------------------------------------------
+ * Masked regression losses (the regression terms of the training step: base_exp.py:588-594 get_depth_loss,
+ * F.smooth_l1_loss(depth_p[fg], depth_l[fg]); :581-586 get_height_loss_bev, the same under bev_mask; :533-537
+ * get_sdf_loss, the mean of (sdf - sdf_bias)^2; :523-531 get_occ_density_loss, F.mse_loss under mask_camera and,
+ * from a second call, under ~mask_camera).  One call evaluates a PACK of 1 <= T <= 8 terms in two launches, and the
+ * gradients of the whole pack in one, without compacting anything.  Term t:
+ *
+ *  inputs     pred [n] contiguous, fp32 or bf16 (pred_dtype), read in place; target [n] fp32, or the constant
+ *             target_value when target_is_const is 1 (the target pointer is then ignored); mask [n] bool bytes or
+ *             NULL.  The pointers may have any element offset (16-byte loads are used where all of a term's are
+ *             aligned for them; the results do not depend on it).
+ *  element    d = float(pred) - target and the element loss in fp32 as aten rounds them: VAMP_REG_SMOOTH_L1 (beta 1)
+ *             z = |d|, z < 1 ? (0.5 z) z : z - 0.5; VAMP_REG_MSE d d.
+ *  loss       S1 = the elements whose mask byte is set (all of them without a mask), S0 the others; mean_k = the
+ *             float64 sum over S_k divided by |S_k|.  losses[t] = mean_1 (VAMP_REG_SET), mean_0 (VAMP_REG_CLEAR) or
+ *             mean_1 + mean_0 (VAMP_REG_BOTH), rounded to fp32 once; counts[t] = (|S1|, |S0|) int64.  CLEAR and BOTH
+ *             need a mask.  Elements are selected, not weighted: a NaN or an infinity in pred or target outside the
+ *             selected side(s) reaches neither the loss nor a gradient.
+ *  |S_k| = 0  mean_k is DEFINED as exactly 0 (and there is no element to receive a gradient from it): the one
+ *             difference from the torch expressions, whose mean of an empty selection is NaN.
+ *  gradient   grad_pred[t] [n] of pred's dtype, every element written once: grad_losses[t] l'(d) / |S_k| at an
+ *             element of a selected side k (l' = d where |d| < 1, else sign(d), a NaN d stays NaN as in aten; 2 d for
+ *             the squared error), formed in
+ *             float64 and rounded once to fp32 (from there to nearest-even bf16), exactly 0 elsewhere.  A NULL entry
+ *             of grad_pred_host skips the term.  `counts` is the forward's output, read on the device.  No gradient
+ *             goes to target.
+ * pred_host, target_host, mask_host and grad_pred_host are HOST arrays of T device pointers, read before the call
+ * returns.  Forward: reg_partial_kernel (term t owns ceil(n / VAMP_REG_TILE) consecutive workgroups; float64 sums
+ * and integer counts per workgroup into the workspace) and one finishing workgroup that adds a term's partials in
+ * index order.  The workspace (8-byte aligned, vamp_reg_loss_workspace_bytes: 24 bytes per workgroup) is forward
+ * scratch and needs no initialisation.  No atomics, no host synchronisation, bitwise repeatable, capturable in a
+ * graph; a term's results do not depend on the other terms of the pack.  Limits: 1 <= T <= 8, 1 <= n < 2^31.
+ * Everything that is refused -- T, n, kind, side, pred_dtype or target_is_const out of range, CLEAR or BOTH without
+ * a mask, a NULL required pointer, a workspace that is too small -- returns VAMP_EINVAL (and a size of 0) before any
+ * launch.
+ * -------------------------------------------------------------------------- */
+#define VAMP_REG_MAX_TERMS 8
+#define VAMP_REG_TILE 4096        /* elements per workgroup */
+enum { VAMP_REG_SMOOTH_L1 = 0, VAMP_REG_MSE = 1 };
+enum { VAMP_REG_SET = 0, VAMP_REG_CLEAR = 1, VAMP_REG_BOTH = 2 };
+typedef struct VampRegTerm {
+  int64_t n;                      /* elements */
+  int32_t kind;                   /* VAMP_REG_SMOOTH_L1 | VAMP_REG_MSE */
+  int32_t side;                   /* VAMP_REG_SET | VAMP_REG_CLEAR | VAMP_REG_BOTH */
+  int32_t pred_dtype;             /* VAMP_F32 | VAMP_BF16 */
+  int32_t target_is_const;        /* 1: the target is target_value */
+  float target_value;
+  int32_t reserved;               /* 0 */
+} VampRegTerm;
+typedef struct VampRegLossDesc {
+  int32_t T;                      /* terms in use */
+  int32_t reserved;               /* 0 */
+  VampRegTerm terms[VAMP_REG_MAX_TERMS];
+} VampRegLossDesc;
+size_t vamp_reg_loss_workspace_bytes(const VampRegLossDesc* d);
+int vamp_reg_loss_forward(const VampRegLossDesc* d, const void* const* pred_host, const float* const* target_host,
+                          const uint8_t* const* mask_host, float* losses, int64_t* counts, void* workspace,
+                          size_t workspace_bytes, void* stream);
+int vamp_reg_loss_backward(const VampRegLossDesc* d, const void* const* pred_host, const float* const* target_host,
+                           const uint8_t* const* mask_host, const int64_t* counts, const float* grad_losses,
+                           void* const* grad_pred_host, void* stream);
 
 #ifdef __cplusplus
 }

@@ -15,12 +15,15 @@ import torch
 
 from .build import lib_path
 
-ABI_VERSION = 13
+ABI_VERSION = 14
 
 VAMP_F32, VAMP_BF16, VAMP_F16 = 0, 1, 2
 VAMP_DENSITY_SIGMOID, VAMP_DENSITY_SDF_LAPLACE = 0, 1
 VAMP_I64, VAMP_I32, VAMP_U8 = 3, 4, 5
 VAMP_SEG_ROWS, VAMP_SEG_PLANES = 0, 1
+VAMP_REG_MAX_TERMS, VAMP_REG_TILE = 8, 4096
+VAMP_REG_SMOOTH_L1, VAMP_REG_MSE = 0, 1
+VAMP_REG_SET, VAMP_REG_CLEAR, VAMP_REG_BOTH = 0, 1, 2
 
 
 class VampLiftDesc(C.Structure):
@@ -114,6 +117,15 @@ class VampSegLossDesc(C.Structure):
                 ("label_dtype", C.c_int32), ("reserved", C.c_int32), ("w_ce", C.c_float), ("w_lv", C.c_float)]
 
 
+class VampRegTerm(C.Structure):
+    _fields_ = [("n", C.c_int64), ("kind", C.c_int32), ("side", C.c_int32), ("pred_dtype", C.c_int32),
+                ("target_is_const", C.c_int32), ("target_value", C.c_float), ("reserved", C.c_int32)]
+
+
+class VampRegLossDesc(C.Structure):
+    _fields_ = [("T", C.c_int32), ("reserved", C.c_int32), ("terms", VampRegTerm * VAMP_REG_MAX_TERMS)]
+
+
 class VampBevBackwardPlan(C.Structure):
     """What vamp_render_bev_backward_ex will launch (vamp_render_bev_backward_plan; include/vampire_hip.h)."""
     _fields_ = [("scan_lds", C.c_int64), ("path", C.c_int32), ("z_lo", C.c_int32), ("z_hi", C.c_int32),
@@ -196,6 +208,7 @@ _ED = C.POINTER(VampDetLossDesc)
 _TT = C.POINTER(VampDetTask)
 _GD = C.POINTER(VampRgbLossDesc)
 _SLD = C.POINTER(VampSegLossDesc)
+_RLD = C.POINTER(VampRegLossDesc)
 
 # name -> (return kind, argtypes); must list every symbol declared in include/vampire_hip.h
 SIGNATURES = {
@@ -299,6 +312,9 @@ SIGNATURES = {
     "vamp_seg_loss_kept_bytes": (_SIZE, [_SLD]),
     "vamp_seg_loss_forward": (_STATUS, [_SLD] + [_P] * 8 + [_P, C.c_size_t, _P, C.c_size_t, _P]),
     "vamp_seg_loss_backward": (_STATUS, [_SLD] + [_P] * 5 + [_P, C.c_size_t, _P]),
+    "vamp_reg_loss_workspace_bytes": (_SIZE, [_RLD]),
+    "vamp_reg_loss_forward": (_STATUS, [_RLD] + [_P] * 5 + [_P, C.c_size_t, _P]),
+    "vamp_reg_loss_backward": (_STATUS, [_RLD] + [_P] * 6 + [_P]),
 }
 
 _lib = None

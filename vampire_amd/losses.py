@@ -1,5 +1,8 @@
 """Training losses on plain tensors (Python over the C ABI).  All work happens in hand-written HIP kernels reached
 through `_capi`; there is no CPU fallback."""
+import collections
+import ctypes as C
+
 import torch
 
 from . import _capi
@@ -8,6 +11,9 @@ from ._tensors import DTYPE_CODES, _logit_layout, _stream
 RGB_MIN_SIDE, RGB_MAX_CHANNELS, RGB_SCALES = 176, 4, 5
 SEG_MIN_CLASSES, SEG_MAX_CLASSES = 2, 32
 _SEG_LABEL_DTYPES = (torch.int64, torch.int32, torch.uint8)
+REG_TILE, REG_MAX_TERMS = _capi.VAMP_REG_TILE, _capi.VAMP_REG_MAX_TERMS
+_REG_KINDS = {"smooth_l1": _capi.VAMP_REG_SMOOTH_L1, "mse": _capi.VAMP_REG_MSE}
+_REG_SIDES = {"set": _capi.VAMP_REG_SET, "clear": _capi.VAMP_REG_CLEAR, "both": _capi.VAMP_REG_BOTH}
 
 
 class _RgbLoss(torch.autograd.Function):
@@ -159,4 +165,118 @@ def seg_loss(logits, labels, mask=None, ce_weight=1.0, lovasz_weight=1.0):
     d, x, y, m = _seg_inputs(logits, labels, mask, ce_weight, lovasz_weight)
     loss, terms, counts = _SegLoss.apply(d, x, y, m)
     loss.terms, loss.n_valid, loss.n_present = terms, counts[0], counts[1]
+    return loss
+
+
+RegTerm = collections.namedtuple("RegTerm", ["pred", "target", "mask", "kind", "side"],
+                                 defaults=(None, "smooth_l1", "set"))
+RegTerm.__doc__ = """One term of ops.reg_losses: the mean `kind` ("smooth_l1", beta 1, or "mse") loss of `pred` against
+`target` (a tensor shaped like pred, or a Python float) over the elements `mask` sets (side "set"), clears ("clear") or
+the sum of both means ("both"); without a mask every element is set."""
+
+
+def _ptr_array(tensors):
+    return (C.c_void_p * REG_MAX_TERMS)(*[None if t is None else t.data_ptr() for t in tensors])
+
+
+class _RegLosses(torch.autograd.Function):
+    """losses, counts = apply(call, *preds); `call` = (desc, workspace bytes, targets, masks).  The forward's workspace
+    is scratch of this call; the backward reads the operands again and `counts`.  The targets and masks are detached
+    constants that are no inputs of the Function: they are kept on ctx as they are, next to the pointer arrays made
+    from them; only the preds and `counts` go through save_for_backward."""
+
+    @staticmethod
+    def forward(ctx, call, *preds):
+        desc, nbytes, targets, masks = call
+        dev = preds[0].device
+        ptrs = (_ptr_array(preds), _ptr_array(targets), _ptr_array(masks))
+        with torch.cuda.device(dev):
+            losses = torch.empty(desc.T, dtype=torch.float32, device=dev)
+            counts = torch.empty(desc.T, 2, dtype=torch.int64, device=dev)
+            ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+            _capi.checked().vamp_reg_loss_forward(desc, *ptrs, losses, counts, ws, nbytes, _stream())
+        ctx.desc, ctx.ptrs, ctx.constants = desc, ptrs, (targets, masks)
+        ctx.save_for_backward(counts, *preds)
+        ctx.mark_non_differentiable(counts)
+        return losses, counts
+
+    @staticmethod
+    def backward(ctx, grad_losses, _grad_counts):
+        counts, *preds = ctx.saved_tensors
+        grads = [torch.empty_like(p) if ctx.needs_input_grad[1 + t] else None for t, p in enumerate(preds)]
+        if any(g is not None for g in grads):
+            gl = grad_losses.to(torch.float32).contiguous()
+            with torch.cuda.device(counts.device):
+                _capi.checked().vamp_reg_loss_backward(ctx.desc, *ctx.ptrs, counts, gl, _ptr_array(grads), _stream())
+        return (None,) + tuple(grads)
+
+
+def _reg_inputs(terms, name="reg_losses"):
+    """Checks and the descriptor of reg_losses: ((desc, workspace bytes, targets, masks), preds) as _RegLosses and the
+    entry points take them."""
+    terms = [t if isinstance(t, RegTerm) else RegTerm(*t) for t in terms]
+    if not 1 <= len(terms) <= REG_MAX_TERMS:
+        raise ValueError(f"{name}: {len(terms)} terms are outside 1 <= T <= {REG_MAX_TERMS}")
+    d = _capi.VampRegLossDesc()
+    d.T = len(terms)
+    preds, targets, masks = [], [], []
+    for k, (pred, target, mask, kind, side) in enumerate(terms):
+        if kind not in _REG_KINDS:
+            raise ValueError(f"{name}: term {k}: kind must be one of {sorted(_REG_KINDS)}, got {kind!r}")
+        if side not in _REG_SIDES:
+            raise ValueError(f"{name}: term {k}: side must be one of {sorted(_REG_SIDES)}, got {side!r}")
+        if not torch.is_tensor(pred) or not pred.is_floating_point():
+            raise TypeError(f"{name}: term {k}: pred must be a floating-point tensor")
+        const = not torch.is_tensor(target)
+        if not const and tuple(target.shape) != tuple(pred.shape):
+            raise ValueError(f"{name}: term {k}: target {tuple(target.shape)} does not match pred {tuple(pred.shape)}")
+        if not const and target.requires_grad:
+            raise ValueError(f"{name}: term {k}: there is no gradient with respect to target")
+        if mask is not None and tuple(mask.shape) != tuple(pred.shape):
+            raise ValueError(f"{name}: term {k}: mask {tuple(mask.shape)} does not match pred {tuple(pred.shape)}")
+        if mask is None and side != "set":
+            raise ValueError(f"{name}: term {k}: side {side!r} needs a mask")
+        if pred.numel() < 1:
+            raise ValueError(f"{name}: term {k}: pred is empty")
+        if not (pred.is_cuda and (const or target.is_cuda) and (mask is None or mask.is_cuda)):
+            raise _capi.VampireHipError(f"{name} needs device tensors (no CPU fallback)")
+        if pred.dtype not in (torch.float32, torch.bfloat16):
+            pred = pred.float()
+        preds.append(pred.contiguous())
+        targets.append(None if const else target.detach().to(torch.float32).contiguous())
+        masks.append(None if mask is None else (mask if mask.dtype == torch.bool else mask != 0).contiguous())
+        m = d.terms[k]
+        m.n, m.kind, m.side, m.pred_dtype = pred.numel(), _REG_KINDS[kind], _REG_SIDES[side], DTYPE_CODES[pred.dtype]
+        m.target_is_const, m.target_value = int(const), float(target) if const else 0.0
+    vamp = _capi.checked()
+    nbytes = vamp.vamp_reg_loss_workspace_bytes(d)
+    if nbytes == 0:
+        raise ValueError(f"{name}: {vamp.vamp_last_error().decode('utf-8', 'replace')}")
+    return (d, nbytes, targets, masks), preds
+
+
+def reg_losses(terms):
+    """The masked regression losses of base_exp.py:523-537 and :581-594 on the device (vamp_reg_loss_*): a pack of 1
+    to 8 RegTerm evaluated in two launches, and the gradients of the whole pack in one, through autograd -- the mean
+    smooth-L1 (beta 1) or squared error of pred against target over the elements the mask sets, clears, or the sum of
+    both means, as F.smooth_l1_loss(pred[mask], target[mask]) and ((pred[mask] - target[mask]) ** 2).mean() give them,
+    without the boolean-mask compaction, so without a host synchronisation; no atomics, bitwise repeatable, capturable
+    in a graph.  pred is read in place when it is contiguous fp32 or bf16 (fp16 / fp64 are cast to fp32, other strides
+    copied); target is cast to fp32; a mask that is not bool is taken as `!= 0`.  The one difference from the torch
+    expressions: the mean over an empty selection is exactly 0, not NaN.  Returns the fp32 [T] losses; the attribute
+    `counts` is the detached int64 [T, 2] tensor of (elements set, elements clear).  The gradient goes to the preds
+    that require one (an element outside the selected side gets exactly 0), in pred's dtype; none goes to a target.
+    The MultiTaskLoss of multitask.py does not use it yet."""
+    call, preds = _reg_inputs(terms)
+    losses, counts = _RegLosses.apply(call, *preds)
+    losses.counts = counts
+    return losses
+
+
+def reg_loss(pred, target, mask=None, kind="smooth_l1", side="set"):
+    """ops.reg_losses for one term: the 0-dim fp32 loss, `counts` int64 [2]."""
+    call, preds = _reg_inputs([RegTerm(pred, target, mask, kind, side)], "reg_loss")
+    losses, counts = _RegLosses.apply(call, *preds)
+    loss = losses[0]
+    loss.counts = counts[0]
     return loss

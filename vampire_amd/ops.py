@@ -26,7 +26,7 @@ from .layers import (voxel_pooling, upsample_trilinear, conv3d_3x3x3, conv3d_bf1
                      conv3d_bf16_supported)
 from .evaluation import (confusion_update, lidarseg_predict, det_postprocess, det_targets, det_loss,  # noqa: F401
                          DetResult, DetTargets)
-from .losses import rgb_loss, seg_loss  # noqa: F401
+from .losses import REG_MAX_TERMS, REG_TILE, RegTerm, reg_loss, reg_losses, rgb_loss, seg_loss  # noqa: F401
 
 
 # det-grid heights the BEV kernels take: their z taps and weights live in fixed LDS tables (kBevMaxOZ, render_bev_dev.hpp)
