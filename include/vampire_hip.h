@@ -27,10 +27,10 @@
 extern "C" {
 #endif
 
-#define VAMP_ABI_VERSION 14  /* bumped whenever entry points or flags are added (round 2: 2, round 3: 3, round 4: 4, round 5: 5, round 6: 6;
+#define VAMP_ABI_VERSION 15  /* bumped whenever entry points or flags are added (round 2: 2, round 3: 3, round 4: 4, round 5: 5, round 6: 6;
                                  7: segmentation metrics; 8: detection post-processing; 9: detection targets;
                                  10: the BEV backward's plan; 11: detection loss; 12: rgb loss; 13: segmentation loss;
-                                 14: masked regression losses) */
+                                 14: masked regression losses; 15: the camera render's plans and workspace layout) */
 
 enum {
   VAMP_OK = 0,
@@ -428,6 +428,86 @@ int vamp_render_camera_backward_acc(const VampRenderDesc* d, const float* geom, 
                                     float* grad_semantic, float* grad_rgb, float* grad_beta,
                                     void* workspace, size_t workspace_bytes, int flags,
                                     void* wait_event, void* stream);
+
+/*
+ * What vamp_render_camera_forward_ex(d, geom, .., workspace_bytes, flags, ..) and vamp_render_camera_backward_acc(d,
+ * geom, mats, .., workspace_bytes, flags, wait_event, ..) will launch (ABI 15): every choice the calls make from the
+ * descriptor, from which of geom / mats they are given, from the flags and from the workspace size, as numbers.  Pure
+ * host functions -- no HIP call, no GPU -- and the very functions the two entry points ask, behind their pointer checks,
+ * before the first launch.  workspace_bytes is the size of a workspace that is there: a NULL workspace counts as 0.
+ * They return VAMP_OK, or the code (and vamp_last_error message) with which the entry point refuses the same arguments:
+ * VAMP_ENOSPC below bytes_needed; for the backward also CELLS_VALID with early termination but no TERM_VALID, a sample /
+ * voxel / cell count beyond 2^31 where the prepare pass runs inside the call, too many depth samples for the per-ray
+ * pass's LDS staging, too many x-runs for the gather, and ACCUMULATE / wait_event on the float-atomic splat.
+ * Fields a path does not use are 0.
+ */
+enum { VAMP_CAMPLAN_FWD_DIRECT = 0,    /* cam_fwd_direct_kernel: one kernel on the channel-first volumes */
+       VAMP_CAMPLAN_FWD_PLANNED = 1,   /* render_cam_fwd_plan_kernel on the channel-last copy */
+       VAMP_CAMPLAN_FWD_MARCH = 2 };   /* render_cam_fwd_kernel: a geom tensor, or more than 128 samples per ray */
+enum { VAMP_CAMPLAN_TERM_NONE = 0,     /* the call does not touch the termination table */
+       VAMP_CAMPLAN_TERM_BUILD = 1,    /* cam_term_kernel runs first */
+       VAMP_CAMPLAN_TERM_CHECK = 2,    /* *_TERM_VALID: read as it is (verified under vamp_debug_checks) */
+       VAMP_CAMPLAN_TERM_WRITE = 3 };  /* a by-product of the one-kernel forward: the workspace can hold it */
+enum { VAMP_CAMPLAN_BWD_CELL = 0,      /* per-ray pass + heavy cells + per-voxel gather */
+       VAMP_CAMPLAN_BWD_SPLAT = 1 };   /* the v1 float-atomic splat: a geom tensor, no mats, or VAMP_CAMBWD_SPLAT */
+typedef struct VampCameraForwardPlan {
+  int64_t bytes_needed;        /* VAMP_ENOSPC below this (0: the workspace may be NULL) */
+  int32_t path;                /* VAMP_CAMPLAN_FWD_* */
+  int32_t ert;                 /* rays stop at their termination index */
+  int32_t term;                /* VAMP_CAMPLAN_TERM_* */
+  int32_t pack;                /* pack_volume_kernel runs (the channel-last copy) */
+  int32_t pack_only;           /* ... and is the last launch of the call (VAMP_CAMFWD_PACK_ONLY) */
+  int32_t save_rows;           /* the sample rows are kept behind the base region */
+  int32_t body;                /* the compiled body: NCH of the one kernel, CP / 4 of the marches (0 with pack_only) */
+  int32_t grid;                /* its workgroups (0 with pack_only) */
+  int32_t reserved[6];         /* 0 */
+} VampCameraForwardPlan;
+int vamp_render_camera_forward_plan(const VampRenderDesc* d, int has_geom, int flags, size_t workspace_bytes,
+                                    VampCameraForwardPlan* out);
+typedef struct VampCameraBackwardPlan {
+  int64_t bytes_needed;        /* VAMP_ENOSPC below this */
+  int64_t ray_lds;             /* dynamic LDS bytes of cam_bwd_ray_kernel */
+  int32_t path;                /* VAMP_CAMPLAN_BWD_* */
+  int32_t pack;                /* pack_volume_kernel runs first (SPLAT without PACKED_VALID) */
+  int32_t parts;               /* 1: per-ray pass, 2: gather, 4: heavy cells (all of them: 7; SPLAT: 0) */
+  int32_t term;                /* VAMP_CAMPLAN_TERM_NONE / _BUILD / _CHECK (per-ray part only) */
+  int32_t samples;             /* the per-ray pass reads the forward's sample rows (SAMPLES_VALID) */
+  int32_t prepare;             /* the prepare pass (rank + scan) runs inside the call: no CELLS_VALID */
+  int32_t ray_cp4, ray_kt;     /* cam_bwd_ray_kernel<T, 4, CP4, KT> */
+  int32_t raise_lds;           /* the dynamic-LDS limit is raised first (ray_lds above 64 KB) */
+  int32_t ray_grid;            /* ray tiles of the per-ray launch (also: the d beta partials it leaves) ... */
+  int32_t list_grid;           /* ... and the list-building workgroups behind them */
+  int32_t heavy_grid;          /* cam_cell_splat_kernel */
+  int32_t heavy_waves;         /* waves per workgroup of it */
+  int32_t gather_grid;         /* cam_bwd_cell_gather_kernel */
+  int32_t accumulate;          /* the gather adds (and visits the listed x-runs only) */
+  int32_t beta_tail;           /* the gather's first workgroup adds up the d beta partials (sdf density) */
+  int32_t splat_grid;          /* SPLAT: render_cam_bwd_kernel */
+  int32_t unpack_grid;         /* SPLAT: unpack_grad_kernel */
+  int32_t reserved[6];         /* 0 */
+} VampCameraBackwardPlan;
+int vamp_render_camera_backward_plan(const VampRenderDesc* d, int has_geom, int has_mats, int flags,
+                                     int has_wait_event, size_t workspace_bytes, VampCameraBackwardPlan* out);
+
+/*
+ * The render workspace, region by region (ABI 15): byte offset and size of
+ *   packed | grad (the v1 splat's gradient copy; it OVERLAYS gcl .. beta_part) | gcl | cnt | off | bsum | boff | aux |
+ *   hcells | part | runs | rank | slot | tile_se | tile_order | records | beta_part | term | rows
+ * in that order (VAMP_RENDERWS_*).  Every region is 256-byte aligned; behind `packed` lies the larger of `grad` and
+ * gcl .. beta_part, then the termination table (vamp_render_term_offset), then -- past vamp_render_workspace_bytes -- the
+ * sample rows (vamp_render_samples_bytes).
+ */
+enum { VAMP_RENDERWS_PACKED = 0, VAMP_RENDERWS_GRAD, VAMP_RENDERWS_GCL, VAMP_RENDERWS_CNT, VAMP_RENDERWS_OFF,
+       VAMP_RENDERWS_BSUM, VAMP_RENDERWS_BOFF, VAMP_RENDERWS_AUX, VAMP_RENDERWS_HCELLS, VAMP_RENDERWS_PART,
+       VAMP_RENDERWS_RUNS, VAMP_RENDERWS_RANK, VAMP_RENDERWS_SLOT, VAMP_RENDERWS_TILE_SE, VAMP_RENDERWS_TILE_ORDER,
+       VAMP_RENDERWS_RECORDS, VAMP_RENDERWS_BETA_PART, VAMP_RENDERWS_TERM, VAMP_RENDERWS_ROWS, VAMP_RENDERWS_REGIONS };
+typedef struct VampRenderWorkspaceLayout {
+  int64_t offset[VAMP_RENDERWS_REGIONS];
+  int64_t bytes[VAMP_RENDERWS_REGIONS];
+  int64_t base_bytes;          /* = vamp_render_workspace_bytes(d) */
+  int64_t bytes_with_rows;     /* = base_bytes + vamp_render_samples_bytes(d) */
+} VampRenderWorkspaceLayout;
+int vamp_render_workspace_layout(const VampRenderDesc* d, VampRenderWorkspaceLayout* out);
 
 /*
  * BEV (top-down) branch, forward (bv2:408-418, 442-461).

@@ -42,6 +42,9 @@ def test_struct_layout_matches_header(lib):
     assert C.sizeof(_capi.VampSampleDesc) == 22 * 4
     assert C.sizeof(_capi.VampConvDesc) == 6 * 4
     assert C.sizeof(_capi.VampBevBackwardPlan) == 40 * 4
+    assert C.sizeof(_capi.VampCameraForwardPlan) == 16 * 4
+    assert C.sizeof(_capi.VampCameraBackwardPlan) == 28 * 4
+    assert C.sizeof(_capi.VampRenderWorkspaceLayout) == (2 * 19 + 2) * 8
 
 
 def test_bad_descriptor_is_rejected_without_gpu(lib):

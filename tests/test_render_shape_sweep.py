@@ -7,8 +7,9 @@ density volume turned into the "empty" regime (as tests/test_deep_tiles.py does)
 samples share tiles with rays that run to the last depth index.
 
 Bars are relative to the largest magnitude of the reference tensor and were set from the measured errors (at most ten
-times the largest error seen over the sweep, never above the 1e-4 of the north star).  The CPU tests at the end map the
-sweep's parameter lists through mirrors of the launchers' dispatch and fail if a compiled body is reached by no case.
+times the largest error seen over the sweep, never above the 1e-4 of the north star).  The CPU tests at the end hold the
+render workspace's layout to the numbers of the commit before it had one definition, compare the library's camera plans
+with Python mirrors, and fail if a compiled body is reached by no case.
 The GPU tests of this file take about 4 s on an MI355X (the float64 oracle on the CPU included)."""
 import ctypes as C
 import dataclasses
@@ -104,7 +105,7 @@ def channel_pack(K):
 
 
 def ray_body(K):
-    """render_bwd_ray.hip: the per-ray backward's (CP / 4, KT) instance."""
+    """render_bwd.hip: camera_backward_plan -- the per-ray backward's (CP / 4, KT) instance."""
     cp = channel_pack(K)
     return (cp // 4, 18 if (cp == 24 and K == 18) else 0)
 
@@ -455,25 +456,384 @@ def test_lift_depth_sweep_against_float64_oracle(dev, D, entry):
     assert not bad, f"D={D} {entry}:\n" + "\n".join(bad)
 
 
+# ---------------------------------------------------------------------------------------------------- CPU: layout, plans
+def case_desc(case, bf16=None):
+    """The render descriptor of a sweep case as the GPU tests build it (B = 2); host only."""
+    from vampire_amd.ops import render_desc
+    cfg = case.cfg
+    return render_desc(cfg, 2, cfg.num_cams, _capi.VAMP_BF16 if (case.bf16 if bf16 is None else bf16) else _capi.VAMP_F32)
+
+
+@functools.lru_cache(maxsize=None)
+def library():
+    from vampire_amd.build import build_library
+    build_library(verbose=False)
+    return _capi.load()
+
+
+def ws_layout(d):
+    """vamp_render_workspace_layout: ({region: (offset, bytes)} in layout order, base_bytes, bytes_with_rows)."""
+    out = _capi.VampRenderWorkspaceLayout()
+    assert library().vamp_render_workspace_layout(C.byref(d), C.byref(out)) == 0
+    return ({n: (out.offset[i], out.bytes[i]) for i, n in enumerate(_capi.RENDERWS_REGIONS)}, out.base_bytes,
+            out.bytes_with_rows)
+
+
+# (vamp_render_workspace_bytes, vamp_render_term_offset, vamp_render_samples_bytes) of the commit before the layout
+# became cam_workspace() (2326e0f, built and asked on the CPU; f32 and bf16 descriptors give the same numbers): the
+# sweep's cases at B = 2 and the presets A, B, D at batch 1 and 8.  The layout was moved, not changed.
+PARENT_LAYOUT = {
+    "S1": (414208, 405760, 110592),
+    "S2": (526592, 518144, 221184),
+    "S3": (638976, 630528, 331776),
+    "S4": (751360, 742912, 442368),
+    "S5": (863744, 855296, 552960),
+    "S63": (7383808, 7375360, 6967296),
+    "S64": (7496192, 7487744, 7077888),
+    "S65": (7608832, 7600384, 7188480),
+    "S127": (14578432, 14569984, 14045184),
+    "S128": (14690816, 14682368, 14155776),
+    "S129": (14803456, 14795008, 14266368),
+    "S160": (18288128, 18279680, 17694720),
+    "S160-K18": (22568192, 22559744, 35389440),
+    "S160-K28": (25421568, 25413120, 47185920),
+    "K1-plain": (2550016, 2541568, 2211840),
+    "K1-catseg": (2550016, 2541568, 2211840),
+    "K5-plain": (2550016, 2541568, 2211840),
+    "K5-catseg": (2550016, 2541568, 2211840),
+    "K6-plain": (2550016, 2541568, 2211840),
+    "K6-catseg": (2550016, 2541568, 2211840),
+    "K9-plain": (3281920, 3273472, 4423680),
+    "K9-catseg": (3281920, 3273472, 4423680),
+    "K17-plain": (3281920, 3273472, 4423680),
+    "K17-catseg": (3281920, 3273472, 4423680),
+    "K18-plain": (3281920, 3273472, 4423680),
+    "K18-catseg": (3281920, 3273472, 4423680),
+    "K20-plain": (3281920, 3273472, 4423680),
+    "K20-catseg": (3281920, 3273472, 4423680),
+    "K21-plain": (3769856, 3761408, 5898240),
+    "K21-catseg": (3769856, 3761408, 5898240),
+    "K25-plain": (3769856, 3761408, 5898240),
+    "K25-catseg": (3769856, 3761408, 5898240),
+    "K28-plain": (3769856, 3761408, 5898240),
+    "K28-catseg": (3769856, 3761408, 5898240),
+    "C1": (2550016, 2541568, 2211840),
+    "C4": (2550016, 2541568, 2211840),
+    "C33": (2550016, 2541568, 2211840),
+    "C64": (2550016, 2541568, 2211840),
+    "C0-catseg": (2550016, 2541568, 2211840),
+    "ragged-36x100": (3719424, 3708416, 5898240),
+    "bf16-K5": (2550016, 2541568, 2211840),
+    "bf16-K9": (3281920, 3273472, 4423680),
+    "bf16-K18": (3281920, 3273472, 4423680),
+    "bf16-K20": (3281920, 3273472, 4423680),
+    "bf16-K28": (3769856, 3761408, 5898240),
+    "A-b1": (522648320, 522377984, 551485440),
+    "A-b8": (4181004800, 4178842112, 4411883520),
+    "B-b1": (446974464, 446704128, 551485440),
+    "B-b8": (3575611648, 3573448960, 4411883520),
+    "D-b1": (2074865664, 2073784320, 2205941760),
+    "D-b8": (16598680320, 16590029568, 17647534080),
+}
+
+
+def layout_descs():
+    from vampire_amd.config import PRESETS
+    from vampire_amd.ops import render_desc
+    for bf16 in (False, True):
+        dt = _capi.VAMP_BF16 if bf16 else _capi.VAMP_F32
+        for c in CASES:
+            yield c.name, case_desc(c, bf16)
+        for preset in "ABD":
+            for B in (1, 8):
+                yield f"{preset}-b{B}", render_desc(PRESETS[preset], B, PRESETS[preset].num_cams, dt)
+
+
+def test_workspace_layout_is_the_parents():
+    """The three byte queries answer what the parent commit answered, and the regions behind them are in order,
+    256-byte aligned and disjoint (the v1 gradient copy overlays Gcl .. beta_part by design) and add up to the totals."""
+    lib = library()
+    n = 0
+    for name, d in layout_descs():
+        got = (lib.vamp_render_workspace_bytes(C.byref(d)), lib.vamp_render_term_offset(C.byref(d)),
+               lib.vamp_render_samples_bytes(C.byref(d)))
+        assert got == PARENT_LAYOUT[name], (name, got, PARENT_LAYOUT[name])
+        regions, base_bytes, with_rows = ws_layout(d)
+        assert list(regions) == list(_capi.RENDERWS_REGIONS)
+        assert all(off % 256 == 0 and nb % 256 == 0 and nb > 0 for off, nb in regions.values()), (name, regions)
+        at = 0
+        for r in _capi.RENDERWS_REGIONS:                      # back to back, but for the overlay and the slack behind it
+            off, nb = regions[r]
+            if r == "grad":
+                assert off == regions["packed"][1] and nb == regions["packed"][1], (name, regions)
+                continue
+            if r == "term":
+                at = max(at, sum(regions["grad"]))
+            assert off == at, (name, r, off, at)
+            at += nb
+        assert sum(regions["term"]) == base_bytes == got[0] and regions["term"][0] == got[1], (name, regions)
+        assert regions["rows"] == (base_bytes, got[2]) and with_rows == base_bytes + got[2], (name, regions)
+        n += 1
+    assert n == 2 * len(PARENT_LAYOUT)
+    assert lib.vamp_render_workspace_layout(None, C.byref(_capi.VampRenderWorkspaceLayout())) == -1
+    assert lib.vamp_render_workspace_layout(C.byref(case_desc(Case("tiny"))), None) == -1
+
+
+SCAN_TILE, RUN_VOX, GATHER_GRID, SPLAT_NW = 2048, 32, 20480, 2     # common.hpp, render_common.hpp, cam_lists.hpp
+FWD_FIELDS = [n for n, _ in _capi.VampCameraForwardPlan._fields_]
+BWD_FIELDS = [n for n, _ in _capi.VampCameraBackwardPlan._fields_]
+ENOSPC, EINVAL = -2, -1
+ERR_CELLS = "requirement failed: CELLS_VALID with early termination needs TERM_VALID"
+ERR_COUNT = "requirement failed: sample / voxel / cell count exceeds 2^31"
+ERR_LDS = "too many depth samples for the LDS staging"
+ERR_RUNS = "requirement failed: too many x-runs"
+ERR_SPLAT = "requirement failed: accumulate / wait_event need the cell-list path"
+
+
+def shape_numbers(d):
+    """What both plans take from the descriptor alone."""
+    tiles = d.B * d.N * ((d.fH + 7) // 8) * ((d.fW + 7) // 8)
+    ncell = d.B * (d.Z + 1) * (d.Y + 1) * (d.X + 1) + 2
+    ncell = (ncell + SCAN_TILE - 1) // SCAN_TILE * SCAN_TILE
+    runs = ((d.X + RUN_VOX - 1) // RUN_VOX) * d.Y * d.Z * d.B
+    regions, base_bytes, with_rows = ws_layout(d)
+    return dict(S=d.D - 1, K=d.K, cp=channel_pack(d.K), ray_grid=(tiles + 7) // 8 * 8, ncell=ncell, runs=runs,
+                rays=d.B * d.N * d.fH * d.fW, voxels=d.B * d.Z * d.Y * d.X, sdf=d.density_mode == _capi.VAMP_DENSITY_SDF_LAPLACE,
+                packed=regions["packed"][1], base=base_bytes, rows=with_rows)
+
+
+def fwd_plan(n, has_geom, flags, ws_bytes):
+    """render_fwd.hip: camera_forward_plan -- the fields of VampCameraForwardPlan, or (code, message tail)."""
+    A = _capi
+    p = dict.fromkeys(FWD_FIELDS, 0)
+    plan = not has_geom and planned(n["S"])
+    p["save_rows"] = int(bool(flags & A.VAMP_CAMFWD_SAVE_SAMPLES) and plan)
+    p["ert"] = int(plan and not flags & A.VAMP_CAMFWD_NO_ERT)
+    p["grid"] = n["ray_grid"]
+    if flags & A.VAMP_CAMFWD_DIRECT and plan:
+        p.update(path=A.VAMP_CAMPLAN_FWD_DIRECT, bytes_needed=n["rows"] if p["save_rows"] else 0,
+                 term=A.VAMP_CAMPLAN_TERM_WRITE if ws_bytes >= n["base"] else A.VAMP_CAMPLAN_TERM_NONE,
+                 body=cam_direct_nch(n["K"]))
+    else:
+        p.update(path=A.VAMP_CAMPLAN_FWD_PLANNED if plan else A.VAMP_CAMPLAN_FWD_MARCH,
+                 bytes_needed=n["rows"] if p["save_rows"] else (n["base"] if p["ert"] else n["packed"]),
+                 term=A.VAMP_CAMPLAN_TERM_NONE if not p["ert"] else
+                 (A.VAMP_CAMPLAN_TERM_CHECK if flags & A.VAMP_CAMFWD_TERM_VALID else A.VAMP_CAMPLAN_TERM_BUILD),
+                 pack=int(not flags & A.VAMP_CAMFWD_PACKED_VALID), pack_only=int(bool(flags & A.VAMP_CAMFWD_PACK_ONLY)),
+                 body=n["cp"] // 4)
+        if p["pack_only"]:
+            p["body"] = p["grid"] = 0
+    if ws_bytes < p["bytes_needed"]:
+        return ENOSPC, f": workspace {ws_bytes} < {p['bytes_needed']} bytes"
+    return p
+
+
+def bwd_plan(n, has_geom, has_mats, flags, has_wait, ws_bytes):
+    """render_bwd.hip: camera_backward_plan -- the fields of VampCameraBackwardPlan, or (code, message tail): the
+    refusals in the order the library makes them."""
+    A = _capi
+    p = dict.fromkeys(BWD_FIELDS, 0)
+    p["bytes_needed"] = n["base"]
+    if ws_bytes < n["base"]:
+        return ENOSPC, f": workspace {ws_bytes} < {n['base']} bytes"
+    p["accumulate"] = int(bool(flags & A.VAMP_CAMBWD_ACCUMULATE))
+    part_ray = not flags & (A.VAMP_CAMBWD_PART_GATHER | A.VAMP_CAMBWD_PART_HEAVY) or bool(flags & A.VAMP_CAMBWD_PART_RAY)
+    if has_geom or not has_mats or flags & A.VAMP_CAMBWD_SPLAT:
+        if p["accumulate"] or has_wait:
+            return EINVAL, ERR_SPLAT
+        p.update(path=A.VAMP_CAMPLAN_BWD_SPLAT, pack=int(not flags & A.VAMP_CAMBWD_PACKED_VALID and part_ray),
+                 splat_grid=(n["rays"] + 255) // 256, unpack_grid=(n["voxels"] + 255) // 256)
+        return p
+    parts = ((1 if flags & A.VAMP_CAMBWD_PART_RAY else 0) | (2 if flags & A.VAMP_CAMBWD_PART_GATHER else 0)
+             | (4 if flags & A.VAMP_CAMBWD_PART_HEAVY else 0)) or 7
+    p.update(path=A.VAMP_CAMPLAN_BWD_CELL, parts=parts)
+    if flags & A.VAMP_CAMBWD_SAMPLES_VALID:
+        p["bytes_needed"] = n["rows"]
+        if ws_bytes < n["rows"]:
+            return ENOSPC, f": workspace {ws_bytes} has no room for the sample rows"
+    p["beta_tail"] = int(n["sdf"] and bool(parts & 2))
+    if part_ray:
+        p["samples"] = int(bool(flags & A.VAMP_CAMBWD_SAMPLES_VALID))
+        p["prepare"] = int(not flags & A.VAMP_CAMBWD_CELLS_VALID)
+        if not flags & A.VAMP_CAMBWD_NO_ERT:
+            p["term"] = A.VAMP_CAMPLAN_TERM_CHECK if flags & A.VAMP_CAMBWD_TERM_VALID else A.VAMP_CAMPLAN_TERM_BUILD
+            if p["term"] == A.VAMP_CAMPLAN_TERM_BUILD and not p["prepare"]:
+                return EINVAL, ERR_CELLS
+        if p["prepare"] and not (0 < n["rays"] * n["S"] < 2 ** 31 - 1 and n["voxels"] < 2 ** 31 - 1 and n["ncell"] < 2 ** 31 - 1):
+            return EINVAL, ERR_COUNT
+        p["ray_cp4"], p["ray_kt"] = ray_body(n["K"])
+        p["ray_lds"] = 3 * ((n["S"] + 3) // 4) * 256 * 4
+        if p["ray_lds"] > 150 * 1024:
+            return EINVAL, ERR_LDS
+        p["raise_lds"] = int(p["ray_lds"] > 64 * 1024)
+        p["ray_grid"] = n["ray_grid"]
+        p["list_grid"] = n["ncell"] // SCAN_TILE + (n["runs"] + 255) // 256
+    elif p["beta_tail"]:
+        p["ray_grid"] = n["ray_grid"]
+    if parts & 6:
+        if n["runs"] >= 2 ** 31 - 1:
+            return EINVAL, ERR_RUNS
+        if parts & 4:
+            p.update(heavy_grid=min(n["ncell"], 4096), heavy_waves={12: 2, 24: SPLAT_NW, 32: 4}[n["cp"]])
+        if parts & 2:
+            p["gather_grid"] = min(n["runs"], GATHER_GRID)
+    return p
+
+
+def ask(fn, struct, *args):
+    """A plan entry point's answer in the mirrors' form: the struct, or (code, whole message)."""
+    out = struct()
+    rc = fn(*args, C.byref(out))
+    return out if rc == 0 else (rc, library().vamp_last_error().decode())
+
+
+def same_plan(got, want, struct, what):
+    """The library's answer `got` is the mirror's `want`: every field, or the refusal's code and message tail."""
+    if isinstance(want, tuple):
+        assert isinstance(got, tuple) and got[0] == want[0] and got[1].endswith(want[1]), (what, got, want)
+        return
+    assert not isinstance(got, tuple), (what, got, want)
+    if bytes(got) != bytes(struct(**{k: v for k, v in want.items() if k != "reserved"})):
+        diff = {k: (getattr(got, k), v) for k, v in want.items() if k != "reserved" and getattr(got, k) != v}
+        assert not diff and list(got.reserved) == [0] * 6, (what, diff)
+
+
+def subsets(bits):
+    return [sum(b for i, b in enumerate(bits) if m >> i & 1) for m in range(1 << len(bits))]
+
+
+def test_camera_plans_are_the_mirrors():
+    """vamp_render_camera_forward_plan and vamp_render_camera_backward_plan -- the functions the two entry points ask
+    before their first launch -- answer what the mirrors predict, field by field and refusal by refusal: every case x
+    geom / mats x every combination of the flags x a workspace one byte below and exactly at each size that matters."""
+    lib, A = library(), _capi
+    fwd_flags = subsets([A.VAMP_CAMFWD_NO_ERT, A.VAMP_CAMFWD_TERM_VALID, A.VAMP_CAMFWD_PACK_ONLY,
+                         A.VAMP_CAMFWD_PACKED_VALID, A.VAMP_CAMFWD_DIRECT, A.VAMP_CAMFWD_SAVE_SAMPLES])
+    bwd_flags = subsets([A.VAMP_CAMBWD_ACCUMULATE, A.VAMP_CAMBWD_PACKED_VALID, A.VAMP_CAMBWD_CELLS_VALID,
+                         A.VAMP_CAMBWD_SPLAT, A.VAMP_CAMBWD_SAMPLES_VALID, A.VAMP_CAMBWD_TERM_VALID,
+                         A.VAMP_CAMBWD_NO_ERT, A.VAMP_CAMBWD_PART_RAY, A.VAMP_CAMBWD_PART_GATHER,
+                         A.VAMP_CAMBWD_PART_HEAVY])
+    assert len(fwd_flags) == 64 and len(bwd_flags) == 1024
+    seen = {k: set() for k in ("fwd path", "fwd term", "fwd body", "bwd path", "bwd term", "raise_lds", "refusal")}
+    for case in CASES:
+        d = case_desc(case)
+        n = shape_numbers(d)
+        ref = C.byref(d)
+        for has_geom in (0, 1):
+            for ws in (0, n["packed"] - 1, n["packed"], n["base"] - 1, n["base"], n["rows"] - 1, n["rows"]):
+                for f in fwd_flags:
+                    got = ask(lib.vamp_render_camera_forward_plan, A.VampCameraForwardPlan, ref, has_geom, f, ws)
+                    want = fwd_plan(n, has_geom, f, ws)
+                    same_plan(got, want, A.VampCameraForwardPlan, (case.name, has_geom, f, ws))
+                    if isinstance(want, dict):
+                        seen["fwd path"].add(want["path"]), seen["fwd term"].add(want["term"])
+                        seen["fwd body"].add((want["path"], want["body"]))
+        for has_geom, has_mats in ((0, 1), (1, 0), (1, 1)):
+            for ws in (n["base"] - 1, n["base"], n["rows"] - 1, n["rows"]):
+                for f in bwd_flags:
+                    got = ask(lib.vamp_render_camera_backward_plan, A.VampCameraBackwardPlan, ref, has_geom, has_mats, f, 0, ws)
+                    want = bwd_plan(n, has_geom, has_mats, f, 0, ws)
+                    same_plan(got, want, A.VampCameraBackwardPlan, (case.name, has_geom, has_mats, f, ws))
+                    if isinstance(want, dict):
+                        seen["bwd path"].add(want["path"]), seen["bwd term"].add(want["term"])
+                        seen["raise_lds"].add(want["raise_lds"])
+                    else:
+                        seen["refusal"].add(want[1] if want[0] == EINVAL else "ENOSPC")
+        # wait_event: refused on the splat with or without ACCUMULATE, nothing to the cell path's plan
+        for f in (0, A.VAMP_CAMBWD_ACCUMULATE, A.VAMP_CAMBWD_SPLAT, A.VAMP_CAMBWD_SPLAT | A.VAMP_CAMBWD_ACCUMULATE):
+            for has_geom in (0, 1):
+                got = ask(lib.vamp_render_camera_backward_plan, A.VampCameraBackwardPlan, ref, has_geom, 1, f, 1, n["rows"])
+                same_plan(got, bwd_plan(n, has_geom, 1, f, 1, n["rows"]), A.VampCameraBackwardPlan, (case.name, has_geom, f))
+    assert seen["fwd path"] == {0, 1, 2} and seen["fwd term"] == {0, 1, 2, 3} and seen["bwd path"] == {0, 1}
+    assert seen["bwd term"] == {0, 1, 2} and seen["raise_lds"] == {0, 1}
+    assert seen["refusal"] == {"ENOSPC", ERR_CELLS, ERR_SPLAT}, seen["refusal"]
+
+
+def test_camera_plan_refusals():
+    """Each refusal of the two plans by code and message -- on descriptors no sweep case reaches: more than 2^31
+    samples, more than 200 depth samples, more x-runs than a grid index -- and a NULL descriptor or plan."""
+    lib, A = library(), _capi
+    huge = 1 << 62
+
+    def bwd(d, flags=0, geom=0, wait=0, ws=huge):
+        return ask(lib.vamp_render_camera_backward_plan, A.VampCameraBackwardPlan, C.byref(d), geom, 1, flags, wait, ws)
+
+    def refused(got, code, tail):
+        assert isinstance(got, tuple) and got[0] == code and got[1].endswith(tail), (got, code, tail)
+
+    tiny = case_desc(Case("tiny"))
+    n = shape_numbers(tiny)
+    refused(bwd(tiny, ws=n["base"] - 1), ENOSPC, f"vamp_render_camera_backward_plan: workspace {n['base'] - 1} < {n['base']} bytes")
+    refused(bwd(tiny, A.VAMP_CAMBWD_SAMPLES_VALID, ws=n["rows"] - 1), ENOSPC,
+            f"workspace {n['rows'] - 1} has no room for the sample rows")
+    refused(bwd(tiny, A.VAMP_CAMBWD_CELLS_VALID), EINVAL, ERR_CELLS)
+    assert not isinstance(bwd(tiny, A.VAMP_CAMBWD_CELLS_VALID | A.VAMP_CAMBWD_PART_GATHER), tuple)   # (no per-ray part)
+    refused(bwd(tiny, A.VAMP_CAMBWD_ACCUMULATE, geom=1), EINVAL, ERR_SPLAT)
+    refused(bwd(tiny, A.VAMP_CAMBWD_SPLAT, wait=1), EINVAL, ERR_SPLAT)
+    many = case_desc(Case("tiny"))
+    many.B, many.fH, many.fW = 6, 2000, 2000                    # 2.9e9 samples
+    refused(bwd(many), EINVAL, ERR_COUNT)
+    same_plan(bwd(many), bwd_plan(shape_numbers(many), 0, 1, 0, 0, huge), A.VampCameraBackwardPlan, "many")
+    cells_valid = A.VAMP_CAMBWD_CELLS_VALID | A.VAMP_CAMBWD_TERM_VALID
+    assert not isinstance(bwd(many, cells_valid), tuple)        # (the prepare pass's limit, where it does not run)
+    deep = case_desc(Case("tiny"))
+    deep.D = 202
+    refused(bwd(deep), EINVAL, ERR_LDS)
+    deep.D = 201
+    assert bwd(deep).ray_lds == 150 * 1024 and bwd(deep).raise_lds == 1
+    wide = case_desc(Case("tiny"))
+    wide.B, wide.Z, wide.Y, wide.X = 33, 510, 2046, 2046        # 2.2e9 x-runs
+    refused(bwd(wide, cells_valid), EINVAL, ERR_RUNS)
+    refused(bwd(wide, A.VAMP_CAMBWD_PART_HEAVY), EINVAL, ERR_RUNS)
+    refused(bwd(wide), EINVAL, ERR_COUNT)                       # (the earlier refusal of a whole call)
+    assert not isinstance(bwd(wide, cells_valid | A.VAMP_CAMBWD_PART_RAY), tuple)
+    for d_, name in ((many, "many"), (deep, "deep"), (wide, "wide")):
+        nn = shape_numbers(d_)
+        for f in (0, cells_valid, A.VAMP_CAMBWD_PART_HEAVY, cells_valid | A.VAMP_CAMBWD_PART_RAY, A.VAMP_CAMBWD_SPLAT):
+            same_plan(bwd(d_, f), bwd_plan(nn, 0, 1, f, 0, huge), A.VampCameraBackwardPlan, (name, f))
+    fwd = ask(lib.vamp_render_camera_forward_plan, A.VampCameraForwardPlan, C.byref(tiny), 0, A.VAMP_CAMFWD_SAVE_SAMPLES, n["rows"] - 1)
+    refused(fwd, ENOSPC, f"vamp_render_camera_forward_plan: workspace {n['rows'] - 1} < {n['rows']} bytes")
+    # a NULL descriptor or plan is refused, not read
+    assert lib.vamp_render_camera_forward_plan(None, 0, 0, 0, C.byref(A.VampCameraForwardPlan())) == EINVAL
+    assert lib.vamp_last_error().decode().endswith("desc is NULL")
+    assert lib.vamp_render_camera_forward_plan(C.byref(tiny), 0, 0, 0, None) == EINVAL
+    assert lib.vamp_last_error().decode().endswith("plan is NULL")
+    assert lib.vamp_render_camera_backward_plan(None, 0, 1, 0, 0, 0, C.byref(A.VampCameraBackwardPlan())) == EINVAL
+    assert lib.vamp_last_error().decode().endswith("desc is NULL")
+    assert lib.vamp_render_camera_backward_plan(C.byref(tiny), 0, 1, 0, 0, 0, None) == EINVAL
+    assert lib.vamp_last_error().decode().endswith("plan is NULL")
+
+
 # ---------------------------------------------------------------------------------------------------- CPU: coverage
 def test_sweep_reaches_every_compiled_body():
     """Every compiled camera-forward (NCH x ERT on / off x f32 / bf16), merged-launch (NCH x f32 / bf16, planned only),
     march / cell-backward (CP, planned and unplanned) and per-ray-backward ((CP / 4, KT)) body is reached by at least
-    one oracle-compared case.  Adding a body to a launcher means adding it here and a case that reaches it."""
+    one oracle-compared case: the bodies are those the library's own plans name for the case's descriptor.  Adding a
+    body to a launcher means adding it here and a case that reaches it."""
+    lib, A = library(), _capi
     nch_bodies = {8, 12, 21, 24, 32}
     cp_bodies = {12, 24, 32}
     ray_bodies = {(3, 0), (6, 18), (6, 0), (8, 0)}
+
+    def forward(c, flags):
+        p = ask(lib.vamp_render_camera_forward_plan, A.VampCameraForwardPlan, C.byref(case_desc(c)), 0, flags, 1 << 62)
+        assert (p.path != A.VAMP_CAMPLAN_FWD_MARCH) == planned(c.S), c.name
+        return p
+
+    def backward(c):
+        return ask(lib.vamp_render_camera_backward_plan, A.VampCameraBackwardPlan, C.byref(case_desc(c)), 0, 1, 0, 0, 1 << 62)
     # the one-kernel forward (with and without termination) and the merged forward run on every planned case, in the
     # case's volume dtype
-    direct = {(cam_direct_nch(c.K), c.bf16, p["ert"]) for c in CASES if planned(c.S)
-              for p in PATHS.values() if p["cam_direct"]}
+    direct = {(forward(c, A.VAMP_CAMFWD_DIRECT | (0 if p["ert"] else A.VAMP_CAMFWD_NO_ERT)).body, c.bf16, p["ert"])
+              for c in CASES if planned(c.S) for p in PATHS.values() if p["cam_direct"]}
     assert direct == {(n, dt, e) for n in nch_bodies for dt in (False, True) for e in (False, True)}, sorted(direct)
-    merged = {(cam_direct_nch(c.K), c.bf16) for c in CASES if planned(c.S)
+    merged = {(forward(c, A.VAMP_CAMFWD_DIRECT).body, c.bf16) for c in CASES if planned(c.S)
               for p in PATHS.values() if p["cam_direct"] and p["ert"] and p["fwd_merged"]}
     assert merged == {(n, dt) for n in nch_bodies for dt in (False, True)}, sorted(merged)
+    assert all(forward(c, A.VAMP_CAMFWD_DIRECT).path == A.VAMP_CAMPLAN_FWD_DIRECT for c in CASES if planned(c.S))
     # planned march / planned cell backward, and their unplanned forms above kPlanMax, at every CP
-    assert {(channel_pack(c.K), planned(c.S)) for c in CASES} >= {(cp, p) for cp in cp_bodies for p in (True, False)}
-    assert {ray_body(c.K) for c in CASES} == ray_bodies
+    assert {(4 * forward(c, 0).body, planned(c.S)) for c in CASES} >= {(cp, p) for cp in cp_bodies for p in (True, False)}
+    assert {(backward(c).ray_cp4, backward(c).ray_kt) for c in CASES} == ray_bodies
     for K in CLASSES:                                          # every class count with cat_seg off and on
         assert {c.cat_seg for c in CASES if c.K == K and c.S == 20 and not c.bf16} == {False, True}, K
     # the plan's word split (64, 128), the per-wave split below NW = 4, and both sides of kPlanMax
@@ -487,8 +847,6 @@ def test_sweep_reaches_every_compiled_body():
 
 # the C++ the mirrors above copy: if one of these lines changes, the mirror (and the coverage table) needs a look
 DISPATCH_SOURCE = {
-    "render_cam_direct_dev.hpp": ["inline int cam_direct_nch(int nch) { return nch <= 8 ? 8 : (nch <= 12 ? 12 : "
-                                  "(nch == 21 ? 21 : (nch <= 24 ? 24 : 32))); }"],
     "render_cam_direct.hip": ["if (nch <= 8) VAMP_CAMD(T, 8);", "else if (nch <= 12) VAMP_CAMD(T, 12);",
                               "else if (nch == 21) VAMP_CAMD(T, 21);", "else if (nch <= 24) VAMP_CAMD(T, 24);",
                               "else VAMP_CAMD(T, 32);"],
@@ -496,15 +854,11 @@ DISPATCH_SOURCE = {
                               "else if (nch == 12) VAMP_MRG(T, 12);", "else if (nch == 21) VAMP_MRG(T, 21);",
                               "else if (nch == 24) VAMP_MRG(T, 24);", "else VAMP_MRG(T, 32);",
                               "return d->D - 1 <= kPlanMax && bev_fwd_fused_supported(d)"],
-    "render_common.hpp": ["const int need = 1 + d->K + 3;", "p.CP = need <= 12 ? 12 : (need <= 24 ? 24 : 32);"],
-    "render_bwd_ray.hip": ["if (P.CP == 12) VAMP_RAY(3, 0); else if (P.CP == 24 && P.K == 18) VAMP_RAY(6, 18); "
-                           "else if (P.CP == 24) VAMP_RAY(6, 0); else VAMP_RAY(8, 0);"],
-    "render_bwd_cell.hip": ["const bool planned = S <= kPlanMax;",
-                            "if (P.CP == 12) VAMP_CELL(3, 2); else if (P.CP == 24) VAMP_CELL(6, VAMP_SPLAT_NW); "
-                            "else VAMP_CELL(8, 4);"],
-    "render_fwd.hip": ["const bool planned = !geom && d->D - 1 <= kPlanMax;",
-                       "if (P.CP == 12) VAMP_CAMP(3); else if (P.CP == 24) VAMP_CAMP(6); else VAMP_CAMP(8);",
-                       "if (P.CP == 12) VAMP_CAM(3); else if (P.CP == 24) VAMP_CAM(6); else VAMP_CAM(8);"],
+    "render_common.hpp": ["const int need = 1 + d->K + 3;", "p.CP = need <= 12 ? 12 : (need <= 24 ? 24 : 32);",
+                          "inline int cam_direct_nch(int nch) { return nch <= 8 ? 8 : (nch <= 12 ? 12 : "
+                          "(nch == 21 ? 21 : (nch <= 24 ? 24 : 32))); }"],
+    # (the marches', the cell backward's and the per-ray pass's dispatch is compared by value:
+    # test_camera_plans_are_the_mirrors)
     "ray_plan.hpp": ["constexpr int kPlanMax = 128;"],
 }
 

@@ -468,14 +468,6 @@ int launch_pack(const RenderParams& P, int in_dtype, const void* dens, const voi
 
 using namespace vamp;
 
-namespace vamp {
-size_t cam_bwd_v2_bytes(const VampRenderDesc* d);
-size_t packed_bytes(const VampRenderDesc* d) {
-  const RenderParams P = to_params(d);
-  return align_up((size_t) d->B * d->Z * d->Y * d->X * P.CP * sizeof(float), 256);
-}
-}  // namespace vamp
-
 extern "C" {
 
 #ifdef VAMP_DUMP_BOXES
@@ -500,8 +492,7 @@ int vamp_debug_stamps(unsigned long long* out16, int reset) {
 size_t vamp_render_workspace_bytes(const VampRenderDesc* d) {
   if (!d) return 0;
   // packed volume + backward scratch (v1: packed gradient volume; v2: per-sample buffers)
-  const size_t pb = packed_bytes(d), v2 = cam_bwd_v2_bytes(d);
-  return pb + (pb > v2 ? pb : v2);
+  return cam_workspace(d, nullptr).offset[VAMP_RENDERWS_TERM];
 }
 
 int vamp_render_camera_forward(const VampRenderDesc* d, const float* geom, const float* mats,
@@ -515,7 +506,7 @@ int vamp_render_camera_forward(const VampRenderDesc* d, const float* geom, const
   VAMP_REQUIRE(mids && density_feature && semantic && rgb && rgb_out && seg_out && depth_out,
                "null pointer");
   VAMP_REQUIRE(beta || d->density_mode == VAMP_DENSITY_SIGMOID, "beta is NULL");
-  const size_t need = packed_bytes(d);
+  const size_t need = cam_workspace(d, nullptr).bytes[VAMP_RENDERWS_PACKED];
   if (!workspace || workspace_bytes < need)
     return fail(VAMP_ENOSPC, "%s: workspace %ld < %ld bytes", __func__, (long) workspace_bytes, (long) need);
   const RenderParams P = to_params(d);

@@ -15,7 +15,7 @@ import torch
 
 from .build import lib_path
 
-ABI_VERSION = 14
+ABI_VERSION = 15
 
 VAMP_F32, VAMP_BF16, VAMP_F16 = 0, 1, 2
 VAMP_DENSITY_SIGMOID, VAMP_DENSITY_SDF_LAPLACE = 0, 1
@@ -139,6 +139,37 @@ class VampBevBackwardPlan(C.Structure):
                 ("beta_reduce_no_vo", C.c_int32), ("reserved", C.c_int32 * 6)]
 
 
+class VampCameraForwardPlan(C.Structure):
+    """What vamp_render_camera_forward_ex will launch (vamp_render_camera_forward_plan; include/vampire_hip.h)."""
+    _fields_ = [("bytes_needed", C.c_int64), ("path", C.c_int32), ("ert", C.c_int32), ("term", C.c_int32),
+                ("pack", C.c_int32), ("pack_only", C.c_int32), ("save_rows", C.c_int32), ("body", C.c_int32),
+                ("grid", C.c_int32), ("reserved", C.c_int32 * 6)]
+
+
+class VampCameraBackwardPlan(C.Structure):
+    """What vamp_render_camera_backward_acc will launch (vamp_render_camera_backward_plan; include/vampire_hip.h)."""
+    _fields_ = [("bytes_needed", C.c_int64), ("ray_lds", C.c_int64), ("path", C.c_int32), ("pack", C.c_int32),
+                ("parts", C.c_int32), ("term", C.c_int32), ("samples", C.c_int32), ("prepare", C.c_int32),
+                ("ray_cp4", C.c_int32), ("ray_kt", C.c_int32), ("raise_lds", C.c_int32), ("ray_grid", C.c_int32),
+                ("list_grid", C.c_int32), ("heavy_grid", C.c_int32), ("heavy_waves", C.c_int32),
+                ("gather_grid", C.c_int32), ("accumulate", C.c_int32), ("beta_tail", C.c_int32),
+                ("splat_grid", C.c_int32), ("unpack_grid", C.c_int32), ("reserved", C.c_int32 * 6)]
+
+
+# regions of the render workspace, in layout order (VAMP_RENDERWS_*; "grad" overlays "gcl" .. "beta_part")
+RENDERWS_REGIONS = ("packed", "grad", "gcl", "cnt", "off", "bsum", "boff", "aux", "hcells", "part", "runs", "rank",
+                    "slot", "tile_se", "tile_order", "records", "beta_part", "term", "rows")
+
+
+class VampRenderWorkspaceLayout(C.Structure):
+    """Byte offset and size of every region of the render workspace (vamp_render_workspace_layout)."""
+    _fields_ = [("offset", C.c_int64 * len(RENDERWS_REGIONS)), ("bytes", C.c_int64 * len(RENDERWS_REGIONS)),
+                ("base_bytes", C.c_int64), ("bytes_with_rows", C.c_int64)]
+
+
+VAMP_CAMPLAN_FWD_DIRECT, VAMP_CAMPLAN_FWD_PLANNED, VAMP_CAMPLAN_FWD_MARCH = 0, 1, 2
+VAMP_CAMPLAN_TERM_NONE, VAMP_CAMPLAN_TERM_BUILD, VAMP_CAMPLAN_TERM_CHECK, VAMP_CAMPLAN_TERM_WRITE = 0, 1, 2, 3
+VAMP_CAMPLAN_BWD_CELL, VAMP_CAMPLAN_BWD_SPLAT = 0, 1
 VAMP_BEVPLAN_PATH_V1, VAMP_BEVPLAN_PATH_NOOP, VAMP_BEVPLAN_PATH_CELL = 0, 1, 2
 VAMP_BEVPLAN_SCAN_NONE, VAMP_BEVPLAN_SCAN_QSCAN21, VAMP_BEVPLAN_SCAN_QSCAN0, VAMP_BEVPLAN_SCAN_Q_SCAN = 0, 1, 2, 3
 (VAMP_BEVPLAN_BODY_NONE, VAMP_BEVPLAN_BODY_COMP, VAMP_BEVPLAN_BODY_PASS, VAMP_BEVPLAN_BODY_COL,
@@ -253,6 +284,10 @@ SIGNATURES = {
     "vamp_render_bev_backward": (_STATUS, [_RD] + [_P] * 19 + [C.POINTER(C.c_float), _P, C.c_size_t, _P]),
     "vamp_render_bev_backward_ex": (_STATUS, [_RD] + [_P] * 19 + [C.POINTER(C.c_float), _P, C.c_size_t, C.c_int, _P]),
     "vamp_render_bev_backward_plan": (_STATUS, [_RD, C.POINTER(C.c_float), C.c_int, C.POINTER(VampBevBackwardPlan)]),
+    "vamp_render_camera_forward_plan": (_STATUS, [_RD, C.c_int, C.c_int, C.c_size_t, C.POINTER(VampCameraForwardPlan)]),
+    "vamp_render_camera_backward_plan": (_STATUS, [_RD, C.c_int, C.c_int, C.c_int, C.c_int, C.c_size_t,
+                                                   C.POINTER(VampCameraBackwardPlan)]),
+    "vamp_render_workspace_layout": (_STATUS, [_RD, C.POINTER(VampRenderWorkspaceLayout)]),
     "vamp_render_indices": (_STATUS, [_RD] + [_P] * 9 + [_P]),
     "vamp_render_camera_direct_taps": (_STATUS, [_RD] + [_P] * 9 + [_P]),
     "vamp_frustum_geometry": (_STATUS, [_RD] + [_P] * 5 + [_P]),

@@ -17,10 +17,6 @@
 
 namespace vamp {
 
-#ifndef VAMP_CELL_HEAVY
-#define VAMP_CELL_HEAVY 32
-#endif
-constexpr int kCellHeavy = VAMP_CELL_HEAVY;   // records per cell beyond which the cell is summed once per corner (cam_cell_splat_kernel)
 #ifndef VAMP_SPLAT_CHUNK
 #define VAMP_SPLAT_CHUNK 256
 #endif
@@ -37,7 +33,6 @@ __host__ __device__ inline int splat_chunks(int n) { return (n + kSplatChunk - 1
 #define VAMP_GATHER_GRID 20480
 #endif
 constexpr int kGatherGrid = VAMP_GATHER_GRID;   // workgroups of the gather at most (a workgroup takes every kGatherGrid-th listed x-run)
-constexpr int kRunVox = 32;                  // voxels (an x-run) per gather workgroup
 constexpr int kListCells = kScanTile;        // cells per list-building workgroup of the cell part
 
 struct CamListArgs {
@@ -53,7 +48,7 @@ struct CamListArgs {
   unsigned first_block;    // blockIdx.x of the first of them in the launch that hosts them
 };
 // render_bwd_cell.hip
-CamListArgs cam_list_args(const VampRenderDesc* d, void* cell_scratch);
+CamListArgs cam_list_args(const VampRenderDesc* d, const CamWorkspace& w);
 
 __device__ __forceinline__ int cell_start(const int* __restrict__ off, const int* __restrict__ boff, long c) {
   return off[c] + boff[c / kScanTile];

@@ -207,3 +207,6 @@ int launch_lift_cells_end(const VampLiftDesc* d, void* scratch, hipStream_t s);
 int lift_cells_scan_job(const VampLiftDesc* d, void* scratch, ScanJob* job);
 
 }  // namespace vamp
+
+// lift.hip: the pair cells' scan as a job for a launch shared with another cell list (vamp_render_camera_prepare_with_lift)
+extern "C" int lift_scan_job(const VampLiftDesc* d, void* workspace, size_t workspace_bytes, vamp::ScanJob* job);

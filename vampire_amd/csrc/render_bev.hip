@@ -21,15 +21,6 @@
 
 namespace vamp {
 
-int launch_bev_bwd_v1(const VampRenderDesc* d, const float* oxs, const float* oys,
-                      const float* ozs, const float* bev_mids, const float* beta,
-                      const void* density_feature, const void* semantic, const void* rgb,
-                      const void* base, const float* g_bev_rgb, const float* g_bev_seg,
-                      const float* g_bev_height, const float* g_voxel_density,
-                      const float* g_voxel_output, float* grad_density_feature,
-                      float* grad_semantic, float* grad_rgb, float* grad_base, float* grad_beta,
-                      void* stream);
-
 // ---------------------------------------------------------------------------
 // backward
 // ---------------------------------------------------------------------------

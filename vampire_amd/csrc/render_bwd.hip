@@ -11,22 +11,10 @@
 //
 // v1: one thread per ray / column, two marches (totals, then splat), float atomics.
 #include "render_common.hpp"
+#include "cam_lists.hpp"
+#include "lift_common.hpp"
 
 namespace vamp {
-
-int launch_pack(const RenderParams& P, int in_dtype, const void* dens, const void* sem,
-                const void* rgb, float* packed, hipStream_t s);
-int launch_cam_bwd_v2(const VampRenderDesc* d, const RenderParams& P, const float* mats,
-                      const float* us, const float* vs, const float* ds, const float* mids,
-                      const float* beta, const void* dens, const void* sem, const void* rgbv, const float* g_rgb,
-                      const float* g_seg, const float* g_depth, float* gdens, float* gsem,
-                      float* grgb, float* grad_beta, void* scratch, int accumulate,
-                      hipEvent_t wait_event, int cells_valid, const float* samples, const int* term,
-                      int parts, hipStream_t s);
-int launch_cam_prepare(const VampRenderDesc* d, const RenderParams& P, const float* mats,
-                       const float* us, const float* vs, const float* ds, void* scratch,
-                       const int* term, int phase, hipStream_t s, bool counters_clean = false,
-                       const ScanJob* also = nullptr);
 
 __device__ __forceinline__ float block_sum_256(float v, float* red) {
   // wave reduce then 4-wave LDS reduce; result valid in thread 0
@@ -339,6 +327,116 @@ render_bev_bwd_kernel(RenderParams P, const float* __restrict__ oxs, const float
   }
 }
 
+// The backward's plan: every choice vamp_render_camera_backward_acc makes, from the descriptor, which of geom / mats
+// it is given, the flags, wait_event given or not and the workspace size; every refusal before the first launch.  No
+// HIP call.
+int camera_backward_plan(const char* who, const VampRenderDesc* d, bool has_geom, bool has_mats, int flags,
+                         bool has_wait_event, size_t workspace_bytes, VampCameraBackwardPlan* out) {
+#define VAMP_PLAN_REQUIRE(cond, msg)                                                        \
+  do {                                                                                      \
+    if (!(cond)) return fail(VAMP_EINVAL, "%s: requirement failed: " msg, who);             \
+  } while (0)
+  VAMP_PLAN_REQUIRE(out != nullptr, "plan is NULL");
+  memset(out, 0, sizeof(*out));
+  if (int e = validate(d)) return e;
+  VampCameraBackwardPlan& p = *out;
+  const RenderParams P = to_params(d);
+  const CamWorkspace w = cam_workspace(d, nullptr);
+  p.bytes_needed = (int64_t) w.base_bytes;
+  if (workspace_bytes < w.base_bytes)
+    return fail(VAMP_ENOSPC, "%s: workspace %ld < %ld bytes", who, (long) workspace_bytes, (long) w.base_bytes);
+  p.accumulate = (flags & VAMP_CAMBWD_ACCUMULATE) != 0;
+  const bool part_ray = !(flags & (VAMP_CAMBWD_PART_GATHER | VAMP_CAMBWD_PART_HEAVY)) || (flags & VAMP_CAMBWD_PART_RAY);
+  // Default: per-ray pass + cell-list gather (render_bwd_ray.hip, render_bwd_cell.hip), which evaluates the frustum
+  // points itself from the matrices and reads the volumes as they are.  A caller-supplied geom tensor, or
+  // VAMP_CAMBWD_SPLAT, takes the v1 float-atomic splat (the independent cross-check), which gathers from a channel-last
+  // copy: one the forward may have left at the head of the workspace (PACKED_VALID).
+  if (has_geom || !has_mats || (flags & VAMP_CAMBWD_SPLAT)) {
+    p.path = VAMP_CAMPLAN_BWD_SPLAT;
+    p.pack = !(flags & VAMP_CAMBWD_PACKED_VALID) && part_ray;
+    VAMP_PLAN_REQUIRE(!p.accumulate && !has_wait_event, "accumulate / wait_event need the cell-list path");
+    p.splat_grid = (int) (((long) d->B * d->N * d->fH * d->fW + 255) / 256);
+    p.unpack_grid = (int) (((long) d->B * d->Z * d->Y * d->X + 255) / 256);
+    return VAMP_OK;
+  }
+  p.path = VAMP_CAMPLAN_BWD_CELL;
+  p.parts = ((flags & VAMP_CAMBWD_PART_RAY) ? kCamPartRay : 0) | ((flags & VAMP_CAMBWD_PART_GATHER) ? kCamPartGather : 0) |
+            ((flags & VAMP_CAMBWD_PART_HEAVY) ? kCamPartHeavy : 0);
+  if (p.parts == 0) p.parts = kCamPartAll;
+  if (flags & VAMP_CAMBWD_SAMPLES_VALID) {
+    p.bytes_needed = (int64_t) w.bytes_with_rows;
+    if (workspace_bytes < w.bytes_with_rows)
+      return fail(VAMP_ENOSPC, "%s: workspace %ld has no room for the sample rows", who, (long) workspace_bytes);
+  }
+  p.beta_tail = P.density_mode == VAMP_DENSITY_SDF_LAPLACE && (p.parts & kCamPartGather);
+  if (part_ray) {
+    p.samples = (flags & VAMP_CAMBWD_SAMPLES_VALID) != 0;
+    p.prepare = !(flags & VAMP_CAMBWD_CELLS_VALID);
+    // early ray termination: the table of the forward (TERM_VALID), or computed here; the cell lists must have been
+    // prepared with the same table
+    if (!(flags & VAMP_CAMBWD_NO_ERT)) {
+      p.term = (flags & VAMP_CAMBWD_TERM_VALID) ? VAMP_CAMPLAN_TERM_CHECK : VAMP_CAMPLAN_TERM_BUILD;
+      VAMP_PLAN_REQUIRE(p.term == VAMP_CAMPLAN_TERM_CHECK || p.prepare, "CELLS_VALID with early termination needs TERM_VALID");
+    }
+    if (p.prepare)
+      if (int e = cam_cells_fit(who, d)) return e;
+    p.ray_cp4 = P.CP / 4;
+    p.ray_kt = (P.CP == 24 && P.K == 18) ? 18 : 0;
+    // the per-ray pass stages three values per sample and lane: [3][ceil(S / 4)][256] floats
+    p.ray_lds = (int64_t) 3 * ((d->D - 1 + 3) / 4) * 256 * (int64_t) sizeof(float);
+    if (p.ray_lds > 150 * 1024) return fail(VAMP_EINVAL, "%s: too many depth samples for the LDS staging", who);
+    p.raise_lds = p.ray_lds > 64 * 1024;
+    p.ray_grid = (int) ray_grid<4>(P);
+    p.list_grid = (int) cam_list_args(d, w).nblocks;
+  } else if (p.beta_tail) {
+    p.ray_grid = (int) ray_grid<4>(P);      // (the d beta partials an earlier call's per-ray pass has left)
+  }
+  if (p.parts & (kCamPartGather | kCamPartHeavy)) {
+    const bool runs_fit = cam_bwd_cell_grids(d, &p.heavy_grid, &p.heavy_waves, &p.gather_grid);
+    VAMP_PLAN_REQUIRE(runs_fit, "too many x-runs");
+    if (!(p.parts & kCamPartHeavy)) p.heavy_grid = p.heavy_waves = 0;
+    if (!(p.parts & kCamPartGather)) p.gather_grid = 0;
+  }
+  return VAMP_OK;
+#undef VAMP_PLAN_REQUIRE
+}
+
+// the v1 float-atomic splat into the gradient copy, then the copy's channel-first unpacking
+static int launch_cam_bwd_v1(const RenderParams& P, const VampCameraBackwardPlan& p, const CamWorkspace& w,
+                             const float* geom, const float* mats, const float* us, const float* vs, const float* ds,
+                             const float* mids, const float* beta, const float* g_rgb, const float* g_seg,
+                             const float* g_depth, float* gdens, float* gsem, float* grgb, float* grad_beta,
+                             hipStream_t s) {
+  if (int ze = launch_zero(w.gpacked, w.bytes[VAMP_RENDERWS_GRAD], s)) return ze;
+  const unsigned grid = (unsigned) p.splat_grid, ugrid = (unsigned) p.unpack_grid;
+#define VAMP_CAMB(CP4)                                                                           \
+  do {                                                                                           \
+    VAMP_TIMED(kProfCamBwdV1, s, (render_cam_bwd_kernel<CP4><<<grid, 256, 0, s>>>(                \
+        P, geom, mats, us, vs, ds, mids, beta, w.packed, g_rgb, g_seg, g_depth, w.gpacked, grad_beta))); \
+    if (int e = check_launch("render_cam_bwd_kernel")) return e;                                 \
+    VAMP_TIMED(kProfUnpack, s, (unpack_grad_kernel<CP4><<<ugrid, 256, 0, s>>>(P, w.gpacked, gdens, gsem, grgb))); \
+  } while (0)
+  if (P.CP == 12) VAMP_CAMB(3); else if (P.CP == 24) VAMP_CAMB(6); else VAMP_CAMB(8);
+#undef VAMP_CAMB
+  return check_launch("unpack_grad_kernel");
+}
+
+static int camera_prepare(const char* who, const VampRenderDesc* d, const float* mats, const float* us, const float* vs,
+                          const float* ds, void* workspace, size_t workspace_bytes, int flags, const ScanJob* also,
+                          void* stream) {
+  if (int e = validate(d)) return e;
+  const CamWorkspace w = cam_workspace(d, workspace);
+  if (!workspace || workspace_bytes < w.base_bytes)
+    return fail(VAMP_ENOSPC, "%s: workspace %ld < %ld bytes", who, (long) workspace_bytes, (long) w.base_bytes);
+  // VAMP_CAMPREP_RANKED: the ranks are drawn (vamp_render_forward_merged with VAMP_RENDERFWD_RANK): the cell scan only
+  const bool ranked = (flags & VAMP_CAMPREP_RANKED) != 0;
+  if (!ranked && !(mats && us && vs && ds)) return fail(VAMP_EINVAL, "%s: requirement failed: null pointer", who);
+  if (int e = cam_cells_fit(who, d)) return e;
+  return launch_cam_cells_prepare(d, to_params(d), mats, us, vs, ds, w,
+                                  (flags & VAMP_CAMPREP_TERM_VALID) ? w.term : nullptr, ranked,
+                                  static_cast<hipStream_t>(stream), (flags & VAMP_CAMPREP_COUNTERS_CLEAN) != 0, also);
+}
+
 }  // namespace vamp
 
 using namespace vamp;
@@ -351,31 +449,11 @@ int vamp_render_camera_prepare(const VampRenderDesc* d, const float* mats, const
   return vamp_render_camera_prepare_ex(d, mats, us, vs, ds, workspace, workspace_bytes, 0, stream);
 }
 
-static int camera_prepare(const VampRenderDesc* d, const float* mats, const float* us, const float* vs,
-                          const float* ds, void* workspace, size_t workspace_bytes, int flags, const ScanJob* also,
-                          void* stream) {
-  if (int e = validate(d)) return e;
-  const size_t need = vamp_render_workspace_bytes(d);
-  if (!workspace || workspace_bytes < need)
-    return fail(VAMP_ENOSPC, "%s: workspace %ld < %ld bytes", __func__, (long) workspace_bytes, (long) need);
-  // the ranks are drawn (vamp_render_forward_merged with VAMP_RENDERFWD_RANK): the cell scan only
-  if (flags & VAMP_CAMPREP_RANKED) return launch_cam_prepare_ranked(d, workspace, static_cast<hipStream_t>(stream), also);
-  VAMP_REQUIRE(mats && us && vs && ds, "null pointer");
-  const RenderParams P = to_params(d);
-  return launch_cam_prepare(d, P, mats, us, vs, ds, static_cast<char*>(workspace) + packed_bytes(d),
-                            (flags & VAMP_CAMPREP_TERM_VALID) ? cam_term_ptr(d, workspace) : nullptr,
-                            /*phase=*/0, static_cast<hipStream_t>(stream),
-                            (flags & VAMP_CAMPREP_COUNTERS_CLEAN) != 0, also);
-}
-
 int vamp_render_camera_prepare_ex(const VampRenderDesc* d, const float* mats, const float* us,
                                   const float* vs, const float* ds, void* workspace,
                                   size_t workspace_bytes, int flags, void* stream) {
-  return camera_prepare(d, mats, us, vs, ds, workspace, workspace_bytes, flags, nullptr, stream);
+  return camera_prepare(__func__, d, mats, us, vs, ds, workspace, workspace_bytes, flags, nullptr, stream);
 }
-
-// lift.hip
-int lift_scan_job(const VampLiftDesc* d, void* workspace, size_t workspace_bytes, ScanJob* job);
 
 int vamp_render_camera_prepare_with_lift(const VampRenderDesc* d, const float* mats, const float* us,
                                          const float* vs, const float* ds, void* workspace, size_t workspace_bytes,
@@ -384,7 +462,7 @@ int vamp_render_camera_prepare_with_lift(const VampRenderDesc* d, const float* m
   VAMP_REQUIRE(lift_desc && lift_workspace, "null pointer");
   ScanJob lift;
   if (int e = lift_scan_job(lift_desc, lift_workspace, lift_workspace_bytes, &lift)) return e;
-  return camera_prepare(d, mats, us, vs, ds, workspace, workspace_bytes, flags, &lift, stream);
+  return camera_prepare(__func__, d, mats, us, vs, ds, workspace, workspace_bytes, flags, &lift, stream);
 }
 
 int vamp_render_camera_backward(const VampRenderDesc* d, const float* geom, const float* mats,
@@ -401,6 +479,11 @@ int vamp_render_camera_backward(const VampRenderDesc* d, const float* geom, cons
                                          workspace_bytes, 0, nullptr, stream);
 }
 
+int vamp_render_camera_backward_plan(const VampRenderDesc* d, int has_geom, int has_mats, int flags,
+                                     int has_wait_event, size_t workspace_bytes, VampCameraBackwardPlan* out) {
+  return camera_backward_plan(__func__, d, has_geom != 0, has_mats != 0, flags, has_wait_event != 0, workspace_bytes, out);
+}
+
 int vamp_render_camera_backward_acc(const VampRenderDesc* d, const float* geom, const float* mats,
                                     const float* us, const float* vs, const float* ds,
                                     const float* mids, const float* beta,
@@ -410,75 +493,31 @@ int vamp_render_camera_backward_acc(const VampRenderDesc* d, const float* geom, 
                                     float* grad_semantic, float* grad_rgb, float* grad_beta,
                                     void* workspace, size_t workspace_bytes, int flags,
                                     void* wait_event, void* stream) {
-  const int accumulate = (flags & VAMP_CAMBWD_ACCUMULATE) ? 1 : 0;
   if (int e = validate(d)) return e;
   VAMP_REQUIRE(geom || (mats && us && vs && ds), "need geom or (mats, us, vs, ds)");
   VAMP_REQUIRE(mids && density_feature && semantic && rgb, "null input");
   VAMP_REQUIRE(grad_density_feature && grad_semantic && grad_rgb, "null output");
   VAMP_REQUIRE((beta && grad_beta) || d->density_mode == VAMP_DENSITY_SIGMOID, "beta / grad_beta is NULL");
-  const size_t pb = packed_bytes(d);
-  const size_t need = vamp_render_workspace_bytes(d);
-  if (!workspace || workspace_bytes < need)
-    return fail(VAMP_ENOSPC, "%s: workspace %ld < %ld bytes", __func__, (long) workspace_bytes, (long) need);
+  VampCameraBackwardPlan p;
+  if (int e = camera_backward_plan(__func__, d, geom != nullptr, mats != nullptr, flags, wait_event != nullptr,
+                                   workspace ? workspace_bytes : 0, &p)) return e;
   const RenderParams P = to_params(d);
+  const CamWorkspace w = cam_workspace(d, workspace);
   hipStream_t s = static_cast<hipStream_t>(stream);
-  float* packed = static_cast<float*>(workspace);
-  float* gpacked = reinterpret_cast<float*>(static_cast<char*>(workspace) + pb);
-  const bool part_ray = !(flags & (VAMP_CAMBWD_PART_GATHER | VAMP_CAMBWD_PART_HEAVY)) || (flags & VAMP_CAMBWD_PART_RAY);
-  // (the default path reads the volumes as they are; only the v1 splat below gathers from a channel-last
-  // copy, which the forward may have left at the head of the workspace)
-  const bool splat = geom || !mats || (flags & VAMP_CAMBWD_SPLAT);
-  if (splat && !(flags & VAMP_CAMBWD_PACKED_VALID) && part_ray)
-    if (int e = launch_pack(P, d->in_dtype, density_feature, semantic, rgb, packed, s)) return e;
-  // Default: per-ray pass + cell-list gather (render_bwd_ray.hip, render_bwd_cell.hip), which
-  // evaluates the frustum points itself from the matrices.  A caller-supplied geom tensor, or
-  // VAMP_CAMBWD_SPLAT, takes the v1 float-atomic splat below (the independent cross-check).
-  int parts = ((flags & VAMP_CAMBWD_PART_RAY) ? kCamPartRay : 0) | ((flags & VAMP_CAMBWD_PART_GATHER) ? kCamPartGather : 0) |
-              ((flags & VAMP_CAMBWD_PART_HEAVY) ? kCamPartHeavy : 0);
-  if (parts == 0) parts = kCamPartAll;
-  if (!geom && mats && !(flags & VAMP_CAMBWD_SPLAT)) {
-    const float* samples = nullptr;
-    if (flags & VAMP_CAMBWD_SAMPLES_VALID) {
-      if (workspace_bytes < need + vamp_render_samples_bytes(d))
-        return fail(VAMP_ENOSPC, "%s: workspace %ld has no room for the sample rows", __func__, (long) workspace_bytes);
-      samples = reinterpret_cast<const float*>(static_cast<char*>(workspace) + need);
-    }
-    // early ray termination: the table of the forward (TERM_VALID), or computed here; the cell
-    // lists must have been prepared with the same table
-    int* term = nullptr;
-    if (!(flags & VAMP_CAMBWD_NO_ERT)) {
-      term = cam_term_ptr(d, workspace);
-      if (!(flags & VAMP_CAMBWD_TERM_VALID) && part_ray) {
-        VAMP_REQUIRE(!(flags & VAMP_CAMBWD_CELLS_VALID), "CELLS_VALID with early termination needs TERM_VALID");
-        if (int e = launch_cam_term(d, P, mats, us, vs, ds, beta, density_feature, term, s)) return e;
-      } else if (part_ray) {
-        if (int e = debug_expect_range(term, (size_t) d->B * d->N * d->fH * d->fW, 0, d->D - 1, s,
-                                       "VAMP_CAMBWD_TERM_VALID: the workspace holds a termination table")) return e;
-      }
-    }
-    return launch_cam_bwd_v2(d, P, mats, us, vs, ds, mids, beta, density_feature, semantic, rgb, g_rgb, g_seg, g_depth,
-                             grad_density_feature, grad_semantic, grad_rgb, grad_beta, gpacked,
-                             accumulate, static_cast<hipEvent_t>(wait_event),
-                             (flags & VAMP_CAMBWD_CELLS_VALID) ? 1 : 0,
-                             samples, term, parts, s);
+  if (p.pack)
+    if (int e = launch_pack(P, d->in_dtype, density_feature, semantic, rgb, w.packed, s)) return e;
+  if (p.path == VAMP_CAMPLAN_BWD_SPLAT)
+    return launch_cam_bwd_v1(P, p, w, geom, mats, us, vs, ds, mids, beta, g_rgb, g_seg, g_depth, grad_density_feature,
+                             grad_semantic, grad_rgb, grad_beta, s);
+  if (p.term == VAMP_CAMPLAN_TERM_BUILD) {
+    if (int e = launch_cam_term(d, P, mats, us, vs, ds, beta, density_feature, w.term, s)) return e;
+  } else if (p.term == VAMP_CAMPLAN_TERM_CHECK) {
+    if (int e = debug_expect_range(w.term, (size_t) d->B * d->N * d->fH * d->fW, 0, d->D - 1, s,
+                                   "VAMP_CAMBWD_TERM_VALID: the workspace holds a termination table")) return e;
   }
-  VAMP_REQUIRE(!accumulate && !wait_event, "accumulate / wait_event need the cell-list path");
-  if (int ze = launch_zero(gpacked, pb, s)) return ze;
-  const long nrays = (long) d->B * d->N * d->fH * d->fW;
-  const unsigned grid = (unsigned) ((nrays + 255) / 256);
-  const long nvox = (long) d->B * d->Z * d->Y * d->X;
-  const unsigned ugrid = (unsigned) ((nvox + 255) / 256);
-#define VAMP_CAMB(CP4)                                                                           \
-  do {                                                                                           \
-    VAMP_TIMED(kProfCamBwdV1, s, (render_cam_bwd_kernel<CP4><<<grid, 256, 0, s>>>(                \
-        P, geom, mats, us, vs, ds, mids, beta, packed, g_rgb, g_seg, g_depth, gpacked, grad_beta))); \
-    if (int e = check_launch("render_cam_bwd_kernel")) return e;                                 \
-    VAMP_TIMED(kProfUnpack, s, (unpack_grad_kernel<CP4><<<ugrid, 256, 0, s>>>(                   \
-        P, gpacked, grad_density_feature, grad_semantic, grad_rgb)));                            \
-  } while (0)
-  if (P.CP == 12) VAMP_CAMB(3); else if (P.CP == 24) VAMP_CAMB(6); else VAMP_CAMB(8);
-#undef VAMP_CAMB
-  return check_launch("unpack_grad_kernel");
+  return launch_cam_bwd_v2(d, P, p, w, mats, us, vs, ds, mids, beta, density_feature, semantic, rgb, g_rgb, g_seg,
+                           g_depth, grad_density_feature, grad_semantic, grad_rgb, grad_beta,
+                           static_cast<hipEvent_t>(wait_event), s);
 }
 
 }  // extern "C"

@@ -359,54 +359,8 @@ cam_bwd_cell_gather_kernel(RenderParams P, const int* __restrict__ off, const in
 // ---------------------------------------------------------------------------
 // host side
 // ---------------------------------------------------------------------------
-struct CellWs {
-  int* cnt;        // [ncell] counters
-  int* off;        // [ncell] tile-local exclusive offsets
-  int* bsum;       // [ntile] tile totals
-  int* boff;       // [ntile] exclusive scan of the tile totals
-  int* aux;        // [ntile] scratch of the level-2 scan, then [ntile] = total, [ntile+1] = heavy cells listed
-  int2* hcells;    // [max(ncell, samples / 16)] list of the heavy cells' chunks: {first record, records}
-  float* part;     // [samples / kCellHeavy + 2][8][CP] per-corner partial sums of the heavy cells
-  int* runs;       // [x-runs] list of the x-runs with records (accumulate mode); aux[ntile + 2] = their number
-  int* rank;       // [tiles][S][64] rank of the sample inside its cell (written for kept inside samples only)
-  int* slot;       // [tiles][S][64] slot in R (-1 = masked): the per-ray pass's note between its two loops
-  int* tile_se;    // [tiles] kept samples of the tile's longest ray
-  int* tile_order; // [tiles] tiles sorted by that, longest first
-  float4* R;       // [samples][2] records in cell order
-  size_t bytes;
-};
-
-static CellWs cell_ws(const VampRenderDesc* d, void* scratch) {
-  const long ncell = cell_count_padded(d->B, d->Z, d->Y, d->X);
-  const long ntile = ncell / kScanTile;
-  const size_t samples = (size_t) d->B * d->N * (d->D - 1) * d->fH * d->fW;
-  // per-sample tables are indexed by 8 x 8 ray tile (ragged tiles padded)
-  const size_t tsamples = (size_t) d->B * d->N * ((d->fH + 7) / 8) * ((d->fW + 7) / 8) * 64 * (d->D - 1);
-  char* p = static_cast<char*>(scratch);
-  CellWs w;
-  w.cnt = reinterpret_cast<int*>(p); p += align_up((size_t) (ncell + kScanPad) * sizeof(int), 256);   // + the scan's ticket word
-  w.off = reinterpret_cast<int*>(p); p += align_up((size_t) ncell * sizeof(int), 256);
-  w.bsum = reinterpret_cast<int*>(p); p += align_up((size_t) ntile * sizeof(int), 256);
-  w.boff = reinterpret_cast<int*>(p); p += align_up((size_t) ntile * sizeof(int), 256);
-  w.aux = reinterpret_cast<int*>(p); p += align_up((size_t) (ntile + 4) * sizeof(int), 256);
-  w.hcells = reinterpret_cast<int2*>(p); p += align_up(std::max<size_t>((size_t) ncell, samples / 16 + 4096) * sizeof(int2), 256);
-  w.part = reinterpret_cast<float*>(p); p += align_up((samples / kCellHeavy + 2) * 8 * (size_t) to_params(d).CP * sizeof(float), 256);
-  w.runs = reinterpret_cast<int*>(p); p += align_up((size_t) d->B * d->Z * d->Y * ((d->X + kRunVox - 1) / kRunVox) * sizeof(int), 256);
-  w.rank = reinterpret_cast<int*>(p); p += align_up(tsamples * sizeof(int), 256);
-  w.slot = reinterpret_cast<int*>(p); p += align_up(tsamples * sizeof(int), 256);
-  const size_t tiles = tsamples / ((size_t) 64 * (d->D - 1));
-  w.tile_se = reinterpret_cast<int*>(p); p += align_up(tiles * sizeof(int), 256);
-  w.tile_order = reinterpret_cast<int*>(p); p += align_up(tiles * sizeof(int), 256);
-  w.R = reinterpret_cast<float4*>(p); p += align_up(samples * 2 * sizeof(float4), 256);
-  w.bytes = (size_t) (p - static_cast<char*>(scratch));
-  return w;
-}
-
-size_t cam_bwd_cell_bytes(const VampRenderDesc* d) { return cell_ws(d, nullptr).bytes; }
-
 // pointers the per-ray pass needs
-CamCellRefs cam_cell_refs(const VampRenderDesc* d, void* scratch) {
-  const CellWs w = cell_ws(d, scratch);
+CamCellRefs cam_cell_refs(const VampRenderDesc* d, const CamWorkspace& w) {
   CamCellRefs r;
   r.rank = w.rank; r.slot = w.slot; r.off = w.off; r.boff = w.boff; r.R = w.R;
   r.tile_order = w.tile_order;
@@ -414,115 +368,107 @@ CamCellRefs cam_cell_refs(const VampRenderDesc* d, void* scratch) {
   return r;
 }
 
-CamRankRefs cam_rank_refs_cells(const VampRenderDesc* d, void* scratch) {
-  const CellWs w = cell_ws(d, scratch);
+CamRankRefs cam_rank_refs(const VampRenderDesc* d, const CamWorkspace& w) {
   return CamRankRefs{w.cnt, w.rank, w.tile_se, (long) (d->Z + 1) * (d->Y + 1) * (d->X + 1), nullptr};
 }
-int launch_cam_cells_zero(const VampRenderDesc* d, void* scratch, hipStream_t s) {
-  const CellWs w = cell_ws(d, scratch);
-  return launch_zero(w.cnt, (size_t) (cell_count_padded(d->B, d->Z, d->Y, d->X) + kScanPad) * sizeof(int), s);
+int launch_cam_counters_zero(const CamWorkspace& w, hipStream_t s) {
+  return launch_zero(w.cnt, (size_t) (w.ncell + kScanPad) * sizeof(int), s);
 }
 
-// phase 0 / 1: rank + scan (what needs the geometry and the termination table); 3: the scan behind a forward that has
-// drawn the ranks itself (mats .. term unused).  (2, the work lists as a launch of their own, is gone: they are built
-// by the tail workgroups of the per-ray pass's launch, cam_lists.hpp.)  The scan's first workgroup sorts the ray tiles
-// deepest first for the per-ray pass.
-int launch_cam_cells_prepare(const VampRenderDesc* d, const RenderParams& P, const float* mats,
-                             const float* us, const float* vs, const float* ds, void* scratch,
-                             const int* term, int phase, hipStream_t s, bool counters_clean, const ScanJob* also) {
-  const CellWs w = cell_ws(d, scratch);
-  const long ncell = cell_count_padded(d->B, d->Z, d->Y, d->X);
+int cam_cells_fit(const char* who, const VampRenderDesc* d) {
   const size_t samples = (size_t) d->B * d->N * (d->D - 1) * d->fH * d->fW;
   const size_t voxels = (size_t) d->B * d->Z * d->Y * d->X;
-  VAMP_REQUIRE(samples > 0 && samples < 0x7fffffffu && voxels < 0x7fffffffu && ncell < 0x7fffffffL,
-               "sample / voxel / cell count exceeds 2^31");
+  if (!(samples > 0 && samples < 0x7fffffffu && voxels < 0x7fffffffu && cell_count_padded(d->B, d->Z, d->Y, d->X) < 0x7fffffffL))
+    return fail(VAMP_EINVAL, "%s: requirement failed: sample / voxel / cell count exceeds 2^31", who);
+  return VAMP_OK;
+}
+
+// (The caller has asked cam_cells_fit.)  The scan's first workgroup sorts the ray tiles deepest first for the per-ray
+// pass.
+int launch_cam_cells_prepare(const VampRenderDesc* d, const RenderParams& P, const float* mats,
+                             const float* us, const float* vs, const float* ds, const CamWorkspace& w,
+                             const int* term, bool ranked, hipStream_t s, bool counters_clean, const ScanJob* also) {
   const long ncell_b = (long) (d->Z + 1) * (d->Y + 1) * (d->X + 1);
   const ScanDuty duty{w.tile_se, w.tile_order, (int) ((long) d->B * d->N * ((d->fH + 7) / 8) * ((d->fW + 7) / 8))};
-  if (phase == 2) return VAMP_OK;
-  if (phase == 3) {
-    if (also) {                     // one launch for this list's scan and another list's (the lift's pair cells)
-      ScanJob mine;
-      if (int e = make_scan_job(w.cnt, w.off, w.bsum, w.boff, w.aux, ncell, &mine)) return e;
-      return launch_cell_scan_pair(mine, *also, s, &duty);
+  if (!ranked) {
+    if (!counters_clean) {          // (VAMP_CAMPREP_COUNTERS_CLEAN: the previous scan left them at zero)
+      if (int ze = launch_cam_counters_zero(w, s)) return ze;
+    } else if (int e = debug_expect_range(w.cnt, (size_t) (w.ncell + kScanPad), 0, 0, s,
+                                          "VAMP_CAMPREP_COUNTERS_CLEAN: the render workspace's cell counters are zero")) {
+      return e;
     }
-    return launch_cell_scan(w.cnt, w.off, w.bsum, w.boff, w.aux, ncell, s, &duty);
+    // (a termination table handed over with *_TERM_VALID holds a number of kept samples per ray)
+    if (int e = debug_expect_range(term, (size_t) d->B * d->N * d->fH * d->fW, 0, d->D - 1, s,
+                                   "VAMP_CAMPREP_TERM_VALID: the workspace holds a termination table")) return e;
+    VAMP_TIMED(kProfCamBwdCount, s, (cam_cells_rank_kernel<<<ray_grid<4>(P), 256, 0, s>>>(
+        P, mats, us, vs, ds, w.cnt, w.rank, ncell_b, term, w.tile_se)));
+    if (int e = check_launch("cam_cells_rank_kernel")) return e;
   }
-  if (!counters_clean) {          // (VAMP_CAMPREP_COUNTERS_CLEAN: the previous scan left them at zero)
-    if (int ze = launch_zero(w.cnt, (size_t) (ncell + kScanPad) * sizeof(int), s)) return ze;
-  } else if (int e = debug_expect_range(w.cnt, (size_t) (ncell + kScanPad), 0, 0, s,
-                                        "VAMP_CAMPREP_COUNTERS_CLEAN: the render workspace's cell counters are zero")) {
-    return e;
-  }
-  // (a termination table handed over with *_TERM_VALID holds a number of kept samples per ray)
-  if (int e = debug_expect_range(term, (size_t) d->B * d->N * d->fH * d->fW, 0, d->D - 1, s,
-                                 "VAMP_CAMPREP_TERM_VALID: the workspace holds a termination table")) return e;
-  VAMP_TIMED(kProfCamBwdCount, s, (cam_cells_rank_kernel<<<ray_grid<4>(P), 256, 0, s>>>(
-      P, mats, us, vs, ds, w.cnt, w.rank, ncell_b, term, w.tile_se)));
-  if (int e = check_launch("cam_cells_rank_kernel")) return e;
-  if (also) {
+  if (also) {                       // one launch for this list's scan and another list's (the lift's pair cells)
     ScanJob mine;
-    if (int e = make_scan_job(w.cnt, w.off, w.bsum, w.boff, w.aux, ncell, &mine)) return e;
+    if (int e = make_scan_job(w.cnt, w.off, w.bsum, w.boff, w.aux, w.ncell, &mine)) return e;
     return launch_cell_scan_pair(mine, *also, s, &duty);
   }
-  return launch_cell_scan(w.cnt, w.off, w.bsum, w.boff, w.aux, ncell, s, &duty);
+  return launch_cell_scan(w.cnt, w.off, w.bsum, w.boff, w.aux, w.ncell, s, &duty);
 }
 
 // what the list-building workgroups behind the per-ray pass's tiles need (cam_lists.hpp)
-CamListArgs cam_list_args(const VampRenderDesc* d, void* scratch) {
-  const CellWs w = cell_ws(d, scratch);
-  const long ncell = cell_count_padded(d->B, d->Z, d->Y, d->X);
-  const long ntile = ncell / kScanTile;
+CamListArgs cam_list_args(const VampRenderDesc* d, const CamWorkspace& w) {
   CamListArgs a;
   a.off = w.off; a.boff = w.boff; a.hcells = w.hcells;
-  a.nhcells = w.aux + ntile + 1;                  // (and the run counter behind it) zeroed by the scan (runtime.hip)
+  a.nhcells = w.aux + w.ntile + 1;                // (and the run counter behind it) zeroed by the scan (runtime.hip)
   a.runs = w.runs; a.nruns = a.nhcells + 1;
   a.ncell_b = (long) (d->Z + 1) * (d->Y + 1) * (d->X + 1);
   a.runs_x = (d->X + kRunVox - 1) / kRunVox;
   a.total_runs = (long) a.runs_x * d->Y * d->Z * d->B;
-  a.ncell = ncell;
-  a.cell_blocks = (unsigned) (ncell / kListCells);
+  a.ncell = w.ncell;
+  a.cell_blocks = (unsigned) (w.ncell / kListCells);
   a.nblocks = a.cell_blocks + (unsigned) ((a.total_runs + 255) / 256);
   a.first_block = 0;
   return a;
 }
 
+// The grids of the two launches below (the backward's plan asks; no HIP call): a gather workgroup owns an x-run, at
+// most kGatherGrid of them run.  False: more x-runs than a grid index holds.
+bool cam_bwd_cell_grids(const VampRenderDesc* d, int* heavy_grid, int* heavy_waves, int* gather_grid) {
+  const CamListArgs a = cam_list_args(d, cam_workspace(d, nullptr));
+  if (a.total_runs >= 0x7fffffffL) return false;
+  const int CP = to_params(d).CP;
+  *heavy_grid = (int) std::min<long>(a.ncell, 4096);
+  *heavy_waves = CP == 12 ? 2 : (CP == 24 ? VAMP_SPLAT_NW : 4);     // (waves of the splat: CP / NW channels each)
+  *gather_grid = (int) std::min<long>(a.total_runs, kGatherGrid);
+  return true;
+}
+
 // the heavy cells' per-corner sums, then the per-voxel gather of the records the per-ray pass has written in cell order
-int launch_cam_bwd_cell(const VampRenderDesc* d, const RenderParams& P, const float* Gcl,
-                        float* gdens, float* gsem, float* grgb, void* scratch, int accumulate,
-                        hipEvent_t wait_event, int parts, BetaTail btail, hipStream_t s) {
-  const CellWs w = cell_ws(d, scratch);
-  const long ncell = cell_count_padded(d->B, d->Z, d->Y, d->X);
-  const long ntile = ncell / kScanTile;
-  const long ncell_b = (long) (d->Z + 1) * (d->Y + 1) * (d->X + 1);
-  const int* nhcells = w.aux + ntile + 1;
+int launch_cam_bwd_cell(const VampRenderDesc* d, const RenderParams& P, const VampCameraBackwardPlan& p,
+                        const CamWorkspace& w, float* gdens, float* gsem, float* grgb, hipEvent_t wait_event,
+                        BetaTail btail, hipStream_t s) {
+  const CamListArgs a = cam_list_args(d, w);
+  const int accumulate = p.accumulate;
   const int* runs = accumulate ? w.runs : nullptr;   // (overwrite mode: every run is stored)
+  const float* Gcl = w.Gcl;
 
   // measured at cfg-B (gather + heavy-VOXEL drain, rounds 1 - 5, us): 8 lanes 145 + 56, 16 lanes 173 + 56, 32 lanes
   // 249 + 56; after early ray termination 68 + 34
   constexpr int gl = kGatherLanes;
-  const int vpb = 256 / gl;
-  const int runs_x = (d->X + vpb - 1) / vpb;
-  const long nblk = (long) runs_x * d->Y * d->Z * d->B;
-  VAMP_REQUIRE(nblk < 0x7fffffffL, "too many x-runs");
-  const unsigned grid = (unsigned) std::min<long>(nblk, kGatherGrid);
-  const unsigned sgrid = (unsigned) std::min<long>(ncell, 4096);
+  const unsigned grid = (unsigned) p.gather_grid, sgrid = (unsigned) p.heavy_grid;
   // PART_HEAVY: the per-cell sums (they touch the partial table only: no need to wait for whoever else writes the
   // gradient buffers); PART_GATHER reads them, so a caller that splits the parts issues HEAVY first, same stream
 #define VAMP_CELL(CP4, NW)                                                                            \
   do {                                                                                              \
-    if (parts & kCamPartHeavy)                                                                      \
+    if (p.parts & kCamPartHeavy)                                                                    \
       VAMP_TIMED(kProfCamBwdOwn, s, (cam_cell_splat_kernel<CP4, NW><<<sgrid, NW * 64, 0, s>>>(      \
-          w.R, Gcl, w.hcells, nhcells, w.part)));                                                   \
-    if (parts & kCamPartGather) {                                                                   \
+          w.R, Gcl, w.hcells, a.nhcells, w.part)));                                                 \
+    if (p.parts & kCamPartGather) {                                                                 \
       /* the gradient buffers are first touched here: whoever else accumulates into them (the BEV   \
          branch on another stream) must be done */                                                  \
       if (wait_event && hipStreamWaitEvent(s, wait_event, 0) != hipSuccess)                         \
         return fail(VAMP_EHIP, "%s: hipStreamWaitEvent failed", __func__);                          \
       VAMP_TIMED(kProfCamBwdBrick, s, (cam_bwd_cell_gather_kernel<CP4, gl><<<grid, 256, 0, s>>>(    \
-          P, w.off, w.boff, w.R, Gcl, gdens, gsem, grgb, ncell_b, runs_x, nblk, accumulate, btail, runs, nhcells + 1, w.part))); \
+          P, w.off, w.boff, w.R, Gcl, gdens, gsem, grgb, a.ncell_b, a.runs_x, a.total_runs, accumulate, btail, runs, a.nruns, w.part))); \
     }                                                                                               \
   } while (0)
-  // (waves of the splat: CP / NW channels each)
   if (P.CP == 12) VAMP_CELL(3, 2); else if (P.CP == 24) VAMP_CELL(6, VAMP_SPLAT_NW); else VAMP_CELL(8, 4);
 #undef VAMP_CELL
   return check_launch("cam_bwd_cell_gather_kernel");

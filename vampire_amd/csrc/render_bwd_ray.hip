@@ -251,107 +251,54 @@ cam_bwd_ray_kernel(RenderParams P, const float* __restrict__ mats, const float* 
 // ---------------------------------------------------------------------------
 // host side
 // ---------------------------------------------------------------------------
-// render_bwd_cell.hip
-size_t cam_bwd_cell_bytes(const VampRenderDesc* d);
-CamCellRefs cam_cell_refs(const VampRenderDesc* d, void* scratch);
-int launch_cam_cells_prepare(const VampRenderDesc* d, const RenderParams& P, const float* mats,
-                             const float* us, const float* vs, const float* ds, void* scratch,
-                             const int* term, int phase, hipStream_t s, bool counters_clean = false,
-                             const ScanJob* also = nullptr);
-int launch_cam_bwd_cell(const VampRenderDesc* d, const RenderParams& P, const float* Gcl,
-                        float* gdens, float* gsem, float* grgb, void* scratch, int accumulate,
-                        hipEvent_t wait_event, int parts, BetaTail btail, hipStream_t s);
-
-static size_t gcl_bytes(const VampRenderDesc* d) {
-  const RenderParams P = to_params(d);
-  return align_up((size_t) d->B * d->N * d->fH * d->fW * P.CP * sizeof(float), 256);
-}
-
-static size_t beta_part_bytes(const VampRenderDesc* d) {
-  return align_up((size_t) ray_grid<4>(to_params(d)) * sizeof(float), 256);
-}
-
-size_t cam_bwd_v2_bytes(const VampRenderDesc* d) { return gcl_bytes(d) + cam_bwd_cell_bytes(d) + beta_part_bytes(d); }
-
-// the cell lists inside the render workspace: [packed volume | Gcl | cell lists | beta partials]
-CamRankRefs cam_rank_refs_cells(const VampRenderDesc* d, void* scratch);
-int launch_cam_cells_zero(const VampRenderDesc* d, void* scratch, hipStream_t s);
-static void* cell_scratch_of(const VampRenderDesc* d, void* workspace) {
-  return static_cast<char*>(workspace) + packed_bytes(d) + gcl_bytes(d);
-}
-CamRankRefs cam_rank_refs(const VampRenderDesc* d, void* workspace) { return cam_rank_refs_cells(d, cell_scratch_of(d, workspace)); }
-int launch_cam_counters_zero(const VampRenderDesc* d, void* workspace, hipStream_t s) {
-  return launch_cam_cells_zero(d, cell_scratch_of(d, workspace), s);
-}
-int launch_cam_prepare_ranked(const VampRenderDesc* d, void* workspace, hipStream_t s, const ScanJob* also) {
-  return launch_cam_cells_prepare(d, to_params(d), nullptr, nullptr, nullptr, nullptr, cell_scratch_of(d, workspace), nullptr,
-                                  /*phase=*/3, s, false, also);
-}
-
-// scratch = workspace region after the packed volume: [Gcl | cell lists | beta partials]
-int launch_cam_prepare(const VampRenderDesc* d, const RenderParams& P, const float* mats,
-                       const float* us, const float* vs, const float* ds, void* scratch,
-                       const int* term, int phase, hipStream_t s, bool counters_clean, const ScanJob* also) {
-  return launch_cam_cells_prepare(d, P, mats, us, vs, ds, static_cast<char*>(scratch) + gcl_bytes(d), term, phase, s,
-                                  counters_clean, also);
-}
-
-int launch_cam_bwd_v2(const VampRenderDesc* d, const RenderParams& P, const float* mats,
-                      const float* us, const float* vs, const float* ds, const float* mids,
-                      const float* beta, const void* dens, const void* sem, const void* rgbv, const float* g_rgb,
-                      const float* g_seg, const float* g_depth, float* gdens, float* gsem,
-                      float* grgb, float* grad_beta, void* scratch, int accumulate,
-                      hipEvent_t wait_event, int cells_valid, const float* samples, const int* term,
-                      int parts, hipStream_t s) {
-  float* Gcl = static_cast<float*>(scratch);
-  void* cell_scratch = static_cast<char*>(scratch) + gcl_bytes(d);
+// launch what the backward's plan (render_bwd.hip: camera_backward_plan) says
+int launch_cam_bwd_v2(const VampRenderDesc* d, const RenderParams& P, const VampCameraBackwardPlan& p,
+                      const CamWorkspace& w, const float* mats, const float* us, const float* vs, const float* ds,
+                      const float* mids, const float* beta, const void* dens, const void* sem, const void* rgbv,
+                      const float* g_rgb, const float* g_seg, const float* g_depth, float* gdens, float* gsem,
+                      float* grgb, float* grad_beta, hipEvent_t wait_event, hipStream_t s) {
   // the ray pass leaves one d beta partial per workgroup; the gather's first workgroup adds them up
   BetaTail btail{nullptr, 0, nullptr, nullptr};
-  if (P.density_mode == VAMP_DENSITY_SDF_LAPLACE && (parts & kCamPartGather))
-    btail = BetaTail{reinterpret_cast<const float*>(static_cast<char*>(cell_scratch) + cam_bwd_cell_bytes(d)),
-                     (int) ray_grid<4>(P), beta, grad_beta};
-  if (!(parts & kCamPartRay))
-    return launch_cam_bwd_cell(d, P, Gcl, gdens, gsem, grgb, cell_scratch, accumulate, wait_event, parts, btail, s);
-  // the sample -> slot table depends on the geometry only; the caller may have prepared it
-  // (cells_valid 1), or its rank + scan half (2, a caller of rounds 2 - 5: nothing left to do here -- the work lists are built by this launch's tail)
-  if (cells_valid != 1)
-    if (int e = launch_cam_cells_prepare(d, P, mats, us, vs, ds, cell_scratch, term, cells_valid == 2 ? 2 : 0, s)) return e;
-  const CamCellRefs cells = cam_cell_refs(d, cell_scratch);
-  float* beta_part = reinterpret_cast<float*>(static_cast<char*>(cell_scratch) + cam_bwd_cell_bytes(d));
-
-  constexpr int LPR = 4;
-  const int S = d->D - 1;
-  const int L = (S + LPR - 1) / LPR;
-  const size_t lds = (size_t) 3 * L * 256 * sizeof(float);
-  if (lds > 150 * 1024) return fail(VAMP_EINVAL, "%s: too many depth samples for the LDS staging", __func__);
-  const unsigned grid = ray_grid<LPR>(P);
-  CamListArgs lists = cam_list_args(d, cell_scratch);
-  lists.first_block = grid;
-  // (the list counters are zeroed by the cell scan and spent by this launch: VAMP_CAMBWD_CELLS_VALID holds for ONE
-  // backward per prepare pass, as the header says)
-  if (int e = debug_expect_range(lists.nhcells, 2, 0, 0, s,
-                                 "VAMP_CAMBWD_CELLS_VALID: no camera backward has run on this workspace since the prepare pass")) return e;
+  if (p.beta_tail) btail = BetaTail{w.beta_part, p.ray_grid, beta, grad_beta};
+  if (p.parts & kCamPartRay) {
+    const int* term = p.term ? w.term : nullptr;
+    const float* samples = p.samples ? w.rows : nullptr;
+    // the sample -> slot table depends on the geometry only; the caller may have prepared it (CELLS_VALID)
+    if (p.prepare)
+      if (int e = launch_cam_cells_prepare(d, P, mats, us, vs, ds, w, term, /*ranked=*/false, s)) return e;
+    const CamCellRefs cells = cam_cell_refs(d, w);
+    constexpr int LPR = 4;
+    const int L = (d->D - 1 + LPR - 1) / LPR;
+    const size_t lds = (size_t) p.ray_lds;
+    const unsigned grid = (unsigned) p.ray_grid;
+    CamListArgs lists = cam_list_args(d, w);
+    lists.first_block = grid;
+    // (the list counters are zeroed by the cell scan and spent by this launch: VAMP_CAMBWD_CELLS_VALID holds for ONE
+    // backward per prepare pass, as the header says)
+    if (int e = debug_expect_range(lists.nhcells, 2, 0, 0, s,
+                                   "VAMP_CAMBWD_CELLS_VALID: no camera backward has run on this workspace since the prepare pass")) return e;
 #define VAMP_RAY_T(T, CP4, KT)                                                                    \
   do {                                                                                            \
     auto kr = cam_bwd_ray_kernel<T, LPR, CP4, KT>;                                                \
-    if (lds > 64 * 1024 &&                                                                        \
+    if (p.raise_lds &&                                                                            \
         hipFuncSetAttribute(reinterpret_cast<const void*>(kr),                                    \
                             hipFuncAttributeMaxDynamicSharedMemorySize, (int) lds) != hipSuccess) \
       return fail(VAMP_EHIP, "%s: cannot raise dynamic LDS", __func__);                           \
-    VAMP_TIMED(kProfCamBwd, s, (kr<<<grid + lists.nblocks, 256, lds, s>>>(P, mats, us, vs, ds, mids, beta, \
+    VAMP_TIMED(kProfCamBwd, s, (kr<<<grid + (unsigned) p.list_grid, 256, lds, s>>>(P, mats, us, vs, ds, mids, beta, \
         static_cast<const T*>(dens), static_cast<const T*>(sem), static_cast<const T*>(rgbv),     \
-        g_rgb, g_seg, g_depth, cells, Gcl, beta_part, samples, term, L, lists)));               \
+        g_rgb, g_seg, g_depth, cells, w.Gcl, w.beta_part, samples, term, L, lists)));             \
   } while (0)
 #define VAMP_RAY(CP4, KT)                                                                         \
   do {                                                                                            \
     if (d->in_dtype == VAMP_F32) VAMP_RAY_T(float, CP4, KT); else VAMP_RAY_T(__hip_bfloat16, CP4, KT); \
   } while (0)
-  if (P.CP == 12) VAMP_RAY(3, 0); else if (P.CP == 24 && P.K == 18) VAMP_RAY(6, 18); else if (P.CP == 24) VAMP_RAY(6, 0); else VAMP_RAY(8, 0);
+    if (p.ray_cp4 == 3) VAMP_RAY(3, 0); else if (p.ray_cp4 == 6 && p.ray_kt == 18) VAMP_RAY(6, 18); else if (p.ray_cp4 == 6) VAMP_RAY(6, 0); else VAMP_RAY(8, 0);
 #undef VAMP_RAY
 #undef VAMP_RAY_T
-  if (int e = check_launch("cam_bwd_ray_kernel")) return e;
-  if (!(parts & (kCamPartGather | kCamPartHeavy))) return VAMP_OK;
-  return launch_cam_bwd_cell(d, P, Gcl, gdens, gsem, grgb, cell_scratch, accumulate, wait_event, parts, btail, s);
+    if (int e = check_launch("cam_bwd_ray_kernel")) return e;
+  }
+  if (!(p.parts & (kCamPartGather | kCamPartHeavy))) return VAMP_OK;
+  return launch_cam_bwd_cell(d, P, p, w, gdens, gsem, grgb, wait_event, btail, s);
 }
 
 }  // namespace vamp

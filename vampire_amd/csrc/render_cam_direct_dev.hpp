@@ -154,8 +154,6 @@ constexpr int kDirectCB = VAMP_DIRECT_CB; // channels whose loads are in flight 
 #ifndef VAMP_DIRECT_NW
 #define VAMP_DIRECT_NW 4
 #endif
-// channel count the kernel is instantiated for (K + 3 rounded up; 21 is the reference's K = 18 at compile time)
-inline int cam_direct_nch(int nch) { return nch <= 8 ? 8 : (nch <= 12 ? 12 : (nch == 21 ? 21 : (nch <= 24 ? 24 : 32))); }
 // dynamic LDS of a tile: tau / weights [S][64], then the merge buffer [NW][NCH][64]
 inline size_t cam_direct_dyn_bytes(int S, int NCH) {
   return sizeof(float) * 64 * (size_t) (S > VAMP_DIRECT_NW * NCH ? S : VAMP_DIRECT_NW * NCH);

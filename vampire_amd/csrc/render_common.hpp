@@ -1,6 +1,7 @@
 // Shared pieces of the camera / BEV render kernels.
 #pragma once
 #include "common.hpp"
+#include "cell_list.hpp"
 
 namespace vamp {
 
@@ -252,24 +253,6 @@ __device__ __forceinline__ float composite_weight(float tau, float cum) { return
 // ---------------------------------------------------------------------------
 constexpr float kTermOpticalDepth = 18.0f;
 
-// bytes of the per-ray table (int per ray), and where it lives in the render workspace: behind
-// the base region [packed | max(gradient copy, backward scratch)]
-size_t packed_bytes(const VampRenderDesc* d);
-size_t cam_bwd_v2_bytes(const VampRenderDesc* d);
-inline size_t cam_term_bytes(const VampRenderDesc* d) {
-  return align_up((size_t) d->B * d->N * d->fH * d->fW * sizeof(int), 256);
-}
-inline size_t render_base_bytes(const VampRenderDesc* d) {
-  const size_t pb = packed_bytes(d), v2 = cam_bwd_v2_bytes(d);
-  return pb + (pb > v2 ? pb : v2);
-}
-inline int* cam_term_ptr(const VampRenderDesc* d, void* workspace) {
-  return reinterpret_cast<int*>(static_cast<char*>(workspace) + render_base_bytes(d));
-}
-int launch_cam_term(const VampRenderDesc* d, const RenderParams& P, const float* mats, const float* us,
-                    const float* vs, const float* ds, const float* beta, const void* density_feature,
-                    int* term, hipStream_t s);
-
 // What a forward that draws the camera backward's cell ranks itself needs of the cell lists (round 6: the rank pass
 // of the prepare step inside the one-kernel camera forward's gather phase, render_cam_direct_dev.hpp): cell counters
 // (zero on entry), the per-sample rank table, the tiles' depths.
@@ -280,13 +263,150 @@ struct CamRankRefs {
   long ncell_b;         // cells per sample of the batch
   float* zero_word;     // not nullptr: the launch also stores 0.f there (the backward's d loss / d beta accumulator)
 };
-// `workspace`: the render workspace (vamp_render_workspace_bytes).  render_bwd_ray.hip
-CamRankRefs cam_rank_refs(const VampRenderDesc* d, void* workspace);
-// zero the cell counters (a forward that draws ranks on a workspace not known clean) / scan them and build the heavy
-// list behind such a forward (what vamp_render_camera_prepare does behind its own rank pass)
-int launch_cam_counters_zero(const VampRenderDesc* d, void* workspace, hipStream_t s);
-// (`also`: another cell list scanned by the same launch -- the lift's, vamp_render_camera_prepare_with_lift)
-int launch_cam_prepare_ranked(const VampRenderDesc* d, void* workspace, hipStream_t s, const ScanJob* also = nullptr);
+
+// what the per-ray pass of the camera backward needs of the cell lists (render_bwd_cell.hip)
+struct CamCellRefs {
+  const int* tile_order; // [tiles] the order in which the per-ray pass takes the tiles (longest first), or nullptr
+  const int* rank;      // [tiles][S][64] rank of a kept inside sample in its cell
+  int* slot;            // [tiles][S][64] scratch of the per-ray pass
+  const int* off;       // cell start = off[c] + boff[c / kScanTile]
+  const int* boff;
+  float4* R;            // [samples][2] records in cell order
+  long ncell_b;         // cells per sample of the batch
+};
+
+// parts of the camera backward a caller may issue separately (VAMP_CAMBWD_PART_*): the per-ray pass
+// (with the cell lists if they are not prepared), the heavy cells' per-corner sums, the per-voxel gather
+constexpr int kCamPartRay = 1, kCamPartGather = 2, kCamPartHeavy = 4, kCamPartAll = 7;
+
+#ifndef VAMP_CELL_HEAVY
+#define VAMP_CELL_HEAVY 32
+#endif
+constexpr int kCellHeavy = VAMP_CELL_HEAVY;   // records per cell beyond which the cell is summed once per corner (cam_cell_splat_kernel)
+constexpr int kRunVox = 32;                  // voxels (an x-run) per gather workgroup
+
+// The render workspace (vamp_render_workspace_bytes, + vamp_render_samples_bytes for `rows`), in this order, every
+// region 256-byte aligned:
+//   packed volumes [B, Z, Y, X, CP] | the larger of { the v1 splat's gradient copy (as large as packed) } and
+//   { Gcl [rays][CP] | the 13 cell-list regions | d beta partials, one per ray tile } | termination table [rays] |
+//   sample rows [8 x 8 ray tile][depth index][channel][64]
+// base_bytes ends behind the termination table.  The forwards touch packed, term and rows (a forward that draws the
+// ranks: cnt, rank, tile_se too), the prepare pass the cell lists, the backward everything.
+struct CamWorkspace {
+  float* packed;
+  float* gpacked;  // overlays Gcl .. beta_part
+  float* Gcl;
+  int* cnt;        // [ncell + kScanPad] counters (+ the scan's ticket word)
+  int* off;        // [ncell] tile-local exclusive offsets
+  int* bsum;       // [ntile] tile totals
+  int* boff;       // [ntile] exclusive scan of the tile totals
+  int* aux;        // [ntile] scratch of the level-2 scan, then [ntile] = total, [ntile+1] = heavy cells listed, [ntile+2] = x-runs listed
+  int2* hcells;    // [max(ncell, samples / 16)] list of the heavy cells' chunks: {first record, records}
+  float* part;     // [samples / kCellHeavy + 2][8][CP] per-corner partial sums of the heavy cells
+  int* runs;       // [x-runs] list of the x-runs with records (accumulate mode)
+  int* rank;       // [tiles][S][64] rank of the sample inside its cell (written for kept inside samples only)
+  int* slot;       // [tiles][S][64] slot in R (-1 = masked): the per-ray pass's note between its two loops
+  int* tile_se;    // [tiles] kept samples of the tile's longest ray
+  int* tile_order; // [tiles] tiles sorted by that, longest first
+  float4* R;       // [samples][2] records in cell order
+  float* beta_part;
+  int* term;
+  float* rows;
+  size_t offset[VAMP_RENDERWS_REGIONS], bytes[VAMP_RENDERWS_REGIONS];   // of the regions above, in that order
+  size_t base_bytes, bytes_with_rows;
+  long ncell, ntile;   // cells (padded to scan tiles) and scan tiles of the lists
+};
+// `workspace` may be nullptr (only the sizes are of use then)
+inline CamWorkspace cam_workspace(const VampRenderDesc* d, void* workspace) {
+  const size_t CP = (size_t) to_params(d).CP;
+  const size_t rays = (size_t) d->B * d->N * d->fH * d->fW, samples = rays * (d->D - 1);
+  // per-sample tables are indexed by 8 x 8 ray tile (ragged tiles padded)
+  const size_t tiles = (size_t) d->B * d->N * ((d->fH + 7) / 8) * ((d->fW + 7) / 8), tsamples = tiles * 64 * (d->D - 1);
+  CamWorkspace w;
+  w.ncell = cell_count_padded(d->B, d->Z, d->Y, d->X);
+  w.ntile = w.ncell / kScanTile;
+  const size_t ncell = (size_t) w.ncell, ntile = (size_t) w.ntile;
+  size_t off = 0;
+  int region = 0;
+  auto take = [&](size_t n) {
+    char* p = workspace ? static_cast<char*>(workspace) + off : nullptr;
+    w.offset[region] = off;
+    w.bytes[region++] = n;
+    off += n;
+    return p;
+  };
+  const size_t pb = align_up((size_t) d->B * d->Z * d->Y * d->X * CP * sizeof(float), 256);
+  w.packed = reinterpret_cast<float*>(take(pb));
+  w.gpacked = reinterpret_cast<float*>(take(pb));
+  off -= pb;
+  w.Gcl = reinterpret_cast<float*>(take(align_up(rays * CP * sizeof(float), 256)));
+  w.cnt = reinterpret_cast<int*>(take(align_up((ncell + kScanPad) * sizeof(int), 256)));
+  w.off = reinterpret_cast<int*>(take(align_up(ncell * sizeof(int), 256)));
+  w.bsum = reinterpret_cast<int*>(take(align_up(ntile * sizeof(int), 256)));
+  w.boff = reinterpret_cast<int*>(take(align_up(ntile * sizeof(int), 256)));
+  w.aux = reinterpret_cast<int*>(take(align_up((ntile + 4) * sizeof(int), 256)));
+  w.hcells = reinterpret_cast<int2*>(take(align_up((ncell > samples / 16 + 4096 ? ncell : samples / 16 + 4096) * sizeof(int2), 256)));
+  w.part = reinterpret_cast<float*>(take(align_up((samples / kCellHeavy + 2) * 8 * CP * sizeof(float), 256)));
+  w.runs = reinterpret_cast<int*>(take(align_up((size_t) d->B * d->Z * d->Y * ((d->X + kRunVox - 1) / kRunVox) * sizeof(int), 256)));
+  w.rank = reinterpret_cast<int*>(take(align_up(tsamples * sizeof(int), 256)));
+  w.slot = reinterpret_cast<int*>(take(align_up(tsamples * sizeof(int), 256)));
+  w.tile_se = reinterpret_cast<int*>(take(align_up(tiles * sizeof(int), 256)));
+  w.tile_order = reinterpret_cast<int*>(take(align_up(tiles * sizeof(int), 256)));
+  w.R = reinterpret_cast<float4*>(take(align_up(samples * 2 * sizeof(float4), 256)));
+  w.beta_part = reinterpret_cast<float*>(take(align_up((size_t) ray_grid<4>(to_params(d)) * sizeof(float), 256)));   // one per workgroup of the per-ray pass
+  if (off < 2 * pb) off = 2 * pb;
+  w.term = reinterpret_cast<int*>(take(align_up(rays * sizeof(int), 256)));
+  w.base_bytes = off;
+  w.rows = reinterpret_cast<float*>(take(align_up(tiles * 64 * (d->D - 1) * CP * sizeof(float), 256)));
+  w.bytes_with_rows = off;
+  return w;
+}
+
+// ---- the camera branch's host functions that cross files, each declared here once ----
+// render_fwd.hip
+int launch_pack(const RenderParams& P, int in_dtype, const void* dens, const void* sem,
+                const void* rgb, float* packed, hipStream_t s);
+int launch_cam_term(const VampRenderDesc* d, const RenderParams& P, const float* mats, const float* us,
+                    const float* vs, const float* ds, const float* beta, const void* density_feature,
+                    int* term, hipStream_t s);
+// The forward's plan for `who` (the entry point whose name a refusal carries): vamp_render_camera_forward_plan.
+// The merged forward asks it too, for its camera half (DIRECT, early termination on).
+int camera_forward_plan(const char* who, const VampRenderDesc* d, bool has_geom, int flags, size_t workspace_bytes,
+                        VampCameraForwardPlan* out);
+// render_bwd_cell.hip
+CamCellRefs cam_cell_refs(const VampRenderDesc* d, const CamWorkspace& w);
+CamRankRefs cam_rank_refs(const VampRenderDesc* d, const CamWorkspace& w);
+// zero the cell counters (a forward that draws ranks on a workspace not known clean)
+int launch_cam_counters_zero(const CamWorkspace& w, hipStream_t s);
+// the prepare pass refuses these shapes; nothing is launched for them (`who` as above)
+int cam_cells_fit(const char* who, const VampRenderDesc* d);
+// The prepare pass: rank + scan (what needs the geometry and the termination table), or -- `ranked` -- only the scan
+// behind a forward that has drawn the ranks itself (mats .. term unused).  `also`: another cell list scanned by the same
+// launch (the lift's, vamp_render_camera_prepare_with_lift).
+int launch_cam_cells_prepare(const VampRenderDesc* d, const RenderParams& P, const float* mats,
+                             const float* us, const float* vs, const float* ds, const CamWorkspace& w,
+                             const int* term, bool ranked, hipStream_t s, bool counters_clean = false,
+                             const ScanJob* also = nullptr);
+// grids of the heavy-cell and gather launches, for the backward's plan; false: too many x-runs
+bool cam_bwd_cell_grids(const VampRenderDesc* d, int* heavy_grid, int* heavy_waves, int* gather_grid);
+int launch_cam_bwd_cell(const VampRenderDesc* d, const RenderParams& P, const VampCameraBackwardPlan& p,
+                        const CamWorkspace& w, float* gdens, float* gsem, float* grgb, hipEvent_t wait_event,
+                        BetaTail btail, hipStream_t s);
+// render_bwd_ray.hip: the cell-list backward, as the plan says
+int launch_cam_bwd_v2(const VampRenderDesc* d, const RenderParams& P, const VampCameraBackwardPlan& p,
+                      const CamWorkspace& w, const float* mats, const float* us, const float* vs, const float* ds,
+                      const float* mids, const float* beta, const void* dens, const void* sem, const void* rgbv,
+                      const float* g_rgb, const float* g_seg, const float* g_depth, float* gdens, float* gsem,
+                      float* grgb, float* grad_beta, hipEvent_t wait_event, hipStream_t s);
+// render_bwd.hip: v1 BEV backward (column threads + float atomics); kept as an independent cross-check
+int launch_bev_bwd_v1(const VampRenderDesc* d, const float* oxs, const float* oys,
+                      const float* ozs, const float* bev_mids, const float* beta,
+                      const void* density_feature, const void* semantic, const void* rgb,
+                      const void* base, const float* g_bev_rgb, const float* g_bev_seg,
+                      const float* g_bev_height, const float* g_voxel_density,
+                      const float* g_voxel_output, float* grad_density_feature,
+                      float* grad_semantic, float* grad_rgb, float* grad_base, float* grad_beta,
+                      void* stream);
 
 // d beta partial sums the BEV backward's scan leaves in the BEV workspace: one per workgroup of bev_scan_kernel, or
 // -- when the forward kept its samples -- of bev_qscan_saved_kernel.  Either count is the larger one, depending on
@@ -332,6 +452,8 @@ inline BevWorkspace bev_workspace(const VampRenderDesc* d, void* workspace) {
   return w;
 }
 
+// channel count the one-kernel camera forward (render_cam_direct.hip, render_fwd_merged.hip) is instantiated for (K + 3 rounded up; 21 is the reference's K = 18 at compile time)
+inline int cam_direct_nch(int nch) { return nch <= 8 ? 8 : (nch <= 12 ? 12 : (nch == 21 ? 21 : (nch <= 24 ? 24 : 32))); }
 // render_cam_direct.hip: plan + density march + scan + channel gather in one kernel, on the
 // channel-first volumes; term_out (may be NULL) receives the per-ray table
 int launch_cam_fwd_direct(const VampRenderDesc* d, const RenderParams& P, const float* mats, const float* us,
@@ -421,20 +543,5 @@ __device__ __forceinline__ void gather_taps(const RenderParams& P, const float* 
     }
   }
 }
-
-// what the per-ray pass of the camera backward needs of the cell lists (render_bwd_cell.hip)
-struct CamCellRefs {
-  const int* tile_order; // [tiles] the order in which the per-ray pass takes the tiles (longest first), or nullptr
-  const int* rank;      // [tiles][S][64] rank of a kept inside sample in its cell
-  int* slot;            // [tiles][S][64] scratch of the per-ray pass
-  const int* off;       // cell start = off[c] + boff[c / kScanTile]
-  const int* boff;
-  float4* R;            // [samples][2] records in cell order
-  long ncell_b;         // cells per sample of the batch
-};
-
-// parts of the camera backward a caller may issue separately (VAMP_CAMBWD_PART_*): the per-ray pass
-// (with the cell lists if they are not prepared), the heavy cells' per-corner sums, the per-voxel gather
-constexpr int kCamPartRay = 1, kCamPartGather = 2, kCamPartHeavy = 4, kCamPartAll = 7;
 
 }  // namespace vamp

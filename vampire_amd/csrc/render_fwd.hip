@@ -495,25 +495,101 @@ int launch_pack(const RenderParams& P, int in_dtype, const void* dens, const voi
   return check_launch("pack_volume_kernel");
 }
 
+// The forward's plan: every choice vamp_render_camera_forward_ex makes, from the descriptor, geom given or not, the
+// flags and the workspace size.  No HIP call.
+int camera_forward_plan(const char* who, const VampRenderDesc* d, bool has_geom, int flags, size_t workspace_bytes,
+                        VampCameraForwardPlan* out) {
+  if (!out) return fail(VAMP_EINVAL, "%s: requirement failed: plan is NULL", who);
+  memset(out, 0, sizeof(*out));
+  if (int e = validate(d)) return e;
+  VampCameraForwardPlan& p = *out;
+  const RenderParams P = to_params(d);
+  const CamWorkspace w = cam_workspace(d, nullptr);
+  // geometry from the matrices and at most kPlanMax samples per ray: the ray plan applies
+  const bool planned = !has_geom && d->D - 1 <= kPlanMax;
+  p.save_rows = (flags & VAMP_CAMFWD_SAVE_SAMPLES) && planned;
+  p.ert = planned && !(flags & VAMP_CAMFWD_NO_ERT);
+  p.grid = (int) ray_grid<4>(P);
+  if ((flags & VAMP_CAMFWD_DIRECT) && planned) {
+    // one kernel on the channel-first volumes (render_cam_direct.hip): no packed copy, the termination table is a
+    // by-product (written when the workspace can hold it); with SAVE_SAMPLES the samples' values stay behind the base
+    // region for the backward's per-ray pass
+    p.path = VAMP_CAMPLAN_FWD_DIRECT;
+    p.bytes_needed = p.save_rows ? (int64_t) w.bytes_with_rows : 0;
+    p.term = workspace_bytes >= w.base_bytes ? VAMP_CAMPLAN_TERM_WRITE : VAMP_CAMPLAN_TERM_NONE;
+    p.body = cam_direct_nch(P.K + 3);
+  } else {
+    p.path = planned ? VAMP_CAMPLAN_FWD_PLANNED : VAMP_CAMPLAN_FWD_MARCH;
+    p.bytes_needed = (int64_t) (p.save_rows ? w.bytes_with_rows : (p.ert ? w.base_bytes : w.bytes[VAMP_RENDERWS_PACKED]));
+    p.term = !p.ert ? VAMP_CAMPLAN_TERM_NONE
+                    : ((flags & VAMP_CAMFWD_TERM_VALID) ? VAMP_CAMPLAN_TERM_CHECK : VAMP_CAMPLAN_TERM_BUILD);
+    // VAMP_CAMFWD_PACK_ONLY / _PACKED_VALID: the channel-last copy as a call of its own (a caller with two streams
+    // packs beside its other work and marches when both are there)
+    p.pack = !(flags & VAMP_CAMFWD_PACKED_VALID);
+    p.pack_only = (flags & VAMP_CAMFWD_PACK_ONLY) != 0;
+    p.body = P.CP / 4;
+    if (p.pack_only) p.body = p.grid = 0;
+  }
+  if (workspace_bytes < (size_t) p.bytes_needed)
+    return fail(VAMP_ENOSPC, "%s: workspace %ld < %ld bytes", who, (long) workspace_bytes, (long) p.bytes_needed);
+  return VAMP_OK;
+}
+
+// the channel-last copy's marches, as the plan says
+static int launch_cam_march(const RenderParams& P, const VampCameraForwardPlan& p, const CamWorkspace& w,
+                            const float* geom, const float* mats, const float* us, const float* vs, const float* ds,
+                            const float* mids, const float* beta, float* rgb_out, float* seg_out, float* depth_out,
+                            hipStream_t s) {
+  const unsigned grid = (unsigned) p.grid;
+  const float* packed = w.packed;
+  const int* term = p.ert ? w.term : nullptr;
+  if (p.path == VAMP_CAMPLAN_FWD_PLANNED) {
+    float* samples = w.rows;
+#define VAMP_CAMP(CP4)                                                                     \
+  do {                                                                                     \
+    if (p.save_rows)                                                                       \
+      VAMP_TIMED(kProfCamFwd, s, (render_cam_fwd_plan_kernel<CP4, true><<<grid, 256, 0, s>>>(  \
+          P, mats, us, vs, ds, mids, beta, packed, rgb_out, seg_out, depth_out, samples, term)));    \
+    else                                                                                   \
+      VAMP_TIMED(kProfCamFwd, s, (render_cam_fwd_plan_kernel<CP4, false><<<grid, 256, 0, s>>>( \
+          P, mats, us, vs, ds, mids, beta, packed, rgb_out, seg_out, depth_out, nullptr, term)));    \
+  } while (0)
+    if (p.body == 3) VAMP_CAMP(3); else if (p.body == 6) VAMP_CAMP(6); else VAMP_CAMP(8);
+#undef VAMP_CAMP
+    return check_launch("render_cam_fwd_plan_kernel");
+  }
+#define VAMP_CAM(CP4)                                                                        \
+  VAMP_TIMED(kProfCamFwd, s, (render_cam_fwd_kernel<4, CP4, true><<<grid, 256, 0, s>>>(      \
+      P, geom, mats, us, vs, ds, mids, beta, packed, rgb_out, seg_out, depth_out)))
+  if (p.body == 3) VAMP_CAM(3); else if (p.body == 6) VAMP_CAM(6); else VAMP_CAM(8);
+#undef VAMP_CAM
+  return check_launch("render_cam_fwd_kernel");
+}
+
 }  // namespace vamp
 
 using namespace vamp;
 
-namespace vamp {
-size_t packed_bytes(const VampRenderDesc* d) {
-  const RenderParams P = to_params(d);
-  return align_up((size_t) d->B * d->Z * d->Y * d->X * P.CP * sizeof(float), 256);
-}
-}  // namespace vamp
-
 extern "C" {
 
+size_t vamp_render_workspace_bytes(const VampRenderDesc* d) { return d ? cam_workspace(d, nullptr).base_bytes : 0; }
 
-size_t vamp_render_workspace_bytes(const VampRenderDesc* d) {
-  if (!d) return 0;
-  // packed volume + backward scratch (v1: packed gradient volume; v2: per-sample buffers) + the
-  // per-ray early-termination table
-  return render_base_bytes(d) + cam_term_bytes(d);
+size_t vamp_render_term_offset(const VampRenderDesc* d) { return d ? cam_workspace(d, nullptr).offset[VAMP_RENDERWS_TERM] : 0; }
+
+size_t vamp_render_samples_bytes(const VampRenderDesc* d) { return d ? cam_workspace(d, nullptr).bytes[VAMP_RENDERWS_ROWS] : 0; }
+
+int vamp_render_workspace_layout(const VampRenderDesc* d, VampRenderWorkspaceLayout* out) {
+  VAMP_REQUIRE(out != nullptr, "layout is NULL");
+  memset(out, 0, sizeof(*out));
+  if (int e = validate(d)) return e;
+  const CamWorkspace w = cam_workspace(d, nullptr);
+  for (int i = 0; i < VAMP_RENDERWS_REGIONS; ++i) {
+    out->offset[i] = (int64_t) w.offset[i];
+    out->bytes[i] = (int64_t) w.bytes[i];
+  }
+  out->base_bytes = (int64_t) w.base_bytes;
+  out->bytes_with_rows = (int64_t) w.bytes_with_rows;
+  return VAMP_OK;
 }
 
 int vamp_render_camera_terminate(const VampRenderDesc* d, const float* mats, const float* us,
@@ -523,21 +599,11 @@ int vamp_render_camera_terminate(const VampRenderDesc* d, const float* mats, con
   if (int e = validate(d)) return e;
   VAMP_REQUIRE(mats && us && vs && ds && density_feature, "null pointer");
   VAMP_REQUIRE(beta || d->density_mode == VAMP_DENSITY_SIGMOID, "beta is NULL");
-  const size_t need = vamp_render_workspace_bytes(d);
-  if (!workspace || workspace_bytes < need)
-    return fail(VAMP_ENOSPC, "%s: workspace %ld < %ld bytes", __func__, (long) workspace_bytes, (long) need);
-  return launch_cam_term(d, to_params(d), mats, us, vs, ds, beta, density_feature, cam_term_ptr(d, workspace),
+  const CamWorkspace w = cam_workspace(d, workspace);
+  if (!workspace || workspace_bytes < w.base_bytes)
+    return fail(VAMP_ENOSPC, "%s: workspace %ld < %ld bytes", __func__, (long) workspace_bytes, (long) w.base_bytes);
+  return launch_cam_term(d, to_params(d), mats, us, vs, ds, beta, density_feature, w.term,
                          static_cast<hipStream_t>(stream));
-}
-
-size_t vamp_render_term_offset(const VampRenderDesc* d) { return d ? render_base_bytes(d) : 0; }
-
-size_t vamp_render_samples_bytes(const VampRenderDesc* d) {
-  if (!d) return 0;
-  const RenderParams P = to_params(d);
-  // [8 x 8 ray tile][depth index][channel][ray of the tile] (ragged tiles padded)
-  const size_t tiles = (size_t) d->B * d->N * ((d->fH + 7) / 8) * ((d->fW + 7) / 8);
-  return align_up(tiles * 64 * (d->D - 1) * P.CP * sizeof(float), 256);
 }
 
 int vamp_render_camera_forward(const VampRenderDesc* d, const float* geom, const float* mats,
@@ -548,6 +614,11 @@ int vamp_render_camera_forward(const VampRenderDesc* d, const float* geom, const
                                size_t workspace_bytes, void* stream) {
   return vamp_render_camera_forward_ex(d, geom, mats, us, vs, ds, mids, beta, density_feature, semantic, rgb,
                                        rgb_out, seg_out, depth_out, workspace, workspace_bytes, 0, stream);
+}
+
+int vamp_render_camera_forward_plan(const VampRenderDesc* d, int has_geom, int flags, size_t workspace_bytes,
+                                    VampCameraForwardPlan* out) {
+  return camera_forward_plan(__func__, d, has_geom != 0, flags, workspace_bytes, out);
 }
 
 int vamp_render_camera_forward_ex(const VampRenderDesc* d, const float* geom, const float* mats,
@@ -561,70 +632,24 @@ int vamp_render_camera_forward_ex(const VampRenderDesc* d, const float* geom, co
   VAMP_REQUIRE(mids && density_feature && semantic && rgb && rgb_out && seg_out && depth_out,
                "null pointer");
   VAMP_REQUIRE(beta || d->density_mode == VAMP_DENSITY_SIGMOID, "beta is NULL");
-  const bool planned = !geom && d->D - 1 <= kPlanMax;
-  if ((flags & VAMP_CAMFWD_DIRECT) && planned) {
-    // one kernel on the channel-first volumes (render_cam_direct.hip): no packed copy, the
-    // termination table is a by-product (written when the workspace can hold it); with SAVE_SAMPLES the
-    // samples' values stay behind the base region for the backward's per-ray pass
-    const bool ert = !(flags & VAMP_CAMFWD_NO_ERT);
-    int* term = (workspace && workspace_bytes >= vamp_render_workspace_bytes(d)) ? cam_term_ptr(d, workspace) : nullptr;
-    float* rows = nullptr;
-    if (flags & VAMP_CAMFWD_SAVE_SAMPLES) {
-      const size_t need = vamp_render_workspace_bytes(d) + vamp_render_samples_bytes(d);
-      if (!workspace || workspace_bytes < need)
-        return fail(VAMP_ENOSPC, "%s: workspace %ld < %ld bytes", __func__, (long) workspace_bytes, (long) need);
-      rows = reinterpret_cast<float*>(static_cast<char*>(workspace) + vamp_render_workspace_bytes(d));
-    }
-    const RenderParams P = to_params(d);
-    return launch_cam_fwd_direct(d, P, mats, us, vs, ds, mids, beta, density_feature, semantic, rgb,
-                                 rgb_out, seg_out, depth_out, term, ert, rows, static_cast<hipStream_t>(stream));
-  }
-  const bool save = (flags & VAMP_CAMFWD_SAVE_SAMPLES) && planned;
-  const bool ert = planned && !(flags & VAMP_CAMFWD_NO_ERT);
-  const size_t need = save ? vamp_render_workspace_bytes(d) + vamp_render_samples_bytes(d)
-                           : (ert ? vamp_render_workspace_bytes(d) : packed_bytes(d));
-  if (!workspace || workspace_bytes < need)
-    return fail(VAMP_ENOSPC, "%s: workspace %ld < %ld bytes", __func__, (long) workspace_bytes, (long) need);
+  VampCameraForwardPlan p;
+  if (int e = camera_forward_plan(__func__, d, geom != nullptr, flags, workspace ? workspace_bytes : 0, &p)) return e;
   const RenderParams P = to_params(d);
+  const CamWorkspace w = cam_workspace(d, workspace);
   hipStream_t s = static_cast<hipStream_t>(stream);
-  float* packed = static_cast<float*>(workspace);
-  float* samples = save ? reinterpret_cast<float*>(static_cast<char*>(workspace) + vamp_render_workspace_bytes(d))
-                        : nullptr;
-  int* term = ert ? cam_term_ptr(d, workspace) : nullptr;
-  if (ert && !(flags & VAMP_CAMFWD_TERM_VALID)) {
-    if (int e = launch_cam_term(d, P, mats, us, vs, ds, beta, density_feature, term, s)) return e;
-  } else if (ert) {
-    if (int e = debug_expect_range(term, (size_t) d->B * d->N * d->fH * d->fW, 0, d->D - 1, s,
+  if (p.path == VAMP_CAMPLAN_FWD_DIRECT)
+    return launch_cam_fwd_direct(d, P, mats, us, vs, ds, mids, beta, density_feature, semantic, rgb, rgb_out, seg_out,
+                                 depth_out, p.term ? w.term : nullptr, p.ert, p.save_rows ? w.rows : nullptr, s);
+  if (p.term == VAMP_CAMPLAN_TERM_BUILD) {
+    if (int e = launch_cam_term(d, P, mats, us, vs, ds, beta, density_feature, w.term, s)) return e;
+  } else if (p.term == VAMP_CAMPLAN_TERM_CHECK) {
+    if (int e = debug_expect_range(w.term, (size_t) d->B * d->N * d->fH * d->fW, 0, d->D - 1, s,
                                    "VAMP_CAMFWD_TERM_VALID: the workspace holds a termination table")) return e;
   }
-  // VAMP_CAMFWD_PACK_ONLY / _PACKED_VALID: the channel-last copy as a call of its own (a caller
-  // with two streams packs beside its other work and marches when both are there)
-  if (!(flags & VAMP_CAMFWD_PACKED_VALID))
-    if (int e = launch_pack(P, d->in_dtype, density_feature, semantic, rgb, packed, s)) return e;
-  if (flags & VAMP_CAMFWD_PACK_ONLY) return VAMP_OK;
-  constexpr int LPR = 4;
-  const unsigned grid = ray_grid<LPR>(P);
-  // geometry from the matrices and at most kPlanMax samples per ray: the planned march
-  if (planned) {
-#define VAMP_CAMP(CP4)                                                                     \
-  do {                                                                                     \
-    if (samples)                                                                           \
-      VAMP_TIMED(kProfCamFwd, s, (render_cam_fwd_plan_kernel<CP4, true><<<grid, 256, 0, s>>>(  \
-          P, mats, us, vs, ds, mids, beta, packed, rgb_out, seg_out, depth_out, samples, term)));    \
-    else                                                                                   \
-      VAMP_TIMED(kProfCamFwd, s, (render_cam_fwd_plan_kernel<CP4, false><<<grid, 256, 0, s>>>( \
-          P, mats, us, vs, ds, mids, beta, packed, rgb_out, seg_out, depth_out, nullptr, term)));    \
-  } while (0)
-    if (P.CP == 12) VAMP_CAMP(3); else if (P.CP == 24) VAMP_CAMP(6); else VAMP_CAMP(8);
-#undef VAMP_CAMP
-    return check_launch("render_cam_fwd_plan_kernel");
-  }
-#define VAMP_CAM(CP4)                                                                        \
-  VAMP_TIMED(kProfCamFwd, s, (render_cam_fwd_kernel<LPR, CP4, true><<<grid, 256, 0, s>>>(    \
-      P, geom, mats, us, vs, ds, mids, beta, packed, rgb_out, seg_out, depth_out)))
-  if (P.CP == 12) VAMP_CAM(3); else if (P.CP == 24) VAMP_CAM(6); else VAMP_CAM(8);
-#undef VAMP_CAM
-  return check_launch("render_cam_fwd_kernel");
+  if (p.pack)
+    if (int e = launch_pack(P, d->in_dtype, density_feature, semantic, rgb, w.packed, s)) return e;
+  if (p.pack_only) return VAMP_OK;
+  return launch_cam_march(P, p, w, geom, mats, us, vs, ds, mids, beta, rgb_out, seg_out, depth_out, s);
 }
 
 int vamp_render_indices(const VampRenderDesc* d, const float* geom, const float* mats,

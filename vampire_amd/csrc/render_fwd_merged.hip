@@ -201,15 +201,13 @@ int vamp_render_forward_merged(const VampRenderDesc* d, const float* mats, const
   VAMP_REQUIRE(beta || d->density_mode == VAMP_DENSITY_SIGMOID, "beta is NULL");
   VAMP_REQUIRE(render_fwd_merged_supported(d), "shapes outside the merged launch's limits (vamp_render_forward_merged_supported)");
   VAMP_REQUIRE(bev_fused_heights_fit(d, ozs_host), "ozs_host is NULL or the heights do not fit the BEV plane slabs (vamp_render_forward_merged_supported)");
-  const size_t base_bytes = vamp_render_workspace_bytes(d);
-  int* term = (workspace && workspace_bytes >= base_bytes) ? cam_term_ptr(d, workspace) : nullptr;
-  float* rows = nullptr;
-  if (flags & VAMP_RENDERFWD_SAVE_SAMPLES) {
-    const size_t need = base_bytes + vamp_render_samples_bytes(d);
-    if (!workspace || workspace_bytes < need)
-      return fail(VAMP_ENOSPC, "%s: workspace %ld < %ld bytes", __func__, (long) workspace_bytes, (long) need);
-    rows = reinterpret_cast<float*>(static_cast<char*>(workspace) + base_bytes);
-  }
+  // the camera half is the one-kernel forward with early termination: its plan says what the render workspace receives
+  VampCameraForwardPlan cam;
+  if (int e = camera_forward_plan(__func__, d, false, VAMP_CAMFWD_DIRECT | ((flags & VAMP_RENDERFWD_SAVE_SAMPLES) ? VAMP_CAMFWD_SAVE_SAMPLES : 0),
+                                  workspace ? workspace_bytes : 0, &cam)) return e;
+  const CamWorkspace cw = cam_workspace(d, workspace);
+  int* term = cam.term ? cw.term : nullptr;
+  float* rows = cam.save_rows ? cw.rows : nullptr;
   float *s0_save = nullptr, *ss_save = nullptr;
   if (flags & VAMP_RENDERFWD_BEV_SAVE) {
     const BevWorkspace w = vamp::bev_workspace(d, bev_workspace);
@@ -224,10 +222,10 @@ int vamp_render_forward_merged(const VampRenderDesc* d, const float* mats, const
   hipStream_t s = static_cast<hipStream_t>(stream);
   if (flags & VAMP_RENDERFWD_RANK) {
     VAMP_REQUIRE(term != nullptr, "VAMP_RENDERFWD_RANK needs the render workspace");
-    rank = cam_rank_refs(d, workspace);
+    rank = cam_rank_refs(d, cw);
     if (flags & VAMP_RENDERFWD_COUNTERS_CLEAN) {
       if (int e = debug_expect_range(rank.cnt, 64, 0, 0, s, "VAMP_RENDERFWD_COUNTERS_CLEAN: the render workspace's cell counters are zero")) return e;
-    } else if (int e = launch_cam_counters_zero(d, workspace, s)) {
+    } else if (int e = launch_cam_counters_zero(cw, s)) {
       return e;
     }
   }

@@ -270,9 +270,7 @@ class HotPath:
             mats, beta, dens = tensors
             self.vamp.vamp_render_camera_terminate(d, mats, self.us, self.vs, self.ds, beta, dens, ws, ws.numel(),
                                                   _stream(stream))
-        off = self.vamp.vamp_render_term_offset(d)
-        n = d.B * d.N * c.fH * c.fW
-        term = ws[off:off + 4 * n].view(torch.int32).view(d.B * d.N, 1, c.fH, c.fW)
+        term = self._term_table(d, ws).view(d.B * d.N, 1, c.fH, c.fW)
         tile_max = torch.nn.functional.max_pool2d(term.float(), 8, ceil_mode=True)
         st["dev"].copy_((tile_max.mean() / float(c.D - 1)).reshape(1))
         st["host"].copy_(st["dev"], non_blocking=True)
@@ -289,6 +287,18 @@ class HotPath:
             self._ws[key] = t
             self._dirty.discard(key)
         return t
+
+    def _render_workspace(self, d, rows=False):
+        """The render workspace of a call on descriptor `d`: with room for the kept sample rows behind it, or without."""
+        nbytes = self.vamp.vamp_render_workspace_bytes(d)
+        if rows:
+            nbytes += self.vamp.vamp_render_samples_bytes(d)
+        return self._workspace("render", nbytes)
+
+    def _term_table(self, d, ws):
+        """The termination table inside the render workspace `ws`: a flat int32 view, one entry per ray."""
+        off = self.vamp.vamp_render_term_offset(d)
+        return ws[off:off + 4 * d.B * d.N * d.fH * d.fW].view(torch.int32)
 
     # ----------------------------------------------------------------- lift
     def lift(self, depth, feat, lift_mats, use_depth=True):
@@ -392,12 +402,11 @@ class HotPath:
         d = self.render_desc(B, N, _dtype_code(dens))
         mats = _chk(render_mats.float(), (B, N, 3, 4, 4), "render_mats")
         beta = (torch.zeros(1, device=self.device) if beta is None else beta.detach().reshape(1).float().contiguous())
-        ws = self._workspace("render", self.vamp.vamp_render_workspace_bytes(d))
+        ws = self._render_workspace(d)
         with torch.cuda.device(self.device):
             self.vamp.vamp_render_camera_terminate(d, mats, self.us, self.vs, self.ds, beta, dens, ws, ws.numel(),
                                                   _stream())
-            off = self.vamp.vamp_render_term_offset(d)
-            term = ws[off:off + 4 * B * N * c.fH * c.fW].view(torch.int32).reshape(B, N, 1, c.fH, c.fW).clone()
+            term = self._term_table(d, ws).reshape(B, N, 1, c.fH, c.fW).clone()
             inside = self.render_indices(render_mats=mats)[0].bool()
         idx = torch.arange(c.D - 1, device=self.device).reshape(1, 1, -1, 1, 1)
         self._pack_gen += 1         # the workspace no longer matches a saved forward
@@ -752,14 +761,11 @@ class _RenderFn(torch.autograd.Function):
         bev_h = torch.empty(B, 1, c.oY, c.oX, dtype=f32, device=dev)
         vdens = torch.empty(B, 1, c.oZ, c.oY, c.oX, dtype=f32, device=dev)
         vout = torch.empty(B, CO, c.oZ, c.oY, c.oX, dtype=f32, device=dev)
-        nbytes = hp.vamp.vamp_render_workspace_bytes(d)
         # training: the camera forward also keeps every inside sample's gathered values (tile-major rows, 256
         # contiguous bytes per tile, depth index and channel), and the backward's per-ray pass reads them back
         # instead of repeating the 8-tap gathers
         save = bool(train and geom is None and hp.impl["save_rows"] and hp.impl["cam_bwd"] != "v1" and (c.D - 1) <= 128)
-        if save:
-            nbytes += hp.vamp.vamp_render_samples_bytes(d)
-        ws = hp._workspace("render", nbytes)
+        ws = hp._render_workspace(d, rows=save)
         # which camera forward: the one kernel with early termination, or copy + planned march (with the
         # termination pre-pass or without) -- from the switches, or ("auto") from what the rays did lately
         ert, direct = hp._camera_forward_choice(geom is None and (c.D - 1) <= 128, geom is None)
@@ -879,10 +885,7 @@ class _RenderFn(torch.autograd.Function):
         cont = lambda t: None if t is None else t.contiguous().float()
         g_rgb, g_seg, g_dep, g_brgb, g_bseg, g_bh, g_vd, g_vo = map(
             cont, (g_rgb, g_seg, g_dep, g_brgb, g_bseg, g_bh, g_vd, g_vo))
-        nbytes = hp.vamp.vamp_render_workspace_bytes(d)
-        if ctx.samples:
-            nbytes += hp.vamp.vamp_render_samples_bytes(d)
-        ws = hp._workspace("render", nbytes)
+        ws = hp._render_workspace(d, rows=ctx.samples)
         ws_bev = hp._workspace("bev", hp.vamp.vamp_render_bev_workspace_bytes(d))
         # every gradient buffer is written in full by the calls below (the BEV branch overwrites,
         # the camera branch adds, or the other way round): no zero fills
