@@ -12,6 +12,8 @@
 #   traffic_<tag>.json / traffic_<tag>_fwd.json         HBM bytes per launch (separate --pmc FETCH_SIZE / WRITE_SIZE passes)
 #   bench_under_rocprof_<tag>.json                      the bench line printed under the profiler
 # usage: tools/collect_profiles.sh <round-tag> [cfg]
+#        ONLY=train_step_one_stream tools/collect_profiles.sh <tag>    just that kernel_stats file (an A/B of two libraries:
+#                                                                      VAMPIRE_HIP_LIB names the library, the tag the side)
 set -u
 TAG=${1:-r06}; CFG=${2:-B}
 ROOT=${GRAFT_REPO_ROOT:-$(pwd)}
@@ -20,8 +22,10 @@ rm -rf $OUT; mkdir -p $OUT
 cd /tmp && export TMPDIR=/tmp
 stats() {   # <name> <header> <script> [args...]
   local name=$1 hdr=$2; shift 2
+  [ -n "${ONLY:-}" ] && [ "$ONLY" != "$name" ] && return
   rm -rf $OUT/st
-  timeout 300 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/st -- python3 "$@" > $OUT/$name.log 2>&1
+  timeout 300 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/st -- python3 "$@" > $OUT/$name.log 2>&1 \
+    || { echo "$name: the profiled run ended with $? (see $OUT/$name.log); nothing more is started"; exit 1; }
   python3 $ROOT/tools/kernel_stats_csv.py $OUT/st $OUT/kernel_stats_${TAG}_$name.csv "$hdr" > /dev/null
   rm -rf $OUT/st
 }
@@ -33,6 +37,7 @@ unset VAMP_ERT VAMP_OVERLAP
 stats train_step_replayed "cfg-$CFG, 1 sample: 20 + 3 eager steps, then 200 replays of the captured two-stream step (tools/try_graph.py)" $ROOT/tools/try_graph.py $CFG 1 200
 stats fwd_pair "cfg-$CFG, 1 sample: the no-grad forward pair, 4 eager calls then 20 + 300 + 300 replays (tools/fwd_graph.py)" $ROOT/tools/fwd_graph.py $CFG 1 300 0
 stats cfg${CFG}_b8_replayed "cfg-$CFG, 8 samples per GPU: 20 + 3 eager steps, then 60 replays of the captured step (tools/try_graph.py)" $ROOT/tools/try_graph.py $CFG 8 60
+[ -n "${ONLY:-}" ] && { ls -la $OUT; exit 0; }
 # the bench line under the profiler (default-path kernels only)
 timeout 300 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/stats -- python3 $ROOT/bench.py --full --cfg $CFG --steps 20 --warmup 5 --no-cpu-baseline --no-extra --no-matrix > $OUT/bench_under_rocprof_$TAG.json 2> $OUT/bench_under_rocprof.log
 rm -rf $OUT/stats

@@ -43,20 +43,31 @@
 namespace vamp {
 
 // ---------------------------------------------------------------------------
-// fill: thread per voxel, the 64 lanes of a wave are 64 x-consecutive voxels
+// fill: thread per voxel, the 64 lanes of a wave are 64 consecutive voxels of one sample's flattened (z, y, x) index
 // ---------------------------------------------------------------------------
+#ifndef VAMP_FILL_NB
+#define VAMP_FILL_NB 3        // cameras per batch: their loads, then their atomics, are in flight together (4: scratch at C = 16)
+#endif
+#ifdef VAMP_LIFT_STAMPS
+// diagnostic build only (tools/debug/fill_stamps.py; -DVAMP_LIFT_STAMPS): per-wave phase stamps of the fill
+__device__ long long g_fill_stamps[16384 * 8];
+#define FSTAMP(i) fst[i] = __builtin_amdgcn_s_memtime()
+#else
+#define FSTAMP(i)
+#endif
+
 template <int CH>
-__global__ void __launch_bounds__(256, 4)
+__global__ void __launch_bounds__(256, 6)
 lift_bwd_fill_kernel(LiftParams P, int cw, int ch, const float* __restrict__ gout,
                      const uint64_t* __restrict__ hits, const unsigned* __restrict__ amask,
                      const float4* __restrict__ ptaps, const int* __restrict__ pcell,
                      int* __restrict__ cnt, const int* __restrict__ off, const int* __restrict__ boff,
-                     float4* __restrict__ recs, int* __restrict__ rowq, int bn_lo, int bn_hi) {
+                     float4* __restrict__ recs, int* __restrict__ rowq, int bn_lo, int bn_hi, int wps) {
   const int tid = threadIdx.x, lane = tid & 63;
   // A duty of the first workgroup, beside its voxels: the order in which the gather takes the image
   // rows -- those with the most pairs first (counting sort by the bit length of a row's pair count), so
   // that its long-running workgroups start early and the light ones fill the tail.
-  if (blockIdx.x == 0 && blockIdx.y == 0 && blockIdx.z == 0) {
+  if (blockIdx.x == 0) {
     __shared__ int cls[34];
     if (tid < 34) cls[tid] = 0;
     __syncthreads();
@@ -75,22 +86,34 @@ lift_bwd_fill_kernel(LiftParams P, int cw, int ch, const float* __restrict__ gou
     __syncthreads();
     for (int r = tid; r < nrow; r += 256) rowq[(long) bn_lo * P.fH + atomicAdd(cls + row_class(r), 1)] = bn_lo * P.fH + r;
   }
-  const int x = blockIdx.x * 64 + lane;
-  const int y = blockIdx.y * 4 + (tid >> 6);
-  const int z = blockIdx.z % P.Z, b = blockIdx.z / P.Z;
-  const bool live = x < P.X && y < P.Y;
-  const int xc = min(x, P.X - 1), yc = min(y, P.Y - 1);
+#ifdef VAMP_LIFT_STAMPS
+  long long fst[6];
+  FSTAMP(0);
+#endif
+  // wave w of the launch: sample w / wps, voxels 64 (w % wps) .. + 63 of its V.  A run of lanes that share a cell
+  // breaks at a row end at most (once per X voxels); with tiles of 64 x 4 voxels the last wave of a row of X = 200
+  // had 8 live lanes of 64 and paid every round trip of a full one.
   const long V = (long) P.Z * P.Y * P.X;
-  const long vox = ((long) z * P.Y + yc) * P.X + xc;
+  // (wave and sample are uniform: every plane and image base below is a scalar, the lane adds its 32-bit voxel)
+  const int wave = __builtin_amdgcn_readfirstlane(blockIdx.x * 4 + (tid >> 6));
+  const int b = wave / wps;
+  const int vox = (wave - b * wps) * 64 + lane;
+  const bool live = b < P.B && vox < V;
 
   // images [bn_lo, bn_hi) of the flattened (sample, camera) index
   const int n_lo = max(0, bn_lo - b * P.N), n_hi = min(P.N, bn_hi - b * P.N);
   const unsigned range = n_hi > n_lo ? (((1u << (n_hi - n_lo)) - 1u) << n_lo) : 0u;
-  const unsigned vmask = live ? (amask[(long) b * V + vox] & range) : 0u;
-  if (!__any(vmask != 0u)) return;                   // (9 % of the voxels are seen by no camera: whole waves of them leave here)
+  const unsigned vmask = live ? ((amask + (long) b * V)[vox] & range) : 0u;
+  // the cameras present in the wave (9 % of the voxels are seen by no camera: whole waves of them leave here)
+  unsigned um = 0;
+  for (int n = n_lo; n < n_hi; ++n)
+    if (__any((vmask >> n) & 1u)) um |= 1u << n;
+  if (um == 0u) return;
+  FSTAMP(1);
 
-  const int nchunk = P.C / CH;
-  const int RS = 2 + P.C / 4;                        // float4 pieces per record
+  const int C = P.C;
+  const int nchunk = C / CH;
+  const int RS = 2 + C / 4;                          // float4 pieces per record
   // The records of a wave's pairs leave through LDS: a lane's 32 + 4 C bytes are one record, but stored by the lane
   // itself they are RS separate 16-byte pieces 16 RS bytes apart (the first build of this kernel: 62 us).  Staged
   // [lane][piece] and written piece by piece with consecutive lanes on consecutive pieces, a record is one run, and
@@ -101,70 +124,107 @@ lift_bwd_fill_kernel(LiftParams P, int cw, int ch, const float* __restrict__ gou
   int* myslot = fslot[tid >> 6];
 
   // the voxel's row grad_out / (hit count + 1e-6), the camera-mean factor of bv2:512-514 -- the same for every
-  // camera of the voxel -- into the lane's LDS row behind the two tap pieces; its loads are in flight under the atomics
-  if (vmask != 0u) {
-    for (int chunk = 0; chunk < nchunk; ++chunk) {
-      const uint64_t hw = hits[((long) b * V + vox) * nchunk + chunk];
-      const float* g = gout + ((long) b * P.C + chunk * CH) * V + vox;
-      float v[CH];
+  // camera of the voxel -- into the lane's LDS row behind the two tap pieces
+  float v[CH];
+  uint64_t hw = 0;
+  auto row_load = [&](int chunk) {
+    if (vmask != 0u) {
+      hw = (hits + (long) b * V * nchunk)[(long) vox * nchunk + chunk];
+#pragma unroll
+      for (int k = 0; k < CH; ++k) v[k] = (gout + ((long) b * C + chunk * CH + k) * V)[vox];
+    }
+  };
+  auto row_stage = [&](int chunk) {
+    if (vmask != 0u) {
 #pragma unroll
       for (int k = 0; k < CH; ++k)
-        v[k] = g[(long) k * V] * __builtin_amdgcn_rcpf((float) ((hw >> (4 * k)) & 15) + 1e-6f);   // 1 ulp: gradients are held to 1e-4
+        v[k] *= __builtin_amdgcn_rcpf((float) ((hw >> (4 * k)) & 15) + 1e-6f);   // 1 ulp: gradients are held to 1e-4
 #pragma unroll
       for (int c4 = 0; c4 < CH; c4 += 4)
         my[lane * RS + 2 + (chunk * CH + c4) / 4] = make_float4(v[c4], v[c4 + 1], v[c4 + 2], v[c4 + 3]);
     }
-  }
+  };
+  // Three dependent round trips per wave: the mask; everything that needs only the mask -- the row and the taps and
+  // cells of the first batch of cameras, in flight together (the row's registers are free again before the atomics);
+  // the cursor atomics with the cells' start offsets beside them.
+  for (int chunk = 0; chunk < nchunk - 1; ++chunk) { row_load(chunk); row_stage(chunk); }
+  row_load(nchunk - 1);
 
-#ifndef VAMP_FILL_NB
-#define VAMP_FILL_NB 4        // (8: 122 registers, fill 43 us; 4: 74 registers, 40.5 us; 3 / 2: the same)
-#endif
-  constexpr int NB = VAMP_FILL_NB;                   // cameras per batch: their atomics are in flight together
-  for (int n0 = n_lo; n0 < n_hi; n0 += NB) {
-    int base[NB], start[NB];
-    long cellk[NB];
+  constexpr int NB = VAMP_FILL_NB;
+  auto batch = [&](auto first) {
+    int nk[NB], base[NB], start[NB], len[NB], cellk[NB], offk[NB], boffk[NB];
     float4 tapk[NB], depk[NB];
-    unsigned actm = 0;
+    int pck[NB];
+#pragma unroll
+    for (int k = 0; k < NB; ++k) {                   // the next NB cameras present (uniform)
+      nk[k] = um ? __ffs(um) - 1 : -1;
+      um &= um - 1u;
+    }
+    // No load of the batch sits in a branch of its own (the wait counters are exact only in straight-line code: a
+    // wait behind a skipped load waits for everything): a lane without the pair reads what the wave's first lane
+    // with it reads.
 #pragma unroll
     for (int k = 0; k < NB; ++k) {
-      const int n = n0 + k;
-      base[k] = 0;
-      start[k] = lane;
-      cellk[k] = 0;
       tapk[k] = make_float4(0.f, 0.f, 0.f, 0.f);
       depk[k] = tapk[k];
-      if (n >= n_hi) continue;                   // uniform
-      const bool act = (vmask >> n) & 1u;
-      if (!__any(act)) continue;                 // uniform: nobody in this wave has a pair with camera n
-      const long bn = (long) b * P.N + n;
-      long cell = 0;
-      if (act) {
-        tapk[k] = ptaps[(bn * V + vox) * 2];
-        depk[k] = ptaps[(bn * V + vox) * 2 + 1];
-        const int pc = pcell[bn * V + vox];
-        cell = (bn * ch + (pc >> 16)) * cw + (pc & 0xffff);
-      }
+      pck[k] = 0;
+      if (nk[k] < 0) continue;                       // uniform
+      const bool act = (vmask >> nk[k]) & 1u;
+      const int lv = act ? vox : vox - lane + (__ffsll((long long) __ballot(act)) - 1);
+      const long iv = ((long) b * P.N + nk[k]) * V;     // uniform
+      tapk[k] = (ptaps + iv * 2)[(long) lv * 2];
+      depk[k] = (ptaps + iv * 2)[(long) lv * 2 + 1];
+      pck[k] = (pcell + iv)[lv];
+    }
+    if (decltype(first)::value) row_stage(nchunk - 1);
+    if (decltype(first)::value) FSTAMP(2);
+#pragma unroll
+    for (int k = 0; k < NB; ++k) {                   // cells and runs of the whole batch, then its atomics back to back
+      base[k] = 0;
+      start[k] = lane;
+      len[k] = 0;
+      cellk[k] = 0;
+      offk[k] = 0;
+      boffk[k] = 0;
+      if (nk[k] < 0) continue;                       // uniform
+      const bool act = (vmask >> nk[k]) & 1u;
+      // (launch_lift_cells_begin: fewer than 2^31 cells)
+      const int cell = act ? (int) ((((long) b * P.N + nk[k]) * ch + (pck[k] >> 16)) * cw + (pck[k] & 0xffff)) : 0;
       cellk[k] = cell;
       const LaneRun r = lane_run(act, cell, lane);
-#ifdef VAMP_FILL_NOATOMIC          // (measurement build: wrong slots)
-      if (r.head) base[k] = 0;
-#else
-      if (r.head) base[k] = atomicAdd(cnt + cell, r.len);
-#endif
-      if (act) { actm |= 1u << k; start[k] = r.start; }
+      if (act) start[k] = r.start;
+      if (r.head) len[k] = r.len;
     }
 #pragma unroll
     for (int k = 0; k < NB; ++k) {
-      const int n = n0 + k;
-      if (n >= n_hi) continue;                   // uniform
-      if (!__any((actm >> k) & 1u)) continue;    // uniform
+      if (nk[k] < 0) continue;                       // uniform
+#ifndef VAMP_FILL_NOATOMIC         // (measurement build: wrong slots)
+      if (len[k] > 0) base[k] = atomicAdd(cnt + cellk[k], len[k]);
+#endif
+      // (the cell is known before the atomic returns: its start offset is asked for beside it)
+      offk[k] = off[cellk[k]];
+      boffk[k] = boff[cellk[k] / kScanTile];
+    }
+    if (decltype(first)::value) FSTAMP(3);
+    // every slot of the batch in front of the first store (a wait for an atomic behind stores waits for the stores)
+    int slotk[NB];
+#pragma unroll
+    for (int k = 0; k < NB; ++k) {
+      slotk[k] = -1;
+      if (nk[k] < 0) continue;                       // uniform
+      const bool act = (vmask >> nk[k]) & 1u;
       const int rb = __shfl(base[k], start[k], 64);
-      const bool act = (actm >> k) & 1u;
-      const long slot = act ? (long) off[cellk[k]] + boff[cellk[k] / kScanTile] + rb + (lane - start[k]) : -1;
+      if (act) slotk[k] = offk[k] + boffk[k] + rb + (lane - start[k]);
+    }
+    if (decltype(first)::value) FSTAMP(4);
+#pragma unroll
+    for (int k = 0; k < NB; ++k) {
+      if (nk[k] < 0) continue;                       // uniform
+      const int slot = slotk[k];
       // (a wave writes and reads its own slab: fence + wave barrier, no instruction on gfx9)
       my[lane * RS] = tapk[k];
       my[lane * RS + 1] = depk[k];
-      myslot[lane] = (int) slot;
+      myslot[lane] = slot;
       __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
       __builtin_amdgcn_wave_barrier();
       __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
@@ -180,7 +240,19 @@ lift_bwd_fill_kernel(LiftParams P, int cw, int ch, const float* __restrict__ gou
       __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
       __builtin_amdgcn_wave_barrier();
     }
+  };
+  batch(std::true_type{});
+  while (um) batch(std::false_type{});               // (more than NB cameras in one wave: none at six cameras)
+#ifdef VAMP_LIFT_STAMPS
+  FSTAMP(5);
+  const int npair_lanes = __popcll(__ballot(vmask != 0u));
+  if (lane == 0 && wave < 16384) {
+    long long* o = g_fill_stamps + (long) wave * 8;
+    for (int i = 0; i < 6; ++i) o[i] = fst[i];
+    o[6] = npair_lanes;
+    o[7] = 1;
   }
+#endif
 }
 
 // ---------------------------------------------------------------------------
@@ -597,6 +669,9 @@ lift_bwd_strip_kernel(LiftParams P, int cw, int ch, int spr, int xgroup, int bn_
 extern "C" int vamp_debug_read_stamps(long long* host, int n) {
   return (int) hipMemcpyFromSymbol(host, HIP_SYMBOL(vamp::g_stamps), (size_t) n * 8 * sizeof(long long));
 }
+extern "C" int vamp_debug_read_fill_stamps(long long* host, int n) {
+  return (int) hipMemcpyFromSymbol(host, HIP_SYMBOL(vamp::g_fill_stamps), (size_t) n * 8 * sizeof(long long));
+}
 namespace vamp {
 #endif
 
@@ -644,11 +719,14 @@ static int launch_cell_t(const VampLiftDesc* d, const LiftParams& P, const float
   const int BN = d->B * d->N;
   const int bn_lo = half == 2 ? BN / 2 : 0, bn_hi = half == 1 ? BN / 2 : BN;
   if (bn_hi <= bn_lo) return VAMP_OK;
-  dim3 grid((d->X + 63) / 64, (d->Y + 3) / 4, d->Z * d->B);
+  // a wave per 64 voxels of a sample's flattened (z, y, x) index, four waves per workgroup
+  const long wps = ((long) d->Z * d->Y * d->X + 63) / 64;
+  VAMP_REQUIRE(wps * 64 < 0x7fffffffL && wps * d->B < 0x7fffffffL, "voxel count exceeds 2^31");
+  const unsigned grid = (unsigned) ((wps * d->B + 3) / 4);
   const size_t fill_lds = (size_t) 4 * 64 * (2 + d->C / 4) * sizeof(float4);      // [wave][lane][record piece]
 #define VAMP_CELL(CH)                                                                            \
   VAMP_TIMED(kProfLiftBwdFill, s, (lift_bwd_fill_kernel<CH><<<grid, 256, fill_lds, s>>>(         \
-      P, g.cw, g.ch, gout, hits, w.amask, w.ptaps, w.pcell, w.cnt, w.off, w.boff, w.recs, w.rowq, bn_lo, bn_hi)))
+      P, g.cw, g.ch, gout, hits, w.amask, w.ptaps, w.pcell, w.cnt, w.off, w.boff, w.recs, w.rowq, bn_lo, bn_hi, (int) wps)))
   if (P.C == 4) VAMP_CELL(4); else if (P.C == 8) VAMP_CELL(8); else VAMP_CELL(16);
 #undef VAMP_CELL
   if (int e = check_launch("lift_bwd_fill_kernel")) return e;
