@@ -27,10 +27,11 @@
 extern "C" {
 #endif
 
-#define VAMP_ABI_VERSION 15  /* bumped whenever entry points or flags are added (round 2: 2, round 3: 3, round 4: 4, round 5: 5, round 6: 6;
+#define VAMP_ABI_VERSION 16  /* bumped whenever entry points or flags are added (round 2: 2, round 3: 3, round 4: 4, round 5: 5, round 6: 6;
                                  7: segmentation metrics; 8: detection post-processing; 9: detection targets;
                                  10: the BEV backward's plan; 11: detection loss; 12: rgb loss; 13: segmentation loss;
-                                 14: masked regression losses; 15: the camera render's plans and workspace layout) */
+                                 14: masked regression losses; 15: the camera render's plans and workspace layout;
+                                 16: the lift's plans and workspace layout) */
 
 enum {
   VAMP_OK = 0,
@@ -177,7 +178,7 @@ int vamp_lift_backward(const VampLiftDesc* d, const float* mats, const float* xs
 #define VAMP_LIFTBWD_CELLS_VALID 1
 /* implementation selectors (tests cross-check them; 0 = the default cell-list gather):
    SPLAT = the per-voxel float-atomic splat; WPP4 / WPP16 (names from round 3's wave-per-pixel gather) make
-   the strip gather stage its pairs in chunks of 64 / 32 instead of 256, so that small inputs cross chunk
+   the strip gather stage its pairs in chunks of 64 / 32 instead of 128, so that small inputs cross chunk
    boundaries too; WPP1 = default */
 #define VAMP_LIFTBWD_SPLAT 2
 #define VAMP_LIFTBWD_WPP1 4
@@ -236,6 +237,87 @@ int vamp_lift_indices(const VampLiftDesc* d, const float* mats, const float* xs,
  */
 int vamp_lift_cull_words(const VampLiftDesc* d, const float* mats, const float* xs, const float* ys,
                          const float* zs, uint32_t* words, int32_t patch[2], int32_t grid[2], void* stream);
+
+/*
+ * What vamp_lift_forward_ex / vamp_lift_forward_logits_ex (has_logits, logits_dtype) and vamp_lift_backward_ex will
+ * launch for (d, flags, workspace_bytes) (ABI 16): every choice the calls make from the descriptor, the flags and the
+ * workspace size, as numbers.  Pure host functions -- no HIP call, no GPU -- and the very functions the entry points ask,
+ * behind their pointer checks, before the first launch.  workspace_bytes is the size of a workspace that is there: a NULL
+ * workspace counts as 0.  They return VAMP_OK, or the code (and vamp_last_error message) with which the entry point
+ * refuses the same arguments: a bad descriptor, a channel count other than 4, 8 or a multiple of 16 up to 64, flags that
+ * exclude each other (FEAT_CHANNEL_LAST with a bf16 descriptor, LOGITS with SPLAT, the logits entry's use_depth /
+ * in_dtype / logits_dtype rules), too many tiles or voxels for a grid index, a shape the cell lists cannot hold (more
+ * than 2^31 pairs or cells, fW or fH above 32766, D above 65534) where the call emits pairs or runs the prepare pass,
+ * too many depth planes for the strip gather's LDS tiles, and VAMP_ENOSPC below bytes_needed.
+ * Fields a path does not use are 0.
+ */
+enum { VAMP_LIFTPLAN_FIRST_NONE = 0,      /* channel-last features, no logits: the forward kernel is the only launch */
+       VAMP_LIFTPLAN_FIRST_PROLOGUE = 1,  /* lift_prologue_kernel: channel-last copy + cull words */
+       VAMP_LIFTPLAN_FIRST_OPERANDS = 2,  /* lift_operands_kernel: softmax + channel-last copy + cull words */
+       VAMP_LIFTPLAN_FIRST_SOFTMAX = 3 }; /* lift_operands_kernel, its softmax tiles only (logits, channel-last features) */
+enum { VAMP_LIFTPLAN_COUNTERS_NONE = 0,   /* no pairs are emitted */
+       VAMP_LIFTPLAN_COUNTERS_ZERO = 1,   /* the cell counters are zero-filled first */
+       VAMP_LIFTPLAN_COUNTERS_CLEAN = 2 };/* VAMP_LIFTFWD_CELLS_CLEAN: promised zero (verified under vamp_debug_checks) */
+enum { VAMP_LIFTPLAN_BWD_CELL = 0,        /* [prepare] + fill + strip gather */
+       VAMP_LIFTPLAN_BWD_SPLAT = 1 };     /* VAMP_LIFTBWD_SPLAT: the per-voxel float-atomic splat */
+typedef struct VampLiftForwardPlan {
+  int64_t bytes_needed;        /* VAMP_ENOSPC below this */
+  int32_t first;               /* VAMP_LIFTPLAN_FIRST_*: the launch in front of the forward kernel */
+  int32_t first_grid;          /* its workgroups */
+  int32_t sm_tiles;            /* ... of which, per image, softmax tiles of 64 pixels (logits only) */
+  int32_t sm_reg;              /* the softmax keeps its bins in registers (D <= 128; 0: the loop variant) */
+  int32_t ptiles;              /* ... and channel-last copy tiles of 64 pixels per image (PROLOGUE, OPERANDS) */
+  int32_t cull_words;          /* the forward kernel reads the first launch's cull words (0: it forms its own) */
+  int32_t coop;                /* lift_fwd_coop_kernel (C = 16, no pairs); 0: lift_fwd_kernel */
+  int32_t ch;                  /* CH of lift_fwd_kernel: 4, 8 or 16 (0 with coop) */
+  int32_t emit;                /* the forward kernel emits the backward's pairs (VAMP_LIFTFWD_EMIT_PAIRS) */
+  int32_t counters;            /* VAMP_LIFTPLAN_COUNTERS_* */
+  int32_t scan;                /* the cell scan runs inside the call (emit without VAMP_LIFTFWD_DEFER_SCAN) */
+  int32_t grid[3];             /* the forward kernel's workgroups */
+  int32_t reserved[6];         /* 0 */
+} VampLiftForwardPlan;
+int vamp_lift_forward_plan(const VampLiftDesc* d, int has_logits, int32_t logits_dtype, int flags,
+                           size_t workspace_bytes, VampLiftForwardPlan* out);
+typedef struct VampLiftBackwardPlan {
+  int64_t bytes_needed;        /* VAMP_ENOSPC below this */
+  int64_t fill_lds;            /* CELL: dynamic LDS bytes of lift_bwd_fill_kernel */
+  int64_t strip_lds;           /* CELL: dynamic LDS bytes of lift_bwd_strip_kernel */
+  int64_t zero_feat_bytes;     /* SPLAT: the zero fill of the feature gradient ... */
+  int64_t zero_depth_bytes;    /* ... and of grad_depth (0 without use_depth) */
+  int32_t path;                /* VAMP_LIFTPLAN_BWD_* */
+  int32_t feat_cl;             /* feat is read, grad_feat written channel-last (VAMP_LIFTBWD_FEAT_CHANNEL_LAST) */
+  int32_t prepare;             /* CELL: the prepare pass (zero fill, pairs kernel, scan) runs inside the call: no CELLS_VALID */
+  int32_t fill_ch;             /* CELL: CH of lift_bwd_fill_kernel ... */
+  int32_t fill_grid;           /* ... and its workgroups */
+  int32_t cap;                 /* CELL: pairs the strip gather stages per chunk: 128 (WPP4: 64, WPP16: 32) */
+  int32_t raise_lds;           /* CELL: the dynamic-LDS limit is raised first (strip_lds above 64 KB) */
+  int32_t vec;                 /* CELL: the strip gather's 16-byte tile I/O (fp32 depth, fW % 4 == 0) */
+  int32_t strip_grid;          /* CELL: lift_bwd_strip_kernel's workgroups */
+  int32_t softmax_bwd;         /* CELL: grad_depth receives the gradient of the logits (VAMP_LIFTBWD_LOGITS) */
+  int32_t to_cl;               /* SPLAT: feat_to_channel_last runs first (no FEAT_CHANNEL_LAST) */
+  int32_t splat_ch;            /* SPLAT: CH of lift_bwd_kernel ... */
+  int32_t splat_grid[3];       /* ... and its workgroups */
+  int32_t to_cf;               /* SPLAT: feat_to_channel_first copies the gradient back (no FEAT_CHANNEL_LAST) */
+  int32_t reserved[6];         /* 0 */
+} VampLiftBackwardPlan;
+int vamp_lift_backward_plan(const VampLiftDesc* d, int flags, size_t workspace_bytes, VampLiftBackwardPlan* out);
+
+/*
+ * The lift workspace, region by region (ABI 16): byte offset and size of
+ *   feat_cl | gfeat_cl | cnt | off | bsum | boff | aux | amask | ptaps | pcell | recs | rowq | cull
+ * in that order (VAMP_LIFTWS_*): the channel-last feature copy, the splat backward's gradient in that layout, the cell
+ * lists (counters, the scan's four levels, camera masks, pair taps, pair cells, records, row queue) and the forward's
+ * camera cull words.  Every region is 256-byte aligned and they lie back to back; total_bytes = vamp_lift_workspace_bytes(d).
+ */
+enum { VAMP_LIFTWS_FEAT_CL = 0, VAMP_LIFTWS_GFEAT_CL, VAMP_LIFTWS_CNT, VAMP_LIFTWS_OFF, VAMP_LIFTWS_BSUM,
+       VAMP_LIFTWS_BOFF, VAMP_LIFTWS_AUX, VAMP_LIFTWS_AMASK, VAMP_LIFTWS_PTAPS, VAMP_LIFTWS_PCELL, VAMP_LIFTWS_RECS,
+       VAMP_LIFTWS_ROWQ, VAMP_LIFTWS_CULL, VAMP_LIFTWS_REGIONS };
+typedef struct VampLiftWorkspaceLayout {
+  int64_t offset[VAMP_LIFTWS_REGIONS];
+  int64_t bytes[VAMP_LIFTWS_REGIONS];
+  int64_t total_bytes;         /* = vamp_lift_workspace_bytes(d) */
+} VampLiftWorkspaceLayout;
+int vamp_lift_workspace_layout(const VampLiftDesc* d, VampLiftWorkspaceLayout* out);
 
 /* ------------------------------------------------------------------------- *
  * RENDER: volume_rendering_from_multiple_views (bv2:391-467) with the density

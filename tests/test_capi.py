@@ -45,6 +45,9 @@ def test_struct_layout_matches_header(lib):
     assert C.sizeof(_capi.VampCameraForwardPlan) == 16 * 4
     assert C.sizeof(_capi.VampCameraBackwardPlan) == 28 * 4
     assert C.sizeof(_capi.VampRenderWorkspaceLayout) == (2 * 19 + 2) * 8
+    assert C.sizeof(_capi.VampLiftForwardPlan) == 22 * 4
+    assert C.sizeof(_capi.VampLiftBackwardPlan) == 32 * 4
+    assert C.sizeof(_capi.VampLiftWorkspaceLayout) == (2 * 13 + 1) * 8
 
 
 def test_bad_descriptor_is_rejected_without_gpu(lib):

@@ -234,7 +234,7 @@ def test_descriptor_layout(lib):
     assert [f[0] for f in _capi.VampRegTerm._fields_] == ["n", "kind", "side", "pred_dtype", "target_is_const",
                                                           "target_value", "reserved"]
     assert [f[0] for f in _capi.VampRegLossDesc._fields_] == ["T", "reserved", "terms"]
-    assert _capi.ABI_VERSION == 15 and lib.vamp_abi_version() == 15
+    assert _capi.ABI_VERSION == 16 and lib.vamp_abi_version() == 16
     assert (ops.REG_TILE, ops.REG_MAX_TERMS) == (_capi.VAMP_REG_TILE, _capi.VAMP_REG_MAX_TERMS) == (4096, 8)
     d = _desc()
     sizes = []

@@ -15,7 +15,7 @@ import torch
 
 from .build import lib_path
 
-ABI_VERSION = 15
+ABI_VERSION = 16
 
 VAMP_F32, VAMP_BF16, VAMP_F16 = 0, 1, 2
 VAMP_DENSITY_SIGMOID, VAMP_DENSITY_SDF_LAPLACE = 0, 1
@@ -167,6 +167,38 @@ class VampRenderWorkspaceLayout(C.Structure):
                 ("base_bytes", C.c_int64), ("bytes_with_rows", C.c_int64)]
 
 
+class VampLiftForwardPlan(C.Structure):
+    """What vamp_lift_forward_ex / vamp_lift_forward_logits_ex will launch (vamp_lift_forward_plan; include/vampire_hip.h)."""
+    _fields_ = [("bytes_needed", C.c_int64), ("first", C.c_int32), ("first_grid", C.c_int32), ("sm_tiles", C.c_int32),
+                ("sm_reg", C.c_int32), ("ptiles", C.c_int32), ("cull_words", C.c_int32), ("coop", C.c_int32),
+                ("ch", C.c_int32), ("emit", C.c_int32), ("counters", C.c_int32), ("scan", C.c_int32),
+                ("grid", C.c_int32 * 3), ("reserved", C.c_int32 * 6)]
+
+
+class VampLiftBackwardPlan(C.Structure):
+    """What vamp_lift_backward_ex will launch (vamp_lift_backward_plan; include/vampire_hip.h)."""
+    _fields_ = [("bytes_needed", C.c_int64), ("fill_lds", C.c_int64), ("strip_lds", C.c_int64),
+                ("zero_feat_bytes", C.c_int64), ("zero_depth_bytes", C.c_int64), ("path", C.c_int32),
+                ("feat_cl", C.c_int32), ("prepare", C.c_int32), ("fill_ch", C.c_int32), ("fill_grid", C.c_int32),
+                ("cap", C.c_int32), ("raise_lds", C.c_int32), ("vec", C.c_int32), ("strip_grid", C.c_int32),
+                ("softmax_bwd", C.c_int32), ("to_cl", C.c_int32), ("splat_ch", C.c_int32),
+                ("splat_grid", C.c_int32 * 3), ("to_cf", C.c_int32), ("reserved", C.c_int32 * 6)]
+
+
+# regions of the lift workspace, in layout order (VAMP_LIFTWS_*)
+LIFTWS_REGIONS = ("feat_cl", "gfeat_cl", "cnt", "off", "bsum", "boff", "aux", "amask", "ptaps", "pcell", "recs", "rowq",
+                  "cull")
+
+
+class VampLiftWorkspaceLayout(C.Structure):
+    """Byte offset and size of every region of the lift workspace (vamp_lift_workspace_layout)."""
+    _fields_ = [("offset", C.c_int64 * len(LIFTWS_REGIONS)), ("bytes", C.c_int64 * len(LIFTWS_REGIONS)),
+                ("total_bytes", C.c_int64)]
+
+
+VAMP_LIFTPLAN_FIRST_NONE, VAMP_LIFTPLAN_FIRST_PROLOGUE, VAMP_LIFTPLAN_FIRST_OPERANDS, VAMP_LIFTPLAN_FIRST_SOFTMAX = 0, 1, 2, 3
+VAMP_LIFTPLAN_COUNTERS_NONE, VAMP_LIFTPLAN_COUNTERS_ZERO, VAMP_LIFTPLAN_COUNTERS_CLEAN = 0, 1, 2
+VAMP_LIFTPLAN_BWD_CELL, VAMP_LIFTPLAN_BWD_SPLAT = 0, 1
 VAMP_CAMPLAN_FWD_DIRECT, VAMP_CAMPLAN_FWD_PLANNED, VAMP_CAMPLAN_FWD_MARCH = 0, 1, 2
 VAMP_CAMPLAN_TERM_NONE, VAMP_CAMPLAN_TERM_BUILD, VAMP_CAMPLAN_TERM_CHECK, VAMP_CAMPLAN_TERM_WRITE = 0, 1, 2, 3
 VAMP_CAMPLAN_BWD_CELL, VAMP_CAMPLAN_BWD_SPLAT = 0, 1
@@ -252,6 +284,9 @@ SIGNATURES = {
     "vamp_profile_read": (_STATUS, [C.c_int, C.POINTER(C.c_char_p), C.POINTER(C.c_int),
                                     C.POINTER(C.c_double)]),
     "vamp_lift_workspace_bytes": (_SIZE, [_LD]),
+    "vamp_lift_workspace_layout": (_STATUS, [_LD, C.POINTER(VampLiftWorkspaceLayout)]),
+    "vamp_lift_forward_plan": (_STATUS, [_LD, C.c_int, C.c_int32, C.c_int, C.c_size_t, C.POINTER(VampLiftForwardPlan)]),
+    "vamp_lift_backward_plan": (_STATUS, [_LD, C.c_int, C.c_size_t, C.POINTER(VampLiftBackwardPlan)]),
     "vamp_lift_forward": (_STATUS, [_LD] + [_P] * 8 + [_P, C.c_size_t, _P]),
     "vamp_lift_forward_logits": (_STATUS, [_LD] + [_P] * 5 + [C.c_int32] + [_P] * 4 + [_P, C.c_size_t, _P]),
     "vamp_lift_forward_ex": (_STATUS, [_LD] + [_P] * 8 + [_P, C.c_size_t, C.c_int, _P]),

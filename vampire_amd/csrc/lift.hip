@@ -14,15 +14,7 @@
 
 namespace vamp {
 
-// tile shape: lanes along x for coalesced stores
-// A wave is a 16 x 4 patch of voxels, not a 64 x 1 row: the exact wave-level camera cull of
-// lift_project<true> skips a camera only when none of the wave's voxels has it in front, and a
-// 6.4 m x 1.6 m patch is on one side of most cameras where a 25.6 m row is not (cfg-B: 47 -> 36 us;
-// 8 x 32 / 16 x 16 / 32 x 8 / 64 x 4 workgroup tiles: 36.5 / 35.7 / 38.2 / 47.1).
-#ifndef VAMP_LIFT_TX
-#define VAMP_LIFT_TX 16
-#define VAMP_LIFT_TY 16
-#endif
+// (the tile shape VAMP_LIFT_TX x VAMP_LIFT_TY: lift_common.hpp)
 #define VAMP_LIFT_TILE VAMP_LIFT_TX, VAMP_LIFT_TY, 1
 #ifndef VAMP_LIFT_COOP
 #define VAMP_LIFT_COOP 1
@@ -75,14 +67,7 @@ __global__ void __launch_bounds__(256) feat_to_channel_last(const T* __restrict_
 // ---------------------------------------------------------------------------
 constexpr unsigned kLiftCullSharedBda = 1u << 15;
 
-struct LiftCull {
-  unsigned* words;      // [B][Z][nyp][nxp]
-  int nxp, nyp;         // patches per row / column of one z plane
-  int px, py;           // patch shape in voxels
-  int group;            // lanes per patch in a cull workgroup: the power of two >= N
-  int bps;              // stand-alone cull: workgroups (256 / group patches each) per sample
-  int ppt;              // forward's first launch: patches per feature tile (N * ptiles tiles per sample)
-};
+// (LiftCull, the words' place in the workspace and their geometry: lift_common.hpp)
 
 // What a cull workgroup keeps per camera of its sample (LDS): A = (K inv(s2e)) inv(bda) in fp32 -- its
 // rounding is what the margins are four orders of magnitude above -- and the image-plane rows of ida.
@@ -93,11 +78,6 @@ struct LiftCullCam {
   int same;           // inv(bda) is camera 0's, bit for bit
 };
 constexpr int kLiftCullMaxCams = 15;
-#ifndef VAMP_CULL_WPW
-#define VAMP_CULL_WPW 4      // (1 / 2 / 4: first launch 9.9 / 9.0 / 9.0 us, forward kernel 28.3 / 28.4 / 28.4 at cfg-B)
-#endif
-constexpr int kCullWpw = VAMP_CULL_WPW;     // waves of lift_fwd_kernel (stacked along y) that share a word: 1, 2 or 4
-constexpr int kCullPX = VAMP_LIFT_TX, kCullPY = 64 / VAMP_LIFT_TX * kCullWpw;
 
 // The cull in three pieces, so that a launch can put its loads beside other loads and its arithmetic behind
 // a barrier it has anyway.  (1) per camera of the sample, once per workgroup: the constants above (wave 0);
@@ -1005,13 +985,15 @@ lift_indices_kernel(LiftParams P, const float* __restrict__ mats, const float* _
 }
 
 // ---------------------------------------------------------------------------
-// host side
+// host side: a plan (lift_forward_plan here, lift_backward_plan in lift_bwd_cell.hip) decides what a call launches and
+// makes every refusal; the executors below launch what it says
 // ---------------------------------------------------------------------------
-static int validate(const VampLiftDesc* d) {
+int lift_validate(const VampLiftDesc* d) {
   VAMP_REQUIRE(d != nullptr, "desc is NULL");
   VAMP_REQUIRE(d->B > 0 && d->N > 0 && d->C > 0, "B, N, C must be positive");
   VAMP_REQUIRE(d->D > 0 && d->fH > 0 && d->fW > 0, "D, fH, fW must be positive");
   VAMP_REQUIRE(d->Z > 0 && d->Y > 0 && d->X > 0, "Z, Y, X must be positive");
+  // (a call that builds the backward's cells asks lift_cells_fit too: fW, fH < 32767 there)
   VAMP_REQUIRE(d->X < 32768 && d->Y < 32768 && d->fW < 32768 && d->fH < 32768,
                "axis too long for int16 taps");
   VAMP_REQUIRE(d->N <= 15, "at most 15 cameras (4-bit hit counters)");
@@ -1020,92 +1002,122 @@ static int validate(const VampLiftDesc* d) {
   return VAMP_OK;
 }
 
-static bool fused_channels_ok(int C) { return C == 4 || C == 8 || (C % 16 == 0 && C <= 64); }
-
-template <typename T>
-static void launch_to_cl(const void* feat, float* out, int BN, int C, int HW, hipStream_t s) {
-  dim3 grid((HW + 63) / 64, (C + 63) / 64, BN);
-  VAMP_TIMED(kProfFeatCL, s, (feat_to_channel_last<T><<<grid, 256, 0, s>>>(static_cast<const T*>(feat), out, C, HW)));
-}
-
-
-struct LiftWs {
-  float* feat_cl;     // [B*N, HW, C]
-  float* gfeat_cl;    // [B*N, HW, C] (v1 backward only)
-  void* cells;        // cell lists of the backward; vamp_lift_prepare fills their offsets
-  LiftCull cull;      // camera cull words of the forward's waves
-  long ncull;
-  size_t bytes;
-};
-
-static LiftWs carve(const VampLiftDesc* d, void* ws) {
-  LiftWs w;
-  const size_t n = align_up((size_t) d->B * d->N * d->fH * d->fW * d->C * sizeof(float), 256);
-  w.feat_cl = static_cast<float*>(ws);
-  w.gfeat_cl = reinterpret_cast<float*>(static_cast<char*>(ws) + n);
-  // the cell lists live behind the copies: the forward must not disturb prepared offsets
-  w.cells = static_cast<char*>(ws) + 2 * n;
-  const size_t ncell_bytes = align_up(lift_bwd_cell_ws_bytes(d), 256);
-  w.cull.words = reinterpret_cast<unsigned*>(static_cast<char*>(ws) + 2 * n + ncell_bytes);
-  w.cull.px = VAMP_LIFT_TX;
-  w.cull.py = kCullPY;
-  w.cull.nxp = (d->X + VAMP_LIFT_TX - 1) / VAMP_LIFT_TX;
-  w.cull.nyp = (d->Y + VAMP_LIFT_TY - 1) / VAMP_LIFT_TY * (4 / kCullWpw);
-  w.ncull = (long) d->B * d->Z * w.cull.nyp * w.cull.nxp;
-  w.cull.group = 1;
-  while (w.cull.group < d->N) w.cull.group *= 2;
-  const int ppb = std::min(256 / w.cull.group, 64);
-  const long per_sample = (long) d->Z * w.cull.nyp * w.cull.nxp;
-  w.cull.bps = (int) ((per_sample + ppb - 1) / ppb);
-  const long tiles = (long) d->N * (((long) d->fH * d->fW + 63) / 64);
-  w.cull.ppt = (int) ((per_sample + tiles - 1) / tiles);
-  w.bytes = 2 * n + ncell_bytes + align_up((size_t) w.ncull * sizeof(unsigned), 256);
-  return w;
-}
-
-
-// `cells` != nullptr: the kernel emits the backward's pairs into that part of the workspace, between
-// the zero fill of the cell counters and their scan (afterwards the workspace is what
-// vamp_lift_prepare leaves: VAMP_LIFTBWD_CELLS_VALID)
-template <typename T>
-static int lift_forward_t(const VampLiftDesc* d, const LiftParams& P, const float* mats,
-                          const float* xs, const float* ys, const float* zs, const void* depth,
-                          const float* feat_cl, float* out, uint64_t* hits, void* cells, bool cells_clean,
-                          const unsigned* cull, hipStream_t s, bool defer_scan = false) {
-  constexpr int TX = VAMP_LIFT_TX, TY = VAMP_LIFT_TY, TZ = 1;
-  dim3 grid((P.X + TX - 1) / TX, (P.Y + TY - 1) / TY, ((P.Z + TZ - 1) / TZ) * P.B);
-  const T* dp = static_cast<const T*>(depth);
-  LiftEmit E{};
-  if (cells) {
-    VAMP_REQUIRE(d->N <= 15, "at most 15 cameras");
-    if (int e = launch_lift_cells_begin(d, cells, s, cells_clean)) return e;
-    E = lift_emit_of(d, cells);
+// The forward's plan: every choice vamp_lift_forward_ex / vamp_lift_forward_logits_ex make, from the descriptor, logits
+// given or not, the flags and the workspace size.  No HIP call.
+static int lift_forward_plan(const char* who, const VampLiftDesc* d, bool has_logits, int logits_dtype, int flags,
+                             size_t workspace_bytes, VampLiftForwardPlan* out) {
+  if (!out) return fail(VAMP_EINVAL, "%s: requirement failed: plan is NULL", who);
+  memset(out, 0, sizeof(*out));
+  if (int e = lift_validate(d)) return e;
+  VampLiftForwardPlan& p = *out;
+  if (has_logits) {
+    VAMP_REQUIRE_AS(who, d->use_depth == 1, "the logits entry is the depth-distribution lift");
+    VAMP_REQUIRE_AS(who, d->in_dtype == VAMP_F32, "feat (and the depth distribution written here) are fp32");
+    VAMP_REQUIRE_AS(who, logits_dtype == VAMP_F32 || logits_dtype == VAMP_BF16, "logits_dtype");
   }
-#define VAMP_FWD(CH, EM)                                                                               \
-  VAMP_TIMED(kProfLiftFwd, s, (lift_fwd_kernel<T, CH, VAMP_LIFT_TILE, EM><<<grid, 256, 0, s>>>(P, mats, xs, ys, zs, dp, feat_cl, out, hits, E, cull)))
+  VAMP_REQUIRE_AS(who, lift_channels_ok(d->C), "C must be 4, 8 or a multiple of 16 (<= 64)");
+  // VAMP_LIFTFWD_FEAT_CHANNEL_LAST: the features are already [B, N, fH, fW, C] fp32 -- no copy, and every workgroup of
+  // the forward kernel forms its own patch's cull word at its head
+  const bool fcl = (flags & VAMP_LIFTFWD_FEAT_CHANNEL_LAST) != 0;
+  VAMP_REQUIRE_AS(who, !fcl || d->in_dtype == VAMP_F32, "VAMP_LIFTFWD_FEAT_CHANNEL_LAST takes fp32 features (and depth)");
+  const LiftWorkspace w = lift_workspace(d, nullptr);
+  p.bytes_needed = (int64_t) w.bytes;
+  // first launch: the softmax tiles of the logits, then the tiles of the channel-last copy (with the cull words)
+  const long BN = (long) d->B * d->N, HW = (long) d->fH * d->fW;
+  const long sm_tiles = has_logits ? (HW + kPix - 1) / kPix : 0, ptiles = fcl ? 0 : (HW + 63) / 64;
+  VAMP_REQUIRE_AS(who, BN * sm_tiles + BN * ptiles < 0x7fffffffL, "too many tiles");
+  p.first = has_logits ? (fcl ? VAMP_LIFTPLAN_FIRST_SOFTMAX : VAMP_LIFTPLAN_FIRST_OPERANDS)
+                       : (fcl ? VAMP_LIFTPLAN_FIRST_NONE : VAMP_LIFTPLAN_FIRST_PROLOGUE);
+  p.first_grid = (int32_t) (BN * sm_tiles + BN * ptiles);
+  p.sm_tiles = (int32_t) sm_tiles;
+  p.sm_reg = has_logits && d->D <= kSplit * kRegBins;
+  p.ptiles = (int32_t) ptiles;
+  p.cull_words = !fcl;
+  // VAMP_LIFTFWD_EMIT_PAIRS: the kernel emits the backward's pairs into the workspace's cells, between the zero fill of
+  // the cell counters and their scan (afterwards the workspace is what vamp_lift_prepare leaves: VAMP_LIFTBWD_CELLS_VALID)
+  p.emit = (flags & VAMP_LIFTFWD_EMIT_PAIRS) != 0;
+  if (p.emit) {
+    if (int e = lift_cells_fit(who, d)) return e;
+    p.counters = (flags & VAMP_LIFTFWD_CELLS_CLEAN) ? VAMP_LIFTPLAN_COUNTERS_CLEAN : VAMP_LIFTPLAN_COUNTERS_ZERO;
+    // (VAMP_LIFTFWD_DEFER_SCAN: the counters stay as counted; vamp_lift_finish_cells or
+    // vamp_render_camera_prepare_with_lift scans them)
+    p.scan = !(flags & VAMP_LIFTFWD_DEFER_SCAN);
+  }
   // C = 16 (the reference's mid_channels), no backward to follow: the kernel with the cooperative feature gather
   // (cfg-B: 28.6 against 31.8 us.  With the pair emission of a training forward its registers spill and it
   // loses, 44.3 against 36.3 -- those calls keep lift_fwd_kernel)
-  const bool coop = P.C == 16 && TX == 16 && TY == 16 && VAMP_LIFT_COOP && !cells;
-  if (coop)
-    VAMP_TIMED(kProfLiftFwd, s, (lift_fwd_coop_kernel<T><<<grid, 256, 0, s>>>(P, mats, xs, ys, zs, dp, feat_cl, out, hits, cull)));
-  else if (cells) {
-    if (P.C == 4) VAMP_FWD(4, true); else if (P.C == 8) VAMP_FWD(8, true); else VAMP_FWD(16, true);
-  } else {
-    if (P.C == 4) VAMP_FWD(4, false); else if (P.C == 8) VAMP_FWD(8, false); else VAMP_FWD(16, false);
-  }
-#undef VAMP_FWD
-  if (int e = check_launch("lift_fwd_kernel")) return e;
-  // (VAMP_LIFTFWD_DEFER_SCAN: the counters stay as counted; vamp_lift_finish_cells or
-  // vamp_render_camera_prepare_with_lift scans them)
-  return (cells && !defer_scan) ? launch_lift_cells_end(d, cells, s) : VAMP_OK;
+  p.coop = d->C == 16 && VAMP_LIFT_TX == 16 && VAMP_LIFT_TY == 16 && VAMP_LIFT_COOP && !p.emit;
+  p.ch = p.coop ? 0 : (d->C == 4 ? 4 : (d->C == 8 ? 8 : 16));
+  p.grid[0] = (d->X + VAMP_LIFT_TX - 1) / VAMP_LIFT_TX;
+  p.grid[1] = (d->Y + VAMP_LIFT_TY - 1) / VAMP_LIFT_TY;
+  p.grid[2] = d->Z * d->B;
+  return lift_workspace_fits(who, w, workspace_bytes);
 }
 
-int launch_lift_cell_prepare(const VampLiftDesc* d, const float* mats, const float* xs,
-                             const float* ys, const float* zs, const void* depth, void* scratch, hipStream_t s) {
+// the forward kernel, as the plan says (T: the depth planes' type)
+template <typename T>
+static int launch_lift_fwd(const LiftParams& P, const VampLiftForwardPlan& p, const LiftWorkspace& w, const float* mats,
+                           const float* xs, const float* ys, const float* zs, const void* depth, const float* feat_cl,
+                           float* out, uint64_t* hits, const unsigned* cull, hipStream_t s) {
+  const dim3 grid(p.grid[0], p.grid[1], p.grid[2]);
+  const T* dp = static_cast<const T*>(depth);
+  const LiftEmit E = p.emit ? lift_emit_of(w) : LiftEmit{};
+#define VAMP_FWD(CH, EM)                                                                               \
+  VAMP_TIMED(kProfLiftFwd, s, (lift_fwd_kernel<T, CH, VAMP_LIFT_TILE, EM><<<grid, 256, 0, s>>>(P, mats, xs, ys, zs, dp, feat_cl, out, hits, E, cull)))
+  if (p.coop)
+    VAMP_TIMED(kProfLiftFwd, s, (lift_fwd_coop_kernel<T><<<grid, 256, 0, s>>>(P, mats, xs, ys, zs, dp, feat_cl, out, hits, cull)));
+  else if (p.emit) {
+    if (p.ch == 4) VAMP_FWD(4, true); else if (p.ch == 8) VAMP_FWD(8, true); else VAMP_FWD(16, true);
+  } else {
+    if (p.ch == 4) VAMP_FWD(4, false); else if (p.ch == 8) VAMP_FWD(8, false); else VAMP_FWD(16, false);
+  }
+#undef VAMP_FWD
+  return check_launch("lift_fwd_kernel");
+}
+
+// Both forward entry points behind their plan.  `logits` (logits entry only) become `depth_out`, which is then the
+// `depth` the forward kernel reads.
+static int launch_lift_forward(const VampLiftDesc* d, const VampLiftForwardPlan& p, const LiftWorkspace& w,
+                               const float* mats, const float* xs, const float* ys, const float* zs, const void* logits,
+                               int logits_dtype, float* depth_out, const void* depth, const void* feat, float* out,
+                               uint64_t* hits, hipStream_t s) {
   const LiftParams P = to_params(d);
-  if (int e = launch_lift_cells_begin(d, scratch, s)) return e;
-  const LiftEmit E = lift_emit_of(d, scratch);
+  const unsigned grid = (unsigned) p.first_grid;
+  if (p.first == VAMP_LIFTPLAN_FIRST_PROLOGUE) {
+    if (d->in_dtype == VAMP_F32)
+      VAMP_TIMED(kProfFeatCL, s, (lift_prologue_kernel<float><<<grid, 256, 0, s>>>(P, static_cast<const float*>(feat), w.feat_cl, p.ptiles, mats, xs, ys, zs, w.cull)));
+    else
+      VAMP_TIMED(kProfFeatCL, s, (lift_prologue_kernel<__hip_bfloat16><<<grid, 256, 0, s>>>(P, static_cast<const __hip_bfloat16*>(feat), w.feat_cl, p.ptiles, mats, xs, ys, zs, w.cull)));
+    if (int e = check_launch("lift_prologue_kernel")) return e;
+  } else if (p.first != VAMP_LIFTPLAN_FIRST_NONE) {
+    const unsigned n_sm = (unsigned) ((long) d->B * d->N * p.sm_tiles);      // (FIRST_SOFTMAX: the whole grid)
+#define VAMP_OPERANDS(TL, REG)                                                                           \
+  VAMP_TIMED(kProfFeatCL, s, (lift_operands_kernel<TL, REG><<<grid, 256, 0, s>>>(                        \
+      P, static_cast<const TL*>(logits), depth_out, p.sm_tiles, n_sm, static_cast<const float*>(feat),   \
+      w.feat_cl, p.ptiles, mats, xs, ys, zs, w.cull)))
+    if (logits_dtype == VAMP_F32) {
+      if (p.sm_reg) VAMP_OPERANDS(float, true); else VAMP_OPERANDS(float, false);
+    } else {
+      if (p.sm_reg) VAMP_OPERANDS(__hip_bfloat16, true); else VAMP_OPERANDS(__hip_bfloat16, false);
+    }
+#undef VAMP_OPERANDS
+    if (int e = check_launch("lift_operands_kernel")) return e;
+  }
+  if (p.counters != VAMP_LIFTPLAN_COUNTERS_NONE)
+    if (int e = launch_lift_cells_begin(w, p.counters == VAMP_LIFTPLAN_COUNTERS_CLEAN, s)) return e;
+  // (no copy in the first launch: the caller's channel-last features, and no cull words either)
+  const float* fsrc = p.cull_words ? w.feat_cl : static_cast<const float*>(feat);
+  const unsigned* cull = p.cull_words ? w.cull.words : nullptr;
+  const int e = d->in_dtype == VAMP_F32
+                    ? launch_lift_fwd<float>(P, p, w, mats, xs, ys, zs, depth, fsrc, out, hits, cull, s)
+                    : launch_lift_fwd<__hip_bfloat16>(P, p, w, mats, xs, ys, zs, depth, fsrc, out, hits, cull, s);
+  return (e || !p.scan) ? e : launch_lift_cells_end(w, s);
+}
+
+int launch_lift_cell_prepare(const VampLiftDesc* d, const LiftParams& P, const LiftWorkspace& w, const float* mats,
+                             const float* xs, const float* ys, const float* zs, const void* depth, hipStream_t s) {
+  if (int e = launch_lift_cells_begin(w, false, s)) return e;
+  const LiftEmit E = lift_emit_of(w);
   constexpr int TX = VAMP_LIFT_TX, TY = VAMP_LIFT_TY;
   dim3 grid((P.X + TX - 1) / TX, (P.Y + TY - 1) / TY, P.Z * P.B);
   if (d->in_dtype == VAMP_F32)
@@ -1113,24 +1125,37 @@ int launch_lift_cell_prepare(const VampLiftDesc* d, const float* mats, const flo
   else
     VAMP_TIMED(kProfLiftBwdCount, s, (lift_pairs_kernel<__hip_bfloat16, TX, TY><<<grid, TX * TY, 0, s>>>(P, mats, xs, ys, zs, static_cast<const __hip_bfloat16*>(depth), E)));
   if (int e = check_launch("lift_pairs_kernel")) return e;
-  return launch_lift_cells_end(d, scratch, s);
+  return launch_lift_cells_end(w, s);
 }
 
+// the per-voxel float-atomic splat, as the plan says (path VAMP_LIFTPLAN_BWD_SPLAT): kept as an independent cross-check
 template <typename T>
-static int lift_backward_t(const VampLiftDesc* d, const LiftParams& P, const float* mats,
-                           const float* xs, const float* ys, const float* zs, const void* depth,
-                           const float* feat_cl, const float* gout, const uint64_t* hits,
-                           float* gdepth, float* gfeat_cl, hipStream_t s) {
-  constexpr int TX = VAMP_LIFT_TX, TY = VAMP_LIFT_TY, TZ = 1;
-  dim3 grid((P.X + TX - 1) / TX, (P.Y + TY - 1) / TY, ((P.Z + TZ - 1) / TZ) * P.B);
+static int launch_lift_bwd_splat(const VampLiftDesc* d, const LiftParams& P, const VampLiftBackwardPlan& p,
+                                 const LiftWorkspace& w, const float* mats, const float* xs, const float* ys,
+                                 const float* zs, const void* depth, const void* feat, const float* gout,
+                                 const uint64_t* hits, float* gdepth, float* gfeat, hipStream_t s) {
+  const int BN = d->B * d->N, HW = d->fH * d->fW;
+  const dim3 tgrid((HW + 63) / 64, (d->C + 63) / 64, BN);
+  // (channel-last features: they are what the splat reads, and the gradient it accumulates is what the caller wants)
+  const float* fsrc = p.feat_cl ? static_cast<const float*>(feat) : w.feat_cl;
+  float* gdst = p.feat_cl ? gfeat : w.gfeat_cl;
+  if (p.to_cl) {
+    VAMP_TIMED(kProfFeatCL, s, (feat_to_channel_last<T><<<tgrid, 256, 0, s>>>(static_cast<const T*>(feat), w.feat_cl, d->C, HW)));
+    if (int e = check_launch("feat_to_channel_last")) return e;
+  }
+  if (int ze = launch_zero(gdst, (size_t) p.zero_feat_bytes, s)) return ze;
+  if (p.zero_depth_bytes)
+    if (int ze = launch_zero(gdepth, (size_t) p.zero_depth_bytes, s)) return ze;
+  const dim3 grid(p.splat_grid[0], p.splat_grid[1], p.splat_grid[2]);
   const T* dp = static_cast<const T*>(depth);
-  if (P.C == 4)
-    VAMP_TIMED(kProfLiftBwdV1, s, (lift_bwd_kernel<T, 4, VAMP_LIFT_TILE><<<grid, 256, 0, s>>>(P, mats, xs, ys, zs, dp, feat_cl, gout, hits, gdepth, gfeat_cl)));
-  else if (P.C == 8)
-    VAMP_TIMED(kProfLiftBwdV1, s, (lift_bwd_kernel<T, 8, VAMP_LIFT_TILE><<<grid, 256, 0, s>>>(P, mats, xs, ys, zs, dp, feat_cl, gout, hits, gdepth, gfeat_cl)));
-  else
-    VAMP_TIMED(kProfLiftBwdV1, s, (lift_bwd_kernel<T, 16, VAMP_LIFT_TILE><<<grid, 256, 0, s>>>(P, mats, xs, ys, zs, dp, feat_cl, gout, hits, gdepth, gfeat_cl)));
-  return check_launch("lift_bwd_kernel");
+#define VAMP_SPLAT(CH)                                                                                  \
+  VAMP_TIMED(kProfLiftBwdV1, s, (lift_bwd_kernel<T, CH, VAMP_LIFT_TILE><<<grid, 256, 0, s>>>(P, mats, xs, ys, zs, dp, fsrc, gout, hits, gdepth, gdst)))
+  if (p.splat_ch == 4) VAMP_SPLAT(4); else if (p.splat_ch == 8) VAMP_SPLAT(8); else VAMP_SPLAT(16);
+#undef VAMP_SPLAT
+  if (int e = check_launch("lift_bwd_kernel")) return e;
+  if (!p.to_cf) return VAMP_OK;
+  VAMP_TIMED(kProfFeatCF, s, (feat_to_channel_first<<<tgrid, 256, 0, s>>>(w.gfeat_cl, gfeat, d->C, HW)));
+  return check_launch("feat_to_channel_first");
 }
 
 }  // namespace vamp
@@ -1139,9 +1164,28 @@ using namespace vamp;
 
 extern "C" {
 
-size_t vamp_lift_workspace_bytes(const VampLiftDesc* d) {
-  if (!d) return 0;
-  return carve(d, nullptr).bytes;
+size_t vamp_lift_workspace_bytes(const VampLiftDesc* d) { return d ? lift_workspace(d, nullptr).bytes : 0; }
+
+int vamp_lift_workspace_layout(const VampLiftDesc* d, VampLiftWorkspaceLayout* out) {
+  VAMP_REQUIRE(out != nullptr, "layout is NULL");
+  memset(out, 0, sizeof(*out));
+  if (int e = lift_validate(d)) return e;
+  const LiftWorkspace w = lift_workspace(d, nullptr);
+  for (int i = 0; i < VAMP_LIFTWS_REGIONS; ++i) {
+    out->offset[i] = (int64_t) w.offset[i];
+    out->bytes[i] = (int64_t) w.region_bytes[i];
+  }
+  out->total_bytes = (int64_t) w.bytes;
+  return VAMP_OK;
+}
+
+int vamp_lift_forward_plan(const VampLiftDesc* d, int has_logits, int32_t logits_dtype, int flags,
+                           size_t workspace_bytes, VampLiftForwardPlan* out) {
+  return lift_forward_plan(__func__, d, has_logits != 0, logits_dtype, flags, workspace_bytes, out);
+}
+
+int vamp_lift_backward_plan(const VampLiftDesc* d, int flags, size_t workspace_bytes, VampLiftBackwardPlan* out) {
+  return lift_backward_plan(__func__, d, flags, workspace_bytes, out);
 }
 
 int vamp_lift_forward(const VampLiftDesc* d, const float* mats, const float* xs, const float* ys,
@@ -1153,41 +1197,15 @@ int vamp_lift_forward(const VampLiftDesc* d, const float* mats, const float* xs,
 int vamp_lift_forward_ex(const VampLiftDesc* d, const float* mats, const float* xs, const float* ys,
                          const float* zs, const void* depth, const void* feat, float* out,
                          uint64_t* hits, void* workspace, size_t workspace_bytes, int flags, void* stream) {
-  if (int e = validate(d)) return e;
+  if (int e = lift_validate(d)) return e;
   VAMP_REQUIRE(mats && xs && ys && zs && feat && out, "null pointer");
   VAMP_REQUIRE(((uintptr_t) mats & 15) == 0, "mats must be 16-byte aligned (the cull reads whole matrix rows)");
   VAMP_REQUIRE(depth || !d->use_depth, "depth is NULL");
-  VAMP_REQUIRE(fused_channels_ok(d->C), "C must be 4, 8 or a multiple of 16 (<= 64)");
-  const LiftWs w = carve(d, workspace);
-  if (!workspace || workspace_bytes < w.bytes)
-    return fail(VAMP_ENOSPC, "%s: workspace %ld < %ld bytes", __func__, (long) workspace_bytes, (long) w.bytes);
-  hipStream_t s = static_cast<hipStream_t>(stream);
-  const LiftParams P = to_params(d);
-  const long BN = (long) d->B * d->N, HW = (long) d->fH * d->fW;
-  void* cells = (flags & VAMP_LIFTFWD_EMIT_PAIRS) ? w.cells : nullptr;
-  const bool clean = (flags & VAMP_LIFTFWD_CELLS_CLEAN) != 0;
-  const bool defer = (flags & VAMP_LIFTFWD_DEFER_SCAN) != 0;
-  if (flags & VAMP_LIFTFWD_FEAT_CHANNEL_LAST) {
-    // the features are already [B, N, fH, fW, C] fp32: no copy, and every workgroup of the forward kernel forms
-    // its own patch's cull word at its head -- the forward is ONE launch
-    VAMP_REQUIRE(d->in_dtype == VAMP_F32, "VAMP_LIFTFWD_FEAT_CHANNEL_LAST takes fp32 features (and depth)");
-    VAMP_REQUIRE(((uintptr_t) feat & 15) == 0, "channel-last feat must be 16-byte aligned");
-    return lift_forward_t<float>(d, P, mats, xs, ys, zs, depth, static_cast<const float*>(feat), out, hits, cells, clean,
-                                 nullptr, s, defer);
-  }
-  // first launch: channel-last copy of the features + the camera cull words of the forward's waves
-  const int ptiles = (int) ((HW + 63) / 64);
-  const long n_cl = BN * ptiles;
-  VAMP_REQUIRE(n_cl < 0x7fffffffL, "too many tiles");
-  const unsigned grid = (unsigned) n_cl;
-  if (d->in_dtype == VAMP_F32)
-    VAMP_TIMED(kProfFeatCL, s, (lift_prologue_kernel<float><<<grid, 256, 0, s>>>(P, static_cast<const float*>(feat), w.feat_cl, ptiles, mats, xs, ys, zs, w.cull)));
-  else
-    VAMP_TIMED(kProfFeatCL, s, (lift_prologue_kernel<__hip_bfloat16><<<grid, 256, 0, s>>>(P, static_cast<const __hip_bfloat16*>(feat), w.feat_cl, ptiles, mats, xs, ys, zs, w.cull)));
-  if (int e = check_launch("lift_prologue_kernel")) return e;
-  if (d->in_dtype == VAMP_F32)
-    return lift_forward_t<float>(d, P, mats, xs, ys, zs, depth, w.feat_cl, out, hits, cells, clean, w.cull.words, s, defer);
-  return lift_forward_t<__hip_bfloat16>(d, P, mats, xs, ys, zs, depth, w.feat_cl, out, hits, cells, clean, w.cull.words, s, defer);
+  VAMP_REQUIRE(!(flags & VAMP_LIFTFWD_FEAT_CHANNEL_LAST) || ((uintptr_t) feat & 15) == 0, "channel-last feat must be 16-byte aligned");
+  VampLiftForwardPlan p;
+  if (int e = lift_forward_plan(__func__, d, false, 0, flags, workspace ? workspace_bytes : 0, &p)) return e;
+  return launch_lift_forward(d, p, lift_workspace(d, workspace), mats, xs, ys, zs, nullptr, 0, nullptr, depth, feat, out,
+                             hits, static_cast<hipStream_t>(stream));
 }
 
 int vamp_lift_forward_logits(const VampLiftDesc* d, const float* mats, const float* xs, const float* ys,
@@ -1202,73 +1220,41 @@ int vamp_lift_forward_logits_ex(const VampLiftDesc* d, const float* mats, const 
                                 const float* zs, const void* logits, int32_t logits_dtype, const float* feat,
                                 float* depth_out, float* out, uint64_t* hits, void* workspace,
                                 size_t workspace_bytes, int flags, void* stream) {
-  if (int e = validate(d)) return e;
+  if (int e = lift_validate(d)) return e;
   VAMP_REQUIRE(mats && xs && ys && zs && logits && feat && depth_out && out, "null pointer");
   VAMP_REQUIRE(((uintptr_t) mats & 15) == 0, "mats must be 16-byte aligned (the cull reads whole matrix rows)");
-  VAMP_REQUIRE(d->use_depth == 1, "the logits entry is the depth-distribution lift");
-  VAMP_REQUIRE(d->in_dtype == VAMP_F32, "feat (and the depth distribution written here) are fp32");
-  VAMP_REQUIRE(logits_dtype == VAMP_F32 || logits_dtype == VAMP_BF16, "logits_dtype");
-  VAMP_REQUIRE(fused_channels_ok(d->C), "C must be 4, 8 or a multiple of 16 (<= 64)");
-  const LiftWs w = carve(d, workspace);
-  if (!workspace || workspace_bytes < w.bytes)
-    return fail(VAMP_ENOSPC, "%s: workspace %ld < %ld bytes", __func__, (long) workspace_bytes, (long) w.bytes);
-  hipStream_t s = static_cast<hipStream_t>(stream);
-  const LiftParams P = to_params(d);
-  const long BN = (long) d->B * d->N, HW = (long) d->fH * d->fW;
-  const long sm_tiles = (HW + kPix - 1) / kPix;
-  const int ptiles = (int) ((HW + 63) / 64);
-  // VAMP_LIFTFWD_FEAT_CHANNEL_LAST: only the softmax tiles; the forward kernel reads the caller's features and forms
-  // its cull words itself
-  const bool fcl = (flags & VAMP_LIFTFWD_FEAT_CHANNEL_LAST) != 0;
-  VAMP_REQUIRE(!fcl || ((uintptr_t) feat & 15) == 0, "channel-last feat must be 16-byte aligned");
-  const long n_sm = BN * sm_tiles, n_cl = fcl ? 0 : BN * ptiles;
-  VAMP_REQUIRE(n_sm + n_cl < 0x7fffffffL, "too many tiles");
-  const unsigned grid = (unsigned) (n_sm + n_cl);
-#define VAMP_OPERANDS(TL, REG)                                                                           \
-  VAMP_TIMED(kProfFeatCL, s, (lift_operands_kernel<TL, REG><<<grid, 256, 0, s>>>(                        \
-      P, static_cast<const TL*>(logits), depth_out, (int) sm_tiles, (unsigned) n_sm, feat, w.feat_cl,    \
-      ptiles, mats, xs, ys, zs, w.cull)))
-  const bool reg = d->D <= kSplit * kRegBins;
-  if (logits_dtype == VAMP_F32) {
-    if (reg) VAMP_OPERANDS(float, true); else VAMP_OPERANDS(float, false);
-  } else {
-    if (reg) VAMP_OPERANDS(__hip_bfloat16, true); else VAMP_OPERANDS(__hip_bfloat16, false);
-  }
-#undef VAMP_OPERANDS
-  if (int e = check_launch("lift_operands_kernel")) return e;
-  return lift_forward_t<float>(d, P, mats, xs, ys, zs, depth_out, fcl ? feat : w.feat_cl, out, hits,
-                               (flags & VAMP_LIFTFWD_EMIT_PAIRS) ? w.cells : nullptr,
-                               (flags & VAMP_LIFTFWD_CELLS_CLEAN) != 0, fcl ? nullptr : w.cull.words, s,
-                               (flags & VAMP_LIFTFWD_DEFER_SCAN) != 0);
+  VAMP_REQUIRE(!(flags & VAMP_LIFTFWD_FEAT_CHANNEL_LAST) || ((uintptr_t) feat & 15) == 0, "channel-last feat must be 16-byte aligned");
+  VampLiftForwardPlan p;
+  if (int e = lift_forward_plan(__func__, d, true, logits_dtype, flags, workspace ? workspace_bytes : 0, &p)) return e;
+  return launch_lift_forward(d, p, lift_workspace(d, workspace), mats, xs, ys, zs, logits, logits_dtype, depth_out,
+                             depth_out, feat, out, hits, static_cast<hipStream_t>(stream));
 }
 
 // the scan a forward with VAMP_LIFTFWD_DEFER_SCAN left out
 int vamp_lift_finish_cells(const VampLiftDesc* d, void* workspace, size_t workspace_bytes, void* stream) {
-  if (int e = validate(d)) return e;
-  const LiftWs w = carve(d, workspace);
-  if (!workspace || workspace_bytes < w.bytes)
-    return fail(VAMP_ENOSPC, "%s: workspace %ld < %ld bytes", __func__, (long) workspace_bytes, (long) w.bytes);
-  return launch_lift_cells_end(d, w.cells, static_cast<hipStream_t>(stream));
+  if (int e = lift_validate(d)) return e;
+  const LiftWorkspace w = lift_workspace(d, workspace);
+  if (int e = lift_workspace_fits(__func__, w, workspace ? workspace_bytes : 0)) return e;
+  return launch_lift_cells_end(w, static_cast<hipStream_t>(stream));
 }
 
 // the same scan as a job for a launch shared with another cell list (render_bwd.hip: vamp_render_camera_prepare_with_lift)
 int lift_scan_job(const VampLiftDesc* d, void* workspace, size_t workspace_bytes, ScanJob* job) {
-  if (int e = validate(d)) return e;
-  const LiftWs w = carve(d, workspace);
-  if (!workspace || workspace_bytes < w.bytes)
-    return fail(VAMP_ENOSPC, "%s: workspace %ld < %ld bytes", __func__, (long) workspace_bytes, (long) w.bytes);
-  return lift_cells_scan_job(d, w.cells, job);
+  if (int e = lift_validate(d)) return e;
+  const LiftWorkspace w = lift_workspace(d, workspace);
+  if (int e = lift_workspace_fits(__func__, w, workspace ? workspace_bytes : 0)) return e;
+  return lift_cells_scan_job(w, job);
 }
 
 int vamp_lift_prepare(const VampLiftDesc* d, const float* mats, const float* xs, const float* ys,
                       const float* zs, const void* depth, void* workspace, size_t workspace_bytes, void* stream) {
-  if (int e = validate(d)) return e;
+  if (int e = lift_validate(d)) return e;
   VAMP_REQUIRE(mats && xs && ys && zs, "null pointer");
   VAMP_REQUIRE(depth || !d->use_depth, "depth is NULL");
-  const LiftWs w = carve(d, workspace);
-  if (!workspace || workspace_bytes < w.bytes)
-    return fail(VAMP_ENOSPC, "%s: workspace %ld < %ld bytes", __func__, (long) workspace_bytes, (long) w.bytes);
-  return launch_lift_cell_prepare(d, mats, xs, ys, zs, depth, w.cells, static_cast<hipStream_t>(stream));
+  if (int e = lift_cells_fit(__func__, d)) return e;
+  const LiftWorkspace w = lift_workspace(d, workspace);
+  if (int e = lift_workspace_fits(__func__, w, workspace ? workspace_bytes : 0)) return e;
+  return launch_lift_cell_prepare(d, to_params(d), w, mats, xs, ys, zs, depth, static_cast<hipStream_t>(stream));
 }
 
 int vamp_lift_backward(const VampLiftDesc* d, const float* mats, const float* xs, const float* ys,
@@ -1279,60 +1265,32 @@ int vamp_lift_backward(const VampLiftDesc* d, const float* mats, const float* xs
                                workspace, workspace_bytes, 0, stream);
 }
 
+// default: cell list + one workgroup per strip of pixels (lift_bwd_cell.hip), no float atomics.
+// VAMP_LIFTBWD_SPLAT selects the per-voxel atomic splat above.
 int vamp_lift_backward_ex(const VampLiftDesc* d, const float* mats, const float* xs, const float* ys,
                           const float* zs, const void* depth, const void* feat,
                           const float* grad_out, const uint64_t* hits, float* grad_depth,
                           float* grad_feat, void* workspace, size_t workspace_bytes, int flags,
                           void* stream) {
-  if (int e = validate(d)) return e;
+  if (int e = lift_validate(d)) return e;
   VAMP_REQUIRE(mats && xs && ys && zs && feat && grad_out && hits && grad_feat, "null pointer");
   VAMP_REQUIRE((depth && grad_depth) || !d->use_depth, "depth / grad_depth is NULL");
-  VAMP_REQUIRE(fused_channels_ok(d->C), "C must be 4, 8 or a multiple of 16 (<= 64)");
-  const LiftWs w = carve(d, workspace);
-  if (!workspace || workspace_bytes < w.bytes)
-    return fail(VAMP_ENOSPC, "%s: workspace %ld < %ld bytes", __func__, (long) workspace_bytes, (long) w.bytes);
-  hipStream_t s = static_cast<hipStream_t>(stream);
+  VampLiftBackwardPlan p;
+  if (int e = lift_backward_plan(__func__, d, flags, workspace ? workspace_bytes : 0, &p)) return e;
   const LiftParams P = to_params(d);
-  const int BN = d->B * d->N, HW = d->fH * d->fW;
-  // VAMP_LIFTBWD_FEAT_CHANNEL_LAST: feat is read, and grad_feat written, as [B, N, fH, fW, C] fp32
-  const bool fcl = (flags & VAMP_LIFTBWD_FEAT_CHANNEL_LAST) != 0;
-  VAMP_REQUIRE(!fcl || d->in_dtype == VAMP_F32, "VAMP_LIFTBWD_FEAT_CHANNEL_LAST takes fp32 features (and depth)");
-  // default: cell list + one wave per pixel (lift_bwd_cell.hip), no float atomics.
-  // VAMP_LIFTBWD_SPLAT selects the per-voxel atomic splat below, kept as an independent cross-check.
-  if (!(flags & VAMP_LIFTBWD_SPLAT)) {
-    // gather variants (same kernel, smaller record chunks: the tests run them to cross the chunk
-    // boundaries at every size)
-    const int wpp = (flags & VAMP_LIFTBWD_WPP1) ? 1 : (flags & VAMP_LIFTBWD_WPP4) ? 4
-                    : (flags & VAMP_LIFTBWD_WPP16) ? 16 : 0;
-    return launch_lift_bwd_cell(d, mats, xs, ys, zs, depth, feat, grad_out, hits, grad_depth,
-                                grad_feat, w.cells, (flags & VAMP_LIFTBWD_CELLS_VALID) != 0, wpp, /*half=*/0,
-                                (flags & VAMP_LIFTBWD_LOGITS) != 0, fcl, s);
-  }
-  VAMP_REQUIRE(!(flags & VAMP_LIFTBWD_LOGITS), "VAMP_LIFTBWD_LOGITS is a feature of the default (cell-list) backward");
-  // (channel-last features: they are what the splat reads, and the gradient it accumulates is what the caller wants)
-  const float* fsrc = fcl ? static_cast<const float*>(feat) : w.feat_cl;
-  float* gdst = fcl ? grad_feat : w.gfeat_cl;
-  if (!fcl) {
-    if (d->in_dtype == VAMP_F32) launch_to_cl<float>(feat, w.feat_cl, BN, d->C, HW, s);
-    else launch_to_cl<__hip_bfloat16>(feat, w.feat_cl, BN, d->C, HW, s);
-    if (int e = check_launch("feat_to_channel_last")) return e;
-  }
-  if (int ze = launch_zero(gdst, (size_t) BN * HW * d->C * sizeof(float), s)) return ze;
-  if (d->use_depth)
-    if (int ze = launch_zero(grad_depth, (size_t) BN * d->D * HW * sizeof(float), s)) return ze;
-  int e = (d->in_dtype == VAMP_F32)
-              ? lift_backward_t<float>(d, P, mats, xs, ys, zs, depth, fsrc, grad_out, hits, grad_depth, gdst, s)
-              : lift_backward_t<__hip_bfloat16>(d, P, mats, xs, ys, zs, depth, fsrc, grad_out, hits, grad_depth, gdst, s);
-  if (e || fcl) return e;
-  dim3 grid((HW + 63) / 64, (d->C + 63) / 64, BN);
-  VAMP_TIMED(kProfFeatCF, s, (feat_to_channel_first<<<grid, 256, 0, s>>>(w.gfeat_cl, grad_feat, d->C, HW)));
-  return check_launch("feat_to_channel_first");
+  const LiftWorkspace w = lift_workspace(d, workspace);
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  if (p.path == VAMP_LIFTPLAN_BWD_CELL)
+    return launch_lift_bwd_cell(d, P, p, w, mats, xs, ys, zs, depth, feat, grad_out, hits, grad_depth, grad_feat, s);
+  if (d->in_dtype == VAMP_F32)
+    return launch_lift_bwd_splat<float>(d, P, p, w, mats, xs, ys, zs, depth, feat, grad_out, hits, grad_depth, grad_feat, s);
+  return launch_lift_bwd_splat<__hip_bfloat16>(d, P, p, w, mats, xs, ys, zs, depth, feat, grad_out, hits, grad_depth, grad_feat, s);
 }
 
 int vamp_lift_forward_dense(const VampLiftDesc* d, const float* mats, const float* xs,
                             const float* ys, const float* zs, const float* frustum_feats,
                             float* out, uint64_t* hits, void* stream) {
-  if (int e = validate(d)) return e;
+  if (int e = lift_validate(d)) return e;
   VAMP_REQUIRE(mats && xs && ys && zs && frustum_feats && out, "null pointer");
   const LiftParams P = to_params(d);
   const long total = (long) d->B * d->Z * d->Y * d->X;
@@ -1345,7 +1303,7 @@ int vamp_lift_forward_dense(const VampLiftDesc* d, const float* mats, const floa
 int vamp_lift_backward_dense(const VampLiftDesc* d, const float* mats, const float* xs,
                              const float* ys, const float* zs, const float* grad_out,
                              const uint64_t* hits, float* grad_frustum_feats, void* stream) {
-  if (int e = validate(d)) return e;
+  if (int e = lift_validate(d)) return e;
   VAMP_REQUIRE(mats && xs && ys && zs && grad_out && hits && grad_frustum_feats, "null pointer");
   const LiftParams P = to_params(d);
   const long total = (long) d->B * d->Z * d->Y * d->X;
@@ -1357,24 +1315,24 @@ int vamp_lift_backward_dense(const VampLiftDesc* d, const float* mats, const flo
 
 int vamp_lift_cull_words(const VampLiftDesc* d, const float* mats, const float* xs, const float* ys,
                          const float* zs, uint32_t* words, int32_t patch[2], int32_t grid[2], void* stream) {
-  if (int e = validate(d)) return e;
+  if (int e = lift_validate(d)) return e;
   VAMP_REQUIRE(patch && grid, "null pointer");
-  LiftWs w = carve(d, nullptr);
-  patch[0] = w.cull.px; patch[1] = w.cull.py;
-  grid[0] = w.cull.nxp; grid[1] = w.cull.nyp;
+  LiftCull cull = lift_workspace(d, nullptr).cull;
+  patch[0] = cull.px; patch[1] = cull.py;
+  grid[0] = cull.nxp; grid[1] = cull.nyp;
   if (!words) return VAMP_OK;
   VAMP_REQUIRE(mats && xs && ys && zs, "null pointer");
   VAMP_REQUIRE(((uintptr_t) mats & 15) == 0, "mats must be 16-byte aligned (the cull reads whole matrix rows)");
-  w.cull.words = words;
-  lift_cull_kernel<<<(unsigned) ((long) d->B * w.cull.bps), 256, 0, static_cast<hipStream_t>(stream)>>>(
-      to_params(d), mats, xs, ys, zs, w.cull);
+  cull.words = words;
+  lift_cull_kernel<<<(unsigned) ((long) d->B * cull.bps), 256, 0, static_cast<hipStream_t>(stream)>>>(
+      to_params(d), mats, xs, ys, zs, cull);
   return check_launch("lift_cull_kernel");
 }
 
 int vamp_lift_indices(const VampLiftDesc* d, const float* mats, const float* xs, const float* ys,
                       const float* zs, uint8_t* valid, int16_t* ix0, int16_t* iy0, int16_t* iz0,
                       void* stream) {
-  if (int e = validate(d)) return e;
+  if (int e = lift_validate(d)) return e;
   VAMP_REQUIRE(mats && xs && ys && zs && valid && ix0 && iy0 && iz0, "null pointer");
   const LiftParams P = to_params(d);
   const long total = (long) d->B * d->N * d->Z * d->Y * d->X;

@@ -678,92 +678,119 @@ namespace vamp {
 // ---------------------------------------------------------------------------
 // host side
 // ---------------------------------------------------------------------------
-size_t lift_bwd_cell_ws_bytes(const VampLiftDesc* d) { return lift_cell_ws(d, nullptr).bytes; }
+int lift_cells_fit(const char* who, const VampLiftDesc* d) {
+  const size_t cap = (size_t) d->B * d->N * d->Z * d->Y * d->X;
+  VAMP_REQUIRE_AS(who, cap < 0x7fffffffu && lift_workspace(d, nullptr).ncell < 0x7fffffffL, "pair / cell count exceeds 2^31");
+  VAMP_REQUIRE_AS(who, d->C % 4 == 0, "C must be a multiple of 4");
+  VAMP_REQUIRE_AS(who, d->fW < 32767 && d->fH < 32767 && d->D < 65535, "feature map too large for the packed cell coordinates");
+  return VAMP_OK;
+}
 
 // zero the counters in front of a kernel that emits pairs / scan them behind it
-int launch_lift_cells_begin(const VampLiftDesc* d, void* scratch, hipStream_t s, bool clean) {
-  const LiftCells g = lift_cells(d);
-  const LiftCellWs w = lift_cell_ws(d, scratch);
-  const size_t cap = (size_t) d->B * d->N * d->Z * d->Y * d->X;
-  VAMP_REQUIRE(cap < 0x7fffffffu && g.ncell < 0x7fffffffL, "pair / cell count exceeds 2^31");
-  VAMP_REQUIRE(d->C % 4 == 0, "C must be a multiple of 4");
-  VAMP_REQUIRE(d->fW < 32767 && d->fH < 32767 && d->D < 65535, "feature map too large for the packed cell coordinates");
+int launch_lift_cells_begin(const LiftWorkspace& w, bool clean, hipStream_t s) {
   if (clean)                        // (VAMP_LIFTFWD_CELLS_CLEAN: the caller vouches for zeroed counters)
-    return debug_expect_range(w.cnt, (size_t) (g.ncell + kScanPad), 0, 0, s, "VAMP_LIFTFWD_CELLS_CLEAN: the lift workspace's cell counters are zero");
-  return launch_zero(w.cnt, (size_t) (g.ncell + kScanPad) * sizeof(int), s);
+    return debug_expect_range(w.cnt, (size_t) (w.ncell + kScanPad), 0, 0, s, "VAMP_LIFTFWD_CELLS_CLEAN: the lift workspace's cell counters are zero");
+  return launch_zero(w.cnt, (size_t) (w.ncell + kScanPad) * sizeof(int), s);
 }
 
-int launch_lift_cells_end(const VampLiftDesc* d, void* scratch, hipStream_t s) {
-  const LiftCells g = lift_cells(d);
-  const LiftCellWs w = lift_cell_ws(d, scratch);
-  return launch_cell_scan(w.cnt, w.off, w.bsum, w.boff, w.aux, g.ncell, s);
+int launch_lift_cells_end(const LiftWorkspace& w, hipStream_t s) {
+  return launch_cell_scan(w.cnt, w.off, w.bsum, w.boff, w.aux, w.ncell, s);
 }
-int lift_cells_scan_job(const VampLiftDesc* d, void* scratch, ScanJob* job) {
-  const LiftCells g = lift_cells(d);
-  const LiftCellWs w = lift_cell_ws(d, scratch);
-  return make_scan_job(w.cnt, w.off, w.bsum, w.boff, w.aux, g.ncell, job);
+int lift_cells_scan_job(const LiftWorkspace& w, ScanJob* job) {
+  return make_scan_job(w.cnt, w.off, w.bsum, w.boff, w.aux, w.ncell, job);
+}
+
+// The backward's plan: every choice vamp_lift_backward_ex makes, from the descriptor, the flags and the workspace size.
+// No HIP call.
+int lift_backward_plan(const char* who, const VampLiftDesc* d, int flags, size_t workspace_bytes, VampLiftBackwardPlan* out) {
+  if (!out) return fail(VAMP_EINVAL, "%s: requirement failed: plan is NULL", who);
+  memset(out, 0, sizeof(*out));
+  if (int e = lift_validate(d)) return e;
+  VampLiftBackwardPlan& p = *out;
+  VAMP_REQUIRE_AS(who, lift_channels_ok(d->C), "C must be 4, 8 or a multiple of 16 (<= 64)");
+  // VAMP_LIFTBWD_FEAT_CHANNEL_LAST: feat is read, and grad_feat written, as [B, N, fH, fW, C] fp32
+  p.feat_cl = (flags & VAMP_LIFTBWD_FEAT_CHANNEL_LAST) != 0;
+  VAMP_REQUIRE_AS(who, !p.feat_cl || d->in_dtype == VAMP_F32, "VAMP_LIFTBWD_FEAT_CHANNEL_LAST takes fp32 features (and depth)");
+  const LiftWorkspace w = lift_workspace(d, nullptr);
+  p.bytes_needed = (int64_t) w.bytes;
+  const long BN = (long) d->B * d->N, HW = (long) d->fH * d->fW;
+  const int ch = d->C == 4 ? 4 : (d->C == 8 ? 8 : 16);
+  if (flags & VAMP_LIFTBWD_SPLAT) {
+    VAMP_REQUIRE_AS(who, !(flags & VAMP_LIFTBWD_LOGITS), "VAMP_LIFTBWD_LOGITS is a feature of the default (cell-list) backward");
+    p.path = VAMP_LIFTPLAN_BWD_SPLAT;
+    p.to_cl = p.to_cf = !p.feat_cl;
+    p.zero_feat_bytes = BN * HW * d->C * (int64_t) sizeof(float);
+    p.zero_depth_bytes = d->use_depth ? BN * d->D * HW * (int64_t) sizeof(float) : 0;
+    p.splat_ch = ch;
+    p.splat_grid[0] = (d->X + VAMP_LIFT_TX - 1) / VAMP_LIFT_TX;
+    p.splat_grid[1] = (d->Y + VAMP_LIFT_TY - 1) / VAMP_LIFT_TY;
+    p.splat_grid[2] = d->Z * d->B;
+    return lift_workspace_fits(who, w, workspace_bytes);
+  }
+  p.path = VAMP_LIFTPLAN_BWD_CELL;
+  p.prepare = !(flags & VAMP_LIFTBWD_CELLS_VALID);
+  if (p.prepare)
+    if (int e = lift_cells_fit(who, d)) return e;
+  // fill: a wave per 64 voxels of a sample's flattened (z, y, x) index, four waves per workgroup
+  const long wps = ((long) d->Z * d->Y * d->X + 63) / 64;
+  VAMP_REQUIRE_AS(who, wps * 64 < 0x7fffffffL && wps * d->B < 0x7fffffffL, "voxel count exceeds 2^31");
+  p.fill_ch = ch;
+  p.fill_grid = (int32_t) ((wps * d->B + 3) / 4);
+  p.fill_lds = (int64_t) 4 * 64 * (2 + d->C / 4) * sizeof(float4);      // [wave][lane][record piece]
+  // gather variants (same kernel, smaller record chunks: the tests run them to cross the chunk boundaries at every
+  // size): pairs staged per chunk, 128 by default
+  p.cap = (flags & VAMP_LIFTBWD_WPP1) ? 128 : ((flags & VAMP_LIFTBWD_WPP4) ? 64 : ((flags & VAMP_LIFTBWD_WPP16) ? 32 : 128));
+  p.strip_lds = (int64_t) (strip_lds_floats(d->use_depth ? d->D : 0, p.cap) * sizeof(float));
+  if (p.strip_lds > 150 * 1024) return fail(VAMP_EINVAL, "%s: D too large for the LDS depth tiles", who);
+  p.raise_lds = p.strip_lds > 64 * 1024;
+  // 16-byte tile I/O needs fp32 depth planes whose strips start on 16-byte boundaries
+  p.vec = d->in_dtype == VAMP_F32 && d->fW % 4 == 0;
+  p.strip_grid = (int32_t) ((unsigned) BN * d->fH * ((d->fW + kS - 1) / kS));
+  p.softmax_bwd = (flags & VAMP_LIFTBWD_LOGITS) != 0;
+  return lift_workspace_fits(who, w, workspace_bytes);
+}
+
+// the fill, as the plan says (the counters are the fill cursors: the scan left them at zero)
+static int launch_lift_fill(const VampLiftDesc* d, const LiftParams& P, const VampLiftBackwardPlan& p, const LiftWorkspace& w,
+                            const float* gout, const uint64_t* hits, hipStream_t s) {
+  const int BN = d->B * d->N;
+  const int wps = (int) (((long) d->Z * d->Y * d->X + 63) / 64);
+#define VAMP_CELL(CH)                                                                                        \
+  VAMP_TIMED(kProfLiftBwdFill, s, (lift_bwd_fill_kernel<CH><<<(unsigned) p.fill_grid, 256, (size_t) p.fill_lds, s>>>(   \
+      P, w.cw, w.ch, gout, hits, w.amask, w.ptaps, w.pcell, w.cnt, w.off, w.boff, w.recs, w.rowq, 0, BN, wps)))
+  if (p.fill_ch == 4) VAMP_CELL(4); else if (p.fill_ch == 8) VAMP_CELL(8); else VAMP_CELL(16);
+#undef VAMP_CELL
+  return check_launch("lift_bwd_fill_kernel");
 }
 
 template <typename T>
-static int launch_cell_t(const VampLiftDesc* d, const LiftParams& P, const float* mats,
-                         const float* xs, const float* ys, const float* zs, const void* depth,
-                         const void* feat, const float* gout, const uint64_t* hits, float* gdepth,
-                         float* gfeat, void* scratch, bool cells_valid, int variant, int half, bool softmax_bwd,
-                         bool fcl, hipStream_t s) {
-  const LiftCells g = lift_cells(d);
-  const LiftCellWs w = lift_cell_ws(d, scratch);
-  if (!cells_valid)
-    if (int e = launch_lift_cell_prepare(d, mats, xs, ys, zs, depth, scratch, s)) return e;
-  // (the counters are the fill cursors: the scan left them at zero)
-  // half 0: all images; 1 / 2: the lower / upper half of the flattened (sample, camera) index
-  const int BN = d->B * d->N;
-  const int bn_lo = half == 2 ? BN / 2 : 0, bn_hi = half == 1 ? BN / 2 : BN;
-  if (bn_hi <= bn_lo) return VAMP_OK;
-  // a wave per 64 voxels of a sample's flattened (z, y, x) index, four waves per workgroup
-  const long wps = ((long) d->Z * d->Y * d->X + 63) / 64;
-  VAMP_REQUIRE(wps * 64 < 0x7fffffffL && wps * d->B < 0x7fffffffL, "voxel count exceeds 2^31");
-  const unsigned grid = (unsigned) ((wps * d->B + 3) / 4);
-  const size_t fill_lds = (size_t) 4 * 64 * (2 + d->C / 4) * sizeof(float4);      // [wave][lane][record piece]
-#define VAMP_CELL(CH)                                                                            \
-  VAMP_TIMED(kProfLiftBwdFill, s, (lift_bwd_fill_kernel<CH><<<grid, 256, fill_lds, s>>>(         \
-      P, g.cw, g.ch, gout, hits, w.amask, w.ptaps, w.pcell, w.cnt, w.off, w.boff, w.recs, w.rowq, bn_lo, bn_hi, (int) wps)))
-  if (P.C == 4) VAMP_CELL(4); else if (P.C == 8) VAMP_CELL(8); else VAMP_CELL(16);
-#undef VAMP_CELL
-  if (int e = check_launch("lift_bwd_fill_kernel")) return e;
-
-  // pairs staged per chunk: 128 by default; the variants exist so that the tests cross chunk
-  // boundaries at every size
-  const int cap = variant == 4 ? 64 : (variant == 16 ? 32 : 128);
-  const int Dd = d->use_depth ? d->D : 0;
-  const size_t lds = strip_lds_floats(Dd, cap) * sizeof(float);
-  if (lds > 150 * 1024) return fail(VAMP_EINVAL, "%s: D too large for the LDS depth tiles", __func__);
+static int launch_cell_t(const VampLiftDesc* d, const LiftParams& P, const VampLiftBackwardPlan& p, const LiftWorkspace& w,
+                         const float* mats, const float* xs, const float* ys, const float* zs, const void* depth,
+                         const void* feat, const float* gout, const uint64_t* hits, float* gdepth, float* gfeat,
+                         hipStream_t s) {
+  // (the one step that can fail without being a launch: in front of the first launch)
+  auto strip = p.vec ? lift_bwd_strip_kernel<T, true> : lift_bwd_strip_kernel<T, false>;
+  if (p.raise_lds &&
+      hipFuncSetAttribute(reinterpret_cast<const void*>(strip), hipFuncAttributeMaxDynamicSharedMemorySize,
+                          (int) p.strip_lds) != hipSuccess)
+    return fail(VAMP_EHIP, "%s: cannot raise dynamic LDS", __func__);
+  if (p.prepare)
+    if (int e = launch_lift_cell_prepare(d, P, w, mats, xs, ys, zs, depth, s)) return e;
+  if (int e = launch_lift_fill(d, P, p, w, gout, hits, s)) return e;
   const int spr = (d->fW + kS - 1) / kS;
-  const unsigned ggrid = (unsigned) (bn_hi - bn_lo) * d->fH * spr;
-  {
-    // 16-byte tile I/O needs fp32 depth planes whose strips start on 16-byte boundaries
-    const bool vec = std::is_same<T, float>::value && d->fW % 4 == 0;
-    auto k = vec ? lift_bwd_strip_kernel<T, true> : lift_bwd_strip_kernel<T, false>;
-    if (lds > 64 * 1024 &&
-        hipFuncSetAttribute(reinterpret_cast<const void*>(k),
-                            hipFuncAttributeMaxDynamicSharedMemorySize, (int) lds) != hipSuccess)
-      return fail(VAMP_EHIP, "%s: cannot raise dynamic LDS", __func__);
-    VAMP_TIMED(kProfLiftBwd, s, (k<<<ggrid, kW * 64, lds, s>>>(
-        P, g.cw, g.ch, spr, spr, bn_lo, cap, static_cast<const T*>(depth), static_cast<const T*>(feat),
-        w.off, w.boff, w.recs, w.rowq, w.cnt, gdepth, gfeat, softmax_bwd ? 1 : 0, fcl ? 1 : 0)));
-  }
+  VAMP_TIMED(kProfLiftBwd, s, (strip<<<(unsigned) p.strip_grid, kW * 64, (size_t) p.strip_lds, s>>>(
+      P, w.cw, w.ch, spr, spr, 0, p.cap, static_cast<const T*>(depth), static_cast<const T*>(feat),
+      w.off, w.boff, w.recs, w.rowq, w.cnt, gdepth, gfeat, p.softmax_bwd, p.feat_cl)));
   return check_launch("lift_bwd_strip_kernel");
 }
 
-int launch_lift_bwd_cell(const VampLiftDesc* d, const float* mats, const float* xs, const float* ys,
-                         const float* zs, const void* depth, const void* feat, const float* gout,
-                         const uint64_t* hits, float* gdepth, float* gfeat, void* scratch,
-                         bool cells_valid, int variant, int half, bool softmax_bwd, bool fcl, hipStream_t s) {
-  const LiftParams P = to_params(d);
+int launch_lift_bwd_cell(const VampLiftDesc* d, const LiftParams& P, const VampLiftBackwardPlan& p, const LiftWorkspace& w,
+                         const float* mats, const float* xs, const float* ys, const float* zs, const void* depth,
+                         const void* feat, const float* gout, const uint64_t* hits, float* gdepth, float* gfeat,
+                         hipStream_t s) {
   if (d->in_dtype == VAMP_F32)
-    return launch_cell_t<float>(d, P, mats, xs, ys, zs, depth, feat, gout, hits, gdepth, gfeat, scratch,
-                                cells_valid, variant, half, softmax_bwd, fcl, s);
-  return launch_cell_t<__hip_bfloat16>(d, P, mats, xs, ys, zs, depth, feat, gout, hits, gdepth, gfeat,
-                                       scratch, cells_valid, variant, half, softmax_bwd, fcl, s);
+    return launch_cell_t<float>(d, P, p, w, mats, xs, ys, zs, depth, feat, gout, hits, gdepth, gfeat, s);
+  return launch_cell_t<__hip_bfloat16>(d, P, p, w, mats, xs, ys, zs, depth, feat, gout, hits, gdepth, gfeat, s);
 }
 
 }  // namespace vamp

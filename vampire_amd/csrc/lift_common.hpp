@@ -3,6 +3,8 @@
 #include "common.hpp"
 #include "cell_list.hpp"
 
+#include <algorithm>
+
 namespace vamp {
 
 struct LiftParams {
@@ -93,29 +95,48 @@ __device__ __forceinline__ LiftTap lift_project(const LiftParams& P, const float
 
 
 // ---------------------------------------------------------------------------
-// Cell lists of the lift backward (lift_bwd_cell.hip).  Cell = (image, floor tap row + 1, floor tap
-// column + 1): (fH + 1) x (fW + 1) cells per camera image.  The FORWARD kernel (grad mode) or the
-// stand-alone prepare kernel counts the valid (voxel, camera) pairs per cell and leaves every
-// pair's taps and its four depth samples in `ptaps` (and `pcell`), indexed by (image, voxel); the
-// backward's fill pass only re-lays them in cell order, each with its voxel's gradient row -- nothing on
-// the backward projects a voxel or reads a depth plane again.
+// The tile of the projecting kernels (lift.hip) and the patch of voxels one camera cull word stands for (the workspace
+// below holds a word per patch).
 // ---------------------------------------------------------------------------
-struct LiftCells {
-  int cw, ch;                        // cells per row / column of one camera
-  long ncell;                        // padded to the scan tile, + 2 for the range ends
+// tile shape: lanes along x for coalesced stores
+// A wave is a 16 x 4 patch of voxels, not a 64 x 1 row: the exact wave-level camera cull of
+// lift_project<true> skips a camera only when none of the wave's voxels has it in front, and a
+// 6.4 m x 1.6 m patch is on one side of most cameras where a 25.6 m row is not (cfg-B: 47 -> 36 us;
+// 8 x 32 / 16 x 16 / 32 x 8 / 64 x 4 workgroup tiles: 36.5 / 35.7 / 38.2 / 47.1).
+#ifndef VAMP_LIFT_TX
+#define VAMP_LIFT_TX 16
+#define VAMP_LIFT_TY 16
+#endif
+#ifndef VAMP_CULL_WPW
+#define VAMP_CULL_WPW 4      // (1 / 2 / 4: first launch 9.9 / 9.0 / 9.0 us, forward kernel 28.3 / 28.4 / 28.4 at cfg-B)
+#endif
+constexpr int kCullWpw = VAMP_CULL_WPW;     // waves of lift_fwd_kernel (stacked along y) that share a word: 1, 2 or 4
+constexpr int kCullPX = VAMP_LIFT_TX, kCullPY = 64 / VAMP_LIFT_TX * kCullWpw;
+
+struct LiftCull {
+  unsigned* words;      // [B][Z][nyp][nxp]
+  int nxp, nyp;         // patches per row / column of one z plane
+  int px, py;           // patch shape in voxels
+  int group;            // lanes per patch in a cull workgroup: the power of two >= N
+  int bps;              // stand-alone cull: workgroups (256 / group patches each) per sample
+  int ppt;              // forward's first launch: patches per feature tile (N * ptiles tiles per sample)
 };
 
-inline LiftCells lift_cells(const VampLiftDesc* d) {
-  LiftCells g;
-  g.cw = d->fW + 1;
-  g.ch = d->fH + 1;
-  const long nc = (long) d->B * d->N * g.cw * g.ch + 2;
-  g.ncell = (nc + kScanTile - 1) / kScanTile * kScanTile;
-  return g;
-}
-
-struct LiftCellWs {
-  int *cnt, *off, *bsum, *boff, *aux;
+// ---------------------------------------------------------------------------
+// The lift workspace (vamp_lift_workspace_bytes; region by region: vamp_lift_workspace_layout), in this order, every
+// region 256-byte aligned and back to back:
+//   feat_cl | gfeat_cl | cnt | off | bsum | boff | aux | amask | ptaps | pcell | recs | rowq | cull words
+// cnt .. rowq are the cell lists of the lift backward (lift_bwd_cell.hip); they lie behind the copies: a forward must
+// not disturb prepared offsets.  Cell = (image, floor tap row + 1, floor tap column + 1): (fH + 1) x (fW + 1) cells per
+// camera image.  The FORWARD kernel (grad mode) or the stand-alone prepare kernel counts the valid (voxel, camera)
+// pairs per cell and leaves every pair's taps and its four depth samples in `ptaps` (and `pcell`), indexed by
+// (image, voxel); the backward's fill pass only re-lays them in cell order, each with its voxel's gradient row --
+// nothing on the backward projects a voxel or reads a depth plane again.
+// ---------------------------------------------------------------------------
+struct LiftWorkspace {
+  float* feat_cl;                    // [B * N, HW, C] channel-last fp32 copy of the features
+  float* gfeat_cl;                   // [B * N, HW, C] the splat backward's gradient in that layout
+  int *cnt, *off, *bsum, *boff, *aux;   // counters (+ the scan's ticket word) and the scan's levels, as launch_cell_scan takes them
   unsigned* amask;                   // [B * V] cameras each voxel has a pair with (N <= 32)
   float4* ptaps;                     // [B * N * V][2] of the pair, voxel order (sparse): {wx1, wy1, wz1, (iz0 + 1) | (ix0 + 1) << 16} |
                                      // its depth samples sum_d w_d depth[d, pixel] at its four pixel taps (32 bytes side by side:
@@ -124,30 +145,77 @@ struct LiftCellWs {
   float4* recs;                      // [cap][2 + C / 4] every pair in cell order: its taps | its depth samples | its voxel's
                                      // row grad_out / (hits + 1e-6) -- everything the gather needs of a pair, one run
   int* rowq;                         // [B * N * fH] image rows, those with the most pairs first
+  LiftCull cull;                     // camera cull words of the forward's waves (cull.words: the last region) and their geometry
+  long ncull;
+  size_t offset[VAMP_LIFTWS_REGIONS], region_bytes[VAMP_LIFTWS_REGIONS];   // of the regions above, in that order
+  int cw, ch;                        // cells per row / column of one camera
+  long ncell;                        // padded to the scan tile, + 2 for the range ends
   size_t bytes;
 };
 
-inline LiftCellWs lift_cell_ws(const VampLiftDesc* d, void* scratch) {
-  const LiftCells g = lift_cells(d);
-  const long ntile = g.ncell / kScanTile;
+// `workspace` may be nullptr (only the sizes and the geometry are of use then)
+inline LiftWorkspace lift_workspace(const VampLiftDesc* d, void* workspace) {
+  LiftWorkspace w;
+  w.cw = d->fW + 1;
+  w.ch = d->fH + 1;
+  const long nc = (long) d->B * d->N * w.cw * w.ch + 2;
+  w.ncell = (nc + kScanTile - 1) / kScanTile * kScanTile;
+  const size_t ncell = (size_t) w.ncell, ntile = ncell / kScanTile;
   // every (voxel, camera) pair can be valid
   const size_t V = (size_t) d->Z * d->Y * d->X;
   const size_t cap = (size_t) d->B * d->N * V;
-  char* p = static_cast<char*>(scratch);
-  LiftCellWs w;
-  w.cnt = reinterpret_cast<int*>(p); p += align_up((size_t) (g.ncell + kScanPad) * sizeof(int), 256);   // + the scan's ticket word
-  w.off = reinterpret_cast<int*>(p); p += align_up((size_t) g.ncell * sizeof(int), 256);
-  w.bsum = reinterpret_cast<int*>(p); p += align_up((size_t) ntile * sizeof(int), 256);
-  w.boff = reinterpret_cast<int*>(p); p += align_up((size_t) ntile * sizeof(int), 256);
-  w.aux = reinterpret_cast<int*>(p); p += align_up((size_t) (ntile + 4) * sizeof(int), 256);
-  w.amask = reinterpret_cast<unsigned*>(p); p += align_up((size_t) d->B * V * sizeof(unsigned), 256);
-  w.ptaps = reinterpret_cast<float4*>(p); p += align_up(cap * 2 * sizeof(float4), 256);
-  w.pcell = reinterpret_cast<int*>(p); p += align_up(cap * sizeof(int), 256);
-  w.recs = reinterpret_cast<float4*>(p); p += align_up(cap * (size_t) (2 + (d->C + 3) / 4) * sizeof(float4), 256);
-  w.rowq = reinterpret_cast<int*>(p); p += align_up((size_t) d->B * d->N * d->fH * sizeof(int), 256);
-  w.bytes = (size_t) (p - static_cast<char*>(scratch));
+  w.cull.px = VAMP_LIFT_TX;
+  w.cull.py = kCullPY;
+  w.cull.nxp = (d->X + VAMP_LIFT_TX - 1) / VAMP_LIFT_TX;
+  w.cull.nyp = (d->Y + VAMP_LIFT_TY - 1) / VAMP_LIFT_TY * (4 / kCullWpw);
+  w.ncull = (long) d->B * d->Z * w.cull.nyp * w.cull.nxp;
+  w.cull.group = 1;
+  while (w.cull.group < d->N) w.cull.group *= 2;
+  const int ppb = std::min(256 / w.cull.group, 64);
+  const long per_sample = (long) d->Z * w.cull.nyp * w.cull.nxp;
+  w.cull.bps = (int) ((per_sample + ppb - 1) / ppb);
+  const long tiles = (long) d->N * (((long) d->fH * d->fW + 63) / 64);
+  w.cull.ppt = (int) ((per_sample + tiles - 1) / tiles);
+  size_t off = 0;
+  int region = 0;
+  auto take = [&](size_t n) {
+    char* p = workspace ? static_cast<char*>(workspace) + off : nullptr;
+    n = align_up(n, 256);
+    w.offset[region] = off;
+    w.region_bytes[region++] = n;
+    off += n;
+    return p;
+  };
+  const size_t feat_bytes = (size_t) d->B * d->N * d->fH * d->fW * d->C * sizeof(float);
+  w.feat_cl = reinterpret_cast<float*>(take(feat_bytes));
+  w.gfeat_cl = reinterpret_cast<float*>(take(feat_bytes));
+  w.cnt = reinterpret_cast<int*>(take((ncell + kScanPad) * sizeof(int)));
+  w.off = reinterpret_cast<int*>(take(ncell * sizeof(int)));
+  w.bsum = reinterpret_cast<int*>(take(ntile * sizeof(int)));
+  w.boff = reinterpret_cast<int*>(take(ntile * sizeof(int)));
+  w.aux = reinterpret_cast<int*>(take((ntile + 4) * sizeof(int)));
+  w.amask = reinterpret_cast<unsigned*>(take((size_t) d->B * V * sizeof(unsigned)));
+  w.ptaps = reinterpret_cast<float4*>(take(cap * 2 * sizeof(float4)));
+  w.pcell = reinterpret_cast<int*>(take(cap * sizeof(int)));
+  w.recs = reinterpret_cast<float4*>(take(cap * (size_t) (2 + (d->C + 3) / 4) * sizeof(float4)));
+  w.rowq = reinterpret_cast<int*>(take((size_t) d->B * d->N * d->fH * sizeof(int)));
+  w.cull.words = reinterpret_cast<unsigned*>(take((size_t) w.ncull * sizeof(unsigned)));
+  w.bytes = off;
   return w;
 }
+
+// the one refusal of a workspace that is too small (callers pass 0 bytes for a NULL workspace)
+inline int lift_workspace_fits(const char* who, const LiftWorkspace& w, size_t workspace_bytes) {
+  if (workspace_bytes < w.bytes)
+    return fail(VAMP_ENOSPC, "%s: workspace %ld < %ld bytes", who, (long) workspace_bytes, (long) w.bytes);
+  return VAMP_OK;
+}
+
+// VAMP_REQUIRE in a function that refuses in the name of its caller `who` (the plans)
+#define VAMP_REQUIRE_AS(who, cond, msg)                                                             \
+  do {                                                                                              \
+    if (!(cond)) return ::vamp::fail(VAMP_EINVAL, "%s: requirement failed: " msg, who);             \
+  } while (0)
 
 // What the projecting kernels hand to lift_emit_pair.
 struct LiftEmit {
@@ -158,14 +226,7 @@ struct LiftEmit {
   int cw, ch;
 };
 
-inline LiftEmit lift_emit_of(const VampLiftDesc* d, void* cells) {
-  const LiftCells g = lift_cells(d);
-  const LiftCellWs w = lift_cell_ws(d, cells);
-  LiftEmit e;
-  e.cnt = w.cnt; e.amask = w.amask; e.ptaps = w.ptaps; e.pcell = w.pcell;
-  e.cw = g.cw; e.ch = g.ch;
-  return e;
-}
+inline LiftEmit lift_emit_of(const LiftWorkspace& w) { return LiftEmit{w.cnt, w.amask, w.ptaps, w.pcell, w.cw, w.ch}; }
 
 // One camera of one voxel, called in WAVE-UNIFORM control flow (exited lanes are fine): counts the
 // pair in its cell -- one atomic per run of lanes with equal cells, x-neighbouring voxels share a
@@ -193,18 +254,30 @@ __device__ __forceinline__ void lift_emit_dep(const LiftEmit& E, bool act, long 
   if (act) E.ptaps[(bn * V + vox) * 2 + 1] = make_float4(dep[0], dep[1], dep[2], dep[3]);
 }
 
+// ---- the lift's host functions that cross files, each declared here once ----
 // lift_bwd_cell.hip
-size_t lift_bwd_cell_ws_bytes(const VampLiftDesc* d);
-int launch_lift_bwd_cell(const VampLiftDesc* d, const float* mats, const float* xs, const float* ys,
-                         const float* zs, const void* depth, const void* feat, const float* gout,
-                         const uint64_t* hits, float* gdepth, float* gfeat, void* scratch,
-                         bool cells_valid, int variant, int half, bool softmax_bwd, bool feat_cl, hipStream_t s);
-int launch_lift_cell_prepare(const VampLiftDesc* d, const float* mats, const float* xs,
-                             const float* ys, const float* zs, const void* depth, void* scratch, hipStream_t s);
-// zero the cell counters (before a kernel that emits pairs) / scan them (after it)
-int launch_lift_cells_begin(const VampLiftDesc* d, void* scratch, hipStream_t s, bool clean = false);
-int launch_lift_cells_end(const VampLiftDesc* d, void* scratch, hipStream_t s);
-int lift_cells_scan_job(const VampLiftDesc* d, void* scratch, ScanJob* job);
+// The shapes the cell lists cannot hold: asked (by the plans, by vamp_lift_prepare) before anything is launched, wherever
+// pairs are emitted or the prepare pass runs (`who`: the entry point whose name a refusal carries)
+int lift_cells_fit(const char* who, const VampLiftDesc* d);
+// the counters in front of a kernel that emits pairs: zeroed, or -- `clean` -- promised zero (verified under vamp_debug_checks)
+int launch_lift_cells_begin(const LiftWorkspace& w, bool clean, hipStream_t s);
+// ... and their scan behind it
+int launch_lift_cells_end(const LiftWorkspace& w, hipStream_t s);
+int lift_cells_scan_job(const LiftWorkspace& w, ScanJob* job);
+// The backward's plan for `who`: vamp_lift_backward_plan.
+int lift_backward_plan(const char* who, const VampLiftDesc* d, int flags, size_t workspace_bytes, VampLiftBackwardPlan* out);
+// the cell-list backward as the plan says (path VAMP_LIFTPLAN_BWD_CELL)
+int launch_lift_bwd_cell(const VampLiftDesc* d, const LiftParams& P, const VampLiftBackwardPlan& plan, const LiftWorkspace& w,
+                         const float* mats, const float* xs, const float* ys, const float* zs, const void* depth,
+                         const void* feat, const float* gout, const uint64_t* hits, float* gdepth, float* gfeat,
+                         hipStream_t s);
+// lift.hip
+// (the caller has asked lift_cells_fit)
+int launch_lift_cell_prepare(const VampLiftDesc* d, const LiftParams& P, const LiftWorkspace& w, const float* mats,
+                             const float* xs, const float* ys, const float* zs, const void* depth, hipStream_t s);
+// the channel counts the fused kernels are compiled for
+inline bool lift_channels_ok(int C) { return C == 4 || C == 8 || (C % 16 == 0 && C <= 64); }
+int lift_validate(const VampLiftDesc* d);
 
 }  // namespace vamp
 

@@ -33,6 +33,27 @@ from .losses import REG_MAX_TERMS, REG_TILE, RegTerm, reg_loss, reg_losses, rgb_
 BEV_MAX_OZ = 64
 
 
+def lift_desc(cfg: PathConfig, B, N, C_, dtype_code, use_depth=True, fhw=None) -> _capi.VampLiftDesc:
+    """The lift descriptor of `cfg` for B samples of N cameras with C_ feature channels; host only, no device needed.
+    `fhw`: size of the image feature map when it is not final_dim / downsample_factor -- the lift
+    samples it in normalised coordinates (bv2:499-507), so any resolution works: the reference's own
+    ResNet-50 + SECONDFPN(upsample_strides=[0.5, 1, 2, 4]) delivers stride-8 maps (32 x 88) beside
+    the stride-4 frustum of the renderer."""
+    c = cfg
+    d = _capi.VampLiftDesc()
+    d.B, d.N, d.C = B, N, C_
+    d.D = c.D if use_depth else 1
+    d.fH, d.fW = (c.fH, c.fW) if fhw is None else (int(fhw[0]), int(fhw[1]))
+    d.Z, d.Y, d.X = c.vZ, c.vY, c.vX
+    d.u_max, d.v_max = float(c.final_dim[1] - 0.5), float(c.final_dim[0] - 0.5)
+    d.u_div, d.v_div = float(c.final_dim[1] - 1), float(c.final_dim[0] - 1)
+    d.d_lo, d.d_hi = c.d_bound[0], c.d_bound[1]
+    d.d_span = c.d_bound[1] - c.d_bound[0]          # python double -> fp32, as torch does
+    d.use_depth = 1 if use_depth else 0
+    d.in_dtype = dtype_code
+    return d
+
+
 def render_desc(cfg: PathConfig, B, N, dtype_code, C_=None) -> _capi.VampRenderDesc:
     """The render descriptor of `cfg` for B samples of N cameras (C_: mid channels, default cfg.mid_channels); host
     only, no device needed."""
@@ -157,23 +178,7 @@ class HotPath:
 
     # ---------------------------------------------------------------- descs
     def lift_desc(self, B, N, C_, dtype_code, use_depth=True, fhw=None) -> _capi.VampLiftDesc:
-        """`fhw`: size of the image feature map when it is not final_dim / downsample_factor -- the lift
-        samples it in normalised coordinates (bv2:499-507), so any resolution works: the reference's own
-        ResNet-50 + SECONDFPN(upsample_strides=[0.5, 1, 2, 4]) delivers stride-8 maps (32 x 88) beside
-        the stride-4 frustum of the renderer."""
-        c = self.cfg
-        d = _capi.VampLiftDesc()
-        d.B, d.N, d.C = B, N, C_
-        d.D = c.D if use_depth else 1
-        d.fH, d.fW = (c.fH, c.fW) if fhw is None else (int(fhw[0]), int(fhw[1]))
-        d.Z, d.Y, d.X = c.vZ, c.vY, c.vX
-        d.u_max, d.v_max = float(c.final_dim[1] - 0.5), float(c.final_dim[0] - 0.5)
-        d.u_div, d.v_div = float(c.final_dim[1] - 1), float(c.final_dim[0] - 1)
-        d.d_lo, d.d_hi = c.d_bound[0], c.d_bound[1]
-        d.d_span = c.d_bound[1] - c.d_bound[0]          # python double -> fp32, as torch does
-        d.use_depth = 1 if use_depth else 0
-        d.in_dtype = dtype_code
-        return d
+        return lift_desc(self.cfg, B, N, C_, dtype_code, use_depth, fhw)
 
     def render_desc(self, B, N, dtype_code, C_=None) -> _capi.VampRenderDesc:
         return render_desc(self.cfg, B, N, dtype_code, C_)
@@ -294,6 +299,10 @@ class HotPath:
         if rows:
             nbytes += self.vamp.vamp_render_samples_bytes(d)
         return self._workspace("render", nbytes)
+
+    def _lift_workspace(self, d):
+        """The lift workspace of a call on descriptor `d`."""
+        return self._workspace("lift", self.vamp.vamp_lift_workspace_bytes(d))
 
     def _term_table(self, d, ws):
         """The termination table inside the render workspace `ws`: a flat int32 view, one entry per ray."""
@@ -510,8 +519,7 @@ class _LiftFn(torch.autograd.Function):
         nchunk = (C_ + 15) // 16
         hits = (torch.empty(B, c.vZ, c.vY, c.vX, nchunk, dtype=torch.int64, device=feat.device)
                 if need_grad else None)
-        nbytes = hp.vamp.vamp_lift_workspace_bytes(d)
-        ws = hp._workspace("lift", nbytes)
+        ws = hp._lift_workspace(d)
         cur = torch.cuda.current_stream()
         hp._lift_gen += 1
         ctx.cells_key = None
@@ -556,8 +564,7 @@ class _LiftFn(torch.autograd.Function):
             gfeat = torch.empty(feat.shape, dtype=torch.float32, device=feat.device)
         gdepth = (torch.empty(depth.shape, dtype=torch.float32, device=feat.device)
                   if use_depth else None)
-        nbytes = hp.vamp.vamp_lift_workspace_bytes(d)
-        ws = hp._workspace("lift", nbytes)
+        ws = hp._lift_workspace(d)
         hp._finish_lift_scan()              # (nobody has run the forward's deferred scan: a lift without a render forward)
         fresh = ctx.cells_key == (hp._lift_gen, ws.data_ptr())       # the forward's pair cells are still in the workspace
         hp._lift_gen += 1                                              # the backward consumes the prepared counters
