@@ -864,7 +864,8 @@ int vamp_density_gate_backward(int64_t B, int32_t C, int64_t cells, int32_t dens
  * plane, gate = tanh (sdf density) or identity (naive).  voxel_output [B, C, oZ, cells], voxel_density
  * [B, 1, oZ, cells] (outputs of vamp_render_forward), weight [Cout, C * oZ] (= Conv2d.weight), bias [Cout] or
  * NULL, out [B, Cout, cells]; fp32, contiguous.  The gated tensor is never materialised.
- * Shapes: C * oZ <= 160, Cout <= 80, oZ <= 32 (vamp_gate_conv1x1_supported; else callers keep aten).
+ * Shapes: C * oZ <= 160, Cout <= 80, oZ <= 32, and the backward's LDS image must fit the CU's 160 KB, which caps
+ * oZ at 20 when C * oZ > 64 and Cout > 16 (vamp_gate_conv1x1_supported; else callers keep aten).
  */
 int vamp_gate_conv1x1_supported(int32_t C, int32_t oZ, int32_t Cout);
 size_t vamp_gate_conv1x1_workspace_bytes(int32_t C, int32_t oZ, int32_t Cout);

@@ -287,8 +287,9 @@ def occupancy_queries(semantic_logits, density_feature, occ_coords, bda_mat, seg
 # producer / consumer glue either side of the path (bv2:550, 627-630)
 # --------------------------------------------------------------------------
 def depth_softmax(logits):
-    """`mapping_along_depth(src).softmax(dim=1)` (bv2:550): logits [B*N, D, fH, fW]."""
-    return logits.float().softmax(dim=1)
+    """`mapping_along_depth(src).softmax(dim=1)` (bv2:550): logits [B*N, D, fH, fW]; float64 logits are evaluated in
+    float64 (the sweeps' high-precision reference), everything else in the reference's fp32."""
+    return (logits if logits.dtype == torch.float64 else logits.float()).softmax(dim=1)
 
 
 def density_gate(voxel_output, voxel_density, density_mode):

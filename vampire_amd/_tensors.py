@@ -44,6 +44,19 @@ def _is_channel_last(feat: torch.Tensor) -> bool:
             and feat.permute(0, 1, 3, 4, 2).is_contiguous() and feat.data_ptr() % 16 == 0)
 
 
+def _needs_aligned_copy(t: torch.Tensor) -> bool:
+    """True when `t` does not start on a 16-byte boundary (a view that begins at an odd element of a larger buffer):
+    the layer kernels read their operands with 4-, 8- and 16-byte loads and assume the allocator's alignment."""
+    return t.data_ptr() % 16 != 0
+
+
+def _aligned(t: torch.Tensor) -> torch.Tensor:
+    """`t` contiguous and starting on a 16-byte boundary: itself when it already is, else a fresh copy (the guard the
+    lift's zero-copy path has in `_is_channel_last`), so that no kernel ever sees a misaligned pointer."""
+    t = t.contiguous()
+    return t.clone() if _needs_aligned_copy(t) else t
+
+
 def _logit_layout(x):
     """(layout, B, S, x) for logits [..., K]: rows when contiguous, planes when the memory is channel-first
     ([B, K, ...] behind a permute(0, 2, .., 1) view, the backbone's occ_logits; leading dimensions in front of the

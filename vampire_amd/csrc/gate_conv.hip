@@ -474,7 +474,8 @@ int vamp_gate_conv1x1_forward(int64_t B, int32_t C, int32_t oZ, int64_t cells, i
   VAMP_REQUIRE(voxel_output && voxel_density && weight && out, "NULL tensor");
   VAMP_REQUIRE(density_mode == VAMP_DENSITY_SIGMOID || density_mode == VAMP_DENSITY_SDF_LAPLACE, "density_mode");
   const GcShape g = gc_shape(C * oZ, Cout, oZ);
-  VAMP_REQUIRE(g.mb != 0, "shape not supported (C * oZ <= 160, Cout <= 80, oZ <= 32): see vamp_gate_conv1x1_supported");
+  VAMP_REQUIRE(g.mb != 0, "shape not supported (C * oZ <= 160, Cout <= 80, oZ <= 32, and oZ <= 20 when C * oZ > 64 and Cout > 16: the "
+               "backward's LDS image): see vamp_gate_conv1x1_supported");
   hipStream_t s = static_cast<hipStream_t>(stream);
   return VAMP_GC_DISPATCH(launch_fwd, B, C * oZ, oZ, cells, Cout, density_mode, voxel_output, voxel_density,
                           weight, bias, out, s);
@@ -490,7 +491,8 @@ int vamp_gate_conv1x1_backward(int64_t B, int32_t C, int32_t oZ, int64_t cells, 
                "NULL tensor");
   VAMP_REQUIRE(density_mode == VAMP_DENSITY_SIGMOID || density_mode == VAMP_DENSITY_SDF_LAPLACE, "density_mode");
   const GcShape g = gc_shape(C * oZ, Cout, oZ);
-  VAMP_REQUIRE(g.mb != 0, "shape not supported (C * oZ <= 160, Cout <= 80, oZ <= 32): see vamp_gate_conv1x1_supported");
+  VAMP_REQUIRE(g.mb != 0, "shape not supported (C * oZ <= 160, Cout <= 80, oZ <= 32, and oZ <= 20 when C * oZ > 64 and Cout > 16: the "
+               "backward's LDS image): see vamp_gate_conv1x1_supported");
   const size_t need = vamp_gate_conv1x1_workspace_bytes(C, oZ, Cout);
   if (!workspace || workspace_bytes < need)
     return fail(VAMP_ENOSPC, "%s: workspace %ld < %ld bytes", __func__, (long) workspace_bytes, (long) need);

@@ -4,7 +4,8 @@ All work happens in hand-written HIP kernels reached through `_capi`; there is n
 import torch
 
 from . import _capi
-from ._tensors import DTYPE_CODES, FLOAT_DTYPES, HALF_DTYPES, _accept, _chk, _dtype_code, _stream, _workspace
+from ._tensors import (DTYPE_CODES, FLOAT_DTYPES, HALF_DTYPES, _accept, _aligned, _chk, _dtype_code, _stream,
+                       _workspace)
 
 
 # ===========================================================================
@@ -27,8 +28,8 @@ class _VoxelPoolingFn(torch.autograd.Function):
         B, C_ = feat.shape[0], feat.shape[-1]
         P = feat[0].numel() // C_
         ctx.in_dtype, ctx.fshape = feat.dtype, tuple(feat.shape)
-        feat = _accept(feat).reshape(B, P, C_).contiguous()
-        geom = _chk(geom.reshape(B, P, 3).to(torch.int32), (B, P, 3), "geom_xyz")
+        feat = _aligned(_accept(feat).reshape(B, P, C_))
+        geom = _aligned(_chk(geom.reshape(B, P, 3).to(torch.int32), (B, P, 3), "geom_xyz"))
         d = _capi.VampPoolDesc(B, C_, P, voxel_num[0], voxel_num[1], voxel_num[2], _dtype_code(feat))
         out = torch.empty(B, voxel_num[1], voxel_num[0], C_, dtype=torch.float32, device=feat.device)
         nbytes = vamp.vamp_voxel_pooling_workspace_bytes(d)
@@ -43,7 +44,7 @@ class _VoxelPoolingFn(torch.autograd.Function):
     def backward(ctx, g):
         (geom,) = ctx.saved_tensors
         d = ctx.desc
-        g = g.permute(0, 2, 3, 1).contiguous().float()
+        g = _aligned(g.permute(0, 2, 3, 1).float())
         gfeat = torch.empty(d.B, d.P, d.C, dtype=torch.float32, device=g.device)
         with torch.cuda.device(g.device):
             _capi.checked().vamp_voxel_pooling_backward(d, geom, g, gfeat, _stream())
@@ -71,7 +72,7 @@ class _UpsampleTrilinearFn(torch.autograd.Function):
         ctx.in_dtype = x.dtype
         if x.dtype not in FLOAT_DTYPES:
             x = x.float()
-        x = x.contiguous()
+        x = _aligned(x)
         ctx.code = DTYPE_CODES[x.dtype]
         B, C_ = x.shape[:2]
         ctx.dtype = x.dtype
@@ -85,7 +86,7 @@ class _UpsampleTrilinearFn(torch.autograd.Function):
     @staticmethod
     def backward(ctx, g):
         dt = ctx.dtype
-        g = g.contiguous().to(dt)
+        g = _aligned(g.to(dt))
         gin = torch.empty(ctx.in_shape, dtype=dt, device=g.device)
         if gin.numel() and g.numel():
             vamp = ctx.vamp
@@ -137,7 +138,7 @@ class _Conv3dBf16Fn(torch.autograd.Function):
             raise TypeError("conv3d_bf16 takes bf16 (or fp16) [B,cin,Z,Y,X] and [cout,cin,3,3,3] tensors of one dtype")
         code = DTYPE_CODES[x.dtype]
         vamp = _capi.checked()
-        x, w = x.contiguous(), w.contiguous()
+        x, w = _aligned(x), _aligned(w)
         d = _conv_desc(x, w)
         if w.shape[1] != d.cin:
             raise ValueError("weight / input channel mismatch")
@@ -151,7 +152,7 @@ class _Conv3dBf16Fn(torch.autograd.Function):
     def backward(ctx, g):
         x, w = ctx.saved_tensors
         vamp, d = ctx.vamp, ctx.desc
-        g = g.contiguous().to(x.dtype)
+        g = _aligned(g.to(x.dtype))
         gx = gw = None
         if ctx.needs_input_grad[0]:
             gx = torch.empty_like(x)
@@ -181,7 +182,7 @@ class _Conv3dFn(torch.autograd.Function):
         if x.dtype != torch.float32 or w.dtype != torch.float32 or x.dim() != 5 or w.dim() != 5:
             raise TypeError("conv3d_3x3x3 takes fp32 [B,cin,Z,Y,X] and [cout,cin,3,3,3] tensors")
         vamp = _capi.checked()
-        x, w = x.contiguous(), w.contiguous()
+        x, w = _aligned(x), _aligned(w)
         d = _conv_desc(x, w)
         if w.shape[1] != d.cin:
             raise ValueError("weight / input channel mismatch")
@@ -195,7 +196,7 @@ class _Conv3dFn(torch.autograd.Function):
     def backward(ctx, g):
         x, w = ctx.saved_tensors
         vamp, d = ctx.vamp, ctx.desc
-        g = g.contiguous().float()
+        g = _aligned(g.float())
         gx = gw = None
         if ctx.needs_input_grad[0]:
             gx = torch.empty_like(x)
