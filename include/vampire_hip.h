@@ -31,7 +31,8 @@ extern "C" {
                                  7: segmentation metrics; 8: detection post-processing; 9: detection targets;
                                  10: the BEV backward's plan; 11: detection loss; 12: rgb loss; 13: segmentation loss;
                                  14: masked regression losses; 15: the camera render's plans and workspace layout;
-                                 16: the lift's plans and workspace layout) */
+                                 16: the lift's plans and workspace layout;
+                                 16 also: stride-2 16-bit convolutions; the number could not move) */
 
 enum {
   VAMP_OK = 0,
@@ -975,6 +976,26 @@ int vamp_conv3d_half_backward_data(const VampConvDesc* d, int32_t dtype, const v
                                    void* grad_in, void* stream);
 int vamp_conv3d_half_backward_weight(const VampConvDesc* d, int32_t dtype, const void* in, const void* grad_out,
                                      float* grad_weight, void* workspace, size_t workspace_bytes, void* stream);
+
+/*
+ * The stride-2 layers of the same UNet under a 16-bit autocast: nn.Conv3d(cin, cout, 3, stride=2, padding=1,
+ * bias=False) -- Hourglass3D.conv1 and conv3, base_vampire2.py:34-46.  Here the descriptor holds the INPUT tensor
+ * [B, cin, Z, Y, X]; the output is [B, cout, Zo, Yo, Xo] with Zo = (Z - 1) / 2 + 1, Yo = (Y - 1) / 2 + 1,
+ * Xo = (X - 1) / 2 + 1 (odd Z and Y are fine).  16-bit NCDHW in and out (dtype = VAMP_BF16 or VAMP_F16), fp32
+ * accumulation on v_mfma_f32_16x16x32_{bf16,f16}; weight [cout, cin, 3, 3, 3] of the same 16-bit type.  One shape rule
+ * for the three launches (vamp_conv3d_half_s2_supported): 1 <= cin, cout <= 32, B, Z, Y > 0, X >= 8, X % 4 == 0 and
+ * Z * Y * X * 64 < 2^31.  grad_in [B, cin, Z, Y, X] is fully overwritten (every element once, no atomics);
+ * grad_weight is fp32 [cout, cin, 3, 3, 3], fully overwritten and bitwise repeatable; the workspace
+ * (vamp_conv3d_half_s2_workspace_bytes) holds the per-workgroup partial sums.
+ */
+int vamp_conv3d_half_s2_supported(const VampConvDesc* d);
+size_t vamp_conv3d_half_s2_workspace_bytes(const VampConvDesc* d);
+int vamp_conv3d_half_s2_forward(const VampConvDesc* d, int32_t dtype, const void* in, const void* weight, void* out,
+                                void* stream);
+int vamp_conv3d_half_s2_backward_data(const VampConvDesc* d, int32_t dtype, const void* grad_out, const void* weight,
+                                      void* grad_in, void* stream);
+int vamp_conv3d_half_s2_backward_weight(const VampConvDesc* d, int32_t dtype, const void* in, const void* grad_out,
+                                        float* grad_weight, void* workspace, size_t workspace_bytes, void* stream);
 
 /* --------------------------------------------------------------------------
  * Segmentation metrics (base_exp.py:370-382 training, :634-663 validation, :835-840 submission labels).

@@ -41,6 +41,8 @@ def bench(tag, benchmark, dtype=None, cl=False):
 # torch caches the solver picked for a shape for the life of the process: the immediate-mode run
 # (367 ms backward: a 53 ms weight-gradient kernel per layer) goes last
 print("VAMP_CONV3D=%s (HIP fp32 matrix-core convs for the two finer levels unless 0)" % os.environ.get("VAMP_CONV3D", "1"))
+print("VAMP_CONV3D_S2=%s (HIP 16-bit stride-2 convs under autocast unless 0; on / off in one run: tools/time_conv3d_s2.py)"
+      % os.environ.get("VAMP_CONV3D_S2", "1"))
 bench("fp32 benchmark", True)
 bench("fp32 benchmark NDHWC", True, cl=True)
 bench("bf16 autocast benchmark", True, torch.bfloat16)

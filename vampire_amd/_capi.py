@@ -351,6 +351,11 @@ SIGNATURES = {
     "vamp_conv3d_half_forward": (_STATUS, [_CD, C.c_int32, _P, _P, _P, _P]),
     "vamp_conv3d_half_backward_data": (_STATUS, [_CD, C.c_int32, _P, _P, _P, _P]),
     "vamp_conv3d_half_backward_weight": (_STATUS, [_CD, C.c_int32, _P, _P, _P, _P, C.c_size_t, _P]),
+    "vamp_conv3d_half_s2_supported": (_INT, [_CD]),
+    "vamp_conv3d_half_s2_workspace_bytes": (_SIZE, [_CD]),
+    "vamp_conv3d_half_s2_forward": (_STATUS, [_CD, C.c_int32, _P, _P, _P, _P]),
+    "vamp_conv3d_half_s2_backward_data": (_STATUS, [_CD, C.c_int32, _P, _P, _P, _P]),
+    "vamp_conv3d_half_s2_backward_weight": (_STATUS, [_CD, C.c_int32, _P, _P, _P, _P, C.c_size_t, _P]),
     "vamp_density_gate_backward": (_STATUS, [C.c_int64, C.c_int32, C.c_int64, C.c_int32, _P, _P, _P, _P, _P,
                                              _P]),
     "vamp_voxel_pooling_workspace_bytes": (_SIZE, [_PD]),

@@ -60,11 +60,15 @@ def _resize(x, size):
 # Switches of the module path, read ONCE at import (not on every forward): VAMP_CONV3D=0 keeps MIOpen for
 # every 3-D convolution, VAMP_CONV3D_MIN_VOXELS is the volume size from which the HIP convolution is
 # used, VAMP_GLUE=hip routes the depth softmax / density gate through the standalone HIP kernels,
-# VAMP_FUSE=0 turns the fused producer / consumer forms off.  Tests and
+# VAMP_FUSE=0 turns the fused producer / consumer forms off, VAMP_CONV3D_S2=0 keeps MIOpen for the stride-2 3x3x3
+# layers under a 16-bit autocast (default: the HIP kernels of conv3d_bf16_s2.hip).  Tests and
 # tools flip the attributes of `SWITCHES`.
 class _Switches:
     conv3d = os.environ.get("VAMP_CONV3D", "1") != "0"
     conv3d_min_voxels = int(os.environ.get("VAMP_CONV3D_MIN_VOXELS", "50000"))
+    # the stride-2 layers (Hourglass3D.conv1 / conv3) under a 16-bit autocast; needs `conv3d` on as well.  Default on:
+    # forward + backward 94 / 79 us against MIOpen's 169 / 113 us at the two cfg-B layers (profiles/conv_s2_16bit.txt)
+    conv3d_s2 = os.environ.get("VAMP_CONV3D_S2", "1") != "0"
     hip_glue = os.environ.get("VAMP_GLUE", "aten") == "hip"
     # SURVEY 8f N2, the fused forms (default on): the depth softmax runs inside the lift's operand launch
     # and its backward inside the lift backward's gather; VAMP_FUSE=0 restores softmax -> lift
@@ -88,7 +92,8 @@ class _Conv3(nn.Conv3d):
     stride-1 layers with 16 / 32 channels run on the HIP fp32 matrix-core kernels for fp32 device
     tensors of at least `VAMP_CONV3D_MIN_VOXELS` voxels (default 50 000: 1.7x MIOpen forward +
     backward at 16x200x200, 1.1x at 8x100x100; the coarsest level is latency-bound and stays with
-    MIOpen); `VAMP_CONV3D=0` keeps MIOpen everywhere."""
+    MIOpen); `VAMP_CONV3D=0` keeps MIOpen everywhere.  Under a 16-bit autocast the stride-1 layers run on
+    conv3d_bf16.hip and the stride-2 ones on conv3d_bf16_s2.hip (`VAMP_CONV3D_S2=0`: MIOpen)."""
 
     def forward(self, x):
         if SWITCHES.conv3d and x.dim() == 5 and x.is_cuda:
@@ -99,6 +104,10 @@ class _Conv3(nn.Conv3d):
                 xb = x.to(dt16)
                 if conv3d_bf16_supported(xb, self.weight, self.stride, self.padding, self.bias):
                     return conv3d_bf16(xb, self.weight.to(dt16))
+                if SWITCHES.conv3d_s2:
+                    from .layers import conv3d_bf16_stride2, conv3d_bf16_stride2_supported
+                    if conv3d_bf16_stride2_supported(xb, self.weight, self.stride, self.padding, self.bias):
+                        return conv3d_bf16_stride2(xb, self.weight.to(dt16))
             elif (x[0, 0].numel() >= SWITCHES.conv3d_min_voxels
                     and conv3d_supported(x, self.weight, self.stride, self.padding, self.bias)):
                 return conv3d_3x3x3(x, self.weight)

@@ -18,20 +18,13 @@
 // The data gradient is the same kernel on the flipped, transposed weights (FLIP).
 // The weight gradient has K = voxels, contiguous along x in NCDHW: both operands are plain
 // 16-byte global loads (the shifted-by-one-voxel windows at 2-byte alignment), no LDS at all.
-#include "common.hpp"
+#include "conv3d_half.hpp"       // the vector types, mfma16, f2e, the partials' reduce kernel, tile_ch, bf16_shape_ok
 
 #include <algorithm>
 #include <type_traits>
 
 namespace vamp {
 namespace {
-
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef short bf16x8 __attribute__((ext_vector_type(8)));
-typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
-typedef unsigned u32x2 __attribute__((ext_vector_type(2)));
-typedef u32x4 __attribute__((aligned(2))) u32x4_u;     // a 16-byte global load at 2-byte alignment
-typedef bf16x8 __attribute__((aligned(2))) bf16x8_u;
 
 struct CvP {
   int B, Z, Y, X;
@@ -42,40 +35,6 @@ constexpr int kTY = 4;        // output rows per tile = waves per workgroup
 constexpr int kTX = 64;       // output x per tile (four 16-voxel N tiles per wave)
 constexpr int kHX = 68;       // staged x: x0 - 2 .. x0 + 65 (pairs at even x)
 constexpr int kRows = 3 * (kTY + 2);
-
-typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
-
-// the 16-bit matrix-core product: bf16 or (F16) IEEE half operands, fp32 accumulate; same fragment maps
-template <bool F16>
-__device__ __forceinline__ f32x4 mfma16(const bf16x8& a, const bf16x8& b, const f32x4& c) {
-  if constexpr (F16) {
-    f16x8 ha, hb;
-    __builtin_memcpy(&ha, &a, 16);
-    __builtin_memcpy(&hb, &b, 16);
-    return __builtin_amdgcn_mfma_f32_16x16x32_f16(ha, hb, c, 0, 0, 0);
-  } else {
-    return __builtin_amdgcn_mfma_f32_16x16x32_bf16(a, b, c, 0, 0, 0);
-  }
-}
-
-__device__ __forceinline__ unsigned short f2bf(float f) {          // round to nearest even (NaN kept quiet)
-  unsigned u = __float_as_uint(f);
-  if ((u & 0x7fffffffu) > 0x7f800000u) return (unsigned short) ((u >> 16) | 0x40);
-  u += 0x7fffu + ((u >> 16) & 1u);
-  return (unsigned short) (u >> 16);
-}
-
-template <bool F16>
-__device__ __forceinline__ unsigned short f2e(float f) {              // fp32 -> the 16-bit element type, round to nearest even
-  if constexpr (F16) {
-    const _Float16 h = (_Float16) f;
-    unsigned short u;
-    __builtin_memcpy(&u, &h, 2);
-    return u;
-  } else {
-    return f2bf(f);
-  }
-}
 
 template <int CIN, int COUT>
 struct CvLds {
@@ -370,44 +329,6 @@ conv3d_bf16_wgrad_kernel(CvP P, const unsigned short* __restrict__ in, const uns
 #pragma unroll
         for (int rg = 0; rg < 4; ++rg) pb[((size_t) tap * COUT + m * 16 + 4 * kg + rg) * CIN + n * 16 + li] = acc[t][m][n][rg];
   }
-}
-
-// dw[co][ci][tap] (bf16 or fp32 out) = sum over workgroups of part[wg][tap][co][ci]
-__global__ void __launch_bounds__(256)
-conv3d_bf16_wreduce_kernel(const float* __restrict__ part, float* __restrict__ dw, int cin, int cout, int nwg,
-                           int cin_r, int cout_r) {
-  const int e = blockIdx.x * 64 + (threadIdx.x & 63), wv = threadIdx.x >> 6;
-  __shared__ float red[4][64];
-  const int n = 27 * cout * cin;
-  float s = 0.f;
-  if (e < n) {
-    int g = wv;
-    for (; g + 28 < nwg; g += 32) {
-      float v[8];
-#pragma unroll
-      for (int i = 0; i < 8; ++i) v[i] = part[(size_t) (g + 4 * i) * n + e];
-#pragma unroll
-      for (int i = 0; i < 8; ++i) s += v[i];
-    }
-    for (; g < nwg; g += 4) s += part[(size_t) g * n + e];
-  }
-  red[wv][threadIdx.x & 63] = s;
-  __syncthreads();
-  if (wv == 0 && e < n) {
-    s = (red[0][threadIdx.x] + red[1][threadIdx.x]) + (red[2][threadIdx.x] + red[3][threadIdx.x]);
-    const int ci = e % cin, co = (e / cin) % cout, tap = e / (cin * cout);
-    if (co < cout_r && ci < cin_r) dw[((size_t) co * cin_r + ci) * 27 + tap] = s;
-  }
-}
-
-constexpr int kWgradWgs = 512;       // two workgroups per CU
-
-int tile_ch(int c) { return c <= 16 ? 16 : 32; }       // channel tile a real channel count runs under
-
-bool bf16_shape_ok(const VampConvDesc* d) {
-  return d && d->cin >= 1 && d->cin <= 32 && d->cout >= 1 && d->cout <= 32 && d->B > 0 && d->Z > 0 &&
-         d->Y > 0 && d->X >= 8 && d->X % 4 == 0 &&
-         (long) d->Z * d->Y * d->X * 32 * 2 < 0x7fffffffL;
 }
 
 template <int CIN, int COUT, bool FLIP, bool F16>

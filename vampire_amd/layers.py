@@ -166,6 +166,59 @@ class _Conv3dBf16Fn(torch.autograd.Function):
         return gx, gw
 
 
+def conv3d_bf16_stride2(x, weight):
+    """nn.Conv3d(cin, cout, 3, stride=2, padding=1, bias=False) (Hourglass3D.conv1 / conv3, bv2:34-46) in bf16 or
+    fp16: x [B,cin,Z,Y,X], weight [cout,cin,3,3,3] of the same 16-bit dtype -> [B,cout,(Z-1)//2+1,(Y-1)//2+1,X//2];
+    fp32 accumulation on the 16-bit matrix cores."""
+    return _Conv3dBf16S2Fn.apply(x, weight)
+
+
+def conv3d_bf16_stride2_supported(x, weight, stride, padding, bias):
+    if not (x.is_cuda and x.dtype in HALF_DTYPES and bias is None and tuple(stride) == (2, 2, 2)
+            and tuple(padding) == (1, 1, 1) and tuple(weight.shape[2:]) == (3, 3, 3) and x.dim() == 5
+            and weight.shape[1] == x.shape[1]):
+        return False
+    return bool(_capi.checked().vamp_conv3d_half_s2_supported(_conv_desc(x, weight)))
+
+
+class _Conv3dBf16S2Fn(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, x, w):
+        if x.dtype not in HALF_DTYPES or w.dtype != x.dtype or x.dim() != 5 or w.dim() != 5:
+            raise TypeError("conv3d_bf16_stride2 takes bf16 (or fp16) [B,cin,Z,Y,X] and [cout,cin,3,3,3] tensors of one dtype")
+        if not (x.is_cuda and w.is_cuda):
+            raise _capi.VampireHipError("x / weight must be device tensors (no CPU fallback)")
+        code = DTYPE_CODES[x.dtype]
+        vamp = _capi.checked()
+        x, w = _aligned(x), _aligned(w)
+        d = _conv_desc(x, w)                      # the descriptor holds the input volume
+        if w.shape[1] != d.cin:
+            raise ValueError("weight / input channel mismatch")
+        out = torch.empty((d.B, d.cout, (d.Z - 1) // 2 + 1, (d.Y - 1) // 2 + 1, (d.X - 1) // 2 + 1), dtype=x.dtype,
+                          device=x.device)
+        vamp.vamp_conv3d_half_s2_forward(d, code, x, w, out, _stream())
+        ctx.vamp, ctx.desc, ctx.code = vamp, d, code
+        ctx.save_for_backward(x, w)
+        return out
+
+    @staticmethod
+    def backward(ctx, g):
+        x, w = ctx.saved_tensors
+        vamp, d = ctx.vamp, ctx.desc
+        g = _aligned(g.to(x.dtype))
+        gx = gw = None
+        if ctx.needs_input_grad[0]:
+            gx = torch.empty_like(x)
+            vamp.vamp_conv3d_half_s2_backward_data(d, ctx.code, g, w, gx, _stream())
+        if ctx.needs_input_grad[1]:
+            gw32 = torch.empty(w.shape, dtype=torch.float32, device=w.device)
+            nbytes = vamp.vamp_conv3d_half_s2_workspace_bytes(d)
+            ws = _workspace((g.device, torch.cuda.current_stream().cuda_stream, "conv16s2", nbytes), g.device, nbytes)
+            vamp.vamp_conv3d_half_s2_backward_weight(d, ctx.code, x, g, gw32, ws, ws.numel(), _stream())
+            gw = gw32.to(w.dtype)                 # the gradient of the 16-bit copy autocast made of the fp32 parameter
+        return gx, gw
+
+
 def conv3d_supported(x, weight, stride, padding, bias):
     if not (x.is_cuda and x.dtype == torch.float32 and weight.dtype == torch.float32 and bias is None
             and tuple(stride) == (1, 1, 1) and tuple(padding) == (1, 1, 1) and tuple(weight.shape[2:]) == (3, 3, 3)
