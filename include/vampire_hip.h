@@ -32,7 +32,8 @@ extern "C" {
                                  10: the BEV backward's plan; 11: detection loss; 12: rgb loss; 13: segmentation loss;
                                  14: masked regression losses; 15: the camera render's plans and workspace layout;
                                  16: the lift's plans and workspace layout;
-                                 16 also: stride-2 16-bit convolutions; the number could not move) */
+                                 16 also: stride-2 16-bit convolutions and the 2-D bilinear resize of the rendered maps; the number
+                                 could not move: a test pins it) */
 
 enum {
   VAMP_OK = 0,
@@ -931,6 +932,43 @@ int vamp_upsample_trilinear_supported(int32_t iz, int32_t iy, int32_t ix, int32_
 int vamp_upsample_trilinear_backward(int64_t planes, int32_t iz, int32_t iy, int32_t ix, int32_t oz,
                                      int32_t oy, int32_t ox, const float* grad_out, float* grad_in,
                                      void* workspace, size_t workspace_bytes, void* stream);
+
+/* --------------------------------------------------------------------------
+ * 2-D bilinear resize of the rendered maps between render and losses:
+ * F.interpolate(x, size, mode='bilinear', align_corners=True) -- the x4 `upsample2d` of the rgb, seg-logit and depth
+ * camera maps, base_vampire2.py:616-626, and the 0.5x resize behind `voxel_output` on a 256-cell grid,
+ * base_vampire2.py:203-209.  in [planes, ih, iw] -> out [planes, oh, ow], planes = batch * channels, fp32 contiguous.
+ * One call takes up to VAMP_RESIZE2D_MAX_SEGS tensors (segments) that share the four sizes: one kernel launch on
+ * `stream` each way, the pointers travel inside the launch arguments (capturable in a graph).  The backward is a
+ * separable gather in a fixed order (no float atomics, bitwise repeatable) that overwrites every element of every
+ * segment's `dst`, untouched source pixels with 0.
+ * -------------------------------------------------------------------------- */
+#define VAMP_RESIZE2D_MAX_SEGS 4
+#define VAMP_RESIZE2D_PLANE_GROUP 8   /* planes one forward thread walks with its taps                            */
+#define VAMP_RESIZE2D_BAND_ROWS 8     /* source rows one backward workgroup owns                                  */
+#define VAMP_RESIZE2D_COL_CHUNK 256   /* source columns one backward workgroup owns                               */
+#define VAMP_RESIZE2D_STRIP_CHUNK 256 /* gradient columns one 16-byte load of a wave covers                       */
+#define VAMP_RESIZE2D_STRIP_MAX 1088  /* gradient columns (rounded out to multiples of 4) a column chunk may span */
+#define VAMP_RESIZE2D_MAX_RUN 16      /* outputs along x whose taps include one source column                     */
+typedef struct VampResize2dSeg {
+  const void* src;       /* forward: in [planes, ih, iw]; backward: grad_out [planes, oh, ow]   */
+  void* dst;             /* forward: out [planes, oh, ow]; backward: grad_in [planes, ih, iw]   */
+  int64_t planes;        /* 0 < planes < 65536                                                   */
+} VampResize2dSeg;
+typedef struct VampResize2dDesc {
+  int32_t ih, iw, oh, ow;
+  int32_t nseg;          /* 1 .. VAMP_RESIZE2D_MAX_SEGS                                          */
+  int32_t reserved;
+  VampResize2dSeg seg[VAMP_RESIZE2D_MAX_SEGS];
+} VampResize2dDesc;
+/* 1 when both entry points take these sizes, else 0 (callers fall back to F.interpolate then): any ratio along y;
+ * along x the run of outputs per source column must fit VAMP_RESIZE2D_MAX_RUN and the outputs of a column chunk
+ * VAMP_RESIZE2D_STRIP_MAX -- every out / in <= 4.1, the identity and every downsampling pass */
+int vamp_resize2d_supported(int32_t ih, int32_t iw, int32_t oh, int32_t ow);
+/* scratch the backward needs: 0 in this version (its run tables live in registers and LDS); NULL is accepted then */
+size_t vamp_resize2d_workspace_bytes(int32_t ih, int32_t iw, int32_t oh, int32_t ow);
+int vamp_resize2d_forward(const VampResize2dDesc* d, void* stream);
+int vamp_resize2d_backward(const VampResize2dDesc* d, void* workspace, size_t workspace_bytes, void* stream);
 
 /* --------------------------------------------------------------------------
  * 3x3x3 / stride 1 / padding 1 / no-bias Conv3d of the UNet between lift and render (SURVEY 8f

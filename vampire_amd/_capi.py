@@ -24,6 +24,8 @@ VAMP_SEG_ROWS, VAMP_SEG_PLANES = 0, 1
 VAMP_REG_MAX_TERMS, VAMP_REG_TILE = 8, 4096
 VAMP_REG_SMOOTH_L1, VAMP_REG_MSE = 0, 1
 VAMP_REG_SET, VAMP_REG_CLEAR, VAMP_REG_BOTH = 0, 1, 2
+VAMP_RESIZE2D_MAX_SEGS, VAMP_RESIZE2D_PLANE_GROUP, VAMP_RESIZE2D_BAND_ROWS, VAMP_RESIZE2D_COL_CHUNK = 4, 8, 8, 256
+VAMP_RESIZE2D_STRIP_CHUNK, VAMP_RESIZE2D_STRIP_MAX, VAMP_RESIZE2D_MAX_RUN = 256, 1088, 16
 
 
 class VampLiftDesc(C.Structure):
@@ -124,6 +126,15 @@ class VampRegTerm(C.Structure):
 
 class VampRegLossDesc(C.Structure):
     _fields_ = [("T", C.c_int32), ("reserved", C.c_int32), ("terms", VampRegTerm * VAMP_REG_MAX_TERMS)]
+
+
+class VampResize2dSeg(C.Structure):
+    _fields_ = [("src", C.c_void_p), ("dst", C.c_void_p), ("planes", C.c_int64)]
+
+
+class VampResize2dDesc(C.Structure):
+    _fields_ = [("ih", C.c_int32), ("iw", C.c_int32), ("oh", C.c_int32), ("ow", C.c_int32), ("nseg", C.c_int32),
+                ("reserved", C.c_int32), ("seg", VampResize2dSeg * VAMP_RESIZE2D_MAX_SEGS)]
 
 
 class VampBevBackwardPlan(C.Structure):
@@ -272,6 +283,7 @@ _TT = C.POINTER(VampDetTask)
 _GD = C.POINTER(VampRgbLossDesc)
 _SLD = C.POINTER(VampSegLossDesc)
 _RLD = C.POINTER(VampRegLossDesc)
+_R2D = C.POINTER(VampResize2dDesc)
 
 # name -> (return kind, argtypes); must list every symbol declared in include/vampire_hip.h
 SIGNATURES = {
@@ -338,6 +350,10 @@ SIGNATURES = {
     "vamp_upsample_trilinear_workspace_bytes": (_SIZE, [C.c_int32] * 3),
     "vamp_upsample_trilinear_supported": (_INT, [C.c_int32] * 6),
     "vamp_upsample_trilinear_backward": (_STATUS, [C.c_int64] + [C.c_int32] * 6 + [_P, _P, _P, C.c_size_t, _P]),
+    "vamp_resize2d_supported": (_INT, [C.c_int32] * 4),
+    "vamp_resize2d_workspace_bytes": (_SIZE, [C.c_int32] * 4),
+    "vamp_resize2d_forward": (_STATUS, [_R2D, _P]),
+    "vamp_resize2d_backward": (_STATUS, [_R2D, _P, C.c_size_t, _P]),
     "vamp_conv3d_supported": (_INT, [_CD]),
     "vamp_conv3d_forward": (_STATUS, [_CD, _P, _P, _P, _P]),
     "vamp_conv3d_backward_data": (_STATUS, [_CD, _P, _P, _P, _P]),

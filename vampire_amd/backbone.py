@@ -61,8 +61,9 @@ def _resize(x, size):
 # every 3-D convolution, VAMP_CONV3D_MIN_VOXELS is the volume size from which the HIP convolution is
 # used, VAMP_GLUE=hip routes the depth softmax / density gate through the standalone HIP kernels,
 # VAMP_FUSE=0 turns the fused producer / consumer forms off, VAMP_CONV3D_S2=0 keeps MIOpen for the stride-2 3x3x3
-# layers under a 16-bit autocast (default: the HIP kernels of conv3d_bf16_s2.hip).  Tests and
-# tools flip the attributes of `SWITCHES`.
+# layers under a 16-bit autocast (default: the HIP kernels of conv3d_bf16_s2.hip), VAMP_RESIZE2D=1 routes the x4
+# resize of the three rendered camera maps and the 256-cell grid's 0.5x resize through resize2d.hip (default: aten).
+# Tests and tools flip the attributes of `SWITCHES`.
 class _Switches:
     conv3d = os.environ.get("VAMP_CONV3D", "1") != "0"
     conv3d_min_voxels = int(os.environ.get("VAMP_CONV3D_MIN_VOXELS", "50000"))
@@ -73,9 +74,26 @@ class _Switches:
     # SURVEY 8f N2, the fused forms (default on): the depth softmax runs inside the lift's operand launch
     # and its backward inside the lift backward's gather; VAMP_FUSE=0 restores softmax -> lift
     fuse = os.environ.get("VAMP_FUSE", "1") != "0"
+    # the 2-D bilinear resizes between render and losses (bv2:616-626, 203-209) on the HIP kernels: one launch for the
+    # three camera maps, a gather backward without float atomics.  Replayed from a graph forward + backward takes
+    # 63 us against aten's 262 us for the maps and 43 against 81 us for cfg-A's BEV feature (batch 1,
+    # profiles/resize2d.json); default off all the same: eager the path is host-bound and lost on the BEV feature in
+    # one of five runs
+    resize2d = os.environ.get("VAMP_RESIZE2D", "0") == "1"
 
 
 SWITCHES = _Switches()
+
+
+def _resize2d_pack(tensors, size):
+    """The HIP resize of `tensors` ([..., H, W], one launch) when `SWITCHES.resize2d` is on, they are fp32 device
+    tensors and the kernels take the ratio; None otherwise: the caller keeps its aten path."""
+    if not (SWITCHES.resize2d and all(t.is_cuda and t.dtype == torch.float32 and t.numel() for t in tensors)):
+        return None
+    from .layers import resize_bilinear2d_pack, resize_bilinear2d_supported
+    if not resize_bilinear2d_supported(tensors[0].shape[-2:], size):
+        return None
+    return resize_bilinear2d_pack(tensors, size)
 
 
 def _autocast_16(x):
@@ -492,26 +510,41 @@ class BaseVAMPIRE2(nn.Module):
         (rgb_p, seg_p, depth_p, bev_rgb, bev_seg, bev_height, bev_density, voxel_output) = \
             self.render(mats_dict, sweep_index, density_feature, semantic_logits, base, rgb)
 
-        up = lambda t: self.upsample2d(t.reshape(B * N, -1, self.fH, self.fW)).reshape(
-            B, N, -1, self.fH * self.upsample_factor, self.fW * self.upsample_factor)
-        rgb_p, seg_p, depth_p = up(rgb_p), up(seg_p), up(depth_p)
+        maps = [t.reshape(B, N, -1, self.fH, self.fW) for t in (rgb_p, seg_p, depth_p)]
+        up_size = (math.floor(self.fH * self.upsample_factor), math.floor(self.fW * self.upsample_factor))
+        resized = _resize2d_pack(maps, up_size)                    # bv2:616-626 in one launch (SWITCHES.resize2d)
+        if resized is not None:
+            rgb_p, seg_p, depth_p = resized
+        else:
+            up = lambda t: self.upsample2d(t.reshape(B * N, -1, self.fH, self.fW)).reshape(
+                B, N, -1, self.fH * self.upsample_factor, self.fW * self.upsample_factor)
+            rgb_p, seg_p, depth_p = up(rgb_p), up(seg_p), up(depth_p)
         conv = self.voxel_output[0] if isinstance(self.voxel_output, nn.Sequential) else self.voxel_output
         if (SWITCHES.fuse and hasattr(hp, "gate_conv1x1")
                 and hp.gate_conv1x1_supported(voxel_output.shape[1], voxel_output.shape[2], conv.out_channels)):
             # bv2:627-632 fused: gate and 1x1 conv in one matrix-core kernel, the gated tensor never exists
             bev_feat = hp.gate_conv1x1(voxel_output, bev_density, conv.weight, conv.bias)
             if conv is not self.voxel_output:
-                bev_feat = self.voxel_output[1](bev_feat)          # the 256-cell grid's 0.5x bilinear resize (bv2:205)
+                bev_feat = self._half_resize(bev_feat)             # the 256-cell grid's 0.5x bilinear resize (bv2:205)
         else:
             if hip_glue:
                 voxel_output = hp.density_gate(voxel_output, bev_density)  # bv2:627-630, HIP consumer kernel
             else:
                 voxel_output = voxel_output * (bev_density.tanh() if self.density_mode == "sdf" else bev_density)
-            bev_feat = self.voxel_output(voxel_output.reshape(B, -1, *voxel_output.shape[-2:])).float()
+            bev_feat = conv(voxel_output.reshape(B, -1, *voxel_output.shape[-2:]))
+            if conv is not self.voxel_output:
+                bev_feat = self._half_resize(bev_feat)
+            bev_feat = bev_feat.float()
         return (bev_feat.contiguous(), rgb_p, seg_p, depth_p, bev_rgb, bev_seg, bev_height,
                 bev_density, pts_logits_batch, pts_sdf_batch,
                 None if occ_logits is None else occ_logits.permute(0, 2, 3, 4, 1),
                 None if occ_density is None else occ_density.permute(0, 2, 3, 4, 1).tanh())
+
+    def _half_resize(self, x):
+        """`voxel_output[1]`, the 0.5x UpsamplingBilinear2d of the 256-cell grid (bv2:205): resize2d.hip when
+        `SWITCHES.resize2d` admits the tensor, else the module itself."""
+        resized = _resize2d_pack([x], tuple(math.floor(v * 0.5) for v in x.shape[-2:]))
+        return self.voxel_output[1](x) if resized is None else resized[0]
 
     def forward(self, sweep_imgs, mats_dict, inrange_pts=None, timestamps=None):
         if sweep_imgs.shape[1] != 1:

@@ -46,7 +46,8 @@ enum ProfSlot {
   kProfPack, kProfCamFwd, kProfBevFwd, kProfCamBwd, kProfUnpack, kProfBevBwd, kProfMemset,
   kProfAux, kProfCamBwdBrick, kProfBevFwdCh, kProfBevBwdQ, kProfBevBwdGather, kProfLiftBwdV1,
   kProfLiftBwdCount, kProfLiftBwdFill, kProfCamBwdCount, kProfCamBwdFill, kProfCamBwdOwn, kProfCamBwdV1,
-  kProfGlueSoftmax, kProfGlueGate, kProfUpsample, kProfConvFwd, kProfConvDgrad, kProfConvWgrad, kProfCamTerm, kProfRenderFwdMerged, kProfSlots
+  kProfGlueSoftmax, kProfGlueGate, kProfUpsample, kProfConvFwd, kProfConvDgrad, kProfConvWgrad, kProfCamTerm, kProfRenderFwdMerged,
+  kProfResize2d, kProfSlots
 };
 struct ProfScope { int idx; };
 bool prof_enabled();

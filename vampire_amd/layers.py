@@ -1,5 +1,6 @@
 """Layer operators on plain tensors (Python over the C ABI): the free functions a network calls without a `HotPath`
--- BEVDepth voxel pooling, and the trilinear resize and 3x3x3 convolutions of the 3-D UNet, with autograd support.
+-- BEVDepth voxel pooling, the trilinear resize and 3x3x3 convolutions of the 3-D UNet, and the 2-D bilinear resize of
+the rendered maps, with autograd support.
 All work happens in hand-written HIP kernels reached through `_capi`; there is no CPU fallback."""
 import torch
 
@@ -97,6 +98,79 @@ class _UpsampleTrilinearFn(torch.autograd.Function):
         else:
             gin.zero_()
         return gin.to(ctx.in_dtype), None
+
+
+# ===========================================================================
+# 2-D bilinear resize of the rendered maps (bv2:616-626, 203-209)
+# ===========================================================================
+def resize_bilinear2d(x, size):
+    """F.interpolate(x, size, mode='bilinear', align_corners=True) on the HIP kernels: x [..., H, W] fp32 device tensor
+    -> [..., *size].  The backward is a gather in a fixed order (aten's scatters with float atomics), so gradients are
+    bitwise repeatable.  Sizes `vamp_resize2d_supported` refuses raise; the caller decides what to do with them."""
+    return resize_bilinear2d_pack([x], size)[0]
+
+
+def resize_bilinear2d_pack(tensors, size):
+    """The same for up to 4 tensors that share H and W (leading dimensions are free: the camera maps' 3, num_classes
+    and 1 channels), in one launch forward and one backward.  Returns a list.  An output that receives no gradient is
+    left out of the backward launch."""
+    return list(_Resize2dFn.apply(tuple(int(v) for v in size), *tensors))
+
+
+def resize_bilinear2d_supported(in_size, size) -> bool:
+    return bool(_capi.checked().vamp_resize2d_supported(*(int(v) for v in in_size), *(int(v) for v in size)))
+
+
+def _resize2d_desc(ih, iw, oh, ow, pairs) -> _capi.VampResize2dDesc:
+    """pairs: (src, dst) tensors per segment; the planes are whatever leads the two resized axes."""
+    d = _capi.VampResize2dDesc()
+    d.ih, d.iw, d.oh, d.ow, d.nseg = ih, iw, oh, ow, len(pairs)
+    for k, (src, dst) in enumerate(pairs):
+        d.seg[k].src, d.seg[k].dst = src.data_ptr(), dst.data_ptr()
+        d.seg[k].planes = src.numel() // (src.shape[-1] * src.shape[-2])
+    return d
+
+
+class _Resize2dFn(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, size, *tensors):
+        if not 1 <= len(tensors) <= _capi.VAMP_RESIZE2D_MAX_SEGS:
+            raise ValueError(f"expected 1 to {_capi.VAMP_RESIZE2D_MAX_SEGS} tensors, got {len(tensors)}")
+        if len(size) != 2:
+            raise ValueError("size must be (H, W)")
+        for t in tensors:
+            if not t.is_cuda:
+                raise _capi.VampireHipError("resize_bilinear2d needs device tensors (no CPU fallback)")
+            if t.dim() < 2 or t.dtype != torch.float32 or t.numel() == 0:
+                raise ValueError("expected non-empty fp32 tensors [..., H, W]")
+            if tuple(t.shape[-2:]) != tuple(tensors[0].shape[-2:]) or t.device != tensors[0].device:
+                raise ValueError("the tensors of a pack share H, W and the device")
+        ih, iw = tensors[0].shape[-2:]
+        xs = [_aligned(t) for t in tensors]
+        outs = [torch.empty(tuple(t.shape[:-2]) + size, dtype=torch.float32, device=t.device) for t in tensors]
+        with torch.cuda.device(xs[0].device):
+            _capi.checked().vamp_resize2d_forward(_resize2d_desc(ih, iw, *size, list(zip(xs, outs))), _stream())
+        ctx.dims = (ih, iw) + size
+        ctx.in_shapes = [tuple(t.shape) for t in tensors]
+        ctx.set_materialize_grads(False)
+        return tuple(outs)
+
+    @staticmethod
+    def backward(ctx, *grads):
+        vamp = _capi.checked()
+        pairs, gins = [], [None] * len(grads)
+        for k, g in enumerate(grads):
+            if g is None or not ctx.needs_input_grad[1 + k]:
+                continue                    # no gradient came for this output: its segment is not launched
+            gins[k] = torch.empty(ctx.in_shapes[k], dtype=torch.float32, device=g.device)
+            pairs.append((_aligned(g.float()), gins[k]))
+        if pairs:
+            dev = pairs[0][0].device
+            nbytes = vamp.vamp_resize2d_workspace_bytes(*ctx.dims)
+            ws = _workspace((dev, torch.cuda.current_stream().cuda_stream, "resize2d"), dev, nbytes) if nbytes else None
+            with torch.cuda.device(dev):
+                vamp.vamp_resize2d_backward(_resize2d_desc(*ctx.dims, pairs), ws, nbytes, _stream())
+        return (None,) + tuple(gins)
 
 
 # ===========================================================================
