@@ -117,14 +117,20 @@ def planned(S):
 # ---------------------------------------------------------------------------------------------------- scenes
 @functools.lru_cache(maxsize=None)
 def scene(case):
-    """CPU tensors: (cfg, render_mats [B,N,3,4,4], volumes (fp32, bf16-rounded for bf16 cases), beta)."""
+    """CPU tensors: (cfg, render_mats [B,N,3,4,4], volumes (fp32, bf16-rounded for bf16 cases), beta).  A case may
+    carry a batch size `B` (2 without) and a factor `empty` on the whole density volume instead of on its low-x half
+    (tests/test_camera_cell_shapes.py: no ray terminates)."""
     cfg = case.cfg
-    s2e, intrin, ida = synthetic.camera_rig(cfg, 2, jitter=1.0, seed=5)
-    bda = synthetic.bda_matrix(2, rot_deg=5.0)
+    B = getattr(case, "B", 2)
+    s2e, intrin, ida = synthetic.camera_rig(cfg, B, jitter=1.0, seed=5)
+    bda = synthetic.bda_matrix(B, rot_deg=5.0)
     rm = render_matrices(s2e, intrin, ida, bda)
-    vols = list(synthetic.render_inputs(cfg, 2, seed=17))
+    vols = list(synthetic.render_inputs(cfg, B, seed=17))
     d = vols[0].clone()
-    d[..., : d.shape[-1] // 2] *= 0.4         # the "empty" regime: s - bias ~ +0.6, sigma ~ 0.012 / m
+    if getattr(case, "empty", None) is None:
+        d[..., : d.shape[-1] // 2] *= 0.4     # the "empty" regime: s - bias ~ +0.6, sigma ~ 0.012 / m
+    else:
+        d *= case.empty
     vols[0] = d
     if case.bf16:
         vols = [v.bfloat16().float() for v in vols]
@@ -239,10 +245,11 @@ def run_path(case, path, dev, seed=4545):
     return errs, calls
 
 
-def check_path(case, path, calls):
-    """The calls that ran are those of the path the case asked for (or, above kPlanMax, of its documented fallback)."""
+def check_path(case, path, calls, merged_ok=True):
+    """The calls that ran are those of the path the case asked for (or, above kPlanMax, of its documented fallback;
+    merged_ok False: the library does not offer the merged launch on the case's BEV geometry, the two launches run)."""
     S = case.S
-    p = PATHS[path]
+    p = dict(PATHS[path], fwd_merged=PATHS[path]["fwd_merged"] and merged_ok)
     names = [n for n, _ in calls.log]
     fwd = calls.flags("vamp_render_camera_forward_ex", -2)
     mrg = calls.flags("vamp_render_forward_merged", -2)
@@ -270,7 +277,8 @@ def check_path(case, path, calls):
     elif p["cam_direct"]:
         assert not mrg and len(fwd) == 2 and all(f & _capi.VAMP_CAMFWD_DIRECT for f in fwd), (names, fwd)
         assert "vamp_render_bev_forward_ex" in names
-        assert bool(fwd[1] & _capi.VAMP_CAMFWD_SAVE_SAMPLES) == p["save_rows"], fwd
+        # (the v1 splat reads no sample rows; it comes here only where the merged launch is not offered)
+        assert bool(fwd[1] & _capi.VAMP_CAMFWD_SAVE_SAMPLES) == (p["save_rows"] and p["cam_bwd"] != "v1"), fwd
     else:
         marches = [f for f in fwd if not (f & _capi.VAMP_CAMFWD_PACK_ONLY)]
         assert not mrg and len(marches) == 2 and all(not (f & _capi.VAMP_CAMFWD_DIRECT) for f in marches), (names, fwd)
