@@ -338,6 +338,69 @@ def test_unet_routing(dev, monkeypatch):
     assert counts(True, None) == [0, 0, 0]
 
 
+# the entry points of each kind `layers.conv3d_kind` names (forward, data gradient, weight gradient)
+KIND_ENTRIES = {None: [], "fp32": ["vamp_conv3d_forward", "vamp_conv3d_backward_data", "vamp_conv3d_backward_weight"],
+                "half": [f"vamp_conv3d_half_{n}" for n in ("forward", "backward_data", "backward_weight")],
+                "half_s2": [f"vamp_conv3d_half_s2_{n}" for n in ("forward", "backward_data", "backward_weight")]}
+
+
+@gpu
+def test_layers_and_heads_call_the_kind_conv3d_kind_names(dev, monkeypatch):
+    """One forward + backward of a `_Conv3` layer at 1x16x4x8x16 (stride 1 and 2; plain, under a bf16 autocast, and
+    under it with the stride-2 switch off) and of the fused heads (plain and under autocast): the convolution entry
+    points recorded are exactly the three of the kind `conv3d_kind` names for the case, none where it names None."""
+    from types import SimpleNamespace
+    from torch import nn
+    from vampire_amd import backbone
+    from vampire_amd.layers import conv3d_kind
+    log = []
+    lib = _capi.load()
+
+    class Rec:
+        def __getattr__(self, name):
+            fn = getattr(lib, name)
+            if not name.startswith("vamp_conv3d_") or name.endswith(("_supported", "_bytes")):
+                return fn
+
+            def call(*a):
+                log.append(name)
+                return fn(*a)
+            return call
+
+    via = _capi.checked(Rec())
+    monkeypatch.setattr(_capi, "checked", lambda through=None: via)
+    monkeypatch.setattr(backbone.SWITCHES, "conv3d", True)
+    monkeypatch.setattr(backbone.SWITCHES, "conv3d_min_voxels", 0)
+    torch.manual_seed(5)
+    x = torch.randn(1, 16, 4, 8, 16, device=dev)
+
+    def check(run, w_shape, stride, dt16, s2, want):
+        monkeypatch.setattr(backbone.SWITCHES, "conv3d_s2", s2)
+        kind = conv3d_kind(tuple(x.shape), w_shape, torch.float32, torch.float32, True, (stride,) * 3, (1, 1, 1), False,
+                           autocast=dt16, min_voxels=0, stride2=s2)
+        assert kind == want, (stride, dt16, s2, kind)
+        log.clear()
+        a = x.clone().requires_grad_(True)
+        with torch.autocast("cuda", dtype=dt16, enabled=dt16 is not None):
+            outs = run(a)
+        torch.autograd.backward(outs, [torch.ones_like(o) for o in outs])
+        assert a.grad is not None and a.grad.shape == x.shape
+        assert sorted(log) == sorted(KIND_ENTRIES[kind]), (stride, dt16, s2, kind, log)
+
+    for stride, dt16, s2, want in ((1, None, True, "fp32"), (1, BF16, True, "half"), (1, BF16, False, "half"),
+                                   (2, None, True, None), (2, BF16, True, "half_s2"), (2, BF16, False, None)):
+        layer = backbone._conv3(16, 32, stride).to(dev)
+        check(lambda a: (layer(a),), (32, 16, 3, 3, 3), stride, dt16, s2, want)
+        assert layer.weight.grad is not None and layer.weight.grad.dtype == torch.float32
+
+    heads = SimpleNamespace(num_classes=4, density_conv=nn.Conv3d(16, 1, 3, 1, 1).to(dev),
+                            seg_conv=nn.Conv3d(16, 4, 3, 1, 1).to(dev),
+                            rgb_conv=nn.Sequential(nn.Conv3d(16, 3, 3, 1, 1), nn.Sigmoid()).to(dev))
+    for dt16, want in ((None, "fp32"), (BF16, "half")):
+        check(lambda a: backbone.BaseVAMPIRE2._heads(heads, a), (32, 16, 3, 3, 3), 1, dt16, True, want)
+        assert heads.seg_conv.weight.grad is not None
+
+
 # =====================================================================================================================
 # CPU
 # =====================================================================================================================
@@ -481,3 +544,52 @@ def test_the_stride1_rule_still_refuses_stride2():
     from vampire_amd.ops import conv3d_bf16_supported
     x, w = torch.zeros(1, 16, 2, 2, 8, dtype=BF16), torch.zeros(16, 16, 3, 3, 3, dtype=BF16)
     assert conv3d_bf16_supported(x, w, (2, 2, 2), (1, 1, 1), None) is False
+
+
+def _kind(x_shape=(1, 16, 4, 8, 16), w_shape=(32, 16, 3, 3, 3), dt=torch.float32, wdt=None, on_device=True, stride=1,
+          padding=1, bias=False, **kw):
+    from vampire_amd.layers import conv3d_kind
+    return conv3d_kind(x_shape, w_shape, dt, dt if wdt is None else wdt, on_device, (stride,) * 3, (padding,) * 3, bias,
+                       **kw)
+
+
+def test_routing_table(lib):
+    """Which convolution runs a layer (`layers.conv3d_kind`, what `_Conv3.forward` and `_heads` ask): the rules of the
+    module path as a table, on the library's host-side shape answers."""
+    V = 4 * 8 * 16
+    x10, x12, c33 = (1, 16, 4, 8, 10), (1, 16, 4, 8, 12), (1, 33, 4, 8, 16)
+    # the three library answers the rows rest on: X = 16 and 12 everywhere, X = 10 fp32 only, cin = 33 nowhere
+    answers = lambda shape: tuple(getattr(lib, f"vamp_conv3d_{n}supported")(_desc(shape[0], shape[1], 32, *shape[2:]))  # noqa: E731
+                                  for n in ("", "bf16_", "half_s2_"))
+    assert answers((1, 16, 4, 8, 16)) == answers(x12) == (1, 1, 1)
+    assert answers(x10) == (1, 0, 0) and answers(c33) == (0, 0, 0)
+    # fp32: fp32 tensors, stride 1, no autocast of any kind, at least min_voxels voxels per channel
+    assert _kind(min_voxels=0) == "fp32" and _kind() == "fp32"
+    assert _kind(min_voxels=V) == "fp32" and _kind(min_voxels=V + 1) is None
+    assert _kind(autocast=torch.float32) is None
+    assert _kind(dt=BF16) is None and _kind(wdt=BF16) is None and _kind(dt=FP16) is None
+    assert _kind(stride=2) is None and _kind(stride=2, stride2=True, min_voxels=0) is None
+    # a 16-bit autocast: stride 1 before stride 2, min_voxels not applied, whatever the operands' dtypes
+    for dt16 in (BF16, FP16):
+        assert _kind(autocast=dt16) == "half"
+        assert _kind(autocast=dt16, min_voxels=V + 1) == "half" and _kind(autocast=dt16, min_voxels=10 ** 9) == "half"
+        assert _kind(autocast=dt16, dt=dt16) == "half" and _kind(autocast=dt16, stride2=False) == "half"
+        assert _kind(autocast=dt16, stride=2) == "half_s2"
+        assert _kind(autocast=dt16, stride=2, min_voxels=10 ** 9) == "half_s2"
+        assert _kind(autocast=dt16, stride=2, stride2=False) is None
+        assert _kind(x12, autocast=dt16) == "half" and _kind(x12, autocast=dt16, stride=2) == "half_s2"
+        # X = 10: the fp32 kernels alone take it
+        assert _kind(x10, autocast=dt16) is None and _kind(x10, autocast=dt16, stride=2) is None
+    assert _kind(x10) == "fp32" and _kind(x12) == "fp32"
+    # what no kernel takes, with and without autocast, at either stride
+    refused = (dict(x_shape=c33, w_shape=(32, 33, 3, 3, 3)), dict(w_shape=(32, 32, 3, 3, 3)), dict(bias=True),
+               dict(padding=0), dict(w_shape=(32, 16, 1, 1, 1)), dict(w_shape=(32, 16, 3, 3)), dict(x_shape=(16, 4, 8, 16)),
+               dict(x_shape=(1, 1, 16, 4, 8, 16)), dict(on_device=False), dict(stride=3))
+    for case, autocast, stride in itertools.product(refused, (None, BF16, FP16), (1, 2)):
+        assert _kind(**{"stride": stride, **case}, autocast=autocast) is None, (case, autocast, stride)
+    # the public predicates are the same rule (host tensors: refused)
+    from vampire_amd.ops import conv3d_supported, conv3d_bf16_supported, conv3d_bf16_stride2_supported
+    x, w = torch.zeros(1, 16, 4, 8, 16), torch.zeros(32, 16, 3, 3, 3)
+    for fn, a, s in ((conv3d_supported, x, 1), (conv3d_bf16_supported, x.to(BF16), 1),
+                     (conv3d_bf16_stride2_supported, x.to(BF16), 2)):
+        assert fn(a, w.to(a.dtype), (s,) * 3, (1, 1, 1), None) is False

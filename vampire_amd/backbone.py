@@ -38,6 +38,7 @@ from torch import nn
 from . import geometry as G
 from .config import PathConfig
 from .density import ModifyLaplaceDensity
+from .layers import conv3d_3x3x3, conv3d_bf16, conv3d_bf16_stride2, conv3d_kind, cuda_autocast
 from .ops import HotPath
 
 
@@ -96,13 +97,20 @@ def _resize2d_pack(tensors, size):
     return resize_bilinear2d_pack(tensors, size)
 
 
-def _autocast_16(x):
-    """bf16 or fp16 when a 16-bit CUDA autocast is on (the reference trains with Lightning's `precision=16`), else None."""
-    if x.is_cuda and torch.is_autocast_enabled():
-        dt = torch.get_autocast_dtype("cuda")
-        if dt in (torch.bfloat16, torch.float16):
-            return dt
-    return None
+def _hip_conv3d(x, weight, stride, padding, bias):
+    """The layer on the HIP kernels `layers.conv3d_kind` names for it under `SWITCHES` and the current autocast (the
+    reference's mixed-precision training: 16-bit operands, as autocast would hand them to MIOpen), or None: the caller
+    keeps aten / MIOpen."""
+    if not SWITCHES.conv3d:
+        return None
+    kind = conv3d_kind(x.shape, weight.shape, x.dtype, weight.dtype, x.is_cuda, stride, padding, bias is not None,
+                       autocast=cuda_autocast(), min_voxels=SWITCHES.conv3d_min_voxels, stride2=SWITCHES.conv3d_s2)
+    if kind is None:
+        return None
+    if kind == "fp32":
+        return conv3d_3x3x3(x, weight)
+    dt16 = cuda_autocast()
+    return (conv3d_bf16 if kind == "half" else conv3d_bf16_stride2)(x.to(dt16), weight.to(dt16))
 
 
 class _Conv3(nn.Conv3d):
@@ -114,22 +122,8 @@ class _Conv3(nn.Conv3d):
     conv3d_bf16.hip and the stride-2 ones on conv3d_bf16_s2.hip (`VAMP_CONV3D_S2=0`: MIOpen)."""
 
     def forward(self, x):
-        if SWITCHES.conv3d and x.dim() == 5 and x.is_cuda:
-            from .layers import conv3d_3x3x3, conv3d_supported, conv3d_bf16, conv3d_bf16_supported
-            dt16 = _autocast_16(x)
-            if dt16 is not None:
-                # the reference's mixed-precision training: 16-bit operands, as autocast would hand them to MIOpen
-                xb = x.to(dt16)
-                if conv3d_bf16_supported(xb, self.weight, self.stride, self.padding, self.bias):
-                    return conv3d_bf16(xb, self.weight.to(dt16))
-                if SWITCHES.conv3d_s2:
-                    from .layers import conv3d_bf16_stride2, conv3d_bf16_stride2_supported
-                    if conv3d_bf16_stride2_supported(xb, self.weight, self.stride, self.padding, self.bias):
-                        return conv3d_bf16_stride2(xb, self.weight.to(dt16))
-            elif (x[0, 0].numel() >= SWITCHES.conv3d_min_voxels
-                    and conv3d_supported(x, self.weight, self.stride, self.padding, self.bias)):
-                return conv3d_3x3x3(x, self.weight)
-        return super().forward(x)
+        y = _hip_conv3d(x, self.weight, self.stride, self.padding, self.bias)
+        return super().forward(x) if y is None else y
 
 
 def _conv3(cin, cout, stride=1):
@@ -424,18 +418,9 @@ class BaseVAMPIRE2(nn.Module):
         launches become one each; biases and the rgb sigmoid follow.  Parameters are untouched."""
         nout = 1 + self.num_classes + 3
         if SWITCHES.conv3d and nout <= 32 and base.dim() == 5 and base.is_cuda:
-            from .layers import conv3d_3x3x3, conv3d_supported, conv3d_bf16, conv3d_bf16_supported
             wd, ws, wr = self.density_conv.weight, self.seg_conv.weight, self.rgb_conv[0].weight
             w = torch.cat([wd, ws, wr, wd.new_zeros((32 - nout,) + tuple(wd.shape[1:]))], 0)
-            y = None
-            dt16 = _autocast_16(base)
-            if dt16 is not None:
-                bb = base.to(dt16)
-                if conv3d_bf16_supported(bb, w, (1, 1, 1), (1, 1, 1), None):
-                    y = conv3d_bf16(bb, w.to(dt16))
-            elif (base[0, 0].numel() >= SWITCHES.conv3d_min_voxels
-                    and conv3d_supported(base, w, (1, 1, 1), (1, 1, 1), None)):
-                y = conv3d_3x3x3(base, w)
+            y = _hip_conv3d(base, w, (1, 1, 1), (1, 1, 1), None)
             if y is not None:
                 K = self.num_classes
                 bias = lambda b: b.view(1, -1, 1, 1, 1)

@@ -10,6 +10,7 @@
 #include <string.h>
 
 #include "../../include/vampire_hip.h"
+#include "elem16.hpp"       // for ldf's bf16 widening alone: the hot-path kernels use nothing else of it
 
 namespace vamp {
 
@@ -147,7 +148,7 @@ __device__ __forceinline__ Vec4 matvec(const float* __restrict__ m, Vec4 p) {
 // element loads with fp32 promotion
 __device__ __forceinline__ float ldf(const float* p, long i) { return p[i]; }
 __device__ __forceinline__ float ldf(const __hip_bfloat16* p, long i) {
-  return __uint_as_float(((uint32_t) reinterpret_cast<const uint16_t*>(p)[i]) << 16);
+  return bf16_to_f32(reinterpret_cast<const uint16_t*>(p)[i]);
 }
 
 __device__ __forceinline__ float nan_to_num(float v) {

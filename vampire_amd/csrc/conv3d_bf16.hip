@@ -18,7 +18,7 @@
 // The data gradient is the same kernel on the flipped, transposed weights (FLIP).
 // The weight gradient has K = voxels, contiguous along x in NCDHW: both operands are plain
 // 16-byte global loads (the shifted-by-one-voxel windows at 2-byte alignment), no LDS at all.
-#include "conv3d_half.hpp"       // the vector types, mfma16, f2e, the partials' reduce kernel, tile_ch, bf16_shape_ok
+#include "conv3d_half.hpp"       // the vector types, mfma16, f32_to_e16, the partials' reduce kernel, tile_ch, bf16_shape_ok
 
 #include <algorithm>
 #include <type_traits>
@@ -175,7 +175,7 @@ conv3d_bf16_fwd_kernel(CvP P, const unsigned short* __restrict__ in, const unsig
           if (x < P.X) {
 #pragma unroll
             for (int rg = 0; rg < 4; ++rg)
-              if (m * 16 + 4 * kg + rg < P.cout) ob[(long) (m * 16 + 4 * kg + rg) * plane + x] = f2e<F16>(acc[m][n][rg]);
+              if (m * 16 + 4 * kg + rg < P.cout) ob[(long) (m * 16 + 4 * kg + rg) * plane + x] = f32_to_e16<F16>(acc[m][n][rg]);
           }
         }
     }

@@ -238,7 +238,7 @@ conv3d_s2_fwd_kernel(S2P P, const unsigned short* __restrict__ in, const unsigne
           if (x < P.Xo) {
 #pragma unroll
             for (int rg = 0; rg < 4; ++rg)
-              if (m * 16 + 4 * kg + rg < P.cout) ob[(long) (m * 16 + 4 * kg + rg) * plane_o + x] = f2e<F16>(acc[m][n][rg]);
+              if (m * 16 + 4 * kg + rg < P.cout) ob[(long) (m * 16 + 4 * kg + rg) * plane_o + x] = f32_to_e16<F16>(acc[m][n][rg]);
           }
         }
     }
@@ -371,7 +371,7 @@ conv3d_s2_dgrad_kernel(S2P P, const unsigned short* __restrict__ gout, const uns
             for (int rg = 0; rg < 4; ++rg)
               if (m * 16 + 4 * kg + rg < P.cin)
                 *reinterpret_cast<unsigned*>(ob + (long) (m * 16 + 4 * kg + rg) * plane_i + x) =
-                    (unsigned) f2e<F16>(acce[m][j][rg]) | ((unsigned) f2e<F16>(acco[m][j][rg]) << 16);
+                    (unsigned) f32_to_e16<F16>(acce[m][j][rg]) | ((unsigned) f32_to_e16<F16>(acco[m][j][rg]) << 16);
           }
         }
     }

@@ -1,8 +1,9 @@
 // What the 16-bit 3x3x3 convolutions share (conv3d_bf16.hip: stride 1, conv3d_bf16_s2.hip: stride 2): the register
-// vector types, the matrix-core product on bf16 or IEEE half operands, the fp32 -> 16-bit rounding, the channel tile
-// and shape rule, and the second launch of the weight gradient (the fixed-order sum of the workgroups' partials).
+// vector types, the matrix-core product on bf16 or IEEE half operands, the channel tile and shape rule, and the second
+// launch of the weight gradient (the fixed-order sum of the workgroups' partials).
 #pragma once
 #include "common.hpp"
+#include "elem16.hpp"       // f32_to_e16: the fp32 -> 16-bit rounding of the stores
 
 namespace vamp {
 namespace {
@@ -26,25 +27,6 @@ __device__ __forceinline__ f32x4 mfma16(const bf16x8& a, const bf16x8& b, const 
     return __builtin_amdgcn_mfma_f32_16x16x32_f16(ha, hb, c, 0, 0, 0);
   } else {
     return __builtin_amdgcn_mfma_f32_16x16x32_bf16(a, b, c, 0, 0, 0);
-  }
-}
-
-__device__ __forceinline__ unsigned short f2bf(float f) {          // round to nearest even (NaN kept quiet)
-  unsigned u = __float_as_uint(f);
-  if ((u & 0x7fffffffu) > 0x7f800000u) return (unsigned short) ((u >> 16) | 0x40);
-  u += 0x7fffu + ((u >> 16) & 1u);
-  return (unsigned short) (u >> 16);
-}
-
-template <bool F16>
-__device__ __forceinline__ unsigned short f2e(float f) {              // fp32 -> the 16-bit element type, round to nearest even
-  if constexpr (F16) {
-    const _Float16 h = (_Float16) f;
-    unsigned short u;
-    __builtin_memcpy(&u, &h, 2);
-    return u;
-  } else {
-    return f2bf(f);
   }
 }
 

@@ -26,6 +26,7 @@
 #include <cmath>
 
 #include "common.hpp"
+#include "wave_reduce.hpp"
 
 namespace vamp {
 namespace {
@@ -79,19 +80,6 @@ __device__ __forceinline__ int task_of_chunk(const LossParams& p, int chunk) {
   return t;
 }
 
-// sum over the workgroup in a fixed order (butterfly per wave, waves in order); the result is valid in thread 0
-template <int WAVES>
-__device__ __forceinline__ double block_sum(double v, double* red) {
-#pragma unroll
-  for (int o = 32; o >= 1; o >>= 1) v += __shfl_xor(v, o, 64);
-  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
-  __syncthreads();
-  double tot = 0.0;
-  if (threadIdx.x == 0)
-    for (int w = 0; w < WAVES; ++w) tot += red[w];
-  return tot;
-}
-
 // ---------------------------------------------------------------------------------------------------------
 // counts
 // ---------------------------------------------------------------------------------------------------------
@@ -121,11 +109,8 @@ __global__ void __launch_bounds__(kCountBlock) loss_counts_kernel(LossParams p, 
   for (long e = head + 4 * nvec + tid; e < n; e += kCountBlock) npos += h[e] == 1.0f ? 1 : 0;
   const uint8_t* m = p.masks + (long) t * p.B * p.K;
   for (long e = tid; e < (long) p.B * p.K; e += kCountBlock) nmask += m[e];
-#pragma unroll
-  for (int o = 32; o >= 1; o >>= 1) {
-    npos += __shfl_xor(npos, o, 64);
-    nmask += __shfl_xor(nmask, o, 64);
-  }
+  npos = wave_sum(npos);
+  nmask = wave_sum(nmask);
   if ((tid & 63) == 0) { red[0][tid >> 6] = npos; red[1][tid >> 6] = nmask; }
   __syncthreads();
   if (tid == 0) {
@@ -199,11 +184,8 @@ __global__ void __launch_bounds__(kFinishBlock) loss_finish_kernel(LossParams p)
     for (int i = p.chunk_off[t] + lane; i < p.chunk_off[t + 1]; i += 64) hs += p.part[i];
     const double* bp = p.part + p.chunk_off[p.T] + (long) t * p.B;
     for (int i = lane; i < p.B; i += 64) bs += bp[i];
-#pragma unroll
-    for (int o = 32; o >= 1; o >>= 1) {
-      hs += __shfl_xor(hs, o, 64);
-      bs += __shfl_xor(bs, o, 64);
-    }
+    hs = wave_sum(hs);
+    bs = wave_sum(bs);
     if (lane == 0) {
       const float f_pos = fmaxf(p.counts[2 * t], 1.0f), f_num = fmaxf(p.counts[2 * t + 1], 1e-4f);
       sterm[t][0] = hs / (double) f_pos;

@@ -18,11 +18,10 @@
 //      the earlier tasks' class counts, zero tail, counts.
 // No atomics outside LDS histograms (integer counts), no host synchronisation: the output is a pure function
 // of the inputs and the launches can be captured in a graph.
-#include <hip/hip_fp16.h>
-
 #include <algorithm>
 
 #include "common.hpp"
+#include "elem16.hpp"
 
 namespace vamp {
 namespace {
@@ -50,28 +49,18 @@ struct DetParams {
   int* nkept;
 };
 
-// ---- 16-bit conversions (c10's: round to nearest even; a NaN becomes the canonical one) ----
-__device__ __forceinline__ float bf2f(uint16_t u) { return __uint_as_float((uint32_t) u << 16); }
-__device__ __forceinline__ uint16_t f2bf(float f) {
-  const uint32_t u = __float_as_uint(f);
-  if (f != f) return 0x7fc0;
-  return (uint16_t) ((u + 0x7fffu + ((u >> 16) & 1u)) >> 16);
-}
-__device__ __forceinline__ float h2f(uint16_t u) { return __half2float(__ushort_as_half(u)); }
-__device__ __forceinline__ uint16_t f2h(float f) { return __half_as_ushort(__float2half_rn(f)); }
-
 template <int DT>
 __device__ __forceinline__ float ld(const void* p, long i) {
   if constexpr (DT == VAMP_F32) return static_cast<const float*>(p)[i];
-  else if constexpr (DT == VAMP_BF16) return bf2f(static_cast<const uint16_t*>(p)[i]);
-  else return h2f(static_cast<const uint16_t*>(p)[i]);
+  else if constexpr (DT == VAMP_BF16) return bf16_to_f32(static_cast<const uint16_t*>(p)[i]);
+  else return f16_to_f32(static_cast<const uint16_t*>(p)[i]);
 }
 // a value torch computes in the input dtype (sigmoid, exp, atan2 of 16-bit tensors): rounded to it, widened back
 template <int DT>
 __device__ __forceinline__ float rnd(float f) {
   if constexpr (DT == VAMP_F32) return f;
-  else if constexpr (DT == VAMP_BF16) return bf2f(f2bf(f));
-  else return h2f(f2h(f));
+  else if constexpr (DT == VAMP_BF16) return bf16_to_f32(f32_to_bf16_c10(f));
+  else return f16_to_f32(f32_to_f16(f));
 }
 
 // aten's sigmoid: 1 / (1 + exp(-x)) in fp32 with the accurate expf, rounded to the input dtype
@@ -484,8 +473,8 @@ __global__ void __launch_bounds__(256) det_merge_kernel(DetParams p, float* __re
       if (c < cs) dst[c] = v[c];
     const long si = (long) b * rows + r;
     if constexpr (DT == VAMP_F32) static_cast<float*>(scores)[si] = v[9];
-    else if constexpr (DT == VAMP_BF16) static_cast<uint16_t*>(scores)[si] = f2bf(v[9]);
-    else static_cast<uint16_t*>(scores)[si] = f2h(v[9]);
+    else if constexpr (DT == VAMP_BF16) static_cast<uint16_t*>(scores)[si] = f32_to_bf16_c10(v[9]);
+    else static_cast<uint16_t*>(scores)[si] = f32_to_f16(v[9]);
     labels[si] = label;
   }
 }

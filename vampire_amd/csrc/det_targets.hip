@@ -23,6 +23,7 @@
 #include <cmath>
 
 #include "common.hpp"
+#include "wave_reduce.hpp"
 
 namespace vamp {
 namespace {
@@ -108,11 +109,7 @@ __global__ void __launch_bounds__(kTgtBlock) tgt_assign_kernel(TgtParams p) {
     const int c = load_class(p, b, i, t);
     n0 += c == 0; n1 += c == 1; n2 += c == 2; n3 += c == 3;
   }
-#pragma unroll
-  for (int o = 32; o >= 1; o >>= 1) {
-    n0 += __shfl_xor(n0, o, 64); n1 += __shfl_xor(n1, o, 64);
-    n2 += __shfl_xor(n2, o, 64); n3 += __shfl_xor(n3, o, 64);
-  }
+  n0 = wave_sum(n0); n1 = wave_sum(n1); n2 = wave_sum(n2); n3 = wave_sum(n3);
   if (lane == 0) { wc[wid][0] = n0; wc[wid][1] = n1; wc[wid][2] = n2; wc[wid][3] = n3; }
   __syncthreads();
   int cnt[kTgtMaxNcls];

@@ -26,6 +26,8 @@
 #include <cmath>
 
 #include "common.hpp"
+#include "elem16.hpp"
+#include "wave_reduce.hpp"
 
 namespace vamp {
 namespace {
@@ -61,15 +63,6 @@ __device__ __forceinline__ int reg_term_of(const RegPack& p, int b) {
   return t;
 }
 
-__device__ __forceinline__ float reg_bf16(uint32_t h) { return __uint_as_float(h << 16); }
-
-// fp32 -> bf16, round to nearest even; NaN stays a quiet NaN
-__device__ __forceinline__ uint32_t reg_to_bf16(float v) {
-  const uint32_t u = __float_as_uint(v);
-  if (v != v) return (u >> 16) | 0x40u;
-  return (u + 0x7FFFu + ((u >> 16) & 1u)) >> 16;
-}
-
 // One group: up to four elements from i0 on, `live` = the bits of those below n, `set` = the bits whose mask byte is
 // set (all live bits without a mask).  tv of a constant target is the constant.
 struct RegGroup {
@@ -85,8 +78,8 @@ __device__ __forceinline__ RegGroup reg_load(const RegPack& p, int t, long i0, l
     g.live = 0xFu;
     if (bf) {
       const uint2 w = *reinterpret_cast<const uint2*>(static_cast<const uint16_t*>(p.pred[t]) + i0);
-      g.pv[0] = reg_bf16(w.x & 0xFFFFu); g.pv[1] = reg_bf16(w.x >> 16);
-      g.pv[2] = reg_bf16(w.y & 0xFFFFu); g.pv[3] = reg_bf16(w.y >> 16);
+      const float4 v = bf16x4_to_f32(w);
+      g.pv[0] = v.x; g.pv[1] = v.y; g.pv[2] = v.z; g.pv[3] = v.w;
     } else {
       const float4 w = *reinterpret_cast<const float4*>(static_cast<const float*>(p.pred[t]) + i0);
       g.pv[0] = w.x; g.pv[1] = w.y; g.pv[2] = w.z; g.pv[3] = w.w;
@@ -112,7 +105,7 @@ __device__ __forceinline__ RegGroup reg_load(const RegPack& p, int t, long i0, l
     g.pv[q] = g.tv[q] = 0.0f;
     if (i0 + q < n) {
       g.live |= 1u << q;
-      g.pv[q] = bf ? reg_bf16(static_cast<const uint16_t*>(p.pred[t])[i0 + q]) : static_cast<const float*>(p.pred[t])[i0 + q];
+      g.pv[q] = bf ? bf16_to_f32(static_cast<const uint16_t*>(p.pred[t])[i0 + q]) : static_cast<const float*>(p.pred[t])[i0 + q];
       g.tv[q] = cst ? p.cval[t] : p.target[t][i0 + q];
       if (!mk || mk[i0 + q] != 0) g.set |= 1u << q;
     }
@@ -124,30 +117,6 @@ __device__ __forceinline__ float reg_elem(int kind, float d) {
   if (kind == VAMP_REG_MSE) return d * d;
   const float z = fabsf(d);
   return z < 1.0f ? (0.5f * z) * z : z - 0.5f;
-}
-
-// sums over the workgroup in a fixed order (butterfly per wave, waves in order); valid in thread 0
-__device__ __forceinline__ double reg_block_sum(double v, double* red) {
-#pragma unroll
-  for (int o = 32; o >= 1; o >>= 1) v += __shfl_xor(v, o, 64);
-  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
-  __syncthreads();
-  double tot = 0.0;
-  if (threadIdx.x == 0)
-    for (int w = 0; w < kRegWaves; ++w) tot += red[w];
-  __syncthreads();
-  return tot;
-}
-__device__ __forceinline__ int reg_block_sum(int v, int* red) {
-#pragma unroll
-  for (int o = 32; o >= 1; o >>= 1) v += __shfl_xor(v, o, 64);
-  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
-  __syncthreads();
-  int tot = 0;
-  if (threadIdx.x == 0)
-    for (int w = 0; w < kRegWaves; ++w) tot += red[w];
-  __syncthreads();
-  return tot;
 }
 
 __global__ void __launch_bounds__(kRegBlock) reg_partial_kernel(RegPack p) {
@@ -177,8 +146,8 @@ __global__ void __launch_bounds__(kRegBlock) reg_partial_kernel(RegPack p) {
       }
     }
   }
-  const double t1 = reg_block_sum(s1, red), t0 = reg_block_sum(s0, red);
-  const int n1 = reg_block_sum(c1, redi), n0 = reg_block_sum(c0, redi);
+  const double t1 = block_sum<kRegWaves>(s1, red), t0 = block_sum<kRegWaves>(s0, red);
+  const int n1 = block_sum<kRegWaves>(c1, redi), n0 = block_sum<kRegWaves>(c0, redi);
   if (threadIdx.x == 0) {
     p.psum[2 * (long) b] = t1;
     p.psum[2 * (long) b + 1] = t0;
@@ -198,14 +167,9 @@ __global__ void __launch_bounds__(kRegBlock) reg_finish_kernel(RegPack p) {
       c1 += p.pcnt[2 * j];
       c0 += p.pcnt[2 * j + 1];
     }
-    int i1 = (int) c1, i0 = (int) c0;                // (n < 2^31)
-#pragma unroll
-    for (int o = 32; o >= 1; o >>= 1) {
-      s1 += __shfl_xor(s1, o, 64);
-      s0 += __shfl_xor(s0, o, 64);
-      i1 += __shfl_xor(i1, o, 64);
-      i0 += __shfl_xor(i0, o, 64);
-    }
+    s1 = wave_sum(s1);
+    s0 = wave_sum(s0);
+    const int i1 = wave_sum((int) c1), i0 = wave_sum((int) c0);                // (n < 2^31)
     if (lane == 0) {
       const double m1 = i1 > 0 ? s1 / (double) i1 : 0.0, m0 = i0 > 0 ? s0 / (double) i0 : 0.0;
       const int side = p.side[t];
@@ -246,8 +210,8 @@ __global__ void __launch_bounds__(kRegBlock) reg_bwd_kernel(RegPack p) {
     if (g.live == 0xFu && p.vec[t]) {
       if (bf) {
         uint2 w;
-        w.x = reg_to_bf16(out[0]) | (reg_to_bf16(out[1]) << 16);
-        w.y = reg_to_bf16(out[2]) | (reg_to_bf16(out[3]) << 16);
+        w.x = f32_to_bf16(out[0]) | ((uint32_t) f32_to_bf16(out[1]) << 16);
+        w.y = f32_to_bf16(out[2]) | ((uint32_t) f32_to_bf16(out[3]) << 16);
         *reinterpret_cast<uint2*>(static_cast<uint16_t*>(p.grad[t]) + i0) = w;
       } else {
         *reinterpret_cast<float4*>(static_cast<float*>(p.grad[t]) + i0) = make_float4(out[0], out[1], out[2], out[3]);
@@ -256,7 +220,7 @@ __global__ void __launch_bounds__(kRegBlock) reg_bwd_kernel(RegPack p) {
 #pragma unroll
       for (int q = 0; q < kRegVec; ++q) {
         if (!((g.live >> q) & 1u)) continue;
-        if (bf) static_cast<uint16_t*>(p.grad[t])[i0 + q] = (uint16_t) reg_to_bf16(out[q]);
+        if (bf) static_cast<uint16_t*>(p.grad[t])[i0 + q] = f32_to_bf16(out[q]);
         else static_cast<float*>(p.grad[t])[i0 + q] = out[q];
       }
     }

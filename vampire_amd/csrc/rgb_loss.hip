@@ -37,6 +37,7 @@
 #include <cmath>
 
 #include "common.hpp"
+#include "wave_reduce.hpp"
 
 namespace vamp {
 namespace {
@@ -78,20 +79,6 @@ struct RgbParams {
 struct RgbLayout {
   size_t part, vd, fac, prodn, pyr, adj, gco, total;  // byte offsets
 };
-
-// sum over the workgroup in a fixed order (butterfly per wave, waves in order); valid in thread 0; `red` is free again
-// on return
-__device__ __forceinline__ double rgb_block_sum(double v, double* red) {
-#pragma unroll
-  for (int o = 32; o >= 1; o >>= 1) v += __shfl_xor(v, o, 64);
-  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
-  __syncthreads();
-  double tot = 0.0;
-  if (threadIdx.x == 0)
-    for (int w = 0; w < kRgbWaves; ++w) tot += red[w];
-  __syncthreads();
-  return tot;
-}
 
 // ---------------------------------------------------------------------------------------------------------
 // forward
@@ -176,7 +163,7 @@ __global__ void __launch_bounds__(kRgbBlock) rgb_fwd_kernel(RgbParams p, int s) 
       acc += (double) val;
     }
   }
-  const double tot = rgb_block_sum(acc, red);
+  const double tot = block_sum<kRgbWaves>(acc, red);
   if (tid == 0) p.part[p.part_off[s] + blockIdx.x] = tot;
   // the pixels this tile owns: its 16 x 32, and what lies behind the valid region for the last tile of a row / column
   const int lrows = ty == p.ty[s] - 1 ? Hs - r0 : kTH, lcols = tx == p.tx[s] - 1 ? Ws - c0 : kTW;
@@ -198,7 +185,7 @@ __global__ void __launch_bounds__(kRgbBlock) rgb_fwd_kernel(RgbParams p, int s) 
       const double d = (double) sx[r][c] - (double) sy[r][c], ad = fabs(d);
       sl += ad < 1.0 ? 0.5 * d * d : ad - 0.5;
     }
-    const double st = rgb_block_sum(sl, red);
+    const double st = block_sum<kRgbWaves>(sl, red);
     if (tid == 0) p.part[p.part_off[kRgbScales] + blockIdx.x] = st;
   }
 }
@@ -212,8 +199,7 @@ __global__ void __launch_bounds__(kRgbBlock) rgb_finish_kernel(RgbParams p) {
     const double* q = p.part + p.part_off[s] + (long) n * cnt;
     double a = 0.0;
     for (int j = lane; j < cnt; j += 64) a += q[j];
-#pragma unroll
-    for (int o = 32; o >= 1; o >>= 1) a += __shfl_xor(a, o, 64);
+    a = wave_sum(a);
     if (lane == 0) {
       const double M = (double) p.C * (p.H[s] - kRgbReach) * (p.W[s] - kRgbReach);
       double v = a / M;
@@ -244,8 +230,8 @@ __global__ void __launch_bounds__(kRgbBlock) rgb_finish_kernel(RgbParams p) {
   const long nsl = (long) p.P * p.tx[0] * p.ty[0];
   const double* q = p.part + p.part_off[kRgbScales];
   for (long j = tid; j < nsl; j += kRgbBlock) b += q[j];
-  const double ms = rgb_block_sum(a, red) / (double) p.N;
-  const double sl = rgb_block_sum(b, red) / ((double) p.P * p.H[0] * p.W[0]);
+  const double ms = block_sum<kRgbWaves>(a, red) / (double) p.N;
+  const double sl = block_sum<kRgbWaves>(b, red) / ((double) p.P * p.H[0] * p.W[0]);
   if (tid == 0) {
     p.terms[0] = (float) sl;
     p.terms[1] = (float) ms;

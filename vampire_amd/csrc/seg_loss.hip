@@ -36,6 +36,7 @@
 #include <cmath>
 
 #include "common.hpp"
+#include "wave_reduce.hpp"
 
 namespace vamp {
 namespace {
@@ -113,30 +114,6 @@ __device__ __forceinline__ void seg_softmax_stats(const float* x, long stride, i
   *sum = s;
 }
 
-// sums over the workgroup in a fixed order (butterfly per wave, waves in order); valid in thread 0
-__device__ __forceinline__ double seg_block_sum(double v, double* red) {
-#pragma unroll
-  for (int o = 32; o >= 1; o >>= 1) v += __shfl_xor(v, o, 64);
-  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
-  __syncthreads();
-  double tot = 0.0;
-  if (threadIdx.x == 0)
-    for (int w = 0; w < kSegWaves; ++w) tot += red[w];
-  __syncthreads();
-  return tot;
-}
-__device__ __forceinline__ int seg_block_sum(int v, int* red) {
-#pragma unroll
-  for (int o = 32; o >= 1; o >>= 1) v += __shfl_xor(v, o, 64);
-  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
-  __syncthreads();
-  int tot = 0;
-  if (threadIdx.x == 0)
-    for (int w = 0; w < kSegWaves; ++w) tot += red[w];
-  __syncthreads();
-  return tot;
-}
-
 // ---------------------------------------------------------------------------------------------------------
 // rows
 // ---------------------------------------------------------------------------------------------------------
@@ -172,8 +149,8 @@ __global__ void __launch_bounds__(kSegBlock) seg_row_kernel(SegParams p) {
       }
     }
   }
-  const double tot = seg_block_sum(ce, red);
-  const int cnt = seg_block_sum(nv, redi);
+  const double tot = block_sum<kSegWaves>(ce, red);
+  const int cnt = block_sum<kSegWaves>(nv, redi);
   if (threadIdx.x == 0) {
     p.cepart[blockIdx.x] = tot;
     p.rowcnt[blockIdx.x] = cnt;
@@ -313,7 +290,7 @@ __global__ void __launch_bounds__(kSegBlock) seg_fg_kernel(SegParams p) {
     const long pos = base + r * kSegBlock + tid;
     if (pos < p.P) n += (int) (vs[pos] >> 31);
   }
-  const int tot = seg_block_sum(n, redi);
+  const int tot = block_sum<kSegWaves>(n, redi);
   if (tid == 0) p.tilefg[(long) c * p.T + t] = tot;
 }
 
@@ -365,7 +342,7 @@ __global__ void __launch_bounds__(kSegBlock) seg_jaccard_kernel(SegParams p) {
     if (p.sorted_err) p.sorted_err[c * p.P + pos] = err;
     if (p.perm) p.perm[c * p.P + pos] = (int) idx;
   }
-  const double tot = seg_block_sum(acc, red);
+  const double tot = block_sum<kSegWaves>(acc, red);
   if (tid == 0) p.lvpart[(long) c * p.T + t] = tot;
 }
 
@@ -380,14 +357,13 @@ __global__ void __launch_bounds__(kSegBlock) seg_finish_kernel(SegParams p) {
     nv += p.rowcnt[j];
     ce += p.cepart[j];
   }
-  const int n = seg_block_sum(nv, redi);
-  const double ces = seg_block_sum(ce, red);
+  const int n = block_sum<kSegWaves>(nv, redi);
+  const double ces = block_sum<kSegWaves>(ce, red);
   for (int c = wave; c < p.C; c += kSegWaves) {
     const double* q = p.lvpart + (long) c * p.T;
     double a = 0.0;
     for (int j = lane; j < p.T; j += 64) a += q[j];
-#pragma unroll
-    for (int o = 32; o >= 1; o >>= 1) a += __shfl_xor(a, o, 64);
+    a = wave_sum(a);
     if (lane == 0) cls[c] = a;
   }
   __syncthreads();

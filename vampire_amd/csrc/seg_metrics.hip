@@ -14,6 +14,7 @@
 //    rank by point id inside each run makes the runs ascending), and one wave per reference point sums its points' rows
 //    in increasing point order -- the order of a sequential CPU index_add_, hence bit-exact against it.
 #include "common.hpp"
+#include "elem16.hpp"
 
 namespace vamp {
 namespace {
@@ -52,9 +53,8 @@ __device__ __forceinline__ void ld_logits(const float* p, long off, float (&v)[V
 template <int V>
 __device__ __forceinline__ void ld_logits(const __hip_bfloat16* p, long off, float (&v)[V]) {
   if constexpr (V == 4) {
-    const uint2 u = *reinterpret_cast<const uint2*>(p + off);
-    v[0] = __uint_as_float(u.x << 16); v[1] = __uint_as_float(u.x & 0xffff0000u);
-    v[2] = __uint_as_float(u.y << 16); v[3] = __uint_as_float(u.y & 0xffff0000u);
+    const float4 x = bf16x4_to_f32(*reinterpret_cast<const uint2*>(p + off));
+    v[0] = x.x; v[1] = x.y; v[2] = x.z; v[3] = x.w;
   } else {
     v[0] = ldf(p, off);
   }

@@ -15,6 +15,7 @@
 // src = scale * o, i0 = (int) src, i1 = i0 + (i0 < in - 1), lambda1 = src - i0, lambda0 = 1 - lambda1.
 // HBM-bound streaming: no MFMA.
 #include "common.hpp"
+#include "elem16.hpp"
 
 namespace vamp {
 namespace {
@@ -34,22 +35,11 @@ __device__ __forceinline__ float axis_scale(int in, int out) {
 struct Bf16 { unsigned short u; };
 struct F16 { unsigned short u; };
 __device__ __forceinline__ float lde(const float* p, long i) { return p[i]; }
-__device__ __forceinline__ float lde(const Bf16* p, long i) { return __uint_as_float((unsigned) p[i].u << 16); }
-__device__ __forceinline__ float lde(const F16* p, long i) {
-  _Float16 h;
-  __builtin_memcpy(&h, &p[i].u, 2);
-  return (float) h;
-}
+__device__ __forceinline__ float lde(const Bf16* p, long i) { return bf16_to_f32(p[i].u); }
+__device__ __forceinline__ float lde(const F16* p, long i) { return f16_to_f32(p[i].u); }
 __device__ __forceinline__ void ste(float* p, long i, float v) { p[i] = v; }
-__device__ __forceinline__ void ste(Bf16* p, long i, float v) {
-  unsigned u = __float_as_uint(v);
-  if ((u & 0x7fffffffu) > 0x7f800000u) u |= 0x400000u; else u += 0x7fffu + ((u >> 16) & 1u);
-  p[i].u = (unsigned short) (u >> 16);
-}
-__device__ __forceinline__ void ste(F16* p, long i, float v) {
-  const _Float16 h = (_Float16) v;
-  __builtin_memcpy(&p[i].u, &h, 2);
-}
+__device__ __forceinline__ void ste(Bf16* p, long i, float v) { p[i].u = f32_to_bf16(v); }
+__device__ __forceinline__ void ste(F16* p, long i, float v) { p[i].u = f32_to_f16(v); }
 
 struct Tap {
   int i0, i1;

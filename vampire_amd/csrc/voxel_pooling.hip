@@ -15,6 +15,7 @@
 // zeros, so the output needs no zero fill.  HBM-bound: the features are read once (4 C bytes per
 // point), the output written once; no MFMA.  The backward is a pure gather.
 #include "common.hpp"
+#include "elem16.hpp"
 
 namespace vamp {
 namespace {
@@ -46,9 +47,7 @@ pool_cells_kernel(PoolParams q, const int* __restrict__ geom, int* __restrict__ 
 // four channels of one point per lane
 __device__ __forceinline__ float4 ld4(const float* p, long i) { return *reinterpret_cast<const float4*>(p + i); }
 __device__ __forceinline__ float4 ld4(const __hip_bfloat16* p, long i) {
-  const uint2 u = *reinterpret_cast<const uint2*>(p + i);
-  return make_float4(__uint_as_float(u.x << 16), __uint_as_float(u.x & 0xffff0000u), __uint_as_float(u.y << 16),
-                     __uint_as_float(u.y & 0xffff0000u));
+  return bf16x4_to_f32(*reinterpret_cast<const uint2*>(p + i));
 }
 
 // One wave per cell.  C % 4 == 0 and C <= 256 (VEC): a lane holds four channels, so a feature row takes

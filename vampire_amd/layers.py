@@ -2,6 +2,9 @@
 -- BEVDepth voxel pooling, the trilinear resize and 3x3x3 convolutions of the 3-D UNet, and the 2-D bilinear resize of
 the rendered maps, with autograd support.
 All work happens in hand-written HIP kernels reached through `_capi`; there is no CPU fallback."""
+import math
+from typing import NamedTuple
+
 import torch
 
 from . import _capi
@@ -176,161 +179,149 @@ class _Resize2dFn(torch.autograd.Function):
 # ===========================================================================
 # 3x3x3 convolutions of the 3-D UNet
 # ===========================================================================
-def _conv_desc(x, w) -> _capi.VampConvDesc:
+def _conv_desc(x_shape, w_shape) -> _capi.VampConvDesc:
     d = _capi.VampConvDesc()
-    d.B, d.cin, d.Z, d.Y, d.X = x.shape
-    d.cout = w.shape[0]
+    d.B, d.cin, d.Z, d.Y, d.X = x_shape
+    d.cout = w_shape[0]
     return d
+
+
+class _ConvKind(NamedTuple):
+    """A row per convolution: the public name, the entry points' stem (+ forward / backward_data / backward_weight),
+    the workspace's size function and tag, the library's shape rule, the stride, `half` (16-bit operands: a dtype
+    code goes to the entry points and the fp32 weight gradient is cast back to the weight's dtype), and whether a
+    wrong dtype or rank is refused before a host tensor."""
+    name: str
+    stem: str
+    workspace_bytes: str
+    tag: str
+    supported: str
+    stride: int
+    half: bool
+    dtype_first: bool = False
+
+
+_CONV_KINDS = {
+    "fp32": _ConvKind("conv3d_3x3x3", "vamp_conv3d_", "vamp_conv3d_workspace_bytes", "conv", "vamp_conv3d_supported",
+                      1, False),
+    "half": _ConvKind("conv3d_bf16", "vamp_conv3d_half_", "vamp_conv3d_bf16_workspace_bytes", "conv16",
+                      "vamp_conv3d_bf16_supported", 1, True),
+    "half_s2": _ConvKind("conv3d_bf16_stride2", "vamp_conv3d_half_s2_", "vamp_conv3d_half_s2_workspace_bytes",
+                         "conv16s2", "vamp_conv3d_half_s2_supported", 2, True, dtype_first=True),
+}
+
+
+def _conv3d_layer_ok(kind, x_shape, w_shape, on_device, stride, padding, has_bias) -> bool:
+    """nn.Conv3d(cin, cout, 3, the kind's stride, 1, bias=False) on a device tensor whose volume the kind's kernels
+    take (the library's answer, which needs no GPU).  Dtypes and autocast are the caller's."""
+    k = _CONV_KINDS[kind]
+    if not (on_device and not has_bias and tuple(stride) == (k.stride,) * 3 and tuple(padding) == (1, 1, 1)
+            and tuple(w_shape[2:]) == (3, 3, 3) and len(x_shape) == 5 and w_shape[1] == x_shape[1]):
+        return False
+    return bool(getattr(_capi.checked(), k.supported)(_conv_desc(x_shape, w_shape)))
+
+
+def conv3d_kind(x_shape, w_shape, x_dtype, w_dtype, on_device, stride, padding, has_bias, autocast=None, min_voxels=0,
+                stride2=True):
+    """Which convolution runs a layer, from plain values: "fp32", "half", "half_s2" or None (aten / MIOpen).
+    `autocast` is the dtype of the enabled CUDA autocast or None.  Under a 16-bit one the operands are cast to it,
+    whatever they are: the stride-1 kernels, else (`stride2`, the switch) the stride-2 ones; `min_voxels` does not
+    apply.  Under no autocast at all: fp32 tensors of at least `min_voxels` voxels per channel, stride 1."""
+    layer = (tuple(x_shape), tuple(w_shape), on_device, stride, padding, has_bias)
+    if autocast in HALF_DTYPES:
+        if _conv3d_layer_ok("half", *layer):
+            return "half"
+        return "half_s2" if stride2 and _conv3d_layer_ok("half_s2", *layer) else None
+    if (autocast is None and x_dtype == w_dtype == torch.float32 and _conv3d_layer_ok("fp32", *layer)
+            and math.prod(x_shape[2:]) >= min_voxels):
+        return "fp32"
+    return None
+
+
+def cuda_autocast():
+    """The dtype of the enabled CUDA autocast (the reference trains with Lightning's `precision=16`), else None."""
+    return torch.get_autocast_dtype("cuda") if torch.is_autocast_enabled() else None
+
+
+def conv3d_supported(x, weight, stride, padding, bias):
+    return conv3d_kind(x.shape, weight.shape, x.dtype, weight.dtype, x.is_cuda, stride, padding, bias is not None,
+                       autocast=cuda_autocast()) == "fp32"
+
+
+def _half_supported(kind, x, weight, stride, padding, bias):
+    return x.dtype in HALF_DTYPES and _conv3d_layer_ok(kind, x.shape, weight.shape, x.is_cuda, stride, padding,
+                                                       bias is not None)
+
+
+def conv3d_bf16_supported(x, weight, stride, padding, bias):
+    return _half_supported("half", x, weight, stride, padding, bias)
+
+
+def conv3d_bf16_stride2_supported(x, weight, stride, padding, bias):
+    return _half_supported("half_s2", x, weight, stride, padding, bias)
 
 
 def conv3d_3x3x3(x, weight):
     """nn.Conv3d(cin, cout, 3, 1, 1, bias=False) (bv2:20, 40-60) on the fp32 matrix cores:
     x [B,cin,Z,Y,X], weight [cout,cin,3,3,3], cin / cout in {16, 32}; fp32 device tensors."""
-    return _Conv3dFn.apply(x, weight)
+    return _Conv3dFn.apply("fp32", x, weight)
 
 
 def conv3d_bf16(x, weight):
     """The same layer in bf16 (what the reference's `precision=16` training hands it): x bf16 [B,cin,Z,Y,X],
     weight bf16 [cout,cin,3,3,3] -> bf16 [B,cout,Z,Y,X]; fp32 accumulation on the bf16 matrix cores."""
-    return _Conv3dBf16Fn.apply(x, weight)
-
-
-def conv3d_bf16_supported(x, weight, stride, padding, bias):
-    if not (x.is_cuda and x.dtype in HALF_DTYPES and bias is None and tuple(stride) == (1, 1, 1)
-            and tuple(padding) == (1, 1, 1) and tuple(weight.shape[2:]) == (3, 3, 3) and x.dim() == 5
-            and weight.shape[1] == x.shape[1]):
-        return False
-    return bool(_capi.checked().vamp_conv3d_bf16_supported(_conv_desc(x, weight)))
-
-
-class _Conv3dBf16Fn(torch.autograd.Function):
-    @staticmethod
-    def forward(ctx, x, w):
-        if not (x.is_cuda and w.is_cuda):
-            raise _capi.VampireHipError("x / weight must be device tensors (no CPU fallback)")
-        if x.dtype not in HALF_DTYPES or w.dtype != x.dtype or x.dim() != 5 or w.dim() != 5:
-            raise TypeError("conv3d_bf16 takes bf16 (or fp16) [B,cin,Z,Y,X] and [cout,cin,3,3,3] tensors of one dtype")
-        code = DTYPE_CODES[x.dtype]
-        vamp = _capi.checked()
-        x, w = _aligned(x), _aligned(w)
-        d = _conv_desc(x, w)
-        if w.shape[1] != d.cin:
-            raise ValueError("weight / input channel mismatch")
-        out = torch.empty((d.B, d.cout, d.Z, d.Y, d.X), dtype=x.dtype, device=x.device)
-        vamp.vamp_conv3d_half_forward(d, code, x, w, out, _stream())
-        ctx.vamp, ctx.desc, ctx.code = vamp, d, code
-        ctx.save_for_backward(x, w)
-        return out
-
-    @staticmethod
-    def backward(ctx, g):
-        x, w = ctx.saved_tensors
-        vamp, d = ctx.vamp, ctx.desc
-        g = _aligned(g.to(x.dtype))
-        gx = gw = None
-        if ctx.needs_input_grad[0]:
-            gx = torch.empty_like(x)
-            vamp.vamp_conv3d_half_backward_data(d, ctx.code, g, w, gx, _stream())
-        if ctx.needs_input_grad[1]:
-            gw32 = torch.empty(w.shape, dtype=torch.float32, device=w.device)
-            nbytes = vamp.vamp_conv3d_bf16_workspace_bytes(d)
-            ws = _workspace((g.device, torch.cuda.current_stream().cuda_stream, "conv16", nbytes), g.device, nbytes)
-            vamp.vamp_conv3d_half_backward_weight(d, ctx.code, x, g, gw32, ws, ws.numel(), _stream())
-            gw = gw32.to(w.dtype)                 # the gradient of the 16-bit copy autocast made of the fp32 parameter
-        return gx, gw
+    return _Conv3dFn.apply("half", x, weight)
 
 
 def conv3d_bf16_stride2(x, weight):
     """nn.Conv3d(cin, cout, 3, stride=2, padding=1, bias=False) (Hourglass3D.conv1 / conv3, bv2:34-46) in bf16 or
     fp16: x [B,cin,Z,Y,X], weight [cout,cin,3,3,3] of the same 16-bit dtype -> [B,cout,(Z-1)//2+1,(Y-1)//2+1,X//2];
     fp32 accumulation on the 16-bit matrix cores."""
-    return _Conv3dBf16S2Fn.apply(x, weight)
-
-
-def conv3d_bf16_stride2_supported(x, weight, stride, padding, bias):
-    if not (x.is_cuda and x.dtype in HALF_DTYPES and bias is None and tuple(stride) == (2, 2, 2)
-            and tuple(padding) == (1, 1, 1) and tuple(weight.shape[2:]) == (3, 3, 3) and x.dim() == 5
-            and weight.shape[1] == x.shape[1]):
-        return False
-    return bool(_capi.checked().vamp_conv3d_half_s2_supported(_conv_desc(x, weight)))
-
-
-class _Conv3dBf16S2Fn(torch.autograd.Function):
-    @staticmethod
-    def forward(ctx, x, w):
-        if x.dtype not in HALF_DTYPES or w.dtype != x.dtype or x.dim() != 5 or w.dim() != 5:
-            raise TypeError("conv3d_bf16_stride2 takes bf16 (or fp16) [B,cin,Z,Y,X] and [cout,cin,3,3,3] tensors of one dtype")
-        if not (x.is_cuda and w.is_cuda):
-            raise _capi.VampireHipError("x / weight must be device tensors (no CPU fallback)")
-        code = DTYPE_CODES[x.dtype]
-        vamp = _capi.checked()
-        x, w = _aligned(x), _aligned(w)
-        d = _conv_desc(x, w)                      # the descriptor holds the input volume
-        if w.shape[1] != d.cin:
-            raise ValueError("weight / input channel mismatch")
-        out = torch.empty((d.B, d.cout, (d.Z - 1) // 2 + 1, (d.Y - 1) // 2 + 1, (d.X - 1) // 2 + 1), dtype=x.dtype,
-                          device=x.device)
-        vamp.vamp_conv3d_half_s2_forward(d, code, x, w, out, _stream())
-        ctx.vamp, ctx.desc, ctx.code = vamp, d, code
-        ctx.save_for_backward(x, w)
-        return out
-
-    @staticmethod
-    def backward(ctx, g):
-        x, w = ctx.saved_tensors
-        vamp, d = ctx.vamp, ctx.desc
-        g = _aligned(g.to(x.dtype))
-        gx = gw = None
-        if ctx.needs_input_grad[0]:
-            gx = torch.empty_like(x)
-            vamp.vamp_conv3d_half_s2_backward_data(d, ctx.code, g, w, gx, _stream())
-        if ctx.needs_input_grad[1]:
-            gw32 = torch.empty(w.shape, dtype=torch.float32, device=w.device)
-            nbytes = vamp.vamp_conv3d_half_s2_workspace_bytes(d)
-            ws = _workspace((g.device, torch.cuda.current_stream().cuda_stream, "conv16s2", nbytes), g.device, nbytes)
-            vamp.vamp_conv3d_half_s2_backward_weight(d, ctx.code, x, g, gw32, ws, ws.numel(), _stream())
-            gw = gw32.to(w.dtype)                 # the gradient of the 16-bit copy autocast made of the fp32 parameter
-        return gx, gw
-
-
-def conv3d_supported(x, weight, stride, padding, bias):
-    if not (x.is_cuda and x.dtype == torch.float32 and weight.dtype == torch.float32 and bias is None
-            and tuple(stride) == (1, 1, 1) and tuple(padding) == (1, 1, 1) and tuple(weight.shape[2:]) == (3, 3, 3)
-            and x.dim() == 5 and weight.shape[1] == x.shape[1] and not torch.is_autocast_enabled()):
-        return False
-    return bool(_capi.checked().vamp_conv3d_supported(_conv_desc(x, weight)))
+    return _Conv3dFn.apply("half_s2", x, weight)
 
 
 class _Conv3dFn(torch.autograd.Function):
+    """The three convolutions, told apart by their row of `_CONV_KINDS`."""
+
     @staticmethod
-    def forward(ctx, x, w):
-        if not (x.is_cuda and w.is_cuda):
+    def forward(ctx, kind, x, w):
+        k = _CONV_KINDS[kind]
+        on_host = not (x.is_cuda and w.is_cuda)
+        if on_host and not k.dtype_first:
             raise _capi.VampireHipError("x / weight must be device tensors (no CPU fallback)")
-        if x.dtype != torch.float32 or w.dtype != torch.float32 or x.dim() != 5 or w.dim() != 5:
-            raise TypeError("conv3d_3x3x3 takes fp32 [B,cin,Z,Y,X] and [cout,cin,3,3,3] tensors")
+        if (x.dtype not in (HALF_DTYPES if k.half else (torch.float32,)) or w.dtype != x.dtype or x.dim() != 5
+                or w.dim() != 5):
+            raise TypeError(f"{k.name} takes {'bf16 (or fp16)' if k.half else 'fp32'} [B,cin,Z,Y,X] and "
+                            f"[cout,cin,3,3,3] tensors{' of one dtype' if k.half else ''}")
+        if on_host:
+            raise _capi.VampireHipError("x / weight must be device tensors (no CPU fallback)")
         vamp = _capi.checked()
         x, w = _aligned(x), _aligned(w)
-        d = _conv_desc(x, w)
+        d = _conv_desc(x.shape, w.shape)          # the descriptor holds the input volume
         if w.shape[1] != d.cin:
             raise ValueError("weight / input channel mismatch")
-        out = torch.empty((d.B, d.cout, d.Z, d.Y, d.X), dtype=torch.float32, device=x.device)
-        vamp.vamp_conv3d_forward(d, x, w, out, _stream())
-        ctx.vamp, ctx.desc = vamp, d
+        out = torch.empty((d.B, d.cout) + tuple((n - 1) // k.stride + 1 for n in (d.Z, d.Y, d.X)), dtype=x.dtype,
+                          device=x.device)
+        ctx.code = (DTYPE_CODES[x.dtype],) if k.half else ()
+        getattr(vamp, k.stem + "forward")(d, *ctx.code, x, w, out, _stream())
+        ctx.vamp, ctx.desc, ctx.kind = vamp, d, k
         ctx.save_for_backward(x, w)
         return out
 
     @staticmethod
     def backward(ctx, g):
         x, w = ctx.saved_tensors
-        vamp, d = ctx.vamp, ctx.desc
-        g = _aligned(g.float())
+        vamp, d, k = ctx.vamp, ctx.desc, ctx.kind
+        g = _aligned(g.to(x.dtype))
         gx = gw = None
-        if ctx.needs_input_grad[0]:
-            gx = torch.empty_like(x)
-            vamp.vamp_conv3d_backward_data(d, g, w, gx, _stream())
         if ctx.needs_input_grad[1]:
-            gw = torch.empty_like(w)
-            nbytes = vamp.vamp_conv3d_workspace_bytes(d)
-            ws = _workspace((g.device, torch.cuda.current_stream().cuda_stream, "conv", nbytes), g.device, nbytes)
-            vamp.vamp_conv3d_backward_weight(d, x, g, gw, ws, ws.numel(), _stream())
-        return gx, gw
+            gx = torch.empty_like(x)
+            getattr(vamp, k.stem + "backward_data")(d, *ctx.code, g, w, gx, _stream())
+        if ctx.needs_input_grad[2]:
+            gw = torch.empty(w.shape, dtype=torch.float32, device=w.device)
+            nbytes = getattr(vamp, k.workspace_bytes)(d)
+            ws = _workspace((g.device, torch.cuda.current_stream().cuda_stream, k.tag, nbytes), g.device, nbytes)
+            getattr(vamp, k.stem + "backward_weight")(d, *ctx.code, x, g, gw, ws, ws.numel(), _stream())
+            if k.half:
+                gw = gw.to(w.dtype)               # the gradient of the 16-bit copy autocast made of the fp32 parameter
+        return None, gx, gw
