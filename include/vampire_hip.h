@@ -32,8 +32,8 @@ extern "C" {
                                  10: the BEV backward's plan; 11: detection loss; 12: rgb loss; 13: segmentation loss;
                                  14: masked regression losses; 15: the camera render's plans and workspace layout;
                                  16: the lift's plans and workspace layout;
-                                 16 also: stride-2 16-bit convolutions and the 2-D bilinear resize of the rendered maps; the number
-                                 could not move: a test pins it) */
+                                 16 also: stride-2 16-bit convolutions, the 2-D bilinear resize of the rendered maps and the
+                                 parameter update; the number could not move: a test pins it) */
 
 enum {
   VAMP_OK = 0,
@@ -1395,6 +1395,76 @@ int vamp_reg_loss_forward(const VampRegLossDesc* d, const void* const* pred_host
 int vamp_reg_loss_backward(const VampRegLossDesc* d, const void* const* pred_host, const float* const* target_host,
                            const uint8_t* const* mask_host, const int64_t* counts, const float* grad_losses,
                            void* const* grad_pred_host, void* stream);
+
+/* --------------------------------------------------------------------------
+ * The parameter update that ends a training step (base_cli.py:61-90 Trainer(gradient_clip_val=35, precision=16);
+ * base_exp.py:931-943 AdamW(lr, weight_decay=1e-7); callbacks/ema.py:23-117 ModelEMA / EMACallback): unscale and clip
+ * the gradients by their global norm, AdamW, the averaged (EMA) weights of every floating-point state entry and the
+ * dynamic loss scale, for any number of tensors in three launches.
+ *
+ *  table      device array of n_param_chunks + n_buffer_chunks VampUpdateChunk, built once by the host: every tensor
+ *             cut into chunks of at most VAMP_UPDATE_CHUNK elements, a chunk never crossing a tensor; the chunks of
+ *             the parameters first, those of the buffers (EMA only) behind them.  `param` and `grad` point at the
+ *             chunk's first element (fp32, contiguous, any element alignment: 16-byte accesses are used where both are
+ *             aligned for them, the results do not depend on it); state_off is the chunk's element offset in the flat
+ *             state arrays, a multiple of 4; kind VAMP_UPDATE_PARAM, or VAMP_UPDATE_EMA_ONLY for a buffer and for a
+ *             parameter that has no gradient in this step (grad NULL).
+ *  state      exp_avg, exp_avg_sq (covering the parameters' state offsets) and ema (covering all), flat fp32 arrays,
+ *             16-byte aligned, in which every tensor starts at a multiple of 4 elements and is padded to one.
+ *  scalars    one VampUpdateScalars in device memory.  The caller initialises lr, step (t), updates (n), scale (S, 1
+ *             without loss scaling) and growth; the call advances the counters and fills in the rest, so a replayed
+ *             graph keeps counting.  t advances unless found_inf; n always advances.
+ *  norm       total_norm = sqrt(sum g g) / S over the parameters with a gradient, the sum in float64 in a fixed
+ *             order; found_inf = the sum is not finite (exactly: some gradient element is inf or NaN).
+ *  clip       clip_coef = min(1, max_norm / (total_norm + 1e-6)), 1 when max_norm <= 0; mult = clip_coef / S.
+ *  element    in fp32, each operation rounded by itself: g' = g mult; p = p (1 - lr wd); m = m + (g' - m)(1 - beta1);
+ *             v = v beta2 + ((1 - beta2) g') g'; p = p - (lr / bc1)(m / (sqrt(v) / sqrt(bc2) + eps));
+ *             e = e d + (1 - d) p with d = ema_decay (1 - exp(-n / 2000)).  The scalars are formed in float64 and
+ *             rounded to fp32 once.  With found_inf set p, m and v keep their bits and the EMA line runs on the
+ *             unchanged p.  A VAMP_UPDATE_EMA_ONLY chunk takes the EMA line only; with ema_decay <= 0 there is no
+ *             EMA, ema may be NULL and the buffer chunks are not visited.
+ *  scale      VAMP_UPDATE_SCALE_DYNAMIC: S x 0.5 on found_inf, x 2 after VAMP_UPDATE_GROWTH_INTERVAL steps without
+ *             one (torch.amp.GradScaler's rule); otherwise S is left as it is.
+ * The workspace (8-byte aligned, vamp_param_update_workspace_bytes: 8 bytes per parameter chunk) needs no
+ * initialisation.  No atomics, no host synchronisation, bitwise repeatable, capturable in a graph; grids depend on
+ * the chunk counts only.  A bad descriptor (no chunks, a beta outside [0, 1), ...), a NULL table, scalar block or
+ * required state array return VAMP_EINVAL (and a size of 0), a workspace that is too small VAMP_ENOSPC, all before
+ * any launch.  The library keeps no state between calls.
+ * -------------------------------------------------------------------------- */
+#define VAMP_UPDATE_CHUNK 4096    /* elements per workgroup */
+#define VAMP_UPDATE_GROWTH_INTERVAL 2000
+enum { VAMP_UPDATE_PARAM = 0, VAMP_UPDATE_EMA_ONLY = 1 };
+enum { VAMP_UPDATE_SCALE_NONE = 0, VAMP_UPDATE_SCALE_STATIC = 1, VAMP_UPDATE_SCALE_DYNAMIC = 2 };
+typedef struct VampUpdateChunk {
+  void* param;                    /* the chunk's first element of the parameter or buffer */
+  const void* grad;               /* the same element of the gradient; NULL for VAMP_UPDATE_EMA_ONLY */
+  int64_t state_off;              /* element offset in exp_avg / exp_avg_sq / ema, a multiple of 4 */
+  int32_t len;                    /* 1 .. VAMP_UPDATE_CHUNK */
+  int32_t kind;                   /* VAMP_UPDATE_PARAM | VAMP_UPDATE_EMA_ONLY */
+} VampUpdateChunk;
+typedef struct VampUpdateScalars {
+  double lr;                      /* in */
+  int64_t step;                   /* in, out: t, optimizer steps taken */
+  int64_t updates;                /* in, out: n, EMA updates made */
+  float scale;                    /* in, out: the loss scale S the gradients carry; afterwards the next one */
+  int32_t growth;                 /* in, out: steps since the scale last changed */
+  int32_t found_inf;              /* out */
+  float total_norm, clip_coef, mult;          /* out */
+  float decay_mul, step_size, bc2_sqrt;       /* out: 1 - lr wd, lr / (1 - beta1^t), sqrt(1 - beta2^t) */
+  float ema_d, ema_1md;                       /* out: d, 1 - d */
+  int32_t reserved[15];
+} VampUpdateScalars;
+typedef struct VampParamUpdateDesc {
+  double beta1, beta2, eps, weight_decay;
+  double max_norm;                /* <= 0: no clipping (the norm is still computed) */
+  double ema_decay;               /* <= 0: no EMA */
+  int32_t n_param_chunks, n_buffer_chunks;
+  int32_t scale_mode;             /* VAMP_UPDATE_SCALE_* */
+  int32_t reserved;               /* 0 */
+} VampParamUpdateDesc;
+size_t vamp_param_update_workspace_bytes(const VampParamUpdateDesc* d);
+int vamp_param_update_step(const VampParamUpdateDesc* d, const void* table, float* exp_avg, float* exp_avg_sq,
+                           float* ema, void* scalars, void* workspace, size_t workspace_bytes, void* stream);
 
 #ifdef __cplusplus
 }

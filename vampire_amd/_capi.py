@@ -26,6 +26,9 @@ VAMP_REG_SMOOTH_L1, VAMP_REG_MSE = 0, 1
 VAMP_REG_SET, VAMP_REG_CLEAR, VAMP_REG_BOTH = 0, 1, 2
 VAMP_RESIZE2D_MAX_SEGS, VAMP_RESIZE2D_PLANE_GROUP, VAMP_RESIZE2D_BAND_ROWS, VAMP_RESIZE2D_COL_CHUNK = 4, 8, 8, 256
 VAMP_RESIZE2D_STRIP_CHUNK, VAMP_RESIZE2D_STRIP_MAX, VAMP_RESIZE2D_MAX_RUN = 256, 1088, 16
+VAMP_UPDATE_CHUNK, VAMP_UPDATE_GROWTH_INTERVAL = 4096, 2000
+VAMP_UPDATE_PARAM, VAMP_UPDATE_EMA_ONLY = 0, 1
+VAMP_UPDATE_SCALE_NONE, VAMP_UPDATE_SCALE_STATIC, VAMP_UPDATE_SCALE_DYNAMIC = 0, 1, 2
 
 
 class VampLiftDesc(C.Structure):
@@ -135,6 +138,26 @@ class VampResize2dSeg(C.Structure):
 class VampResize2dDesc(C.Structure):
     _fields_ = [("ih", C.c_int32), ("iw", C.c_int32), ("oh", C.c_int32), ("ow", C.c_int32), ("nseg", C.c_int32),
                 ("reserved", C.c_int32), ("seg", VampResize2dSeg * VAMP_RESIZE2D_MAX_SEGS)]
+
+
+class VampUpdateChunk(C.Structure):
+    """One entry of the parameter update's chunk table (device memory; optim.py builds it as a numpy record array)."""
+    _fields_ = [("param", C.c_void_p), ("grad", C.c_void_p), ("state_off", C.c_int64), ("len", C.c_int32),
+                ("kind", C.c_int32)]
+
+
+class VampUpdateScalars(C.Structure):
+    """The parameter update's scalar block (device memory, 128 bytes)."""
+    _fields_ = [("lr", C.c_double), ("step", C.c_int64), ("updates", C.c_int64), ("scale", C.c_float),
+                ("growth", C.c_int32), ("found_inf", C.c_int32), ("total_norm", C.c_float), ("clip_coef", C.c_float),
+                ("mult", C.c_float), ("decay_mul", C.c_float), ("step_size", C.c_float), ("bc2_sqrt", C.c_float),
+                ("ema_d", C.c_float), ("ema_1md", C.c_float), ("reserved", C.c_int32 * 15)]
+
+
+class VampParamUpdateDesc(C.Structure):
+    _fields_ = [("beta1", C.c_double), ("beta2", C.c_double), ("eps", C.c_double), ("weight_decay", C.c_double),
+                ("max_norm", C.c_double), ("ema_decay", C.c_double), ("n_param_chunks", C.c_int32),
+                ("n_buffer_chunks", C.c_int32), ("scale_mode", C.c_int32), ("reserved", C.c_int32)]
 
 
 class VampBevBackwardPlan(C.Structure):
@@ -284,6 +307,7 @@ _GD = C.POINTER(VampRgbLossDesc)
 _SLD = C.POINTER(VampSegLossDesc)
 _RLD = C.POINTER(VampRegLossDesc)
 _R2D = C.POINTER(VampResize2dDesc)
+_PUD = C.POINTER(VampParamUpdateDesc)
 
 # name -> (return kind, argtypes); must list every symbol declared in include/vampire_hip.h
 SIGNATURES = {
@@ -406,6 +430,8 @@ SIGNATURES = {
     "vamp_reg_loss_workspace_bytes": (_SIZE, [_RLD]),
     "vamp_reg_loss_forward": (_STATUS, [_RLD] + [_P] * 5 + [_P, C.c_size_t, _P]),
     "vamp_reg_loss_backward": (_STATUS, [_RLD] + [_P] * 6 + [_P]),
+    "vamp_param_update_workspace_bytes": (_SIZE, [_PUD]),
+    "vamp_param_update_step": (_STATUS, [_PUD] + [_P] * 5 + [_P, C.c_size_t, _P]),
 }
 
 _lib = None
