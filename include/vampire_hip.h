@@ -119,7 +119,10 @@ int vamp_lift_forward(const VampLiftDesc* d, const float* mats, const float* xs,
 /* with EMIT_PAIRS: the caller asserts that the cell counters in `workspace` are zero -- as a zero-filled
    buffer has them, and as every completed vamp_lift_forward_ex(EMIT_PAIRS) / vamp_lift_prepare /
    vamp_lift_backward on this workspace leaves them (the scan zeroes what it has read, the backward's gather
-   the cursors of the fill) -- so the zero fill in front of the kernel is skipped */
+   the cursors of the fill) -- so the zero fill in front of the kernel is skipped.  The promise is about the counter
+   region of THIS descriptor in THIS buffer (region VAMP_LIFTWS_CNT of vamp_lift_workspace_layout): the region's
+   offset moves with B, N, C, fH and fW, so a call of another descriptor on the same buffer leaves other bytes zero,
+   and its own regions may lie over this one */
 #define VAMP_LIFTFWD_CELLS_CLEAN 2
 /* (ABI 6) `feat` is handed over CHANNEL-LAST, [B, N, fH, fW, C] fp32 (in_dtype VAMP_F32; 16-byte aligned) -- the
    memory of a torch.channels_last [B*N, C, fH, fW] tensor, what the producing convolution (channel_lower,
@@ -463,7 +466,7 @@ int vamp_render_camera_prepare(const VampRenderDesc* d, const float* mats, const
    `workspace` keeps (the backward must then be given VAMP_CAMBWD_TERM_VALID too) */
 #define VAMP_CAMPREP_TERM_VALID 1
 #define VAMP_CAMPREP_RANKED 8   /* (ABI 6) the ranks have been drawn by vamp_render_forward_merged(VAMP_RENDERFWD_RANK): only the cell scan runs (mats .. ds may be NULL; the backward's work lists are built inside the per-ray pass's launch) */
-#define VAMP_CAMPREP_COUNTERS_CLEAN 4   /* the caller asserts that the cell counters in `workspace` are zero (a zero-filled buffer, or one a completed prepare pass has run on: its scan zeroes what it reads): no zero fill */
+#define VAMP_CAMPREP_COUNTERS_CLEAN 4   /* the caller asserts that the cell counters in `workspace` are zero (a zero-filled buffer, or one a completed prepare pass has run on: its scan zeroes what it reads): no zero fill.  The promise is about the counter region of THIS descriptor in THIS buffer (vamp_render_workspace_layout): its offset moves with the descriptor, so a completed pass of another descriptor on the same buffer does not make it true */
 /* (2: VAMP_CAMPREP_RANK_ONLY of rounds 2-4, the prepare pass in two phases: measured slower twice, removed in round 5) */
 int vamp_render_camera_prepare_ex(const VampRenderDesc* d, const float* mats, const float* us,
                                   const float* vs, const float* ds, void* workspace,
@@ -653,7 +656,8 @@ int vamp_render_bev_forward_ex(const VampRenderDesc* d, const float* oxs, const 
    stream ordered behind this call); afterwards `workspace` holds what vamp_render_camera_prepare_ex
    (VAMP_CAMPREP_TERM_VALID) leaves, and the backward takes VAMP_CAMBWD_CELLS_VALID.  The three launches on two streams
    of a training forward (camera kernel, BEV forward, prepare pass beside it) become one launch + one small one.
-   COUNTERS_CLEAN: as VAMP_CAMPREP_COUNTERS_CLEAN (otherwise the counters are zero-filled first). */
+   COUNTERS_CLEAN: as VAMP_CAMPREP_COUNTERS_CLEAN, a promise about the counter region of this descriptor in this
+   buffer (otherwise the counters are zero-filled first). */
 #define VAMP_RENDERFWD_RANK 4
 #define VAMP_RENDERFWD_COUNTERS_CLEAN 8
 int vamp_render_forward_merged_supported(const VampRenderDesc* d, const float* ozs_host);

@@ -1787,12 +1787,12 @@ def test_debug_checks_catch_broken_promises(dev):
         hp._ws["lift"].fill_(1)
         with pytest.raises(_capi.VampireHipError, match="promise broken.*CELLS_CLEAN"):
             train_step(model, data)
-        hp._ws["lift"].zero_(); hp._dirty.discard("lift")
+        hp._ws["lift"].zero_(); hp._counters.fresh("lift", hp._ws["lift"].data_ptr())
         # counters not zero under VAMP_CAMPREP_COUNTERS_CLEAN (the forward's prepare pass)
-        hp._ws["render"].fill_(1); hp._dirty.discard("render")
+        hp._ws["render"].fill_(1); hp._counters.fresh("render", hp._ws["render"].data_ptr())
         with pytest.raises(_capi.VampireHipError, match="promise broken"):
             train_step(model, data)
-        hp._ws["render"].zero_(); hp._dirty.discard("render")
+        hp._ws["render"].zero_(); hp._counters.fresh("render", hp._ws["render"].data_ptr())
         # a termination table that is not one, handed to the planned march with VAMP_CAMFWD_TERM_VALID
         hp.impl["cam_direct"] = False
         d = hp.render_desc(2, cfg.num_cams, _capi.VAMP_F32)

@@ -224,7 +224,7 @@ int vamp_render_forward_merged(const VampRenderDesc* d, const float* mats, const
     VAMP_REQUIRE(term != nullptr, "VAMP_RENDERFWD_RANK needs the render workspace");
     rank = cam_rank_refs(d, cw);
     if (flags & VAMP_RENDERFWD_COUNTERS_CLEAN) {
-      if (int e = debug_expect_range(rank.cnt, 64, 0, 0, s, "VAMP_RENDERFWD_COUNTERS_CLEAN: the render workspace's cell counters are zero")) return e;
+      if (int e = debug_expect_range(cw.cnt, (size_t) (cw.ncell + kScanPad), 0, 0, s,"VAMP_RENDERFWD_COUNTERS_CLEAN: the render workspace's cell counters are zero")) return e;
     } else if (int e = launch_cam_counters_zero(cw, s)) {
       return e;
     }

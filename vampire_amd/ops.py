@@ -81,6 +81,52 @@ def render_desc(cfg: PathConfig, B, N, dtype_code, C_=None) -> _capi.VampRenderD
     return d
 
 
+class CounterState:
+    """Which cell counters of the lift and render workspaces are known to be zero; host only, no device needed.
+
+    The counters (`cnt`) lie behind regions whose sizes follow the descriptor (lift_common.hpp, render_common.hpp), so
+    "known zero" is a fact about (workspace key, buffer address, the (offset, bytes) of `cnt` for one descriptor), never
+    about the key alone: a call of another descriptor on the same buffer zeroes other bytes, and its own regions may lie
+    over these.  Per key the state is one (address, range) pair, range None standing for every range of a buffer that
+    has been zero-filled and not used since; no entry = nothing known.  A *_CLEAN promise is sent only on `begin`
+    returning True; without it the library zero-fills."""
+
+    def __init__(self):
+        self._zero = {}
+
+    def fresh(self, key, addr):
+        """A new zero-filled buffer: every range is clean until the first call on it."""
+        self._zero[key] = (addr, None)
+
+    def use(self, key, addr, rng):
+        """A call of the layout whose counters are `rng` is about to work on the buffer.  No region of a layout
+        overlaps that layout's own counters (but for the v1 camera splat's gradient copy: its backward calls `spoil`),
+        so they stay what they were; what was known of any other range is void."""
+        z = self._zero.get(key)
+        if z is not None and z[0] == addr and z[1] in (None, rng):
+            self._zero[key] = (addr, rng)
+        else:
+            self._zero.pop(key, None)
+
+    def begin(self, key, addr, rng):
+        """A pass that counts into `rng` starts: True if the range is known zero.  From here the counters are in
+        flight -- not clean -- until `done`; a call that raises in between leaves them so."""
+        z = self._zero.pop(key, None)
+        return z is not None and z[0] == addr and z[1] in (None, rng)
+
+    def done(self, key, addr, rng):
+        """The pass over `rng` has been issued in full (its scan zeroes what it reads): clean for this range and for
+        no other.  (A pass that ends on a buffer the key no longer names -- a larger one has replaced it since -- says
+        nothing about the new one.)"""
+        z = self._zero.get(key)
+        if z is None or z[0] == addr:
+            self._zero[key] = (addr, rng)
+
+    def spoil(self, key):
+        """Something may have left any counters of the buffer non-zero."""
+        self._zero.pop(key, None)
+
+
 class HotPath:
     """Device constants + operators for one PathConfig on one device."""
 
@@ -114,7 +160,8 @@ class HotPath:
         self._cam_sel = {"mode": "direct", "calls": 0,
                          "dev": torch.full((1,), -1.0, dtype=f32, device=dev),
                          "host": torch.full((1,), -1.0, dtype=f32).pin_memory() if dev.type == "cuda" else torch.full((1,), -1.0)}
-        self._dirty = set()         # workspaces whose cell counters a call in flight (or one that raised) may have left non-zero
+        self._counters = CounterState()     # which cell counters of the "lift" / "render" workspaces are known zero
+        self._cnt_ranges = {}               # (key, descriptor bytes) -> (offset, bytes) of that layout's counters
         # Implementation selectors (host-side state of this object; the library itself keeps none):
         # "cell" = the default cell-list gathers, "v1" = the float-atomic splats kept as independent
         # cross-checks for the tests; lift_wpp forces the lift gather's waves per pixel (0 = auto).
@@ -203,13 +250,29 @@ class HotPath:
         if cur != st:
             cur.wait_stream(st)
         self.vamp.vamp_lift_finish_cells(d, ws, ws.numel(), _stream(cur))
-        self._dirty.discard("lift")         # scanned: the counters are back at zero
+        self._counters.done("lift", ws.data_ptr(), self._cnt_range("lift", d))      # scanned: back at zero
 
-    def _cam_clean_flag(self):
-        """VAMP_CAMPREP_COUNTERS_CLEAN when the render workspace's cell counters are known to be zero (fresh
-        zero-filled buffer, or the last prepare pass on it was issued in full); marks them in flight."""
-        clean = "render" not in self._dirty
-        self._dirty.add("render")
+    def _cnt_range(self, key, d):
+        """(offset, bytes) of the cell counters in the "lift" / "render" workspace of descriptor `d`, from the library's
+        own layout; asked once per descriptor."""
+        k = (key, bytes(d))
+        r = self._cnt_ranges.get(k)
+        if r is None:
+            ask = _capi.checked()           # (a host-only query: not through a test's call recorder)
+            if key == "lift":
+                lay, i = _capi.VampLiftWorkspaceLayout(), _capi.LIFTWS_REGIONS.index("cnt")
+                ask.vamp_lift_workspace_layout(d, lay)
+            else:
+                lay, i = _capi.VampRenderWorkspaceLayout(), _capi.RENDERWS_REGIONS.index("cnt")
+                ask.vamp_render_workspace_layout(d, lay)
+            r = self._cnt_ranges[k] = (int(lay.offset[i]), int(lay.bytes[i]))
+        return r
+
+    def _cam_clean_flag(self, d, ws):
+        """VAMP_CAMPREP_COUNTERS_CLEAN when the cell counters of descriptor `d` in the render workspace `ws` are known
+        to be zero (fresh zero-filled buffer, or the last pass on it was one of this layout and was issued in full);
+        marks them in flight."""
+        clean = self._counters.begin("render", ws.data_ptr(), self._cnt_range("render", d))
         return _capi.VAMP_CAMPREP_COUNTERS_CLEAN if clean else 0
 
     # ------------------------------------------------- which camera forward (bv2:191-194: both density modes are first class)
@@ -287,11 +350,11 @@ class HotPath:
     def _workspace(self, key, nbytes):
         t = self._ws.get(key)
         if t is None or t.numel() < nbytes:
-            # zero-filled once: the cell counters inside start clean, and every completed pass leaves them
-            # clean again (VAMP_LIFTFWD_CELLS_CLEAN / VAMP_CAMPREP_COUNTERS_CLEAN), so no step zeroes them
+            # zero-filled once: the cell counters inside start clean, and every completed pass leaves its own layout's
+            # clean again (VAMP_LIFTFWD_CELLS_CLEAN / VAMP_CAMPREP_COUNTERS_CLEAN), so no steady-state step zeroes them
             t = torch.zeros(max(nbytes, 256), dtype=torch.uint8, device=self.device)
             self._ws[key] = t
-            self._dirty.discard(key)
+            self._counters.fresh(key, t.data_ptr())
         return t
 
     def _render_workspace(self, d, rows=False):
@@ -299,11 +362,15 @@ class HotPath:
         nbytes = self.vamp.vamp_render_workspace_bytes(d)
         if rows:
             nbytes += self.vamp.vamp_render_samples_bytes(d)
-        return self._workspace("render", nbytes)
+        ws = self._workspace("render", nbytes)
+        self._counters.use("render", ws.data_ptr(), self._cnt_range("render", d))
+        return ws
 
     def _lift_workspace(self, d):
         """The lift workspace of a call on descriptor `d`."""
-        return self._workspace("lift", self.vamp.vamp_lift_workspace_bytes(d))
+        ws = self._workspace("lift", self.vamp.vamp_lift_workspace_bytes(d))
+        self._counters.use("lift", ws.data_ptr(), self._cnt_range("lift", d))
+        return ws
 
     def _term_table(self, d, ws):
         """The termination table inside the render workspace `ws`: a flat int32 view, one entry per ray."""
@@ -534,9 +601,9 @@ class _LiftFn(torch.autograd.Function):
             hp._finish_lift_scan()          # (an earlier forward's deferred scan: its counters must be spent first)
             if hp.impl["defer_lift_scan"]:
                 flags |= _capi.VAMP_LIFTFWD_DEFER_SCAN
-            if "lift" not in hp._dirty:
+            if hp._counters.begin("lift", ws.data_ptr(), hp._cnt_range("lift", d)):
                 flags |= _capi.VAMP_LIFTFWD_CELLS_CLEAN
-            hp._dirty.add("lift")           # (until this call has been issued in full)
+            # (the counters are in flight until this call has been issued in full)
             ctx.cells_key = (hp._lift_gen, ws.data_ptr())
         if logits:
             hp.vamp.vamp_lift_forward_logits_ex(d, mats, hp.xs, hp.ys, hp.zs, lg, _dtype_code(lg), feat, depth, out,
@@ -546,8 +613,8 @@ class _LiftFn(torch.autograd.Function):
                                         ws.numel(), flags, _stream(cur))
         if flags & _capi.VAMP_LIFTFWD_DEFER_SCAN:
             hp._lift_scan_pending = (d, ws, cur)      # (the counters stay in flight until the scan)
-        else:
-            hp._dirty.discard("lift")       # emit + scan issued: the counters are back at zero
+        elif flags & _capi.VAMP_LIFTFWD_EMIT_PAIRS:
+            hp._counters.done("lift", ws.data_ptr(), hp._cnt_range("lift", d))      # emit + scan issued: back at zero
         if need_grad:
             ctx.hp, ctx.desc, ctx.use_depth = hp, d, use_depth
             ctx.save_for_backward(depth if use_depth else feat, feat, mats, hits)
@@ -578,11 +645,11 @@ class _LiftFn(torch.autograd.Function):
             flags |= _capi.VAMP_LIFTBWD_FEAT_CHANNEL_LAST
         flags |= {1: _capi.VAMP_LIFTBWD_WPP1, 4: _capi.VAMP_LIFTBWD_WPP4,
                   16: _capi.VAMP_LIFTBWD_WPP16}.get(hp.impl["lift_wpp"], 0)
-        hp._dirty.add("lift")
+        hp._counters.begin("lift", ws.data_ptr(), hp._cnt_range("lift", d))
         hp.vamp.vamp_lift_backward_ex(d, mats, hp.xs, hp.ys, hp.zs, depth if use_depth else None, feat, g, hits,
                                      gdepth, gfeat, ws, ws.numel(), flags, _stream())
         if hp.impl["lift_bwd"] == "cell":
-            hp._dirty.discard("lift")       # the gather has re-zeroed the fill's cursors
+            hp._counters.done("lift", ws.data_ptr(), hp._cnt_range("lift", d))     # the gather has re-zeroed the fill's cursors
         if ctx.logits and hp.impl["lift_bwd"] == "v1":
             # (the cross-check implementation returns the gradient of the distribution)
             gdepth = depth * (gdepth - (depth * gdepth).sum(2, keepdim=True))
@@ -834,7 +901,7 @@ class _RenderFn(torch.autograd.Function):
             elif op == "prep":
                 ranked = bool(flags & _capi.VAMP_CAMPREP_RANKED)       # (the forward drew the ranks: scan + work lists only)
                 pend = hp._lift_scan_pending
-                pflags = flags | (0 if ranked else hp._cam_clean_flag())
+                pflags = flags | (0 if ranked else hp._cam_clean_flag(d, ws))
                 if pend is not None and pend[2] == cur:
                     # a lift forward's pair cells are due too: both scans in one launch.  (The lift ran on `cur`; this
                     # op's stream is `cur` or the side stream, which has waited for `cur` above and which `cur` waits
@@ -843,11 +910,11 @@ class _RenderFn(torch.autograd.Function):
                     hp.vamp.vamp_render_camera_prepare_with_lift(
                         d, mats, hp.us, hp.vs, hp.ds, ws, ws.numel(), pflags, pend[0], pend[1], pend[1].numel(),
                         _stream(st))
-                    hp._dirty.discard("lift")
+                    hp._counters.done("lift", pend[1].data_ptr(), hp._cnt_range("lift", pend[0]))
                 else:
                     hp.vamp.vamp_render_camera_prepare_ex(d, mats, hp.us, hp.vs, hp.ds, ws, ws.numel(), pflags,
                                                          _stream(st))
-                hp._dirty.discard("render")
+                hp._counters.done("render", ws.data_ptr(), hp._cnt_range("render", d))
                 ctx.cells = True
             elif op == "render":
                 hp.vamp.vamp_render_forward_merged(
@@ -855,7 +922,7 @@ class _RenderFn(torch.autograd.Function):
                     dens, sem, rgb, base, rgb_p, seg_p, dep_p, bev_rgb, bev_seg, bev_h, vdens, vout, ws, ws.numel(),
                     ws_bev, ws_bev.numel() if bev_save else 0, ctx.gbeta0 if train else None,
                     (_capi.VAMP_RENDERFWD_SAVE_SAMPLES if save else 0) | (_capi.VAMP_RENDERFWD_BEV_SAVE if bev_save else 0)
-                    | flags | (_capi.VAMP_RENDERFWD_COUNTERS_CLEAN if (flags & _capi.VAMP_RENDERFWD_RANK) and hp._cam_clean_flag() else 0),
+                    | flags | (_capi.VAMP_RENDERFWD_COUNTERS_CLEAN if (flags & _capi.VAMP_RENDERFWD_RANK) and hp._cam_clean_flag(d, ws) else 0),
                     _stream(st))
                 # (with VAMP_RENDERFWD_RANK the counters stay "in flight" until the "prep" op behind has scanned them)
             else:
@@ -910,15 +977,22 @@ class _RenderFn(torch.autograd.Function):
         tab_key = (ws_bev.data_ptr(), d.B)
         cur, side = torch.cuda.current_stream(), hp._side_stream()
         cell_impl, bev_cell = hp.impl["cam_bwd"] != "v1", hp.impl["bev_bwd"] != "v1"
+        fresh = ctx.pack_key == (hp._pack_gen, ws.data_ptr())
         plan = render_backward_plan(
             two=side is not None, matrices=geom is None, cell_impl=cell_impl,
-            fresh=ctx.pack_key == (hp._pack_gen, ws.data_ptr()), cells=ctx.cells, samples=ctx.samples, ert=ctx.ert,
+            fresh=fresh, cells=ctx.cells, samples=ctx.samples, ert=ctx.ert,
             packed=ctx.packed, bev_cell=bev_cell, bev_saved=ctx.bev_key == (hp._bev_gen, ws_bev.data_ptr()),
             tab_valid=hp._bev_tab_key == tab_key)
+        cnt_rng = hp._cnt_range("render", d)
+        relists = cell_impl and geom is None and ctx.cells and not fresh
         if not cell_impl or geom is not None or not ctx.cells:
             # the v1 splat keeps a packed gradient copy where the cell lists live, and a backward that builds
             # its own cell lists may stop half way: either way the counters there are no longer known zero
-            hp._dirty.add("render")
+            hp._counters.spoil("render")
+        elif relists:
+            # the forward's cell lists are gone: this backward counts and scans again (zero-filling first), and the
+            # counters are in flight until its calls have been issued in full
+            hp._counters.begin("render", ws.data_ptr(), cnt_rng)
         hp._pack_gen += 1                                       # the backward scribbles after the copy only,
         ctx.pack_key = None                                     # but a second backward must not assume so
         streams, events = {"cur": cur, "side": side}, {}
@@ -945,6 +1019,8 @@ class _RenderFn(torch.autograd.Function):
                 events[r].record(st)
         if forked:
             cur.wait_stream(side)
+        if relists:
+            hp._counters.done("render", ws.data_ptr(), cnt_rng)
         grad_beta = gbeta.reshape(ctx.beta_shape) if hp.cfg.density_mode == "sdf" else None
         dt = ctx.in_dtypes
         return (None, gd.to(dt[0]), gs.to(dt[1]), gb.to(dt[2]), gr.to(dt[3]), grad_beta, None, None, None)
