@@ -37,6 +37,14 @@ def _accept(t):
     return t.float()
 
 
+def _accept_float(t, name):
+    """`_accept` for an operand that has to hold real numbers: an integer or bool tensor is a caller's mistake (labels,
+    indices or a mask in a volume's place), not something to promote."""
+    if t is not None and not t.is_floating_point():
+        raise TypeError(f"{name}: expected a floating-point tensor, got {t.dtype}")
+    return _accept(t)
+
+
 def _is_channel_last(feat: torch.Tensor) -> bool:
     """feat [B, N, C, fH, fW] whose memory is [B, N, fH, fW, C] (a torch.channels_last producer's output, reshaped):
     what the lift wants -- it samples a pixel's C features as one run -- and takes zero-copy."""
@@ -78,6 +86,23 @@ def _chk(t: torch.Tensor, shape, name):
     if tuple(t.shape) != tuple(shape):
         raise ValueError(f"{name}: expected shape {tuple(shape)}, got {tuple(t.shape)}")
     return t.contiguous()
+
+
+def _mats(t: torch.Tensor, B, N, name):
+    """Prepared camera matrices [B, N, 3, 4, 4] as the kernels read them: fp32, contiguous, and on a 16-byte boundary
+    (the lift's camera cull loads whole matrix rows and the library refuses anything else).  48 floats per camera: the
+    copy of a view that starts at an odd element costs nothing."""
+    return _aligned(_chk(t.float(), (B, N, 3, 4, 4), name))
+
+
+def _scalar(t: torch.Tensor, name):
+    """A one-element device parameter (the learnable beta) as the kernels read it: fp32 [1], whatever shape, dtype or
+    strides (an expanded tensor) the caller's has."""
+    if not t.is_cuda:
+        raise _capi.VampireHipError(f"{name} must be a device tensor (no CPU fallback)")
+    if t.numel() != 1:
+        raise ValueError(f"{name}: expected one element, got shape {tuple(t.shape)}")
+    return t.reshape(1).float().contiguous()
 
 
 _scratch = {}

@@ -20,7 +20,8 @@ import torch
 from . import _capi
 from .config import PathConfig
 from . import geometry as G
-from ._tensors import _accept, _chk, _density_code, _dtype_code, _is_channel_last, _stream
+from ._tensors import (_accept, _accept_float, _chk, _density_code, _dtype_code, _is_channel_last, _mats, _scalar,
+                       _stream)
 # the operators that take no HotPath live in modules of their own; their public names stay importable from here
 from .layers import (voxel_pooling, upsample_trilinear, conv3d_3x3x3, conv3d_bf16, conv3d_supported,  # noqa: F401
                      conv3d_bf16_supported, conv3d_bf16_stride2, conv3d_bf16_stride2_supported,
@@ -401,7 +402,7 @@ class HotPath:
         shp = (B, N, c.vZ, c.vY, c.vX)
         valid = torch.empty(shp, dtype=torch.uint8, device=self.device)
         ix0, iy0, iz0 = (torch.empty(shp, dtype=torch.int16, device=self.device) for _ in range(3))
-        mats = _chk(lift_mats.float(), (B, N, 3, 4, 4), "lift_mats")
+        mats = _mats(lift_mats, B, N, "lift_mats")
         self.vamp.vamp_lift_indices(d, mats, self.xs, self.ys, self.zs, valid, ix0, iy0, iz0, _stream())
         return valid, ix0, iy0, iz0
 
@@ -412,7 +413,7 @@ class HotPath:
         B, N = lift_mats.shape[:2]
         d = self.lift_desc(B, N, 4, _capi.VAMP_F32, use_depth)
         patch, grid = (C.c_int32 * 2)(), (C.c_int32 * 2)()
-        mats = _chk(lift_mats.float(), (B, N, 3, 4, 4), "lift_mats")
+        mats = _mats(lift_mats, B, N, "lift_mats")
         self.vamp.vamp_lift_cull_words(d, None, None, None, None, None, patch, grid, None)
         words = torch.empty(B, c.vZ, grid[1], grid[0], dtype=torch.int32, device=self.device)
         self.vamp.vamp_lift_cull_words(d, mats, self.xs, self.ys, self.zs, words, patch, grid, _stream())
@@ -475,10 +476,10 @@ class HotPath:
         pre-pass + the index kernel, a host sync."""
         c = self.cfg
         B, N = render_mats.shape[:2]
-        dens = _chk(_accept(density_feature), (B, 1, c.vZ, c.vY, c.vX), "density_feature")
+        dens = _chk(_accept_float(density_feature, "density_feature"), (B, 1, c.vZ, c.vY, c.vX), "density_feature")
         d = self.render_desc(B, N, _dtype_code(dens))
         mats = _chk(render_mats.float(), (B, N, 3, 4, 4), "render_mats")
-        beta = (torch.zeros(1, device=self.device) if beta is None else beta.detach().reshape(1).float().contiguous())
+        beta = torch.zeros(1, device=self.device) if beta is None else _scalar(beta.detach(), "beta")
         ws = self._render_workspace(d)
         with torch.cuda.device(self.device):
             self.vamp.vamp_render_camera_terminate(d, mats, self.us, self.vs, self.ds, beta, dens, ws, ws.numel(),
@@ -509,6 +510,20 @@ class HotPath:
         """bv2:596-604: (occ_logits [B,K,oz,oy,ox], occ_density [B,1,oz,oy,ox]) on the occ grid
         rotated by bda[:3,:3] (a tiny torch matmul; the two resamplings are HIP kernels)."""
         B = semantic_logits.shape[0]
+        if not occ_coords.is_cuda or not (bda_mat is None or bda_mat.is_cuda):
+            raise _capi.VampireHipError("occ_coords and bda_mat must be device tensors (no CPU fallback)")
+        if occ_coords.dim() != 4 or occ_coords.shape[-1] != 3:
+            raise ValueError(f"occ_coords: expected shape [n0, n1, n2, 3], got {tuple(occ_coords.shape)}")
+        if bda_mat is not None and (bda_mat.dim() != 3 or bda_mat.shape[0] != B or min(bda_mat.shape[1:]) < 3):
+            raise ValueError(f"bda_mat: expected shape ({B}, 4, 4), got {tuple(bda_mat.shape)}")
+        # (both volumes and beta before the first of the two resamplings is launched)
+        c = self.cfg
+        semantic_logits = _chk(_accept_float(semantic_logits, "semantic_logits"),
+                               (B, semantic_logits.shape[1], c.vZ, c.vY, c.vX), "semantic_logits")
+        density_feature = _chk(_accept_float(density_feature, "density_feature"), (B, 1, c.vZ, c.vY, c.vX),
+                               "density_feature")
+        if beta is not None:
+            _scalar(beta, "beta")
         # R @ c for every grid point as one [P,3] x [3,3] product per sample (the reference's
         # broadcast of 640k 3x3 matmuls, bv2:599, costs 8 ms on the GPU)
         if bda_mat is None:      # the static grid of BaseLSSImpaintor / BaseLSS / BaseBiLinear
@@ -554,14 +569,16 @@ class _LiftFn(torch.autograd.Function):
         B, N, C_ = feat.shape[:3]
         ctx.logits = logits
         ctx.in_dtypes = (depth.dtype if use_depth else None, feat.dtype)
-        feat = _accept(feat)
+        feat = _accept_float(feat, "feat")
         if logits:
             # `depth` holds the logits (their own dtype); the kernel writes the fp32 distribution
-            lg = _chk(_accept(depth), (B, N, c.D) + tuple(feat.shape[-2:]), "depth logits")
+            lg = _chk(_accept_float(depth, "depth logits"), (B, N, c.D) + tuple(feat.shape[-2:]), "depth logits")
             feat = feat.float()
             depth = torch.empty(lg.shape, dtype=torch.float32, device=lg.device)
         elif use_depth:
-            depth = _accept(depth)
+            # (checked like every other operand: the kernel reads B * N * D * fH * fW contiguous elements, and the
+            # tensor saved for the backward is this one)
+            depth = _chk(_accept_float(depth, "depth"), (B, N, c.D) + tuple(feat.shape[-2:]), "depth")
             if depth.dtype != feat.dtype:               # mixed inputs (e.g. fp32 softmax output + half features)
                 depth, feat = depth.float(), feat.float()
         code = _dtype_code(feat)
@@ -578,7 +595,7 @@ class _LiftFn(torch.autograd.Function):
                 raise ValueError(f"feat: expected shape {(B, N, C_) + fhw}, got {tuple(feat.shape)}")
         else:
             feat = _chk(feat, (B, N, C_) + fhw, "feat")
-        mats = _chk(mats.float(), (B, N, 3, 4, 4), "lift_mats")
+        mats = _mats(mats, B, N, "lift_mats")
         out = torch.empty(B, C_, c.vZ, c.vY, c.vX, dtype=torch.float32, device=feat.device)
         # (the caller's grad mode comes in as an argument: inside forward it is always off and
         # needs_input_grad ignores torch.no_grad(), under which the backward's hit words / prepare
@@ -666,7 +683,7 @@ class _LiftDenseFn(torch.autograd.Function):
         d = hp.lift_desc(B, N, C_, _capi.VAMP_F32, use_depth, fhw=tuple(ff.shape[-2:]))
         d.D = D
         ff = _chk(ff.float(), (B, N, C_, D) + tuple(ff.shape[-2:]), "frustum_feats")
-        mats = _chk(mats.float(), (B, N, 3, 4, 4), "lift_mats")
+        mats = _mats(mats, B, N, "lift_mats")
         out = torch.empty(B, C_, c.vZ, c.vY, c.vX, dtype=torch.float32, device=ff.device)
         nchunk = (C_ + 15) // 16
         hits = (torch.empty(B, c.vZ, c.vY, c.vX, nchunk, dtype=torch.int64, device=ff.device)
@@ -807,7 +824,8 @@ class _RenderFn(torch.autograd.Function):
         N = (geom if geom is not None else mats).shape[1]
         C_ = base.shape[1]
         ctx.in_dtypes = tuple(t.dtype for t in (dens, sem, base, rgb))
-        dens, sem, base, rgb = (_accept(t) for t in (dens, sem, base, rgb))
+        dens, sem, base, rgb = (_accept_float(t, nm) for t, nm in zip(
+            (dens, sem, base, rgb), ("density_feature", "semantic_logits", "voxel_features", "rgb")))
         if len({t.dtype for t in (dens, sem, base, rgb)}) > 1:
             dens, sem, base, rgb = (t.float() for t in (dens, sem, base, rgb))
         d = hp.render_desc(B, N, _dtype_code(dens), C_)
@@ -821,7 +839,7 @@ class _RenderFn(torch.autograd.Function):
         else:
             mats = _chk(mats.float(), (B, N, 3, 4, 4), "render_mats")
         ctx.beta_shape = beta.shape
-        beta = beta.reshape(1).float().contiguous()
+        beta = _scalar(beta, "beta")
         dev, f32 = dens.device, torch.float32
         K = c.num_classes
         CO = C_ + (K if c.cat_seg else 0)
@@ -1033,7 +1051,7 @@ class _SamplePointsFn(torch.autograd.Function):
         c = hp.cfg
         B, C_ = volume.shape[:2]
         ctx.in_dtype = volume.dtype
-        volume = _chk(_accept(volume), (B, C_, c.vZ, c.vY, c.vX), "volume")
+        volume = _chk(_accept_float(volume, "volume"), (B, C_, c.vZ, c.vY, c.vX), "volume")
         P = points.shape[1]
         points = _chk(points.float(), (B, P, 3), "points")
         d = _capi.VampSampleDesc()
@@ -1053,7 +1071,7 @@ class _SamplePointsFn(torch.autograd.Function):
         for i in range(3):
             d.lattice[i] = int(lattice[i]) if lattice is not None else 0
         ctx.beta_shape = beta.shape
-        beta = beta.reshape(1).float().contiguous()
+        beta = _scalar(beta, "beta")
         out = torch.empty((B, P, C_) if channel_last else (B, C_, P), dtype=torch.float32,
                           device=volume.device)
         hp.vamp.vamp_sample_points_forward(d, volume, beta, points, P, out, _stream())
@@ -1083,7 +1101,7 @@ class _DepthSoftmaxFn(torch.autograd.Function):
         if not logits.is_cuda:
             raise _capi.VampireHipError("logits must be a device tensor (no CPU fallback)")
         ctx.in_dtype = logits.dtype
-        logits = _accept(logits).contiguous()
+        logits = _accept_float(logits, "logits").contiguous()
         images, D = logits.shape[:2]
         HW = logits[0, 0].numel()
         out = torch.empty(logits.shape, dtype=torch.float32, device=logits.device)
@@ -1109,8 +1127,8 @@ class _DensityGateFn(torch.autograd.Function):
         if not (vo.is_cuda and vd.is_cuda):
             raise _capi.VampireHipError("voxel_output / voxel_density must be device tensors (no CPU fallback)")
         B, C_ = vo.shape[:2]
-        vd = _chk(vd.float(), (B, 1) + tuple(vo.shape[2:]), "voxel_density")
-        vo = vo.float().contiguous()
+        vd = _chk(_accept_float(vd, "voxel_density").float(), (B, 1) + tuple(vo.shape[2:]), "voxel_density")
+        vo = _accept_float(vo, "voxel_output").float().contiguous()
         cells = vd[0].numel()
         mode = _density_code(hp.cfg)
         out = torch.empty_like(vo)
@@ -1139,9 +1157,9 @@ class _GateConvFn(torch.autograd.Function):
         plane = tuple(vo.shape[3:])
         cells = int(math.prod(plane))
         cout = weight.shape[0]
-        vd = _chk(vd.float(), (B, 1, oZ) + plane, "voxel_density")
-        vo = vo.float().contiguous()
-        w = _chk(weight.float().reshape(cout, -1), (cout, C_ * oZ), "weight")
+        vd = _chk(_accept_float(vd, "voxel_density").float(), (B, 1, oZ) + plane, "voxel_density")
+        vo = _accept_float(vo, "voxel_output").float().contiguous()
+        w = _chk(_accept_float(weight, "weight").float().reshape(cout, -1), (cout, C_ * oZ), "weight")
         bs = None if bias is None else _chk(bias.float(), (cout,), "bias")
         mode = _density_code(hp.cfg)
         out = torch.empty((B, cout) + plane, dtype=torch.float32, device=vo.device)
