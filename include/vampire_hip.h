@@ -33,7 +33,8 @@ extern "C" {
                                  14: masked regression losses; 15: the camera render's plans and workspace layout;
                                  16: the lift's plans and workspace layout;
                                  16 also: stride-2 16-bit convolutions, the 2-D bilinear resize of the rendered maps and the
-                                 parameter update; the number could not move: a test pins it) */
+                                 parameter update, the lidar-point label rasteriser; the number could not move: a test
+                                 pins it) */
 
 enum {
   VAMP_OK = 0,
@@ -1469,6 +1470,73 @@ typedef struct VampParamUpdateDesc {
 size_t vamp_param_update_workspace_bytes(const VampParamUpdateDesc* d);
 int vamp_param_update_step(const VampParamUpdateDesc* d, const void* table, float* exp_avg, float* exp_avg_sq,
                            float* ema, void* scalars, void* workspace, size_t workspace_bytes, void* stream);
+
+/* --------------------------------------------------------------------------
+ * Camera and BEV training labels rasterised from the lidar points: the reference loader's depth_transform
+ * (nusc_det_seg_dataset.py:178-231) behind the margins of map_pointcloud_to_image (:362-367), get_bev_seg_map
+ * (:233-265) and the every-s-th-pixel pick of get_downsampled_gt (base_exp.py:596-632), for all B samples and N
+ * cameras on the device.
+ * Inputs: points [B, M, point_cols] fp32 (x y z [intensity]) in the bda-augmented ego frame, labels [B, M]
+ * (label_dtype), counts [B] int32 (rows i >= counts[b] of sample b do nothing; NULL: all M rows count), lidar2cam
+ * [B, N, 4, 4] fp32 (points to camera frame), intrin [B, N, 4, 4] fp32, aug [B, N, 8] float64 in DEVICE memory:
+ * resize, crop_x, crop_y, flip (0 | 1), cos, sin of the rotation, 0, 0 -- so the augmentation can change under a
+ * replayed graph.
+ *
+ *  camera     per camera, every step one fp32 operation in this order (no FMA):
+ *    frame    xc = ((m00 x + m01 y) + m02 z) + m03, yc and zc likewise with rows 1 and 2 of lidar2cam; depth = zc.
+ *    pixel    u = ((k00 xc + k01 yc) + k02 zc) / ((k20 xc + k21 yc) + k22 zc), v likewise with row 1 of intrin.
+ *    margins  keep iff depth > 0, u > 1, u < raw_w - 1, v > 1, v < raw_h - 1 (:362-367).
+ *    augment  u *= (float) resize, v *= (float) resize; u -= crop_x, v -= crop_y; flip: u = W - u; u -= W / 2,
+ *             v -= H / 2; rotation in float64 as numpy's matmul computes it, u' = cos u + sin v, v' = -sin u + cos v,
+ *             each rounded to fp32; u += W / 2, v += H / 2 (:193-211).
+ *    valid    iff 0 <= u < W and 0 <= v < H, tested on the floats before any conversion (NaN, +-Inf, 1e30 and
+ *             -0.5, which would truncate to 0, fall out); the pixel (iv, iu) is the truncation of (v, u).
+ *    stride   the point is dropped unless iu % stride == 0 and iv % stride == 0; the cell is (iv / stride,
+ *             iu / stride): exactly map[::stride, ::stride] of the full-resolution map.
+ *    winner   the smallest depth (:225 sorts by -depth, the last write wins); equal depths go to the LOWEST point
+ *             index.  The reference's order among equal depths is that of an unstable argsort, i.e. undefined: the
+ *             tie rule is this library's.  key = (bits(depth) << 32) | index under a 64-bit unsigned atomic min.
+ *  BEV        coordinates in float64 as numpy makes them: cx = ((double) x - origin_x) / size, cy likewise, origin =
+ *             bound_lo - size / 2 computed by the caller; keep iff cx > 1, cx < nx - 1, cy > 1, cy < ny - 1, z > z_lo
+ *             and z < z_hi (the z comparison in fp32); the cell is (trunc(cy), trunc(cx)); the largest z wins (:258
+ *             sorts by height, the last write wins), equal heights go to the lowest index (ours again; -0.0 ranks
+ *             below +0.0).  key = (ordered(z) << 32) | (0xFFFFFFFF - index) under a 64-bit unsigned atomic max,
+ *             ordered the monotone map of fp32 bits to uint32; key 0 is an empty cell.
+ *             The map is [ny, nx], rows along y, columns along x.  That equals the reference for its square grids;
+ *             its own indexing (a map shaped by (x, y) written at [y, x]) is inconsistent when nx != ny.
+ * Outputs, every element written: cam_depth [B, N, h, w] fp32 (the winner's depth bits, 0 when empty), cam_seg
+ * [B, N, h, w] int64 (labels[winner] & 0xFF, 0 when empty), cam_fg [B, N, h, w] uint8 (depth > 0), h = H / stride,
+ * w = W / stride; bev_seg [B, ny, nx] int64, bev_height [B, ny, nx] fp32 (0 when empty), bev_mask [B, ny, nx] uint8.
+ * The three camera outputs may be NULL together and the three BEV outputs likewise: that part is skipped (and
+ * lidar2cam, intrin, aug are not read without the camera part); both parts NULL is an error.
+ * Limits: 1 <= B <= 4096, 1 <= N <= 16, 0 <= M <= 2^24, point_cols 3 | 4, label_dtype VAMP_U8 | VAMP_I64,
+ * 1 <= H, W, ny, nx <= 8192, stride >= 1 dividing H and W, 1 <= raw_w, raw_h <= 65536, size > 0, z_lo < z_hi,
+ * B N h w and B ny nx <= 2^33.  Every argument is checked before any device work: a failed check returns VAMP_EINVAL
+ * (and a workspace size of 0) with a message, a workspace that is NULL or too small VAMP_ENOSPC.
+ * Three launches on `stream` (fill, scatter with one thread per point, resolve with one thread per cell; no scatter
+ * when M = 0), no host synchronisation, no float atomics: integer min / max do not depend on the arrival order, so
+ * the output is a pure function of the inputs, bitwise repeatable, and the call can be captured in a graph.  The
+ * workspace (16-byte aligned, vamp_lidar_labels_workspace_bytes: 8 bytes per cell of both parts) needs no
+ * initialisation.
+ * -------------------------------------------------------------------------- */
+typedef struct VampLidarLabelDesc {
+  double origin_x, origin_y;      /* BEV: bound_lo - size / 2 */
+  double size;                    /* BEV cell size */
+  int32_t B, N, M;
+  int32_t point_cols;             /* 3 | 4 */
+  int32_t label_dtype;            /* VAMP_U8 | VAMP_I64 */
+  int32_t H, W;                   /* final_dim */
+  int32_t stride;
+  int32_t raw_w, raw_h;           /* the raw image the intrinsics belong to */
+  int32_t ny, nx;
+  float z_lo, z_hi;
+  int32_t reserved[2];            /* 0 */
+} VampLidarLabelDesc;
+size_t vamp_lidar_labels_workspace_bytes(const VampLidarLabelDesc* d);
+int vamp_lidar_labels(const VampLidarLabelDesc* d, const float* points, const void* labels, const int32_t* counts,
+                      const float* lidar2cam, const float* intrin, const double* aug, float* cam_depth,
+                      int64_t* cam_seg, uint8_t* cam_fg, int64_t* bev_seg, float* bev_height, uint8_t* bev_mask,
+                      void* workspace, size_t workspace_bytes, void* stream);
 
 #ifdef __cplusplus
 }

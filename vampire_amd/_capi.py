@@ -160,6 +160,14 @@ class VampParamUpdateDesc(C.Structure):
                 ("n_buffer_chunks", C.c_int32), ("scale_mode", C.c_int32), ("reserved", C.c_int32)]
 
 
+class VampLidarLabelDesc(C.Structure):
+    _fields_ = [("origin_x", C.c_double), ("origin_y", C.c_double), ("size", C.c_double),
+                ("B", C.c_int32), ("N", C.c_int32), ("M", C.c_int32), ("point_cols", C.c_int32),
+                ("label_dtype", C.c_int32), ("H", C.c_int32), ("W", C.c_int32), ("stride", C.c_int32),
+                ("raw_w", C.c_int32), ("raw_h", C.c_int32), ("ny", C.c_int32), ("nx", C.c_int32),
+                ("z_lo", C.c_float), ("z_hi", C.c_float), ("reserved", C.c_int32 * 2)]
+
+
 class VampBevBackwardPlan(C.Structure):
     """What vamp_render_bev_backward_ex will launch (vamp_render_bev_backward_plan; include/vampire_hip.h)."""
     _fields_ = [("scan_lds", C.c_int64), ("path", C.c_int32), ("z_lo", C.c_int32), ("z_hi", C.c_int32),
@@ -308,6 +316,7 @@ _SLD = C.POINTER(VampSegLossDesc)
 _RLD = C.POINTER(VampRegLossDesc)
 _R2D = C.POINTER(VampResize2dDesc)
 _PUD = C.POINTER(VampParamUpdateDesc)
+_LLD = C.POINTER(VampLidarLabelDesc)
 
 # name -> (return kind, argtypes); must list every symbol declared in include/vampire_hip.h
 SIGNATURES = {
@@ -432,6 +441,8 @@ SIGNATURES = {
     "vamp_reg_loss_backward": (_STATUS, [_RLD] + [_P] * 6 + [_P]),
     "vamp_param_update_workspace_bytes": (_SIZE, [_PUD]),
     "vamp_param_update_step": (_STATUS, [_PUD] + [_P] * 5 + [_P, C.c_size_t, _P]),
+    "vamp_lidar_labels_workspace_bytes": (_SIZE, [_LLD]),
+    "vamp_lidar_labels": (_STATUS, [_LLD] + [_P] * 12 + [_P, C.c_size_t, _P]),
 }
 
 _lib = None
