@@ -31,6 +31,10 @@ ph0 = buf[:, 1] - buf[:, 0]; stage = buf[:, 2]; cons = buf[:, 3]; epi = buf[:, 5
 other = dur - ph0 - stage - cons - epi
 for name, v in (("phase0", ph0), ("stage", stage), ("consume", cons), ("epilogue", epi), ("other", other)):
     print("  %-9s mean %8.0f  p50 %8.0f p90 %8.0f max %8.0f  share %.2f" % (name, v.mean(), *np.percentile(v, [50, 90]), v.max(), v.sum() / dur.sum()))
+heavy = dur >= np.percentile(dur, 90)           # the heaviest decile of strips: the ones the kernel's span follows
+print("heaviest decile: mean %.2f us per WG; shares" % rdur[heavy].mean(),
+      " ".join("%s %.2f" % (name, v[heavy].sum() / dur[heavy].sum())
+               for name, v in (("phase0", ph0), ("stage", stage), ("consume", cons), ("epilogue", epi), ("other", other))))
 st = (buf[:, 6] - r0)
 print("starts by decile of span:", np.histogram(st, bins=10, range=(0, span))[0].tolist())
 print("ends by decile of span:", np.histogram(buf[:, 7] - r0, bins=10, range=(0, span))[0].tolist())

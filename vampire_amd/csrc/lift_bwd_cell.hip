@@ -14,11 +14,12 @@
 //           the strip are those of the cell rows iy, iy + 1, columns x0 .. x0 + 16: two contiguous ranges
 //           of the cell-ordered records.  The workgroup stages them in LDS (lane = pair for the taps, four lanes
 //           per pair for the gradient row: plain streaming reads, every load of a chunk in flight at once and
-//           none of them dependent on another), then consumes them lane = (pixel, channel
-//           quad): a pixel's pairs are one contiguous sub-range (its two cells are adjacent), the four
-//           waves take every fourth pair of it, the channel dot product is a 4-lane DPP sum, the depth
-//           terms go to the strip's LDS tile of 64-bit fixed-point sums.  No float atomics, no cross-lane folds;
-//           depth-gradient planes leave as 64-byte runs.
+//           none of them dependent on another, none in a branch), then consumes them dealt by PAIR, whatever
+//           pixels the pairs fall on: the depth terms lane = (pair, role) -- the pair's channels dotted with the
+//           features of the role's pixel -- into the strip's LDS tile of 64-bit fixed-point sums, the feature
+//           gradient as [16 pixels x 4 pairs] x [4 pairs x 16 channels] products of the fp32 matrix cores, blocks of
+//           four pairs dealt round-robin to the waves.  No float atomics, no cross-lane folds; depth-gradient planes
+//           leave as 64-byte runs.
 //
 // Round 6 changed what a pair carries (review item 2: "change the tile, not the order").  Through round 5 the fill
 // wrote a 41 MB channel-last TABLE of normalised gradient rows, one per voxel, and 20-byte pair records beside it;
@@ -260,15 +261,10 @@ lift_bwd_fill_kernel(LiftParams P, int cw, int ch, const float* __restrict__ gou
 // ---------------------------------------------------------------------------
 constexpr int kS = 16;               // pixels per strip: depth planes move as 64-byte runs
 constexpr int kW = 4;                // waves per workgroup
-constexpr int kSlots = 4 * kW;       // lanes a pixel's pairs are dealt to (4 per wave)
-constexpr int kRow = 24;             // floats per staged pair: 16 channels + 2 x {w dep, w wz0, w wz1, iz0}
+constexpr int kRow = 24;             // floats per staged pair: 16 channels + {w dep A, w dep B, column << 16 | iz0 + 1, -} + 2 x {w wz0, w wz1}
 constexpr int kFix = 44;             // fixed-point depth sums: |term| < 2^41, 2^10 .. 2^20 terms fit
 
-__device__ __forceinline__ float quad_sum(float v) {
-  v += __builtin_amdgcn_update_dpp(0.f, v, 0xB1, 0xf, 0xf, false);    // quad_perm [1,0,3,2]
-  v += __builtin_amdgcn_update_dpp(0.f, v, 0x4E, 0xf, 0xf, false);    // quad_perm [2,3,0,1]
-  return v;
-}
+typedef float f32x4 __attribute__((ext_vector_type(4)));
 __device__ __forceinline__ float wave_max(float v) {
 #pragma unroll
   for (int o = 32; o > 0; o >>= 1) v = fmaxf(v, __shfl_xor(v, o, 64));
@@ -294,8 +290,8 @@ __device__ long long g_stamps[16384 * 8];
 #endif
 
 static size_t strip_lds_floats(int D, int cap) {
-  // 64-bit gtile + stage (staged pairs | feature tile | lane-reduction buffer | the softmax backward's depth columns)
-  // + cell starts + per-pixel scale exponents + softmax partials + chunk maxima
+  // 64-bit gtile + stage (staged pairs | the waves' grad_feat tiles | the softmax backward's depth columns)
+  // + cell starts + per-pixel scale exponents + softmax partials (in the consume phase: the feature tile) + chunk maxima
   return (size_t) D * kS * 2 + (size_t) std::max(std::max(cap * kRow, kW * kS * 16), D * kS) + 2 * (kS + 2) + kS + 17 * kS + 8;
 }
 
@@ -338,7 +334,7 @@ lift_bwd_strip_kernel(LiftParams P, int cw, int ch, int spr, int xgroup, int bn_
   const long HW = (long) P.fH * P.fW;
   const long V = (long) P.Z * P.Y * P.X;
   const long pix0 = (long) iy * P.fW + x0;
-  const int p = lane >> 2, sl = wv * 4 + (lane & 3); // consume phase: lane = (pixel, slot)
+  float* ftile = red;                                               // [kS][16] the strip's features of a channel chunk (consume phase)
 
 #ifdef VAMP_LIFT_STAMPS
   long long st0 = STAMP(), st_stage = 0, st_cons = 0, st2 = 0;
@@ -381,38 +377,25 @@ lift_bwd_strip_kernel(LiftParams P, int cw, int ch, int spr, int xgroup, int bn_
 
   const int n0 = offs[np + 1] - offs[0];             // pairs of cell row iy
   const int NP = n0 + offs[kS + 2 + np + 1] - offs[kS + 2];   // pairs of both cell rows
-  const int efl = efp[p];
   int eg = -1000;                                    // uniform: current exponent of the table rows
 
   for (int c0 = 0; c0 < C; c0 += 16) {               // channel chunk
     const int nq = min(4, (C - c0) / 4);             // float4 pieces of this chunk
-    // the pixel's 16 features of this chunk, through LDS ([pixel][channel]: one load per thread)
-    __syncthreads();
+    // the strip's 16 x 16 features of this chunk, in the reduction buffer (idle until the softmax epilogue) as
+    // [pixel][channel] with the 16-byte piece index xor-ed by pixel / 4: the depth lanes below read the rows of
+    // arbitrary pixels, and the same piece of all 16 rows then sits in 16 different bank quads.  (No barrier here:
+    // the buffer's last readers are two barriers back, the next ones behind the two barriers of the first chunk.)
     {
       // (consecutive threads = consecutive pixels of a channel plane, or consecutive channels of a channel-last row)
       const int cc = fcl ? tid % 16 : tid / kS, pp = fcl ? tid / 16 : tid % kS;
-      stage[pp * 16 + cc] = (c0 + cc < C && pp < np) ? feat_at(c0 + cc, pp) : 0.f;
+      ftile[pp * 16 + ((((cc >> 2) ^ (pp >> 2)) & 3) << 2) + (cc & 3)] = (c0 + cc < C && pp < np) ? feat_at(c0 + cc, pp) : 0.f;
     }
-    __syncthreads();
-    float ft[16], acc[16];
+    // grad_feat of the chunk: four 16 x 16 accumulator tiles of the matrix cores per wave (column = channel = lane & 15,
+    // row = pixel = 4 (lane >> 4) + register): sixteen partial sums per element over the workgroup, as many as the
+    // lane-per-(pixel, slot) loop before it kept, so the fp32 sums are as short
+    f32x4 acc[4];
 #pragma unroll
-    for (int k = 0; k < 4; ++k) {
-      const float4 f = reinterpret_cast<const float4*>(stage + p * 16)[k];
-      ft[4 * k] = f.x; ft[4 * k + 1] = f.y; ft[4 * k + 2] = f.z; ft[4 * k + 3] = f.w;
-    }
-#pragma unroll
-    for (int c = 0; c < 16; ++c) acc[c] = 0.f;
-    // this pixel's pairs in the concatenation [cell row iy | cell row iy + 1]: cells (x0 + p) [the
-    // pixel is their x1 tap, role A] and (x0 + p + 1) [x0 tap, role B] of either row
-    int lo_h[2], mid_h[2], hi_h[2];
-#pragma unroll
-    for (int h = 0; h < 2; ++h) {
-      const int* oh = offs + h * (kS + 2);
-      const int base = h ? n0 - oh[0] : -oh[0];
-      lo_h[h] = oh[p] + base;
-      mid_h[h] = oh[p + 1] + base;
-      hi_h[h] = p < np ? oh[p + 2] + base : lo_h[h];
-    }
+    for (int k = 0; k < 4; ++k) acc[k] = f32x4{0.f, 0.f, 0.f, 0.f};
     // The loads of the stage phase run one chunk ahead, and none depends on another: a pair's record sits at its
     // POSITION in the cell-ordered list (round 6: the gradient row travels in the record; through round 5 a pair's
     // voxel index had to arrive before its table row could be asked for).
@@ -421,32 +404,28 @@ lift_bwd_strip_kernel(LiftParams P, int cw, int ch, int spr, int xgroup, int bn_
     const int jA = 32 * wv + lane;
     const bool laneA = lane < 32 && jA < cap;
     const int RS = 2 + C / 4;                        // float4 pieces per record
-    auto rec_at = [&](int t) -> long { return (long) (t >= n0 ? offs[kS + 2] + (t - n0) : offs[0] + t) * RS; };
+    // (No load sits in a branch: a lane without a pair of its own reads the strip's last record, and what it read is
+    // dropped when the chunk is staged.  Behind a skipped load the wait counters cannot be exact, and a wait for this
+    // chunk's registers would also wait for everything asked for since.)
+    const int o0 = offs[0], o1 = offs[kS + 2];
+    auto rec_at = [&](int t) -> long {
+      const int tt = min(t, NP - 1);
+      return (long) (tt >= n0 ? o1 + (tt - n0) : o0 + tt) * RS;
+    };
     auto load_taps = [&](int tc, float4& rc, float4& dp) {
-      rc = make_float4(0.f, 0.f, 0.f, 0.f);
-      dp = rc;
-      const int t = tc + jA;
-      if (laneA && t < NP) {
-        const long pos = rec_at(t);
-        rc = recs[pos];
-        dp = recs[pos + 1];
-      }
+      const long pos = rec_at(tc + 32 * wv + (lane & 31));
+      rc = recs[pos];
+      dp = recs[pos + 1];
     };
     auto load_rows = [&](int tc, float4 (&g)[2]) {
 #pragma unroll
-      for (int s2 = 0; s2 < 2; ++s2) {
-        const int jj = 32 * wv + 16 * s2 + (lane >> 2), k = lane & 3;
-        g[s2] = make_float4(0.f, 0.f, 0.f, 0.f);
-        // the voxel's row of grad_out / (hits + 1e-6), this chunk of channels
-        if (jj < cap && tc + jj < NP && k < nq) g[s2] = recs[rec_at(tc + jj) + 2 + c0 / 4 + k];
-      }
+      for (int s2 = 0; s2 < 2; ++s2)                   // the voxel's row of grad_out / (hits + 1e-6), this chunk of channels
+        g[s2] = recs[rec_at(tc + 32 * wv + 16 * s2 + (lane >> 2)) + 2 + c0 / 4 + min(lane & 3, nq - 1)];
     };
-    float4 rcA, dpA, gA[2];
-    load_taps(0, rcA, dpA);
-    load_rows(0, gA);
-    for (int t0 = 0; t0 < NP; t0 += cap) {
+    // one chunk: staged from the registers it was loaded into, which then take the next chunk
+    auto chunk = [&](int t0, float4& rcA, float4& dpA, float4 (&gA)[2]) {
       const int nst = min(cap, NP - t0);
-      __syncthreads();                               // the previous chunk (or the feature tile) is consumed
+      __syncthreads();                               // the previous chunk (or the last channel chunk's tile sum) is consumed
 #ifdef VAMP_LIFT_STAMPS
       long long sa = STAMP();
 #endif
@@ -467,21 +446,28 @@ lift_bwd_strip_kernel(LiftParams P, int cw, int ch, int spr, int xgroup, int bn_
         // y1 tap when the pair comes from cell row iy (h = 0), its y0 tap from cell row iy + 1
         const float dpy[2] = {h ? dpA.x : dpA.z, h ? dpA.y : dpA.w};     // [x tap] of this row
         float* st = stage + jA * kRow;
+        // the pair's cell column in the strip, 0 .. np, travels with both roles beside iz0 + 1 (an integer in a float's
+        // bits: never an operand of arithmetic): the consume phase no longer knows a pair's pixels from its position
+        const float tag = __int_as_float(((col - x0) << 16) | (pk & 0xffff));
+        float wd[2], w0[2], w1[2];
 #pragma unroll
         for (int role = 0; role < 2; ++role) {       // role A: the pixel is the x1 tap, role B: the x0 tap
           const int pr = col - role - x0;
           const bool pin = pr >= 0 && pr < np;
           const float wj = wy * (role ? 1.0f - rc.x : rc.x);
           const float dep = dpy[1 - role];
-          reinterpret_cast<float4*>(st)[4 + role] =
-              make_float4(pin ? wj * dep : 0.f, (pin && z0in) ? wj * wz0v : 0.f, (pin && z1in) ? wj * wz1v : 0.f,
-                          __int_as_float(iz0));
+          wd[role] = pin ? wj * dep : 0.f;
+          w0[role] = (pin && z0in) ? wj * wz0v : 0.f;
+          w1[role] = (pin && z1in) ? wj * wz1v : 0.f;
         }
+        // {w dep A, w dep B, tag, -} is what the grad_feat lanes read, {w wz0, w wz1} of a role what its depth lane reads
+        reinterpret_cast<float4*>(st)[4] = make_float4(wd[0], wd[1], tag, 0.f);
+        reinterpret_cast<float4*>(st)[5] = make_float4(w0[0], w1[0], w0[1], w1[1]);
       }
 #pragma unroll
       for (int s2 = 0; s2 < 2; ++s2) {
         const int j = 32 * wv + 16 * s2 + (lane >> 2);
-        const float4 g4 = gA[s2];
+        const float4 g4 = (j < nst && (lane & 3) < nq) ? gA[s2] : make_float4(0.f, 0.f, 0.f, 0.f);
         gm = fmaxf(gm, fmaxf(fmaxf(fabsf(g4.x), fabsf(g4.y)), fmaxf(fabsf(g4.z), fabsf(g4.w))));
         if (j < nst) reinterpret_cast<float4*>(stage + j * kRow)[lane & 3] = g4;
       }
@@ -506,51 +492,72 @@ lift_bwd_strip_kernel(LiftParams P, int cw, int ch, int spr, int xgroup, int bn_
 #ifdef VAMP_LIFT_STAMPS
       long long sb = STAMP(); st_stage += sb - sa;
 #endif
-      // ---- consume: lane = (pixel, slot), the pair's 16 channels in the lane
-      const int sce = kFix - eg - efl;
-#pragma unroll
-      for (int h = 0; h < 2; ++h) {
-        const int lo = max(lo_h[h], t0), hi = min(hi_h[h], t0 + nst), mid = mid_h[h];
-        for (int r = lo + sl; __any(r < hi); r += kSlots) {
-          const bool in = r < hi;
-          const float4* sr = reinterpret_cast<const float4*>(stage + (in ? r - t0 : 0) * kRow);
-          const float4 ax = sr[r < mid ? 4 : 5];
-          const float pwj = in ? ax.x : 0.f;
+      // ---- consume.  The work of a chunk is dealt by pair, not by pixel: its cost does not depend on how the pairs
+      // spread over the strip's pixels (the records are in cell order: a dense chunk is the pairs of one or two cells,
+      // two or four pixels).
+      // Depth terms: lane = (pair, role).  The pair's channels dotted with the features of the role's pixel, a chain of
+      // sixteen fmaf in channel order from zero, then the two fixed-point adds.
+      if (D > 0) {
+        for (int j = tid >> 1; j < nst; j += NT / 2) {
+          const float4* sr = reinterpret_cast<const float4*>(stage + j * kRow);
+          const float2 wz = *reinterpret_cast<const float2*>(stage + j * kRow + 20 + 2 * (tid & 1));
+          const int tag = __float_as_int(stage[j * kRow + 18]);
+          const int pr = min(max((tag >> 16) - (tid & 1), 0), kS - 1);   // (outside the strip: both weights are zero)
+          const float4* fr = reinterpret_cast<const float4*>(ftile + pr * 16);
           float dot = 0.f;
 #pragma unroll
           for (int k = 0; k < 4; ++k) {
-            const float4 g = sr[k];
-            acc[4 * k] = __builtin_fmaf(pwj, g.x, acc[4 * k]);
-            acc[4 * k + 1] = __builtin_fmaf(pwj, g.y, acc[4 * k + 1]);
-            acc[4 * k + 2] = __builtin_fmaf(pwj, g.z, acc[4 * k + 2]);
-            acc[4 * k + 3] = __builtin_fmaf(pwj, g.w, acc[4 * k + 3]);
-            dot = __builtin_fmaf(ft[4 * k], g.x, dot);
-            dot = __builtin_fmaf(ft[4 * k + 1], g.y, dot);
-            dot = __builtin_fmaf(ft[4 * k + 2], g.z, dot);
-            dot = __builtin_fmaf(ft[4 * k + 3], g.w, dot);
+            const float4 g = sr[k], f = fr[(k ^ (pr >> 2)) & 3];
+            dot = __builtin_fmaf(f.x, g.x, dot);
+            dot = __builtin_fmaf(f.y, g.y, dot);
+            dot = __builtin_fmaf(f.z, g.z, dot);
+            dot = __builtin_fmaf(f.w, g.w, dot);
           }
-          if (D > 0) {
-            const float w0 = in ? ax.y * dot : 0.f, w1 = in ? ax.z * dot : 0.f;
-            unsigned long long* gp = reinterpret_cast<unsigned long long*>(gtile + __float_as_int(ax.w) * kS + p);
-            if (w0 != 0.f) atomicAdd(gp, fixed_of(w0, sce));
-            if (w1 != 0.f) atomicAdd(gp + kS, fixed_of(w1, sce));
-          }
+          const float w0 = wz.x * dot, w1 = wz.y * dot;
+          const int sce = kFix - eg - efp[pr];
+          unsigned long long* gp = reinterpret_cast<unsigned long long*>(gtile + ((tag & 0xffff) - 1) * kS + pr);
+          if (w0 != 0.f) atomicAdd(gp, fixed_of(w0, sce));
+          if (w1 != 0.f) atomicAdd(gp + kS, fixed_of(w1, sce));
         }
+      }
+      // grad_feat[pixel][channel] += W[pixel][pair] G[pair][channel] on the fp32 matrix cores (v_mfma_f32_16x16x4_f32:
+      // per element a chain of fmaf over the four pairs in order), a block of four pairs per instruction, the blocks
+      // dealt round-robin to the waves and to each wave's four accumulators.  A: lane = (pixel = lane & 15, pair =
+      // lane >> 4), the pair's w dep of the role whose pixel this is, or zero; B: lane = (pair, channel = lane & 15).
+      // Behind the chunk's end BOTH are selected zero: what lies there is stale, 0 x NaN is NaN.
+      // Four blocks a turn, one per accumulator: their operands are asked for together.
+      auto operands = [&](int bi, float& a, float& b) {
+        const int j = 4 * bi + (lane >> 4);
+        const float* sr = stage + min(j, cap - 1) * kRow;
+        const float2 wd = *reinterpret_cast<const float2*>(sr + 16);
+        const int dx = (__float_as_int(sr[18]) >> 16) - (lane & 15);  // 0: the pixel is the pair's x1 tap, 1: its x0 tap
+        const float g = sr[lane & 15];
+        const bool in = j < nst;
+        a = in ? (dx == 0 ? wd.x : (dx == 1 ? wd.y : 0.f)) : 0.f;
+        b = in ? g : 0.f;
+      };
+      for (int bi = wv; 4 * bi < nst; bi += 4 * kW) {      // (uniform)
+        float a[4], b[4];
+#pragma unroll
+        for (int k = 0; k < 4; ++k) operands(bi + k * kW, a[k], b[k]);
+#pragma unroll
+        for (int k = 0; k < 4; ++k) acc[k] = __builtin_amdgcn_mfma_f32_16x16x4f32(a[k], b[k], acc[k], 0, 0, 0);
       }
 #ifdef VAMP_LIFT_STAMPS
       __syncthreads();
       st_cons += STAMP() - sb;
 #endif
+    };
+    if (NP > 0) {                                    // (uniform)
+      float4 rcA, dpA, gA[2];
+      load_taps(0, rcA, dpA);
+      load_rows(0, gA);
+      for (int t0 = 0; t0 < NP; t0 += cap) chunk(t0, rcA, dpA, gA);
     }
-    // grad_feat: the four slots of a wave by DPP, the four waves through LDS
-#pragma unroll
-    for (int c = 0; c < 16; ++c) acc[c] = quad_sum(acc[c]);
+    // grad_feat: the wave's four tiles added, the four waves through LDS
     __syncthreads();
-    if ((lane & 3) == 0) {
 #pragma unroll
-      for (int k = 0; k < 4; ++k)
-        reinterpret_cast<float4*>(stage + (wv * kS + p) * 16)[k] = make_float4(acc[4 * k], acc[4 * k + 1], acc[4 * k + 2], acc[4 * k + 3]);
-    }
+    for (int r = 0; r < 4; ++r) stage[(wv * kS + 4 * (lane >> 4) + r) * 16 + (lane & 15)] = (acc[0][r] + acc[1][r]) + (acc[2][r] + acc[3][r]);
     __syncthreads();
 #ifdef VAMP_LIFT_STAMPS
     st2 = STAMP();
