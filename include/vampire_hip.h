@@ -33,7 +33,7 @@ extern "C" {
                                  14: masked regression losses; 15: the camera render's plans and workspace layout;
                                  16: the lift's plans and workspace layout;
                                  16 also: stride-2 16-bit convolutions, the 2-D bilinear resize of the rendered maps and the
-                                 parameter update, the lidar-point label rasteriser; the number could not move: a test
+                                 parameter update, the lidar-point label rasteriser, the camera images; the number could not move: a test
                                  pins it) */
 
 enum {
@@ -1537,6 +1537,89 @@ int vamp_lidar_labels(const VampLidarLabelDesc* d, const float* points, const vo
                       const float* lidar2cam, const float* intrin, const double* aug, float* cam_depth,
                       int64_t* cam_seg, uint8_t* cam_fg, int64_t* bev_seg, float* bev_height, uint8_t* bev_mask,
                       void* workspace, size_t workspace_bytes, void* stream);
+
+/* --------------------------------------------------------------------------
+ * Camera images on the device: the reference loader's img_transform (nusc_det_seg_dataset.py:118-146: Pillow's
+ * resize, crop, transpose(FLIP_LEFT_RIGHT) and rotate) followed by mmcv.imnormalize (:679-681), for all B samples and
+ * N cameras, with the (resize, resize_dims, crop, flip, rotate) values of sample_ida_augmentation (:472-499).
+ * For one raw RGB frame raw[raw_h, raw_w, 3] uint8, resize_dims = (newW, newH), crop = (x0, y0, x0 + W, y0 + H) and
+ * final_dim = (H, W), rules 1 - 5 apply in this order.  Rules 1 - 4 restate Pillow's arithmetic and are pinned
+ * byte for byte against Pillow 12.2.0 by tests/golden/camera_images.npz (the reference does not pin Pillow); rule 5
+ * restates mmcv.imnormalize, and its parity with OpenCV is UNPINNED: neither OpenCV nor mmcv was at hand.
+ *
+ *  1 resize   Image.resize without a resample argument: bicubic, a = -0.5, two separable passes, horizontal first,
+ *             with a uint8 image between them.  Per axis with sizes in -> out, in float64: scale = in / out,
+ *             fs = max(scale, 1), support = 2 fs, ss = 1 / fs.  For output index i: c = (i + 0.5) scale,
+ *             lo = max((int) (c - support + 0.5), 0), hi = min((int) (c + support + 0.5), in); the taps are
+ *             k[j] = cubic((j + lo - c + 0.5) ss) for j < hi - lo, with cubic(x) = ((1.5 |x| - 2.5) |x|) |x| + 1 for
+ *             |x| < 1, (((|x| - 5) |x| + 8) |x| - 4) (-0.5) for |x| < 2, else 0; they are divided by their sum, taken
+ *             from left to right, and made fixed-point: ki = (int) (k 2^22 + 0.5) for k >= 0, (int) (k 2^22 - 0.5)
+ *             for k < 0, (int) truncating.  A pass computes clip(0, 255, (2^21 + sum_j ki[j] pix[lo + j]) >> 22) per
+ *             channel in int32 (255 sum |ki| stays below 2^31 for these taps), the shift arithmetic.
+ *  2 crop     pixel (x, y) of the crop is resized pixel (x + x0, y + y0), 0 where that lies outside the resized
+ *             image (y0 may be negative, x0 + W may exceed newW).
+ *  3 flip     x -> W - 1 - x.
+ *  4 rotate   Image.rotate(angle): nearest neighbour about the centre, no expand, zero fill.  In float64:
+ *             a = -radians(angle mod 360), m = [round(cos a, 15), round(sin a, 15), 0, round(-sin a, 15),
+ *             round(cos a, 15), 0], m[2] = m[0] (-W / 2) + m[1] (-H / 2) + W / 2, m[5] = m[3] (-W / 2) + m[4] (-H / 2)
+ *             + H / 2; with FIX(v) = floor(v 65536 + 0.5): a0, a1, a3, a4 = FIX(m[0]), FIX(m[1]), FIX(m[3]), FIX(m[4]),
+ *             a2 = FIX(m[2] + 0.5 m[0] + 0.5 m[1]), a5 = FIX(m[5] + 0.5 m[3] + 0.5 m[4]).  Output (x, y) takes source
+ *             ((a2 + y a1 + x a0) >> 16, (a5 + y a4 + x a3) >> 16), arithmetic shifts in int32, 0 where the source is
+ *             outside W x H.  Angle 0 is the identity by the same formula.  |angle| < 45 is the caller's to keep
+ *             (Pillow switches to transposes at multiples of 90).
+ *  5 normalise out[c] = ((float) img[c'] - mean[c]) * std_inv[c], c' = 2 - c if to_rgb else c (OpenCV's BGR -> RGB swap
+ *             applied to Pillow's RGB image: a quirk of the reference, kept), std_inv[c] = (float) (1 / (double) std[c])
+ *             computed by the caller; one fp32 rounding per operation, no fused multiply-add; planar [3, H, W].
+ *
+ * All float64 work is the caller's: the kernels read int32 plan tables in DEVICE memory, so the augmentation can
+ * change under a replayed graph.  Per (b, n), for only the W resized columns and H resized rows the crop window
+ * touches:
+ *   col_first, col_count [B, N, W], col_taps [B, N, taps_x, W]: lo, hi - lo and ki of resized column x0 + x (tap-major);
+ *              count 0 for a column outside the resized image; row_first, row_count [B, N, H], row_taps [B, N, taps_y, H]
+ *              likewise for resized row y0 + y.
+ *   consts     [B, N, VAMP_IMG_CONST_COLS]: a0 .. a5, x0, y0, newW, newH, flip (0 | 1), zeros (the kernels read a0 .. a5
+ *              and flip; the crop is in the tables).
+ * Range: at most VAMP_IMG_MAX_TAPS = 16 taps per output (scale = in / out up to about 3.7 per axis, i.e. resize down
+ * to about 0.27; the reference draws 0.386 .. 0.55 and evaluates at 0.44; resize above 1 keeps support 2 and 4 - 5
+ * taps), and a raw footprint of at most VAMP_IMG_FOOT_W x VAMP_IMG_FOOT_H pixels under any VAMP_IMG_TILE_H x
+ * VAMP_IMG_TILE_W tile of the crop window; the descriptor carries the plan's tap capacities (the tables' strides) and
+ * its largest footprint, and a plan beyond the range is refused.  The kernels clamp every window to the raw image and
+ * to the footprint, so no table content can make them read or write out of bounds.
+ * Inputs: raw uint8, element (b, n, y, x, c) at raw + b raw_b_stride + n raw_n_stride + y raw_row_stride + 3 x + c
+ * (any row alignment).  Outputs, every element written: out [B, N, 3, H, W] fp32 | bf16 (round-to-nearest-even of the
+ * fp32 value), 16-byte aligned, NULL with out_dtype VAMP_IMG_OUT_NONE; out_u8 [B, N, H, W, 3], the image of rule 4,
+ * 4-byte aligned, or NULL; at least one of the two.
+ * Limits: 1 <= B <= 4096, 1 <= N <= 16, B N <= 65535, 1 <= raw_h, raw_w <= 65536, 1 <= H, W <= 4096.  Every argument
+ * is checked before any device work: a failed check returns VAMP_EINVAL (and a workspace size of 0) with a message, a
+ * workspace that is NULL or too small VAMP_ENOSPC.  Two launches on `stream` (resample: footprint to LDS, horizontal
+ * pass to a uint8 LDS tile, vertical pass to a uint8 staging image in the workspace; finish: rotate, flip, normalise),
+ * no atomics, no host synchronisation, bitwise repeatable, capturable in a graph.  The workspace (16-byte aligned,
+ * B N H align16(3 W) bytes) needs no initialisation.
+ * -------------------------------------------------------------------------- */
+#define VAMP_IMG_MAX_TAPS 16
+#define VAMP_IMG_TILE_W 64
+#define VAMP_IMG_TILE_H 8
+#define VAMP_IMG_FOOT_W 272
+#define VAMP_IMG_FOOT_H 48
+#define VAMP_IMG_CONST_COLS 16
+#define VAMP_IMG_OUT_NONE (-1)
+typedef struct VampImageDesc {
+  int64_t raw_b_stride, raw_n_stride, raw_row_stride;   /* bytes */
+  int32_t B, N;
+  int32_t raw_h, raw_w;
+  int32_t H, W;                   /* final_dim */
+  int32_t taps_x, taps_y;         /* tap capacity of col_taps / row_taps, 1 .. VAMP_IMG_MAX_TAPS */
+  int32_t foot_w, foot_h;         /* the plan's largest raw footprint under one tile, 1 .. VAMP_IMG_FOOT_W / _H */
+  int32_t out_dtype;              /* VAMP_F32 | VAMP_BF16 | VAMP_IMG_OUT_NONE */
+  int32_t to_rgb;                 /* 0 | 1 */
+  float mean[3], std_inv[3];
+  int32_t reserved[2];            /* 0 */
+} VampImageDesc;
+size_t vamp_camera_images_workspace_bytes(const VampImageDesc* d);
+int vamp_camera_images(const VampImageDesc* d, const uint8_t* raw, const int32_t* col_first, const int32_t* col_count,
+                       const int32_t* col_taps, const int32_t* row_first, const int32_t* row_count,
+                       const int32_t* row_taps, const int32_t* consts, void* out, uint8_t* out_u8, void* workspace,
+                       size_t workspace_bytes, void* stream);
 
 #ifdef __cplusplus
 }

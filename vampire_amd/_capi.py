@@ -29,6 +29,8 @@ VAMP_RESIZE2D_STRIP_CHUNK, VAMP_RESIZE2D_STRIP_MAX, VAMP_RESIZE2D_MAX_RUN = 256,
 VAMP_UPDATE_CHUNK, VAMP_UPDATE_GROWTH_INTERVAL = 4096, 2000
 VAMP_UPDATE_PARAM, VAMP_UPDATE_EMA_ONLY = 0, 1
 VAMP_UPDATE_SCALE_NONE, VAMP_UPDATE_SCALE_STATIC, VAMP_UPDATE_SCALE_DYNAMIC = 0, 1, 2
+VAMP_IMG_MAX_TAPS, VAMP_IMG_TILE_W, VAMP_IMG_TILE_H, VAMP_IMG_FOOT_W, VAMP_IMG_FOOT_H = 16, 64, 8, 272, 48
+VAMP_IMG_CONST_COLS, VAMP_IMG_OUT_NONE = 16, -1
 
 
 class VampLiftDesc(C.Structure):
@@ -166,6 +168,14 @@ class VampLidarLabelDesc(C.Structure):
                 ("label_dtype", C.c_int32), ("H", C.c_int32), ("W", C.c_int32), ("stride", C.c_int32),
                 ("raw_w", C.c_int32), ("raw_h", C.c_int32), ("ny", C.c_int32), ("nx", C.c_int32),
                 ("z_lo", C.c_float), ("z_hi", C.c_float), ("reserved", C.c_int32 * 2)]
+
+
+class VampImageDesc(C.Structure):
+    _fields_ = [("raw_b_stride", C.c_int64), ("raw_n_stride", C.c_int64), ("raw_row_stride", C.c_int64),
+                ("B", C.c_int32), ("N", C.c_int32), ("raw_h", C.c_int32), ("raw_w", C.c_int32),
+                ("H", C.c_int32), ("W", C.c_int32), ("taps_x", C.c_int32), ("taps_y", C.c_int32),
+                ("foot_w", C.c_int32), ("foot_h", C.c_int32), ("out_dtype", C.c_int32), ("to_rgb", C.c_int32),
+                ("mean", C.c_float * 3), ("std_inv", C.c_float * 3), ("reserved", C.c_int32 * 2)]
 
 
 class VampBevBackwardPlan(C.Structure):
@@ -317,6 +327,7 @@ _RLD = C.POINTER(VampRegLossDesc)
 _R2D = C.POINTER(VampResize2dDesc)
 _PUD = C.POINTER(VampParamUpdateDesc)
 _LLD = C.POINTER(VampLidarLabelDesc)
+_IMD = C.POINTER(VampImageDesc)
 
 # name -> (return kind, argtypes); must list every symbol declared in include/vampire_hip.h
 SIGNATURES = {
@@ -443,6 +454,8 @@ SIGNATURES = {
     "vamp_param_update_step": (_STATUS, [_PUD] + [_P] * 5 + [_P, C.c_size_t, _P]),
     "vamp_lidar_labels_workspace_bytes": (_SIZE, [_LLD]),
     "vamp_lidar_labels": (_STATUS, [_LLD] + [_P] * 12 + [_P, C.c_size_t, _P]),
+    "vamp_camera_images_workspace_bytes": (_SIZE, [_IMD]),
+    "vamp_camera_images": (_STATUS, [_IMD] + [_P] * 10 + [_P, C.c_size_t, _P]),
 }
 
 _lib = None
