@@ -839,6 +839,59 @@ int vamp_sample_points_backward(const VampSampleDesc* d, const void* volume, con
                                 void* workspace, size_t workspace_bytes, void* stream);
 
 /* --------------------------------------------------------------------------
+ * The four point queries of a step in one call (base_vampire2.py:576-609): the same values as the
+ * four vamp_sample_points_forward calls above -- the same fp32 chain, bit for bit -- from packed
+ * points with per-sample counts, and ONE backward: one cell list over both point sets and all
+ * samples, one gather that overwrites grad_semantic and grad_density once each.
+ *   pts_logits  [B, M, K]       bv2:590   border padding, channel-last   (lidar points)
+ *   pts_sdf     [B, M]          bv2:594-595  zeros padding x inside mask (when want_sdf)
+ *   occ_logits  [B, K, P_occ]   bv2:603   border padding                 (the bda-rotated occ grid, bv2:599-602)
+ *   occ_density [B, 1, P_occ]   bv2:604   zeros padding of density(density_feature); no tanh (bv2:609)
+ * counts [B] int32 on the device (NULL: all M rows), clamped to [0, M] in the kernels: rows i >= counts[b] of
+ * `points` and of the upstream gradients are never read, their output rows are exact 0.
+ * Launches do not depend on B; no float atomics on the volumes' gradients; no host synchronisation.
+ * -------------------------------------------------------------------------- */
+typedef struct {
+  int32_t B, K;            /* samples, semantic channels (K + 1 <= 32: the backward's widest gradient row) */
+  int32_t Z, Y, X;
+  float lo[3], span[3];    /* as in VampSampleDesc (bv2:581-586) */
+  int32_t density_mode;    /* VAMP_DENSITY_*; with sdf_bias / beta_min as in VampRenderDesc */
+  float sdf_bias, beta_min;
+  int32_t sem_dtype, den_dtype;   /* VAMP_F32 | VAMP_BF16 of `semantic` and of `density` */
+  int32_t M;               /* lidar-point capacity per sample; 0 = no lidar part */
+  int32_t want_sdf;        /* pts_sdf is asked for (the sdf density, bv2:593) */
+  int32_t P_occ;           /* occupancy points per sample; 0 = no occupancy part */
+  int32_t occ_shared;      /* occ_points is [1, P_occ, 3] for all samples (the static grid of
+                              base_lss_impaintor.py:611-616) instead of [B, P_occ, 3] */
+  int32_t lattice[3];      /* the occupancy points' lattice hint, as in VampSampleDesc */
+} VampQueryDesc;
+
+/* 1 when the entry points below take the descriptor (bv2:576-609 at these shapes), else 0 */
+int vamp_point_queries_supported(const VampQueryDesc* d);
+/* bytes of the backward's workspace (bv2:576-609); 0 for a descriptor that is refused */
+size_t vamp_point_queries_workspace_bytes(const VampQueryDesc* d);
+/*
+ * bv2:590, 594-595, 603, 604.  semantic [B, K, Z, Y, X], density [B, 1, Z, Y, X] (may be NULL when neither
+ * want_sdf nor P_occ asks for it); points [B, M, 3] fp32 ego-frame; occ_points [B | 1, P_occ, 3]; beta as in the
+ * render entry points (read only for occ_density with the sdf density).  Outputs fp32, fully overwritten.
+ */
+int vamp_point_queries_forward(const VampQueryDesc* d, const void* semantic, const void* density,
+                               const float* beta, const float* points, const int32_t* counts,
+                               const float* occ_points, float* pts_logits, float* pts_sdf,
+                               float* occ_logits, float* occ_density, void* stream);
+/*
+ * The backward of bv2:590, 594-595, 603, 604 in one pass.  g_* are the upstream gradients of the four outputs
+ * (any may be NULL: zero).  grad_semantic [B, K, Z, Y, X] and grad_density [B, 1, Z, Y, X] (NULL where
+ * `density` may be) fp32 are fully overwritten, once; grad_beta (1 float, may be NULL) is ACCUMULATED into.
+ */
+int vamp_point_queries_backward(const VampQueryDesc* d, const void* density, const float* beta,
+                                const float* points, const int32_t* counts, const float* occ_points,
+                                const float* g_pts_logits, const float* g_pts_sdf,
+                                const float* g_occ_logits, const float* g_occ_density,
+                                float* grad_semantic, float* grad_density, float* grad_beta,
+                                void* workspace, size_t workspace_bytes, void* stream);
+
+/* --------------------------------------------------------------------------
  * Producer / consumer steps either side of the path.
  *   depth softmax  base_vampire2.py:550  `mapping_along_depth(src).softmax(dim=1)`:
  *                  logits [images, D, HW] (fp32 | bf16, images = B * N cameras, HW = fH * fW)

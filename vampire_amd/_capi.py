@@ -75,6 +75,18 @@ class VampSampleDesc(C.Structure):
 
 
 VAMP_PAD_ZEROS, VAMP_PAD_BORDER = 0, 1
+
+
+class VampQueryDesc(C.Structure):
+    _fields_ = [("B", C.c_int32), ("K", C.c_int32),
+                ("Z", C.c_int32), ("Y", C.c_int32), ("X", C.c_int32),
+                ("lo", C.c_float * 3), ("span", C.c_float * 3),
+                ("density_mode", C.c_int32), ("sdf_bias", C.c_float), ("beta_min", C.c_float),
+                ("sem_dtype", C.c_int32), ("den_dtype", C.c_int32),
+                ("M", C.c_int32), ("want_sdf", C.c_int32), ("P_occ", C.c_int32), ("occ_shared", C.c_int32),
+                ("lattice", C.c_int32 * 3)]
+
+
 class VampConfDesc(C.Structure):
     _fields_ = [("B", C.c_int64), ("S", C.c_int64), ("K", C.c_int32), ("layout", C.c_int32),
                 ("pred_dtype", C.c_int32), ("target_dtype", C.c_int32), ("Kc", C.c_int32),
@@ -314,6 +326,7 @@ _P = TensorPtr
 _LD = C.POINTER(VampLiftDesc)
 _RD = C.POINTER(VampRenderDesc)
 _SD = C.POINTER(VampSampleDesc)
+_QYD = C.POINTER(VampQueryDesc)
 _CD = C.POINTER(VampConvDesc)
 _PD = C.POINTER(VampPoolDesc)
 _QD = C.POINTER(VampConfDesc)
@@ -385,6 +398,10 @@ SIGNATURES = {
     "vamp_sample_points_forward": (_STATUS, [_SD, _P, _P, _P, C.c_int64, _P, _P]),
     "vamp_sample_points_workspace_bytes": (_SIZE, [_SD, C.c_int64]),
     "vamp_sample_points_backward": (_STATUS, [_SD, _P, _P, _P, C.c_int64, _P, _P, _P, _P, C.c_size_t, _P]),
+    "vamp_point_queries_supported": (_INT, [_QYD]),
+    "vamp_point_queries_workspace_bytes": (_SIZE, [_QYD]),
+    "vamp_point_queries_forward": (_STATUS, [_QYD] + [_P] * 11),
+    "vamp_point_queries_backward": (_STATUS, [_QYD] + [_P] * 13 + [C.c_size_t, _P]),
     "vamp_depth_softmax_forward": (_STATUS, [C.c_int64, C.c_int32, C.c_int64, _P, C.c_int32, _P, _P]),
     "vamp_depth_softmax_backward": (_STATUS, [C.c_int64, C.c_int32, C.c_int64, _P, _P, _P, _P]),
     "vamp_density_gate_forward": (_STATUS, [C.c_int64, C.c_int32, C.c_int64, C.c_int32, _P, _P, _P, _P]),

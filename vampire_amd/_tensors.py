@@ -105,6 +105,16 @@ def _scalar(t: torch.Tensor, name):
     return t.reshape(1).float().contiguous()
 
 
+def _pad_samples(*lists):
+    """Per-sample lists of tensors [n_b, ...] (the lists agreeing on every n_b) -> one padded [B, M, ...] tensor per
+    list, zero-filled behind each sample's rows, and the int32 counts [B] on the samples' device.  The counts come
+    from the shapes, one scalar fill per sample: nothing is read back from the device and nothing is copied to it."""
+    pad = torch.nn.utils.rnn.pad_sequence
+    dev = lists[0][0].device
+    counts = torch.stack([torch.full((), p.shape[0], dtype=torch.int32, device=dev) for p in lists[0]])
+    return tuple(pad(list(l), batch_first=True) for l in lists) + (counts,)
+
+
 _scratch = {}
 
 

@@ -63,7 +63,9 @@ def _resize(x, size):
 # used, VAMP_GLUE=hip routes the depth softmax / density gate through the standalone HIP kernels,
 # VAMP_FUSE=0 turns the fused producer / consumer forms off, VAMP_CONV3D_S2=0 keeps MIOpen for the stride-2 3x3x3
 # layers under a 16-bit autocast (default: the HIP kernels of conv3d_bf16_s2.hip), VAMP_RESIZE2D=1 routes the x4
-# resize of the three rendered camera maps and the 256-cell grid's 0.5x resize through resize2d.hip (default: aten).
+# resize of the three rendered camera maps and the 256-cell grid's 0.5x resize through resize2d.hip (default: aten),
+# VAMP_QUERIES=fused answers the lidar-point and occupancy queries with one `HotPath.point_queries` call (default:
+# split, one `sample_points` call per sample and volume plus `occupancy_queries`).
 # Tests and tools flip the attributes of `SWITCHES`.
 class _Switches:
     conv3d = os.environ.get("VAMP_CONV3D", "1") != "0"
@@ -81,6 +83,9 @@ class _Switches:
     # profiles/resize2d.json); default off all the same: eager the path is host-bound and lost on the BEV feature in
     # one of five runs
     resize2d = os.environ.get("VAMP_RESIZE2D", "0") == "1"
+    # the point queries of bv2:576-609: "split" = 2 B + 2 `sample_points` calls, each an autograd node with a cell list
+    # and a full-size gradient volume of its own; "fused" = one `point_queries` call, one backward
+    queries = os.environ.get("VAMP_QUERIES", "split")
 
 
 SWITCHES = _Switches()
@@ -473,24 +478,28 @@ class BaseVAMPIRE2(nn.Module):
         # lidar-point queries (bv2:576-596) and occupancy resampling on the bda-rotated Occ3D grid
         # (bv2:597-609): HIP point resampling, `hp` may be an oracle stand-in on CPU
         beta = self._beta()
-        pts_logits_batch, pts_sdf_batch = [], []
-        if inrange_pts is not None:
-            for i in range(B):
-                pts = inrange_pts[i][None].float()
-                pts_logits_batch.append(hp.sample_points(semantic_logits[[i]].float(), pts, padding="border",
-                                                         channel_last=True)[0])
-                if self.density_mode == "sdf":
-                    pts_sdf_batch.append(hp.sample_points(density_feature[[i]].float(), pts,
-                                                          mask_outside=True)[0, 0])
-        if not occupancy:
-            occ_logits = occ_density = None
-        elif self._ROTATE_OCC:
-            occ_logits, occ_density = hp.occupancy_queries(semantic_logits.float(), density_feature.float(),
-                                                           self.occ_coords, mats_dict.get("bda_mat", None), beta)
+        if SWITCHES.queries == "fused" and hasattr(hp, "point_queries"):
+            pts_logits_batch, pts_sdf_batch, occ_logits, occ_density = self._fused_queries(
+                hp, semantic_logits, density_feature, beta, mats_dict, inrange_pts, occupancy)
         else:
-            # static grid (base_lss_impaintor.py:611-616): the same queries without the bda rotation
-            occ_logits, occ_density = hp.occupancy_queries(semantic_logits.float(), density_feature.float(),
-                                                           self._occ_points, None, beta)
+            pts_logits_batch, pts_sdf_batch = [], []
+            if inrange_pts is not None:
+                for i in range(B):
+                    pts = inrange_pts[i][None].float()
+                    pts_logits_batch.append(hp.sample_points(semantic_logits[[i]].float(), pts, padding="border",
+                                                             channel_last=True)[0])
+                    if self.density_mode == "sdf":
+                        pts_sdf_batch.append(hp.sample_points(density_feature[[i]].float(), pts,
+                                                              mask_outside=True)[0, 0])
+            if not occupancy:
+                occ_logits = occ_density = None
+            elif self._ROTATE_OCC:
+                occ_logits, occ_density = hp.occupancy_queries(semantic_logits.float(), density_feature.float(),
+                                                               self.occ_coords, mats_dict.get("bda_mat", None), beta)
+            else:
+                # static grid (base_lss_impaintor.py:611-616): the same queries without the bda rotation
+                occ_logits, occ_density = hp.occupancy_queries(semantic_logits.float(), density_feature.float(),
+                                                               self._occ_points, None, beta)
 
         (rgb_p, seg_p, depth_p, bev_rgb, bev_seg, bev_height, bev_density, voxel_output) = \
             self.render(mats_dict, sweep_index, density_feature, semantic_logits, base, rgb)
@@ -524,6 +533,33 @@ class BaseVAMPIRE2(nn.Module):
                 bev_density, pts_logits_batch, pts_sdf_batch,
                 None if occ_logits is None else occ_logits.permute(0, 2, 3, 4, 1),
                 None if occ_density is None else occ_density.permute(0, 2, 3, 4, 1).tanh())
+
+    def _fused_queries(self, hp, semantic_logits, density_feature, beta, mats_dict, inrange_pts, occupancy):
+        """The queries of bv2:576-609 as ONE `point_queries` call (SWITCHES.queries == "fused"): (pts_logits_batch,
+        pts_sdf_batch, occ_logits, occ_density) with the shapes of the split path -- the per-sample results are the
+        slices [b, :n_b] of the packed outputs."""
+        B = semantic_logits.shape[0]
+        sdf = self.density_mode == "sdf"
+        points = None if inrange_pts is None else [inrange_pts[i].float() for i in range(B)]
+        occ_points = shp = None
+        if occupancy:
+            if self._ROTATE_OCC:
+                grid, bda = self.occ_coords, mats_dict.get("bda_mat", None)
+            else:       # static grid (base_lss_impaintor.py:611-616): [1, P, 3] for all samples
+                grid, bda = self._occ_points, None
+            occ_points, shp = hp.occupancy_points(grid, bda), tuple(grid.shape[:3])
+        pts_logits_batch, pts_sdf_batch, occ_logits, occ_density = [], [], None, None
+        if points is None and occ_points is None:
+            return pts_logits_batch, pts_sdf_batch, occ_logits, occ_density
+        q = hp.point_queries(semantic_logits.float(), density_feature.float(), beta, points=points,
+                             sdf=sdf and points is not None, occ_points=occ_points, lattice=shp)
+        if points is not None:
+            pts_logits_batch = [q.pts_logits[b, :p.shape[0]] for b, p in enumerate(points)]
+            if sdf:
+                pts_sdf_batch = [q.pts_sdf[b, :p.shape[0]] for b, p in enumerate(points)]
+        if occ_points is not None:
+            occ_logits, occ_density = q.occ_logits.reshape(B, -1, *shp), q.occ_density.reshape(B, 1, *shp)
+        return pts_logits_batch, pts_sdf_batch, occ_logits, occ_density
 
     def _half_resize(self, x):
         """`voxel_output[1]`, the 0.5x UpsamplingBilinear2d of the 256-cell grid (bv2:205): resize2d.hip when

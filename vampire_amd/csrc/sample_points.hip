@@ -12,7 +12,7 @@
 // applied to the eight taps on the fly.  Backward: the same cell-list scheme as the render
 // backward (cell_list.hpp): rank -> scan -> fill -> per-voxel gather, no float atomics, with
 // the activation's derivative applied once per voxel.
-#include "cell_list.hpp"
+#include "point_sample.hpp"
 
 #include <algorithm>
 
@@ -21,15 +21,6 @@ namespace vamp {
 constexpr int kPtsHeavy = 256;
 constexpr int PGL = 8;                 // lanes per voxel in the gather
 constexpr int PVPB = 256 / PGL;
-
-struct SampleParams {
-  int B, C, Z, Y, X, Pb;
-  float lo[3], span[3];
-  int border, mask_outside, activation, channel_last;
-  int density_mode;
-  float sdf_bias, beta_min;
-  int n0, n12;             // lattice hint: n0 points along axis 0, n1 * n2 per axis-0 step (0 = none)
-};
 
 static SampleParams to_params(const VampSampleDesc* d, int points_per_sample) {
   SampleParams p;
@@ -60,40 +51,11 @@ static int validate(const VampSampleDesc* d, long n) {
   return VAMP_OK;
 }
 
-// density parameters when the activation is on (beta is only read then)
-__device__ __forceinline__ DensityParams pts_density(const SampleParams& P, const float* __restrict__ beta_raw) {
-  if (P.activation) return load_density(P.density_mode, beta_raw, P.beta_min, P.sdf_bias);
-  DensityParams dp;
-  dp.mode = VAMP_DENSITY_SIGMOID; dp.beta = 1.f; dp.ib = 1.f; dp.bias = 0.f;
-  return dp;
-}
-
-// continuous tap coordinates of a point (aten: normalise by the bounds, unnormalise with
-// align_corners=True, clip for 'border'), and the reference's inside mask
-struct PointTap {
-  float fx, fy, fz;
-  bool inside;       // all(-1 <= n <= 1)        (bv2:587-589)
-};
-__device__ __forceinline__ PointTap point_tap(const SampleParams& P, const float* __restrict__ pt) {
-  const float gx = ((pt[0] - P.lo[0]) / P.span[0]) * 2.0f - 1.0f;
-  const float gy = ((pt[1] - P.lo[1]) / P.span[1]) * 2.0f - 1.0f;
-  const float gz = ((pt[2] - P.lo[2]) / P.span[2]) * 2.0f - 1.0f;
-  PointTap t;
-  t.inside = gx >= -1.0f && gx <= 1.0f && gy >= -1.0f && gy <= 1.0f && gz >= -1.0f && gz <= 1.0f;
-  t.fx = ((gx + 1.0f) / 2.0f) * (float) (P.X - 1);
-  t.fy = ((gy + 1.0f) / 2.0f) * (float) (P.Y - 1);
-  t.fz = ((gz + 1.0f) / 2.0f) * (float) (P.Z - 1);
-  if (P.border) {                     // clip_coordinates: min(size - 1, max(coord, 0)); nan -> 0
-    t.fx = fminf((float) (P.X - 1), fmaxf(t.fx, 0.f));
-    t.fy = fminf((float) (P.Y - 1), fmaxf(t.fy, 0.f));
-    t.fz = fminf((float) (P.Z - 1), fmaxf(t.fz, 0.f));
-  }
-  return t;
-}
-
 // ---------------------------------------------------------------------------
 // forward
 // ---------------------------------------------------------------------------
+// (the taps, weights and fma order below are also point_sample.hpp's point_taps8 / taps8_sample, which
+// point_queries.hip uses; this kernel keeps its own statement of them, so that its code is what it was)
 template <typename T>
 __global__ void __launch_bounds__(256)
 sample_points_fwd_kernel(SampleParams P, const T* __restrict__ vol, const float* __restrict__ beta_raw,
@@ -205,25 +167,6 @@ sample_points_grad_rows_kernel(SampleParams P, const float* __restrict__ gout, f
     float v = 0.f;
     if (c < P.C) v = P.channel_last ? gout[gid * P.C + c] : gout[(b * P.C + c) * P.Pb + p];
     G[gid * CP + c] = v;
-  }
-}
-
-template <int CP4>
-__device__ __forceinline__ void point_accumulate(const CellRanges& cr, int k, const float4* __restrict__ R,
-                                                 const float* __restrict__ G, float fix, float fiy,
-                                                 float fiz, float (&acc)[CP4 * 4]) {
-  constexpr int CP = CP4 * 4;
-  const bool in = k < cr.tot;
-  const float4 a = R[cell_pos(cr, min(k, cr.tot - 1))];
-  const float wt = in ? cell_tap_weight(a.x, fix) * cell_tap_weight(a.y, fiy) * cell_tap_weight(a.z, fiz) : 0.f;
-  const float4* g4 = reinterpret_cast<const float4*>(G + (long) __float_as_int(a.w) * CP);
-#pragma unroll
-  for (int c4 = 0; c4 < CP4; ++c4) {
-    const float4 f = g4[c4];
-    acc[c4 * 4] = __builtin_fmaf(wt, f.x, acc[c4 * 4]);
-    acc[c4 * 4 + 1] = __builtin_fmaf(wt, f.y, acc[c4 * 4 + 1]);
-    acc[c4 * 4 + 2] = __builtin_fmaf(wt, f.z, acc[c4 * 4 + 2]);
-    acc[c4 * 4 + 3] = __builtin_fmaf(wt, f.w, acc[c4 * 4 + 3]);
   }
 }
 

@@ -10,7 +10,7 @@ import numpy as np
 import torch
 
 from . import _capi
-from ._tensors import DTYPE_CODES, _aligned, _stream, _workspace
+from ._tensors import DTYPE_CODES, _aligned, _pad_samples, _stream, _workspace
 
 _LABEL_DTYPES = (torch.uint8, torch.int64)
 
@@ -53,10 +53,7 @@ def _pack_points(points, labels, counts):
         raise ValueError("every sample needs points [n, 3 | 4] and labels [n]")
     if len({p.shape[1] for p in points}) != 1:
         raise ValueError("the samples' points must share one column count")
-    pad = torch.nn.utils.rnn.pad_sequence
-    dev = points[0].device
-    counts = torch.stack([torch.full((), p.shape[0], dtype=torch.int32, device=dev) for p in points])
-    return pad(list(points), batch_first=True), pad(list(labels), batch_first=True), counts
+    return _pad_samples(points, labels)
 
 
 def _bev_grid(bev):

@@ -535,6 +535,38 @@ class HotPath:
         dens = self.sample_points(density_feature, pts, activation=True, beta=beta, lattice=shp)
         return logits.reshape(B, -1, *shp), dens.reshape(B, 1, *shp)
 
+    def occupancy_points(self, occ_coords, bda_mat):
+        """The occ grid [n0, n1, n2, 3] as the points `point_queries` takes: rotated by bda[:3, :3] per sample (bv2:599)
+        -> [B, P, 3], with the torch.matmul of `occupancy_queries` (the same bits); bda_mat None: the static grid of
+        BaseLSSImpaintor / BaseLSS / BaseBiLinear -> [1, P, 3], shared by all samples."""
+        if not occ_coords.is_cuda or not (bda_mat is None or bda_mat.is_cuda):
+            raise _capi.VampireHipError("occ_coords and bda_mat must be device tensors (no CPU fallback)")
+        if occ_coords.dim() != 4 or occ_coords.shape[-1] != 3:
+            raise ValueError(f"occ_coords: expected shape [n0, n1, n2, 3], got {tuple(occ_coords.shape)}")
+        if bda_mat is None:
+            return occ_coords.reshape(1, -1, 3).float()
+        if bda_mat.dim() != 3 or min(bda_mat.shape[1:]) < 3:
+            raise ValueError(f"bda_mat: expected shape (B, 4, 4), got {tuple(bda_mat.shape)}")
+        return torch.matmul(occ_coords.reshape(1, -1, 3).float(), bda_mat[:, :3, :3].float().transpose(1, 2))
+
+    def point_queries(self, semantic_logits, density_feature, beta=None, *, points=None, counts=None, sdf=False,
+                      occ_points=None, lattice=None):
+        """The four point queries of a step (bv2:576-609) in one operator and one autograd node: one forward launch per
+        point set, one backward with one cell list that writes each volume's gradient once.  Same bits as the four
+        `sample_points` / `occupancy_queries` calls.
+
+        semantic_logits [B, K, Z, Y, X] (K + 1 <= 32), density_feature [B, 1, Z, Y, X] (None when neither `sdf` nor
+        `occ_points` asks for it); fp32 or bf16 each, gradients come back in each volume's dtype.
+        points: per-sample list of [n_b, 3] ego-frame points, padded here without reading anything back, or a packed
+        [B, M, 3] tensor with `counts` (int32 [B] on the device; None: all M rows).  Rows beyond a count are never
+        read (they may hold NaN) and their output rows are exact 0; with packed inputs the call can be captured in a
+        graph and replayed with other counts.  sdf: also return pts_sdf (bv2:594-595).
+        occ_points: [B, P, 3] or [1, P, 3] (`occupancy_points`); lattice: the grid's (n0, n1, n2), a layout hint.
+        Returns PointQueries(pts_logits [B, M, K], pts_sdf [B, M], occ_logits [B, K, P], occ_density [B, 1, P]); the
+        parts not asked for are None.  occ_density is the sampled density, without the module's tanh."""
+        from .queries import point_queries
+        return point_queries(self, semantic_logits, density_feature, beta, points=points, counts=counts, sdf=sdf,
+                             occ_points=occ_points, lattice=lattice)
 
     # ------------------------------------------------- producer / consumer glue (SURVEY 8f N2)
     def depth_softmax(self, logits):
