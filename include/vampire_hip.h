@@ -33,8 +33,8 @@ extern "C" {
                                  14: masked regression losses; 15: the camera render's plans and workspace layout;
                                  16: the lift's plans and workspace layout;
                                  16 also: stride-2 16-bit convolutions, the 2-D bilinear resize of the rendered maps and the
-                                 parameter update, the lidar-point label rasteriser, the camera images; the number could not move: a test
-                                 pins it) */
+                                 parameter update, the lidar-point label rasteriser, the camera images, detection scoring; the number
+                                 could not move: a test pins it) */
 
 enum {
   VAMP_OK = 0,
@@ -1673,6 +1673,68 @@ int vamp_camera_images(const VampImageDesc* d, const uint8_t* raw, const int32_t
                        const int32_t* col_taps, const int32_t* row_first, const int32_t* row_count,
                        const int32_t* row_taps, const int32_t* consts, void* out, uint8_t* out_u8, void* workspace,
                        size_t workspace_bytes, void* stream);
+
+/* --------------------------------------------------------------------------
+ * Detection scoring, the per-batch half: what the reference leaves to the nuScenes devkit's NuScenesEval behind
+ * src/evaluators/det_evaluators.py:61-117 (`_evaluate_single`; the attribute of a prediction is the speed rule of
+ * :254-274, the class ranges, distance thresholds and the 2 m true-positive threshold are `detection_cvpr_2019`,
+ * loaded at :50-55), fed by `test_step`'s get_bboxes results (src/exps/nuscenes/base_exp.py:665-746).  This is the
+ * project's own restatement of the published protocol; parity with the devkit is unpinned.
+ * Inputs: the detections of vamp_det_postprocess -- boxes [B, M, box_cols] fp32 (x y z dx dy dz yaw [vx vy]), scores
+ * [B, M] (score_dtype), labels [B, M] int32, counts [B] int32 -- and the padded ground truth gt_boxes [B, G, box_cols]
+ * fp32, gt_labels [B, G] (gt_label_dtype; a padding row carries -1), gt_attrs [B, G] int8 (index of the attribute name
+ * or -1 for none; NULL with has_attrs 0: no ground truth has one).
+ *
+ *  filter     a box counts when sqrt(x^2 + y^2) < class_range[class], in float64 from the fp32 centre.
+ *  order      per (sample, class) the surviving predictions by score descending, higher row first among equals.
+ *  match      per distance threshold its own taken set: the prediction takes the nearest not yet taken ground truth of
+ *             its class and sample (squared xy distance in float64, lowest row among equals) when that distance is
+ *             strictly below the threshold, and is a false positive otherwise -- it never falls back to a farther one.
+ *  errors     of the match at dist_th_tp, in float64, rounded to fp32: centre distance; 1 - IoU of the aligned sizes;
+ *             |yaw difference| folded to period pi (VAMP_DET_EVAL_HALF_PERIOD) or 2 pi; velocity difference; 1 -
+ *             [attribute equal], NaN when the ground truth has none.  An error the class does not define (flags) is NaN.
+ *  records    32 bytes per detection row at slot (cursor + b) M + row of `records`: fp32 score; a word with the class in
+ *             bits 0-7, valid in bit 8 and the thresholds' true-positive bits in 16-19; the five fp32 errors (trans,
+ *             scale, orient, vel, attr; NaN without a match at dist_th_tp); one zero word.  Every slot of the batch is
+ *             written once, rows at or beyond counts[b] and filtered rows as invalid (all zero).
+ *  state      int64: [0] the sample cursor (read here; the caller adds B on the same stream afterwards), [1] samples
+ *             with counts[b] > max_boxes_per_sample, [2] (sample, class) pairs with more than VAMP_DET_EVAL_GT_CAP
+ *             ground-truth boxes, [3] labels outside [0, num_classes) (padding excepted), [4] batches that did not fit
+ *             (cursor + B > max_samples: nothing else is written), [8 + c] the surviving ground truth of class c.
+ *             All by integer atomic adds.
+ * Limits: 1 <= B <= 4096, 1 <= M <= VAMP_DET_EVAL_MAX_WIDTH, 0 <= G <= 2^20, box_cols 7 | 9, 1 <= num_classes <=
+ * VAMP_DET_EVAL_MAX_CLASSES, ascending positive thresholds with dist_th_tp among them, max_samples M < 2^31.  Every
+ * argument is checked before any device work.  One launch on `stream`, one workgroup per (sample, class); no float
+ * atomics, no host synchronisation, the record bytes are a pure function of the inputs; capturable in a graph.
+ * -------------------------------------------------------------------------- */
+#define VAMP_DET_EVAL_MAX_CLASSES 16
+#define VAMP_DET_EVAL_GT_CAP 256        /* ground-truth boxes of one class in one sample held in LDS */
+#define VAMP_DET_EVAL_MAX_WIDTH 2048
+#define VAMP_DET_EVAL_RECORD_BYTES 32
+#define VAMP_DET_EVAL_STATE_WORDS 24    /* int64 words of `state`: 8 counters, then VAMP_DET_EVAL_MAX_CLASSES npos */
+enum { VAMP_DET_EVAL_HALF_PERIOD = 1, VAMP_DET_EVAL_HAS_ORIENT = 2, VAMP_DET_EVAL_HAS_VEL = 4, VAMP_DET_EVAL_HAS_ATTR = 8 };
+typedef struct VampDetEvalDesc {
+  double class_range[VAMP_DET_EVAL_MAX_CLASSES];   /* metres */
+  double dist_ths[4];                              /* ascending */
+  double dist_th_tp;                               /* one of dist_ths */
+  int32_t B, M, G;
+  int32_t box_cols;                                /* 7 | 9 */
+  int32_t score_dtype;                             /* VAMP_F32 | VAMP_BF16 | VAMP_F16 */
+  int32_t gt_label_dtype;                          /* VAMP_I32 | VAMP_I64 */
+  int32_t has_attrs;                               /* 0 | 1 */
+  int32_t num_classes;
+  int32_t max_boxes_per_sample;
+  int32_t max_samples;                             /* capacity of `records` in samples */
+  int32_t class_flags[VAMP_DET_EVAL_MAX_CLASSES];  /* VAMP_DET_EVAL_* bits */
+  int32_t attr_moving[VAMP_DET_EVAL_MAX_CLASSES];  /* predicted attribute above 0.2 m/s, -1: none */
+  int32_t attr_still[VAMP_DET_EVAL_MAX_CLASSES];   /* ... and at or below */
+  int32_t reserved[2];                             /* 0 */
+} VampDetEvalDesc;
+int vamp_det_eval_supported(const VampDetEvalDesc* d);
+size_t vamp_det_eval_record_bytes(const VampDetEvalDesc* d);
+int vamp_det_eval_update(const VampDetEvalDesc* d, const float* boxes, const void* scores, const int32_t* labels,
+                         const int32_t* counts, const float* gt_boxes, const void* gt_labels, const int8_t* gt_attrs,
+                         void* records, int64_t* state, void* stream);
 
 #ifdef __cplusplus
 }

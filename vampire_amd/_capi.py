@@ -31,6 +31,9 @@ VAMP_UPDATE_PARAM, VAMP_UPDATE_EMA_ONLY = 0, 1
 VAMP_UPDATE_SCALE_NONE, VAMP_UPDATE_SCALE_STATIC, VAMP_UPDATE_SCALE_DYNAMIC = 0, 1, 2
 VAMP_IMG_MAX_TAPS, VAMP_IMG_TILE_W, VAMP_IMG_TILE_H, VAMP_IMG_FOOT_W, VAMP_IMG_FOOT_H = 16, 64, 8, 272, 48
 VAMP_IMG_CONST_COLS, VAMP_IMG_OUT_NONE = 16, -1
+VAMP_DET_EVAL_MAX_CLASSES, VAMP_DET_EVAL_GT_CAP, VAMP_DET_EVAL_MAX_WIDTH = 16, 256, 2048
+VAMP_DET_EVAL_RECORD_BYTES, VAMP_DET_EVAL_STATE_WORDS = 32, 24
+VAMP_DET_EVAL_HALF_PERIOD, VAMP_DET_EVAL_HAS_ORIENT, VAMP_DET_EVAL_HAS_VEL, VAMP_DET_EVAL_HAS_ATTR = 1, 2, 4, 8
 
 
 class VampLiftDesc(C.Structure):
@@ -190,6 +193,16 @@ class VampImageDesc(C.Structure):
                 ("mean", C.c_float * 3), ("std_inv", C.c_float * 3), ("reserved", C.c_int32 * 2)]
 
 
+class VampDetEvalDesc(C.Structure):
+    _fields_ = [("class_range", C.c_double * VAMP_DET_EVAL_MAX_CLASSES), ("dist_ths", C.c_double * 4),
+                ("dist_th_tp", C.c_double), ("B", C.c_int32), ("M", C.c_int32), ("G", C.c_int32),
+                ("box_cols", C.c_int32), ("score_dtype", C.c_int32), ("gt_label_dtype", C.c_int32),
+                ("has_attrs", C.c_int32), ("num_classes", C.c_int32), ("max_boxes_per_sample", C.c_int32),
+                ("max_samples", C.c_int32), ("class_flags", C.c_int32 * VAMP_DET_EVAL_MAX_CLASSES),
+                ("attr_moving", C.c_int32 * VAMP_DET_EVAL_MAX_CLASSES),
+                ("attr_still", C.c_int32 * VAMP_DET_EVAL_MAX_CLASSES), ("reserved", C.c_int32 * 2)]
+
+
 class VampBevBackwardPlan(C.Structure):
     """What vamp_render_bev_backward_ex will launch (vamp_render_bev_backward_plan; include/vampire_hip.h)."""
     _fields_ = [("scan_lds", C.c_int64), ("path", C.c_int32), ("z_lo", C.c_int32), ("z_hi", C.c_int32),
@@ -341,6 +354,7 @@ _R2D = C.POINTER(VampResize2dDesc)
 _PUD = C.POINTER(VampParamUpdateDesc)
 _LLD = C.POINTER(VampLidarLabelDesc)
 _IMD = C.POINTER(VampImageDesc)
+_DED = C.POINTER(VampDetEvalDesc)
 
 # name -> (return kind, argtypes); must list every symbol declared in include/vampire_hip.h
 SIGNATURES = {
@@ -473,6 +487,9 @@ SIGNATURES = {
     "vamp_lidar_labels": (_STATUS, [_LLD] + [_P] * 12 + [_P, C.c_size_t, _P]),
     "vamp_camera_images_workspace_bytes": (_SIZE, [_IMD]),
     "vamp_camera_images": (_STATUS, [_IMD] + [_P] * 10 + [_P, C.c_size_t, _P]),
+    "vamp_det_eval_supported": (_INT, [_DED]),
+    "vamp_det_eval_record_bytes": (_SIZE, [_DED]),
+    "vamp_det_eval_update": (_STATUS, [_DED] + [_P] * 9 + [_P]),
 }
 
 _lib = None

@@ -497,3 +497,175 @@ def det_loss(task_preds, targets, code_weights, loss_bbox_weight=0.25, *, counts
     loss, terms = _DetLoss.apply(d, len(keys), heat, anno, inds, masks, counts, *flat)
     loss.terms = terms
     return loss
+
+
+# ===========================================================================
+# detection scoring (det_evaluators.py:61-117, :254-274; base_exp.py:665-746)
+# ===========================================================================
+# the attribute names a ground-truth attribute index points into
+ATTRIBUTE_NAMES = ("cycle.with_rider", "cycle.without_rider", "pedestrian.moving", "pedestrian.standing",
+                   "pedestrian.sitting_lying_down", "vehicle.moving", "vehicle.parked", "vehicle.stopped")
+# detection_cvpr_2019's class ranges (metres)
+CLASS_RANGE = {"car": 50.0, "truck": 50.0, "bus": 50.0, "trailer": 50.0, "construction_vehicle": 50.0,
+               "pedestrian": 40.0, "motorcycle": 40.0, "bicycle": 40.0, "traffic_cone": 30.0, "barrier": 30.0}
+# det_evaluators.py:24-35 and :254-274: class -> (attribute above 0.2 m/s, attribute at or below), '' for none
+_DEFAULT_ATTRIBUTE = {"car": "vehicle.parked", "pedestrian": "pedestrian.moving", "trailer": "vehicle.parked",
+                      "truck": "vehicle.parked", "bus": "vehicle.moving", "motorcycle": "cycle.without_rider",
+                      "construction_vehicle": "vehicle.parked", "bicycle": "cycle.without_rider", "barrier": "",
+                      "traffic_cone": ""}
+
+
+def predicted_attributes(name):
+    """(moving, still): the attribute names det_evaluators.py:254-274 gives a prediction of class `name`."""
+    default = _DEFAULT_ATTRIBUTE[name]
+    if name in ("car", "construction_vehicle", "bus", "truck", "trailer"):
+        moving = "vehicle.moving"
+    elif name in ("bicycle", "motorcycle"):
+        moving = "cycle.with_rider"
+    else:
+        moving = default
+    still = "pedestrian.standing" if name == "pedestrian" else "vehicle.stopped" if name == "bus" else default
+    return moving, still
+
+
+@dataclasses.dataclass
+class DetEvalState:
+    """What det_eval_update accumulates, all on the device: `records` int32 [max_samples * max_dets, 8] (per
+    detection row: the fp32 score's bits; class | valid << 8 | true-positive bits << 16; the bits of the five fp32
+    errors trans, scale, orient, vel, attr; 0) and `state` int64 [24]: the sample cursor, the four error counters
+    (samples over max_boxes_per_sample, (sample, class) pairs over the ground-truth cap, labels outside the class
+    list, batches that did not fit) at 1 .. 4 and npos per class from 8 on."""
+    records: torch.Tensor
+    state: torch.Tensor
+    class_names: tuple
+    max_samples: int
+    max_dets: int
+    class_range: tuple
+    dist_ths: tuple = (0.5, 1.0, 2.0, 4.0)
+    dist_th_tp: float = 2.0
+    max_boxes_per_sample: int = 500
+
+    @classmethod
+    def new(cls, class_names, max_samples, max_dets, device="cuda", class_range=None, **protocol):
+        names = tuple(class_names)
+        ranges = CLASS_RANGE if class_range is None else class_range
+        missing = [n for n in names if n not in ranges or n not in _DEFAULT_ATTRIBUTE]
+        if missing:
+            raise ValueError(f"no class range or attribute rule for {missing}")
+        if not 1 <= len(names) <= _capi.VAMP_DET_EVAL_MAX_CLASSES:
+            raise ValueError(f"{len(names)} classes (1 to {_capi.VAMP_DET_EVAL_MAX_CLASSES})")
+        self = cls(None, None, names, int(max_samples), int(max_dets), tuple(float(ranges[n]) for n in names), **protocol)
+        self.dist_ths = tuple(float(t) for t in self.dist_ths)
+        nbytes = _capi.checked().vamp_det_eval_record_bytes(self.desc(1, 0, 9, torch.float32, torch.int64, False))
+        if nbytes == 0:
+            raise ValueError(f"det_eval: {_capi.checked().vamp_last_error().decode('utf-8', 'replace')}")
+        self.records = torch.zeros(nbytes // 32, 8, dtype=torch.int32, device=device)
+        self.state = torch.zeros(_capi.VAMP_DET_EVAL_STATE_WORDS, dtype=torch.int64, device=device)
+        return self
+
+    def desc(self, B, G, cols, score_dtype, label_dtype, has_attrs):
+        d = _capi.VampDetEvalDesc()
+        d.B, d.M, d.G, d.box_cols = B, self.max_dets, G, cols
+        d.score_dtype, d.gt_label_dtype, d.has_attrs = DTYPE_CODES[score_dtype], DTYPE_CODES[label_dtype], int(has_attrs)
+        d.num_classes, d.max_boxes_per_sample, d.max_samples = len(self.class_names), int(self.max_boxes_per_sample), self.max_samples
+        for h in range(4):
+            d.dist_ths[h] = self.dist_ths[h]
+        d.dist_th_tp = float(self.dist_th_tp)
+        for c, name in enumerate(self.class_names):
+            d.class_range[c] = self.class_range[c]
+            flags = _capi.VAMP_DET_EVAL_HAS_ORIENT | _capi.VAMP_DET_EVAL_HAS_VEL | _capi.VAMP_DET_EVAL_HAS_ATTR
+            if name == "traffic_cone":
+                flags = 0
+            elif name == "barrier":
+                flags = _capi.VAMP_DET_EVAL_HAS_ORIENT | _capi.VAMP_DET_EVAL_HALF_PERIOD
+            d.class_flags[c] = flags
+            moving, still = predicted_attributes(name)
+            d.attr_moving[c] = ATTRIBUTE_NAMES.index(moving) if moving else -1
+            d.attr_still[c] = ATTRIBUTE_NAMES.index(still) if still else -1
+        return d
+
+    def reset(self):
+        self.state.zero_()
+
+
+def _pack_gt(gt_boxes, gt_labels, gt_attrs):
+    """Per-sample lists -> padded [B, G, 7 | 9], [B, G] (label -1) and [B, G] int8 (attribute -1) on the device,
+    without a host synchronisation; packed tensors pass through."""
+    if isinstance(gt_boxes, torch.Tensor):
+        if not isinstance(gt_labels, torch.Tensor) or not (gt_attrs is None or isinstance(gt_attrs, torch.Tensor)):
+            raise ValueError("gt_boxes is a packed tensor but gt_labels or gt_attrs is not")
+        return gt_boxes, gt_labels, gt_attrs
+    lists = [gt_boxes, gt_labels] + ([] if gt_attrs is None else [gt_attrs])
+    if any(len(l) != len(gt_boxes) for l in lists) or len(gt_boxes) == 0:
+        raise ValueError(f"{[len(l) for l in lists]} tensors per list (one per sample, at least one)")
+    if not all(x.is_cuda for l in lists for x in l):
+        raise _capi.VampireHipError("det_eval_update needs device tensors (no CPU fallback)")
+    if any(b.dtype != torch.float32 for b in gt_boxes):
+        raise TypeError(f"gt_boxes must be fp32, got {sorted({str(b.dtype) for b in gt_boxes})}")
+    if len({l.dtype for l in gt_labels}) != 1:
+        raise TypeError(f"gt_labels must share one dtype, got {sorted({str(l.dtype) for l in gt_labels})}")
+    if gt_attrs is not None and any(a.dtype != torch.int8 for a in gt_attrs):
+        raise TypeError(f"gt_attrs must be int8, got {sorted({str(a.dtype) for a in gt_attrs})}")
+    for s, (bx, lb) in enumerate(zip(gt_boxes, gt_labels)):
+        if bx.dim() != 2 or lb.dim() != 1 or bx.shape[0] != lb.shape[0] \
+                or (gt_attrs is not None and tuple(gt_attrs[s].shape) != tuple(lb.shape)):
+            raise ValueError(f"sample {s}: expected gt boxes [n, 7 | 9] with labels (and attributes) [n], got "
+                             f"{tuple(bx.shape)} and {tuple(lb.shape)}")
+    if len({b.shape[1] for b in gt_boxes}) != 1:
+        raise ValueError(f"gt_boxes differ in width: {sorted({b.shape[1] for b in gt_boxes})}")
+    pad = torch.nn.utils.rnn.pad_sequence
+    return (pad(list(gt_boxes), batch_first=True), pad(list(gt_labels), batch_first=True, padding_value=-1),
+            None if gt_attrs is None else pad(list(gt_attrs), batch_first=True, padding_value=-1))
+
+
+def det_eval_update(state, det, gt_boxes, gt_labels, gt_attrs=None):
+    """One validation batch of the nuScenes detection protocol (vamp_det_eval_update): per sample, class
+    and distance threshold the greedy nearest-centre matching of the range-filtered detections, in score order, to
+    the range-filtered ground truth, and the five true-positive errors of the matches at the 2 m threshold.  One
+    launch on the current stream, then `cursor += B`; no host synchronisation, capturable in a graph (with packed
+    ground truth).  state: a DetEvalState; det: a DetResult as det_postprocess returns it; gt_boxes, gt_labels: per-sample
+    lists ([n_b, 9 | 7] fp32 in the ego frame, [n_b] int32 | int64) as the loader's get_gt gives them, or packed
+    [B, G, 9 | 7] and [B, G] tensors whose padding rows carry label -1; gt_attrs: None (no ground truth has an
+    attribute) or int8 indices into ATTRIBUTE_NAMES (-1: none), shaped like the labels.  Errors are counted in
+    `state.state` (see DetEvalState); nothing is raised for them here."""
+    if not isinstance(det, DetResult):
+        raise TypeError(f"det must be a DetResult, got {type(det).__name__}")
+    if not all(x.is_cuda for x in (det.boxes, det.scores, det.labels, det.counts)):
+        raise _capi.VampireHipError("det_eval_update needs device tensors (no CPU fallback)")
+    gtb, gtl, gta = _pack_gt(gt_boxes, gt_labels, gt_attrs)
+    if not (gtb.is_cuda and gtl.is_cuda and (gta is None or gta.is_cuda)):
+        raise _capi.VampireHipError("det_eval_update needs device tensors (no CPU fallback)")
+    if det.boxes.dtype != torch.float32 or det.labels.dtype != torch.int32 or det.counts.dtype != torch.int32:
+        raise TypeError("det must hold fp32 boxes, int32 labels and int32 counts")
+    if det.scores.dtype not in FLOAT_DTYPES:
+        raise TypeError(f"scores must be fp32, bf16 or fp16, got {det.scores.dtype}")
+    if gtb.dtype != torch.float32:
+        raise TypeError(f"gt_boxes must be fp32, got {gtb.dtype}")
+    if gtl.dtype not in _LABEL_DTYPES:
+        raise TypeError(f"gt_labels must be int32 or int64, got {gtl.dtype}")
+    if gta is not None and gta.dtype != torch.int8:
+        raise TypeError(f"gt_attrs must be int8, got {gta.dtype}")
+    if det.boxes.dim() != 3 or det.boxes.shape[2] not in (7, 9):
+        raise ValueError(f"det.boxes {tuple(det.boxes.shape)} is not [B, M, 7 | 9]")
+    B, M, cols = det.boxes.shape
+    if tuple(det.scores.shape) != (B, M) or tuple(det.labels.shape) != (B, M) or tuple(det.counts.shape) != (B,):
+        raise ValueError(f"det holds scores {tuple(det.scores.shape)}, labels {tuple(det.labels.shape)}, counts "
+                         f"{tuple(det.counts.shape)} for boxes {tuple(det.boxes.shape)}")
+    if M != state.max_dets:
+        raise ValueError(f"det is {M} rows wide, the state was made for {state.max_dets}")
+    if gtb.dim() != 3 or gtb.shape[0] != B or gtb.shape[2] != cols or tuple(gtl.shape) != tuple(gtb.shape[:2]) \
+            or (gta is not None and tuple(gta.shape) != tuple(gtl.shape)):
+        raise ValueError(f"expected gt boxes [{B}, G, {cols}] with labels (and attributes) [{B}, G], got "
+                         f"{tuple(gtb.shape)} and {tuple(gtl.shape)}")
+    G = gtb.shape[1]
+    d = state.desc(B, G, cols, det.scores.dtype, gtl.dtype, gta is not None)
+    vamp = _capi.checked()
+    if not vamp.vamp_det_eval_supported(d):
+        raise ValueError(f"det_eval_update: {vamp.vamp_last_error().decode('utf-8', 'replace')}")
+    dev = det.boxes.device
+    with torch.cuda.device(dev):
+        vamp.vamp_det_eval_update(d, det.boxes.contiguous(), det.scores.contiguous(), det.labels.contiguous(),
+                                  det.counts.contiguous(), gtb.contiguous(), gtl.contiguous(),
+                                  None if gta is None else gta.contiguous(), state.records, state.state, _stream())
+        state.state[:1] += B              # the cursor, on the same stream: a captured update appends on every replay
+    return state

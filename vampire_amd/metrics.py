@@ -145,3 +145,137 @@ class SegEvaluator:
                 raise ValueError(f"{int(bad)} points map outside the {len(labels)} reference points")
             out.append(pred.to(torch.uint8))
         return out
+
+
+# =============================================================================================
+# detection: nuScenes mAP, true-positive errors and NDS (det_evaluators.py:61-117)
+# =============================================================================================
+TP_ERRORS = ("trans_err", "scale_err", "orient_err", "vel_err", "attr_err")           # the records' error order
+ERR_NAME_MAPPING = {"trans_err": "mATE", "scale_err": "mASE", "orient_err": "mAOE", "vel_err": "mAVE",
+                    "attr_err": "mAAE"}                                                # det_evaluators.py:16-22
+
+
+def _cummean(x):
+    """Running mean that ignores NaN: 0 while no finite value has been seen, ones when there is none at all."""
+    nan = np.isnan(x)
+    if nan.all():
+        return np.ones(len(x))
+    count = np.cumsum(~nan)
+    total = np.cumsum(np.where(nan, 0.0, x))
+    return np.divide(total, count, out=np.zeros_like(total), where=count != 0)
+
+
+class DetEvaluator:
+    """Streaming nuScenes detection scores (`detection_cvpr_2019` as DESIGN 8.19 restates it; parity with the
+    devkit is unpinned): `update()` per validation batch runs `evaluation.det_eval_update` -- one HIP launch, no host
+    synchronisation --, `compute()` at the epoch's end sorts the records per class on the device, brings them to
+    the host and finishes the 101-point curves and the scores in float64; `reset()` starts over.
+
+    class_names: the head's classes in label order; max_samples: the capacity in samples; max_dets: the width of
+    the DetResult (tasks x post_max_size).  protocol: class_range ({name: metres}), dist_ths, dist_th_tp,
+    max_boxes_per_sample, min_recall, min_precision, mean_ap_weight (the defaults are detection_cvpr_2019's)."""
+
+    def __init__(self, class_names, max_samples, max_dets, device="cuda", *, min_recall=0.1, min_precision=0.1,
+                 mean_ap_weight=5.0, **protocol):
+        self.min_recall, self.min_precision, self.mean_ap_weight = float(min_recall), float(min_precision), float(mean_ap_weight)
+        self.state = evaluation.DetEvalState.new(class_names, max_samples, max_dets, device, **protocol)
+        self.class_names = self.state.class_names
+
+    def update(self, det, gt_boxes, gt_labels, gt_attrs=None):
+        evaluation.det_eval_update(self.state, det, gt_boxes, gt_labels, gt_attrs)
+
+    def reset(self):
+        self.state.reset()
+
+    def test_step(self, model, batch):
+        """base_exp.py:665-746 on the 15-entry validation batch: the model in eval mode without gradients, the
+        boxes decoded on the device (get_bboxes_device), then update with the batch's ground truth (entries 4, 5).
+        Returns the DetResult."""
+        was_training = model.training
+        model.eval()
+        try:
+            with torch.no_grad():
+                outputs = model(batch[0], batch[1], inrange_pts=batch[6], lidar_seg=False)
+                det = model.get_bboxes_device(outputs[0])
+            self.update(det, batch[4], batch[5])
+        finally:
+            model.train(was_training)
+        return det
+
+    def _sorted_records(self):
+        """The valid records ordered by class, then score descending, then slot descending (the devkit's reversed
+        ascending sort of (score, index)), as host arrays, with the counters; the one synchronisation."""
+        st = self.state
+        words = st.state.cpu().numpy()                                   # the synchronisation
+        errors = dict(zip(("samples with more than max_boxes_per_sample boxes",
+                           f"(sample, class) pairs with more than {evaluation._capi.VAMP_DET_EVAL_GT_CAP} ground-truth boxes",
+                           "labels outside the class list", "batches beyond max_samples"), words[1:5].tolist()))
+        if any(errors.values()):
+            raise ValueError("detection evaluation: " + ", ".join(f"{v} {k}" for k, v in errors.items() if v))
+        nrec = int(words[0]) * st.max_dets
+        rec = st.records[:nrec]
+        word = rec[:, 1]
+        idx = torch.nonzero((word >> 8) & 1).flatten().flip(0)           # slots, descending
+        score = rec[:, 0].view(torch.float32)[idx]
+        idx = idx[torch.sort(score, stable=True, descending=True).indices]
+        idx = idx[torch.sort(word[idx] & 0xff, stable=True).indices]
+        rec = rec[idx].cpu().numpy()
+        npos = words[8:8 + len(self.class_names)]
+        return rec, npos
+
+    def compute(self, prefix="pts_bbox_NuScenes"):
+        """{prefix}/{class}_AP_dist_{d}, {prefix}/{class}_{err}, {prefix}/mATE .. mAAE, {prefix}/NDS, {prefix}/mAP
+        (det_evaluators.py:99-116, unrounded).  Raises ValueError while an error counter is non-zero."""
+        st = self.state
+        rec, npos = self._sorted_records()
+        cls = rec[:, 1] & 0xff
+        conf_all = rec[:, 0].copy().view(np.float32).astype(np.float64)
+        tp_all = (rec[:, 1] >> 16) & 0xf
+        err_all = rec[:, 2:7].copy().view(np.float32).astype(np.float64)
+        tp_h = st.dist_ths.index(float(st.dist_th_tp))
+        first = int(round(100 * self.min_recall)) + 1
+        grid = np.linspace(0, 1, 101)
+        out, aps, tps = {}, [], {e: [] for e in TP_ERRORS}
+        for c, name in enumerate(self.class_names):
+            sel = cls == c
+            conf, bits, errs = conf_all[sel], tp_all[sel], err_all[sel]
+            class_aps = []
+            for h, dist in enumerate(st.dist_ths):
+                tp = ((bits >> h) & 1).astype(bool)
+                if npos[c] == 0 or not tp.any():                         # the "no predictions" curve
+                    prec, conf_i, curves = np.zeros(101), np.zeros(101), {e: np.ones(101) for e in TP_ERRORS}
+                else:
+                    tpc, fpc = np.cumsum(tp).astype(np.float64), np.cumsum(~tp).astype(np.float64)
+                    rec_c = tpc / float(npos[c])
+                    prec = np.interp(grid, rec_c, tpc / (fpc + tpc), right=0)
+                    conf_i = np.interp(grid, rec_c, conf, right=0)
+                    curves = {}
+                    if h == tp_h:
+                        for k, e in enumerate(TP_ERRORS):
+                            mean = _cummean(errs[tp, k])
+                            curves[e] = np.interp(conf_i[::-1], conf[tp][::-1], mean[::-1])[::-1]
+                ap = float(np.mean(np.clip(prec[first:] - self.min_precision, 0, None))) / (1.0 - self.min_precision)
+                class_aps.append(ap)
+                out[f"{prefix}/{name}_AP_dist_{dist}"] = ap
+                if h == tp_h:
+                    nz = np.nonzero(conf_i)[0]
+                    last = int(nz[-1]) if len(nz) else 0
+                    for e in TP_ERRORS:
+                        if (name == "traffic_cone" and e in ("attr_err", "vel_err", "orient_err")) \
+                                or (name == "barrier" and e in ("attr_err", "vel_err")):
+                            v = float("nan")
+                        else:
+                            v = 1.0 if last < first else float(np.mean(curves[e][first:last + 1]))
+                        out[f"{prefix}/{name}_{e}"] = v
+                        tps[e].append(v)
+            aps.append(float(np.mean(class_aps)))
+        mean_ap = float(np.mean(aps))
+        total = self.mean_ap_weight * mean_ap
+        for e in TP_ERRORS:
+            vals = np.asarray(tps[e])
+            m = float(np.mean(vals[~np.isnan(vals)])) if (~np.isnan(vals)).any() else float("nan")
+            out[f"{prefix}/{ERR_NAME_MAPPING[e]}"] = m
+            total += max(1.0 - m, 0.0)
+        out[f"{prefix}/NDS"] = total / (self.mean_ap_weight + len(TP_ERRORS))
+        out[f"{prefix}/mAP"] = mean_ap
+        return out

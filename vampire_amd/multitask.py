@@ -657,15 +657,16 @@ def multitask_step(model, loss_fn, batch, optimizer=None, amp_dtype=torch.bfloat
     return loss
 
 
-def synthetic_val_batch(cfg: PathConfig, batch, seed=0, device="cpu", num_points=2000, num_ref=None):
+def synthetic_val_batch(cfg: PathConfig, batch, seed=0, device="cpu", num_points=2000, num_ref=None, *, num_boxes=12):
     """A `collate_fn(mode='valid')`-shaped batch (nusc_det_seg_dataset.py:1018-1043, 15 entries) of seeded
     synthetic data, the tuple `validation_step` unpacks (base_exp.py:636): images, the five matrix stacks,
     timestamps, metas, boxes / labels, lidar points + labels, ref labels / ref index, lidar tokens, Occ3D
     labels + masks.  `ref_index` maps the points onto `num_ref` reference points (default num_points + 10%)
-    with repeats and with reference points no point maps to."""
+    with repeats and with reference points no point maps to; entries 4 and 5 are `num_boxes` ground-truth boxes
+    [num_boxes, 9] and labels per sample (what DetEvaluator.test_step scores against)."""
     g = torch.Generator().manual_seed(seed)
     num_ref = num_points + num_points // 10 if num_ref is None else num_ref
-    tr = synthetic_batch(cfg, batch, seed=seed, device=device, num_points=num_points)
+    tr = synthetic_batch(cfg, batch, seed=seed, device=device, num_points=num_points, num_boxes=num_boxes)
     K = cfg.num_classes
     mv = lambda t: t.to(device)
     ref_labels = [mv(torch.randint(0, K - 1, (num_ref,), generator=g)) for _ in range(batch)]
