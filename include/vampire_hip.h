@@ -1686,7 +1686,9 @@ int vamp_camera_images(const VampImageDesc* d, const uint8_t* raw, const int32_t
  * or -1 for none; NULL with has_attrs 0: no ground truth has one).
  *
  *  filter     a box counts when sqrt(x^2 + y^2) < class_range[class], in float64 from the fp32 centre.
- *  order      per (sample, class) the surviving predictions by score descending, higher row first among equals.
+ *  order      per (sample, class) the surviving predictions by score descending, higher row first among equals.  -0
+ *             equals +0; a NaN of either sign and any payload orders above every number (+inf included), and NaNs are
+ *             equal among themselves: higher row first.  The record keeps the score's bits as they came.
  *  match      per distance threshold its own taken set: the prediction takes the nearest not yet taken ground truth of
  *             its class and sample (squared xy distance in float64, lowest row among equals) when that distance is
  *             strictly below the threshold, and is a false positive otherwise -- it never falls back to a farther one.

@@ -106,7 +106,9 @@ def o_match(samples, names=NAMES):
                 pb = [float(v) for v in smp["boxes"][r]]
                 if int(smp["labels"][r]) == c and math.sqrt(pb[0] * pb[0] + pb[1] * pb[1]) < RANGE[name]:
                     preds.append((float(smp["scores"][r]), s, r, pb))
-        order = [i for _, i in sorted((p[0], i) for i, p in enumerate(preds))][::-1]
+        # a NaN of either sign orders above every number and NaNs are equal among themselves (-0.0 == 0.0 as floats)
+        order = [t[-1] for t in sorted((math.isnan(p[0]), 0.0 if math.isnan(p[0]) else p[0], i)
+                                       for i, p in enumerate(preds))][::-1]
         bits = {i: 0 for i in order}
         errs = {i: None for i in order}
         for h, th in enumerate(THS):
@@ -247,7 +249,9 @@ def dev():
     return torch.device("cuda:0")
 
 
-def det_result(samples, width, dev, score_dtype=torch.float32, counts=None):
+def det_result(samples, width, dev, score_dtype=torch.float32, counts=None, raw_scores=None):
+    """raw_scores: a [B, width] tensor of score_dtype to hand over as it is (bit patterns a conversion from the samples'
+    fp32 scores would not keep, such as a NaN's sign in bf16); the samples' scores are then its values in fp32."""
     B, cols = len(samples), samples[0]["boxes"].shape[1]
     boxes, scores = torch.zeros(B, width, cols), torch.zeros(B, width)
     labels, cnt = torch.zeros(B, width, dtype=torch.int32), torch.zeros(B, dtype=torch.int32)
@@ -257,7 +261,12 @@ def det_result(samples, width, dev, score_dtype=torch.float32, counts=None):
         labels[b, :n], cnt[b] = torch.from_numpy(s["labels"]).int(), n
     if counts is not None:
         cnt = torch.tensor(counts, dtype=torch.int32)
-    return E.DetResult(boxes.to(dev), scores.to(score_dtype).to(dev), labels.to(dev), cnt.to(dev))
+    if raw_scores is not None:
+        assert raw_scores.dtype == score_dtype and tuple(raw_scores.shape) == (B, width)
+        assert torch.equal(raw_scores.float().isnan(), scores.isnan())       # (the samples' fp32 scores are its values;
+        assert torch.equal(raw_scores.float().nan_to_num(7.0), scores.nan_to_num(7.0))     # a NaN's bits are the caller's)
+    scores = scores.to(score_dtype) if raw_scores is None else raw_scores
+    return E.DetResult(boxes.to(dev), scores.to(dev), labels.to(dev), cnt.to(dev))
 
 
 def gt_lists(samples, dev, label_dtype=torch.int64):
@@ -302,7 +311,8 @@ def check_records(rows, samples, width, names=NAMES):
                 assert not row.any(), f"sample {s} row {r}: expected an invalid (all-zero) record, got {row}"
                 continue
             c, score, bits, errs = want[(s, r)]
-            assert row[0] == np.float32(score).view(np.int32), (s, r, "score")
+            assert row[0] == samples[s]["scores"][r:r + 1].view(np.int32)[0], (s, r, "score")       # (a NaN's bits too)
+            assert math.isnan(score) or np.float32(score) == samples[s]["scores"][r]
             assert row[1] == (c | 1 << 8 | bits << 16), (s, r, f"class/valid/tp word {row[1]:#x}, oracle class {c} bits {bits:#x}")
             assert row[7] == 0
             for k, e in enumerate(ERRS):
@@ -329,16 +339,17 @@ def check_scores(got, want):
             assert abs(g - w) <= 16 * 2.0 ** -24 * max(1.0, abs(w)), (k, g, w)
 
 
-def run_case(samples, dev, width, max_samples=None, batches=None, **kw):
-    """Feed `samples` (in `batches` of the given sizes, default one) and hold records, npos and scores to the oracle."""
-    ev = metrics.DetEvaluator(NAMES, max_samples or len(samples), width, dev)
+def run_case(samples, dev, width, max_samples=None, batches=None, names=NAMES, protocol=None, **kw):
+    """Feed `samples` (in `batches` of the given sizes, default one) and hold records, npos and scores to the oracle.
+    names: the evaluator's class list; protocol: DetEvaluator's keyword arguments (max_boxes_per_sample)."""
+    ev = metrics.DetEvaluator(names, max_samples or len(samples), width, dev, **(protocol or {}))
     at = 0
     for n in batches or [len(samples)]:
         update(ev, samples[at:at + n], dev, width, **kw)
         at += n
-    matched = check_records(record_rows(ev, len(samples)), samples, width)
-    assert ev.state.state[8:8 + len(NAMES)].tolist() == [m["npos"] for m in matched]
-    check_scores(ev.compute(), o_scores(matched))
+    matched = check_records(record_rows(ev, len(samples)), samples, width, names)
+    assert ev.state.state[8:8 + len(names)].tolist() == [m["npos"] for m in matched]
+    check_scores(ev.compute(), o_scores(matched, names))
     return ev, matched
 
 

@@ -23,8 +23,8 @@ from conftest import ROOT
 from vampire_amd import _capi
 from vampire_amd.config import CFG_TINY
 from test_hip_parity import close
-from test_sample_points_sweep import (ACT_BETA_BAR, ACT_GRAD_BAR, GRAD_CAP, GRAD_CAP_CROWD, K_BWD_TREE, K_BWD_WEIGHT,
-                                      K_PTS_HEAVY, U, Case, axes, crowd_points, ratio, reference, shared_hot,
+from test_sample_points_sweep import (ACT_BETA_BAR, ACT_GRAD_BAR, BF16_GRAD_REL, GRAD_CAP, GRAD_CAP_CROWD, K_BWD_TREE,
+                                      K_BWD_WEIGHT, K_PTS_HEAVY, U, Case, axes, crowd_points, ratio, reference, shared_hot,
                                       structured_points, to_ego, voxel_records)
 from test_operator_contract import ROUNDING, RUN_ATOL, RUN_RTOL
 
@@ -84,17 +84,19 @@ def beta_of(case, dev, grad=False):
     return torch.tensor(case.beta, device=dev, requires_grad=grad) if case.act == "sdf" else None
 
 
-def split_calls(hp, case, sem, den, beta, pts, counts, occ_pts, sdf=True):
+def split_calls(hp, case, sem, den, beta, pts, counts, occ_pts, sdf=True, want=(True, True, True, True)):
     """The four existing calls on the same inputs: per-sample pts_logits / pts_sdf on the rows that count, and the two
-    occupancy resamplings on the points given (the rotation is the caller's, as in `occupancy_points`)."""
+    occupancy resamplings on the points given (the rotation is the caller's, as in `occupancy_points`).  want: which
+    of (pts_logits, pts_sdf, occ_logits, occ_density) to make; the others come back as an empty list or None."""
     pl, ps = [], []
-    for b in range(case.B):
+    for b in range(case.B if want[0] or (want[1] and sdf) else 0):
         p = pts[b, :counts[b]][None]
-        pl.append(hp.sample_points(sem[[b]], p, padding="border", channel_last=True)[0])
-        if sdf:
+        if want[0]:
+            pl.append(hp.sample_points(sem[[b]], p, padding="border", channel_last=True)[0])
+        if want[1] and sdf:
             ps.append(hp.sample_points(den[[b]], p, mask_outside=True)[0, 0])
-    ol = hp.sample_points(sem, occ_pts, padding="border")
-    od = hp.sample_points(den, occ_pts, activation=True, beta=beta)
+    ol = hp.sample_points(sem, occ_pts, padding="border") if want[2] else None
+    od = hp.sample_points(den, occ_pts, activation=True, beta=beta) if want[3] else None
     return pl, ps, ol, od
 
 
@@ -170,12 +172,12 @@ def test_parts_can_be_left_out(dev):
 def run(hp, sem, den, beta, ups, **kw):
     """Forward + backward of one call on fresh leaves: (outputs, (grad_semantic, grad_density, grad_beta | None))."""
     s = sem.detach().clone().requires_grad_(True)
-    d = den.detach().clone().requires_grad_(True)
+    d = None if den is None else den.detach().clone().requires_grad_(True)
     b = None if beta is None else beta.detach().clone().requires_grad_(True)
     q = hp.point_queries(s, d, b, **kw)
-    outs = [(o, u) for o, u in zip(q, ups) if o is not None]
+    outs = [(o, u) for o, u in zip(q, ups) if o is not None and u is not None]
     torch.autograd.backward([o for o, _ in outs], [u for _, u in outs])
-    return q, (s.grad, d.grad, None if b is None else b.grad)
+    return q, (s.grad, None if d is None else d.grad, None if b is None else b.grad)
 
 
 def two_run(a, b, what):
@@ -233,10 +235,10 @@ def part_bar(ref, act):
     return torch.minimum((K_BWD_WEIGHT + n + K_BWD_TREE) * U * ref.A_g, cap.expand_as(ref.A_g))
 
 
-def crowded_scene(case):
+def crowded_scene(case, sites=((4, 2, 2), (20, 9, 2))):
     """B = 3.  Sample 0: a voxel with 200 lidar + 100 occupancy records (heavy through the union alone) and one with
     600 lidar records; sample 1: plain sets; sample 2: count 0.  Returns (pts [3, M, 3], counts, occ [3, P, 3], sites)."""
-    s_union, s_big = (4, 2, 2), (20, 9, 2)
+    s_union, s_big = sites
     border = dataclasses.replace(case, padding="border")
     lid = [lidar_points(case, 150)[b] for b in range(3)]
     lid = [torch.where(p.isfinite().all(-1, keepdim=True), p, torch.zeros(())) for p in lid]
@@ -254,6 +256,118 @@ def crowded_scene(case):
                         for a, (bnd, n) in enumerate(axes(case.cfg))], dim=-1)
     occ = torch.stack([torch.cat([rot[0], extra]), torch.cat([rot[1], fill]), torch.cat([rot[2], fill])])
     return pts, counts, occ, (s_union, s_big)
+
+
+def gradient_check(dev, case, scene, *, f64=True, lidar=True, occupancy=True, sdf=True, shared=False,
+                   given=(True, True, True, True), den_dtype=F32, tag=None):
+    """One fused backward on `scene` (crowded_scene's tuple) against the float64 gather summed over the queries asked
+    for, and against the sum of the existing backward calls of the same queries, both at the sum of the parts' bars
+    (part_bar; grad_beta at ACT_BETA_BAR of the sum of its terms' magnitudes).  lidar / occupancy: the point sets given;
+    sdf: pts_sdf asked for; shared: one [1, P, 3] grid (sample 0's) for every sample; given: which of the four outputs
+    get an upstream gradient (the others add nothing, in the references as well); den_dtype bfloat16: the density
+    volume's values are bf16 values and grad_density comes back rounded once to bf16, which the comparison allows for
+    as the sweep's `errors` does.  With f64 false the float64 figures are printed and not held (beta = 0).  Prints every
+    fraction of its bar and returns {(reference, gradient): fraction}."""
+    K = case.C
+    tag = tag or f"K{K} beta{case.beta}"
+    hp = shared_hot(case.cfg, dev)
+    sem, den = volumes(case)
+    if den_dtype != F32:
+        den = den.to(den_dtype).float()
+    pts, counts, occ, (s_union, s_big) = scene
+    B = case.B
+    if shared:
+        occ = occ[:1]
+    occ_b = occ.expand(B, -1, -1)
+    M, P = pts.shape[1], occ.shape[1]
+    gen = torch.Generator().manual_seed(11 + K)
+    ups = [torch.randn(s, generator=gen) for s in ((B, M, K), (B, M), (B, K, P), (B, 1, P))]
+    has = (lidar, lidar and sdf, occupancy, occupancy)
+    ups = [u if g else torch.zeros_like(u) for u, g in zip(ups, given)]          # (the references' upstream: zeros)
+    ups_dev = [u.to(dev) if h and g else None for u, h, g in zip(ups, has, given)]
+    assert any(u is not None for u in ups_dev)
+    # the float64 parts: rows beyond a count carry no gradient and sit at a harmless interior point
+    live = torch.arange(M)[None] < torch.tensor(counts)[:, None]
+    centre = torch.tensor([to_ego(1.5 if n > 2 else 0.5, bnd, n) for bnd, n in axes(case.cfg)], dtype=F32)
+    p_ref = torch.where(live[..., None], pts, centre)
+    u0 = torch.where(live[..., None], ups[0], torch.zeros(())).permute(0, 2, 1)
+    u1 = torch.where(live, ups[1], torch.zeros(()))[:, None]
+    c_sem = dataclasses.replace(case, padding="border", act="")
+    c_sdf = dataclasses.replace(case, C=1, mask=True, act="")
+    c_den = dataclasses.replace(case, C=1)
+    refs = {}
+    if has[0]:
+        refs["pl"] = reference(c_sem, sem, p_ref, u0)
+    if has[1]:
+        refs["ps"] = reference(c_sdf, den, p_ref, u1)
+    if has[2]:
+        refs["ol"], refs["od"] = reference(c_sem, sem, occ_b, ups[2]), reference(c_den, den, occ_b, ups[3])
+    # record counts of the lidar parts: the rows that count alone (the bars take them from here)
+    for key, c_part in (("pl", c_sem), ("ps", c_sdf)):
+        if key in refs:
+            refs[key].nrec = torch.cat([voxel_records(case.cfg, pts[b:b + 1, :n], c_part.border, c_part.mask)
+                                        for b, n in enumerate(counts)])
+    # the crowds are there
+    zero_n = torch.zeros(B, case.Z, case.Y, case.X, dtype=torch.int64)
+    n_l = refs["pl"].nrec if lidar else zero_n
+    n_o = voxel_records(case.cfg, occ_b, True, False) if occupancy else zero_n
+    at = lambda n, s: int(n[0, s[2], s[1], s[0]])
+    if lidar:
+        assert at(n_l, s_union) == 200 and at(n_l, s_big) >= 600, (at(n_l, s_union), at(n_l, s_big))
+    if occupancy:
+        assert at(n_o, s_union) == 100, at(n_o, s_union)
+    zero_v = torch.zeros(B, 1, case.Z, case.Y, case.X, dtype=F64)
+    parts = lambda keys, acts: (sum((refs[k].gvol for k in keys if k in refs), zero_v),
+                                sum((part_bar(refs[k], a) for k, a in zip(keys, acts) if k in refs), zero_v))
+    ref_sem, bar_sem = parts(("pl", "ol"), (False, False))
+    ref_den, bar_den = parts(("ps", "od"), (False, True))
+    want_den = has[1] or occupancy
+    want_beta = occupancy and case.act == "sdf"
+    bar_beta = ACT_BETA_BAR * max(refs["od"].gscale, 1e-300) if want_beta else None
+
+    to = lambda t: t.to(dev)
+    cnt = torch.tensor(counts, dtype=torch.int32, device=dev)
+    bt = beta_of(case, dev) if occupancy else None
+    den_dev = to(den).to(den_dtype) if want_den else None
+    kw = {}
+    if lidar:
+        kw.update(points=to(pts), counts=cnt, sdf=sdf)
+    if occupancy:
+        kw.update(occ_points=to(occ))
+    _, got = run(hp, to(sem), den_dev, bt, ups_dev, **kw)
+    assert (got[1] is not None) == want_den and (got[2] is not None) == want_beta
+    assert got[1] is None or got[1].dtype == den_dtype
+    # the existing backward calls of the same queries, summed
+    s = to(sem).requires_grad_(True)
+    # (a 16-bit density leaf would get each call's gradient rounded to 16 bits and their sum rounded again: the calls
+    # run on the same values in fp32, as in test_dtype_mixes, and the fused gradient's one rounding is allowed for below)
+    d = den_dev.float().clone().requires_grad_(True) if want_den else None
+    b = bt.clone().requires_grad_(True) if bt is not None else None
+    want = [u is not None for u in ups_dev]
+    pl, ps, ol, od = split_calls(hp, case, s, d, b, to(pts), counts, to(occ_b).contiguous(), sdf, want)
+    outs = pl + ps + [o for o in (ol, od) if o is not None]
+    gr = ([ups_dev[k][i, :n] for k, part in ((0, pl), (1, ps)) if part for i, n in enumerate(counts)]
+          + [ups_dev[k] for k, o in ((2, ol), (3, od)) if o is not None])
+    torch.autograd.backward(outs, gr)
+    grad64 = lambda t, like: torch.zeros_like(like) if t is None or t.grad is None else t.grad.cpu().double()
+    calls = (grad64(s, ref_sem), grad64(d, ref_den), float(b.grad) if want_beta and b.grad is not None else 0.0)
+    seen, bad = {}, []
+    for name, ref_g in (("float64", (ref_sem, ref_den, refs["od"].gbeta if want_beta else None)), ("four calls", calls)):
+        figures = [("grad_semantic", ratio((got[0].cpu().double() - ref_g[0]).abs(), bar_sem))]
+        if want_den:
+            d_den = (got[1].cpu().double() - ref_g[1]).abs()
+            if den_dtype == torch.bfloat16:           # the fp32 gradient rounded once to bf16's 8-bit significand
+                d_den = (d_den - BF16_GRAD_REL * ref_g[1].abs()).clamp_min(0)
+            figures.append(("grad_density", ratio(d_den, bar_den)))
+        if want_beta:
+            figures.append(("grad_beta", abs(float(got[2]) - ref_g[2]) / bar_beta))
+        for what, e in figures:
+            print(f"SEEN {tag} vs {name} {what}: {e:.3e} of the bar")
+            seen[(name, what)] = e
+            if not e <= 1.0 and (f64 or name != "float64"):
+                bad.append(f"{name} {what}: {e:.3e} of the bar")
+    assert not bad, "\n".join(bad)
+    return seen, n_l, n_o
 
 
 @gpu
@@ -274,59 +388,7 @@ def test_gradients_against_float64(dev, K, beta, f64):
     away from the four existing calls, which are as far from float64 as it is: the figure is the activation's, which
     this operator shares with `sample_points` unchanged."""
     case = qcase(K, 33, 3, "sdf", beta)
-    hp = shared_hot(case.cfg, dev)
-    sem, den = volumes(case)
-    pts, counts, occ, (s_union, s_big) = crowded_scene(case)
-    M, P = pts.shape[1], occ.shape[1]
-    gen = torch.Generator().manual_seed(11 + K)
-    ups = [torch.randn(s, generator=gen) for s in ((3, M, K), (3, M), (3, K, P), (3, 1, P))]
-    # the float64 parts: rows beyond a count carry no gradient and sit at a harmless interior point
-    live = torch.arange(M)[None] < torch.tensor(counts)[:, None]
-    centre = torch.tensor([to_ego(1.5, bnd, n) for bnd, n in axes(case.cfg)], dtype=F32)
-    p_ref = torch.where(live[..., None], pts, centre)
-    u0 = torch.where(live[..., None], ups[0], torch.zeros(())).permute(0, 2, 1)
-    u1 = torch.where(live, ups[1], torch.zeros(()))[:, None]
-    c_sem = dataclasses.replace(case, padding="border", act="")
-    c_sdf = dataclasses.replace(case, C=1, mask=True, act="")
-    c_den = dataclasses.replace(case, C=1)
-    refs = dict(pl=reference(c_sem, sem, p_ref, u0), ps=reference(c_sdf, den, p_ref, u1),
-                ol=reference(c_sem, sem, occ, ups[2]), od=reference(c_den, den, occ, ups[3]))
-    # record counts of the lidar parts: the rows that count alone (the bars take them from here)
-    for key, c_part in (("pl", c_sem), ("ps", c_sdf)):
-        refs[key].nrec = torch.cat([voxel_records(case.cfg, pts[b:b + 1, :n], c_part.border, c_part.mask)
-                                    for b, n in enumerate(counts)])
-    # the crowds are there
-    n_l, n_o = refs["pl"].nrec, voxel_records(case.cfg, occ, True, False)
-    at = lambda n, s: int(n[0, s[2], s[1], s[0]])
-    assert at(n_l, s_union) == 200 and at(n_o, s_union) == 100, (at(n_l, s_union), at(n_o, s_union))
-    assert at(n_l, s_big) >= 600
-    ref_sem, bar_sem = refs["pl"].gvol + refs["ol"].gvol, part_bar(refs["pl"], False) + part_bar(refs["ol"], False)
-    ref_den, bar_den = refs["ps"].gvol + refs["od"].gvol, part_bar(refs["ps"], False) + part_bar(refs["od"], True)
-    bar_beta = ACT_BETA_BAR * max(refs["od"].gscale, 1e-300)
-
-    to = lambda t: t.to(dev)
-    cnt = torch.tensor(counts, dtype=torch.int32, device=dev)
-    bt = beta_of(case, dev)
-    _, got = run(hp, to(sem), to(den), bt, [to(u) for u in ups], points=to(pts), counts=cnt, sdf=True, occ_points=to(occ))
-    # the four existing backward calls, summed
-    s = to(sem).requires_grad_(True)
-    d = to(den).requires_grad_(True)
-    b = bt.clone().requires_grad_(True)
-    pl, ps, ol, od = split_calls(hp, case, s, d, b, to(pts), counts, to(occ))
-    outs = pl + ps + [ol, od]
-    gr = [to(ups[0])[i, :n] for i, n in enumerate(counts)] + [to(ups[1])[i, :n] for i, n in enumerate(counts)] + [to(ups[2]), to(ups[3])]
-    torch.autograd.backward(outs, gr)
-    bad = []
-    for name, ref_g in (("float64", (ref_sem, ref_den, refs["od"].gbeta)),
-                        ("four calls", (s.grad.cpu().double(), d.grad.cpu().double(), float(b.grad)))):
-        e_sem = ratio((got[0].cpu().double() - ref_g[0]).abs(), bar_sem)
-        e_den = ratio((got[1].cpu().double() - ref_g[1]).abs(), bar_den)
-        e_beta = abs(float(got[2]) - ref_g[2]) / bar_beta
-        for what, e in (("grad_semantic", e_sem), ("grad_density", e_den), ("grad_beta", e_beta)):
-            print(f"SEEN K{K} beta{beta} vs {name} {what}: {e:.3e} of the bar")
-            if not e <= 1.0 and (f64 or name != "float64"):
-                bad.append(f"{name} {what}: {e:.3e} of the bar")
-    assert not bad, "\n".join(bad)
+    _, n_l, n_o = gradient_check(dev, case, crowded_scene(case), f64=f64)
     assert int(n_l[2].sum()) == 0 and int(n_o[2].sum()) > 0            # sample 2: no lidar point, its grid alone
 
 

@@ -67,9 +67,11 @@ __device__ __forceinline__ float ev_score(const EvParams& p, long k) {
   return p.score_dtype == VAMP_BF16 ? bf16_to_f32(u) : f16_to_f32(u);
 }
 
-// an integer that orders like the score (a total order: -0 counts as +0, a NaN lies above every number)
+// an integer that orders like the score (a total order: -0 counts as +0; a NaN of either sign and any payload gets the
+// one key above +inf's, so that NaNs tie and the higher row goes first, as the host's descending sort has them)
 __device__ __forceinline__ uint32_t ev_key(float s) {
   const uint32_t u = __float_as_uint(s + 0.0f);
+  if ((u & 0x7fffffffu) > 0x7f800000u) return 0xffffffffu;
   return (u >> 31) ? ~u : (u | 0x80000000u);
 }
 

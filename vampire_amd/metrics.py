@@ -165,6 +165,16 @@ def _cummean(x):
     return np.divide(total, count, out=np.zeros_like(total), where=count != 0)
 
 
+def _score_keys(bits):
+    """int64 keys that order like the fp32 scores whose bit patterns `bits` (int32) holds, by the rule of
+    vamp_det_eval_update: -0 equals +0, a NaN of either sign and any payload lies above +inf and NaNs are equal.  (A
+    float sort is not asked: the device's radix sort places a NaN by its bits, one with the sign bit set below -inf.)"""
+    score = bits.view(torch.float32)
+    u = (score + 0.0).view(torch.int32).long() & 0xffffffff
+    keys = torch.where(u >= 0x80000000, 0xffffffff - u, u + 0x80000000)
+    return torch.where(score != score, torch.full_like(keys, 0xffffffff), keys)
+
+
 class DetEvaluator:
     """Streaming nuScenes detection scores (`detection_cvpr_2019` as DESIGN 8.19 restates it; parity with the
     devkit is unpinned): `update()` per validation batch runs `evaluation.det_eval_update` -- one HIP launch, no host
@@ -216,8 +226,7 @@ class DetEvaluator:
         rec = st.records[:nrec]
         word = rec[:, 1]
         idx = torch.nonzero((word >> 8) & 1).flatten().flip(0)           # slots, descending
-        score = rec[:, 0].view(torch.float32)[idx]
-        idx = idx[torch.sort(score, stable=True, descending=True).indices]
+        idx = idx[torch.sort(_score_keys(rec[idx, 0]), stable=True, descending=True).indices]
         idx = idx[torch.sort(word[idx] & 0xff, stable=True).indices]
         rec = rec[idx].cpu().numpy()
         npos = words[8:8 + len(self.class_names)]
