@@ -88,13 +88,15 @@ def ema_loop(ema_sd, model_sd, updates, decay):
 
 
 def run_torch(case, dtype, device):
-    """clip_grad_norm_ + AdamW(foreach=False) + the EMA loop in `dtype` on `device`; a skipped step moves the EMA only."""
+    """clip_grad_norm_ + AdamW(foreach=False) + the EMA loop in `dtype` on `device`; a skipped step moves the EMA only.
+    `case["net"]` is any module (tests/test_step_kernels_sweep.py brings its own); `case["betas"]` stands in for BETAS."""
     net = copy.deepcopy(case["net"]).to(device=device, dtype=dtype)
-    net.bn.num_batches_tracked.fill_(7)
+    if hasattr(net, "bn"):
+        net.bn.num_batches_tracked.fill_(7)
     ema = {k: v.detach().clone() for k, v in net.state_dict().items()}
     params = list(net.parameters())
-    opt = torch.optim.AdamW(params, lr=case["lrs"][0], betas=BETAS, eps=EPS, weight_decay=case["weight_decay"],
-                            foreach=False)
+    opt = torch.optim.AdamW(params, lr=case["lrs"][0], betas=case.get("betas", BETAS), eps=EPS,
+                            weight_decay=case["weight_decay"], foreach=False)
     updates = UPDATES0
     for k in range(case["steps"]):
         with torch.no_grad():

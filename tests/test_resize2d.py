@@ -166,7 +166,8 @@ REFUSED = (4, 4, 4, 40)
 
 
 def case_inputs(name):
-    p, ih, iw, oh, ow = CASES[name]
+    """`name`: a key of CASES, or a (planes, ih, iw, oh, ow) of the caller's own (tests/test_step_kernels_sweep.py)."""
+    p, ih, iw, oh, ow = CASES[name] if isinstance(name, str) else name
     rng = np.random.default_rng(abs(hash((p, ih, iw, oh, ow))) % 2 ** 32)
     return (rng.standard_normal((p, ih, iw)).astype(np.float32), rng.standard_normal((p, oh, ow)).astype(np.float32))
 

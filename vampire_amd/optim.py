@@ -99,9 +99,19 @@ class ParamUpdate:
 
     The parameters and buffers must keep their storage for the updater's life.  A gradient may move: step() compares
     every `p.grad.data_ptr()` with the chunk table and uploads a new table when one changed; a parameter without a
-    gradient is skipped as torch skips it (its EMA still moves).  In a multi-GPU step, call step() after the gradients
-    are averaged (GradSync.finish()): the average carries one rank's inf to every rank, so no collective is needed.
-    """
+    gradient is left out of the norm and keeps its p, m and v on that step, as torch skips it (its EMA still moves).
+    In a multi-GPU step, call step() after the gradients are averaged (GradSync.finish()): the average carries one
+    rank's inf to every rank, so no collective is needed.
+
+    One difference from torch.optim.AdamW: the step count t of the bias corrections 1 - beta^t is ONE counter for all
+    parameters (stats["step"]: the steps without an overflow), where torch keeps one per parameter that counts the
+    gradients that parameter has had.  The two agree for a parameter that has a gradient on every step, and for one
+    that never has one (the reference's lidar-seg head with lidar_seg=False); they differ for a parameter whose
+    gradient is missing on some steps and present on a later one.  Where a gradient first appears at global step 3
+    with the default betas, torch moves the parameter by lr sign(g) and this update by ((1 - beta1) / (1 - beta1^3)) /
+    sqrt((1 - beta2) / (1 - beta2^3)) = 0.639 of that; for a first appearance at step t the factor is that expression
+    with t in place of 3 (0.98 at t = 100, 2.5 at t = 1000, towards (1 - beta1) / sqrt(1 - beta2) = 3.16), and the
+    parameter's next steps differ from torch's likewise until its own moments have filled."""
 
     def __init__(self, model, lr, betas=(0.9, 0.999), eps=1e-8, weight_decay=1e-7, max_norm=35.0, ema_decay=0.9990,
                  ema_updates=0, loss_scale=None):
