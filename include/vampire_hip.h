@@ -33,7 +33,7 @@ extern "C" {
                                  14: masked regression losses; 15: the camera render's plans and workspace layout;
                                  16: the lift's plans and workspace layout;
                                  16 also: stride-2 16-bit convolutions, the 2-D bilinear resize of the rendered maps and the
-                                 parameter update, the lidar-point label rasteriser, the camera images, detection scoring; the number
+                                 parameter update, the lidar-point label rasteriser, the camera images, detection scoring, batch normalisation; the number
                                  could not move: a test pins it) */
 
 enum {
@@ -1737,6 +1737,68 @@ size_t vamp_det_eval_record_bytes(const VampDetEvalDesc* d);
 int vamp_det_eval_update(const VampDetEvalDesc* d, const float* boxes, const void* scores, const int32_t* labels,
                          const int32_t* counts, const float* gt_boxes, const void* gt_labels, const int8_t* gt_attrs,
                          void* records, int64_t* state, void* stream);
+
+/* --------------------------------------------------------------------------
+ * Batch normalisation of an [N, C, H, W] NCHW-contiguous tensor with the ReLU and the residual add that follow it in
+ * the encoders, synchronised over `world` ranks (base_cli.py:78, 91 Trainer(sync_batchnorm=True): Lightning turns every
+ * BatchNorm2d of the model into a synchronised one).  Four steps, so that the caller's collective can sit between
+ * the first and the second of each direction; world = 1 is the plain single-GPU norm.  x, residual, y, dy, dx and
+ * grad_residual share one element type (dtype: VAMP_F32 | VAMP_BF16 | VAMP_F16) and must be 16-byte aligned; weight,
+ * bias, the running statistics, saved and the gradients of weight and bias are fp32; the rows are float64.
+ *
+ *  partial_stats     row [2 C + 1] of THIS rank: n = N H W, then per channel mean and M2 = sum (x - mean)^2, float64,
+ *                    per workgroup over VAMP_BN_CHUNK elements of a channel (sums of x - first element, so nothing
+ *                    cancels), the chunks merged in index order by Chan's formula.
+ *  apply             rows [world, 2 C + 1] in rank order, merged per channel in rank order by Chan's formula
+ *                    (n = na + nb, delta = mb - ma, mean = ma + delta nb / n, M2 = M2a + M2b + delta^2 na nb / n);
+ *                    var = M2 / n, invstd = 1 / sqrt(var + eps).  y = act(weight (x - mean) invstd + bias [+ residual])
+ *                    in fp32, rounded once to dtype; act is ReLU (a NaN stays a NaN) or none.  saved [3, C] fp32
+ *                    receives mean, invstd and the low word of the float64 mean (mean = saved[0] + saved[2]), which
+ *                    the backward takes.  update_running: running_mean = (1 - momentum) running_mean + momentum mean,
+ *                    running_var = (1 - momentum) running_var + momentum var n / (n - 1) with the global n, one
+ *                    workgroup per channel writing them; num_batches_tracked (int64, may be NULL) is incremented.
+ *                    training = 0 (evaluation): mean and 1 / sqrt(running_var + eps) come from the running statistics,
+ *                    rows is not read, nothing is updated, saved may be NULL.
+ *  backward_partial  dz = dy where y > 0 (or y is NaN), else 0, under ReLU -- y the saved output, there is no mask --
+ *                    else dz = dy.  row [2 C] of this rank: per channel sum dz and sum dz (x - mean), float64, fixed
+ *                    order; grad_bias = sum dz and grad_weight = invstd sum dz (x - mean) of this rank in fp32.
+ *  backward_apply    rows [world, 2 C] added in rank order, the global n from stat_rows (the forward's rows);
+ *                    dx = weight invstd (dz - sum dz / n - (x - mean) invstd^2 sum dz (x - mean) / n),
+ *                    grad_residual = dz (has_residual), each rounded once to dtype, every element written once.
+ * Launches at world = 1: two per direction when N H W <= VAMP_BN_CHUNK (one workgroup per channel), else three (the
+ * chunks' partials are merged by a launch of their own).  No atomics, no host synchronisation, bitwise repeatable,
+ * capturable in a graph.  The workspace (8-byte aligned, vamp_bn_workspace_bytes: 24 bytes per channel and chunk)
+ * needs no initialisation and is free again after each call.
+ * Limits, checked before any launch (VAMP_EINVAL with a message, and a workspace size of 0): C >= 1, N, H, W >= 1,
+ * N H W < 2^31, C ceil(N H W / VAMP_BN_CHUNK) < 2^31, 1 <= world <= VAMP_BN_MAX_WORLD, a known dtype and act,
+ * has_residual with its pointer, float64 rows 8-byte aligned; a workspace that is NULL or too small VAMP_ENOSPC.
+ * -------------------------------------------------------------------------- */
+#define VAMP_BN_CHUNK 4096        /* elements of one channel per workgroup */
+#define VAMP_BN_MAX_WORLD 64
+enum { VAMP_BN_ACT_NONE = 0, VAMP_BN_ACT_RELU = 1 };
+typedef struct VampBatchNormDesc {
+  double eps, momentum;
+  int32_t N, C, H, W;
+  int32_t dtype;                  /* VAMP_F32 | VAMP_BF16 | VAMP_F16 */
+  int32_t act;                    /* VAMP_BN_ACT_* */
+  int32_t has_residual;           /* 0 | 1 */
+  int32_t training;               /* 0: evaluation (running statistics) | 1 */
+  int32_t world;                  /* ranks whose rows are merged, 1 .. VAMP_BN_MAX_WORLD */
+  int32_t update_running;         /* 0 | 1: apply updates the running statistics (training only) */
+  int32_t reserved[2];            /* 0 */
+} VampBatchNormDesc;
+size_t vamp_bn_workspace_bytes(const VampBatchNormDesc* d);
+int vamp_bn_partial_stats(const VampBatchNormDesc* d, const void* x, double* row, void* workspace,
+                          size_t workspace_bytes, void* stream);
+int vamp_bn_apply(const VampBatchNormDesc* d, const void* x, const void* residual, const double* rows,
+                  const float* weight, const float* bias, float* running_mean, float* running_var,
+                  int64_t* num_batches_tracked, void* y, float* saved, void* stream);
+int vamp_bn_backward_partial(const VampBatchNormDesc* d, const void* dy, const void* x, const void* y,
+                             const float* saved, double* row, float* grad_weight, float* grad_bias, void* workspace,
+                             size_t workspace_bytes, void* stream);
+int vamp_bn_backward_apply(const VampBatchNormDesc* d, const void* dy, const void* x, const void* y,
+                           const float* saved, const float* weight, const double* rows, const double* stat_rows,
+                           void* dx, void* grad_residual, void* stream);
 
 #ifdef __cplusplus
 }

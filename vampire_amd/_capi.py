@@ -34,6 +34,8 @@ VAMP_IMG_CONST_COLS, VAMP_IMG_OUT_NONE = 16, -1
 VAMP_DET_EVAL_MAX_CLASSES, VAMP_DET_EVAL_GT_CAP, VAMP_DET_EVAL_MAX_WIDTH = 16, 256, 2048
 VAMP_DET_EVAL_RECORD_BYTES, VAMP_DET_EVAL_STATE_WORDS = 32, 24
 VAMP_DET_EVAL_HALF_PERIOD, VAMP_DET_EVAL_HAS_ORIENT, VAMP_DET_EVAL_HAS_VEL, VAMP_DET_EVAL_HAS_ATTR = 1, 2, 4, 8
+VAMP_BN_CHUNK, VAMP_BN_MAX_WORLD = 4096, 64
+VAMP_BN_ACT_NONE, VAMP_BN_ACT_RELU = 0, 1
 
 
 class VampLiftDesc(C.Structure):
@@ -203,6 +205,13 @@ class VampDetEvalDesc(C.Structure):
                 ("attr_still", C.c_int32 * VAMP_DET_EVAL_MAX_CLASSES), ("reserved", C.c_int32 * 2)]
 
 
+class VampBatchNormDesc(C.Structure):
+    _fields_ = [("eps", C.c_double), ("momentum", C.c_double), ("N", C.c_int32), ("C", C.c_int32), ("H", C.c_int32),
+                ("W", C.c_int32), ("dtype", C.c_int32), ("act", C.c_int32), ("has_residual", C.c_int32),
+                ("training", C.c_int32), ("world", C.c_int32), ("update_running", C.c_int32),
+                ("reserved", C.c_int32 * 2)]
+
+
 class VampBevBackwardPlan(C.Structure):
     """What vamp_render_bev_backward_ex will launch (vamp_render_bev_backward_plan; include/vampire_hip.h)."""
     _fields_ = [("scan_lds", C.c_int64), ("path", C.c_int32), ("z_lo", C.c_int32), ("z_hi", C.c_int32),
@@ -355,6 +364,7 @@ _PUD = C.POINTER(VampParamUpdateDesc)
 _LLD = C.POINTER(VampLidarLabelDesc)
 _IMD = C.POINTER(VampImageDesc)
 _DED = C.POINTER(VampDetEvalDesc)
+_BND = C.POINTER(VampBatchNormDesc)
 
 # name -> (return kind, argtypes); must list every symbol declared in include/vampire_hip.h
 SIGNATURES = {
@@ -490,6 +500,11 @@ SIGNATURES = {
     "vamp_det_eval_supported": (_INT, [_DED]),
     "vamp_det_eval_record_bytes": (_SIZE, [_DED]),
     "vamp_det_eval_update": (_STATUS, [_DED] + [_P] * 9 + [_P]),
+    "vamp_bn_workspace_bytes": (_SIZE, [_BND]),
+    "vamp_bn_partial_stats": (_STATUS, [_BND, _P, _P, _P, C.c_size_t, _P]),
+    "vamp_bn_apply": (_STATUS, [_BND] + [_P] * 10 + [_P]),
+    "vamp_bn_backward_partial": (_STATUS, [_BND] + [_P] * 7 + [_P, C.c_size_t, _P]),
+    "vamp_bn_backward_apply": (_STATUS, [_BND] + [_P] * 9 + [_P]),
 }
 
 _lib = None

@@ -8,21 +8,25 @@ import torch
 import torch.nn.functional as F
 from torch import nn
 
+from .norm import build_norm, is_fused
+
 
 # =============================================================================================
 class _BasicBlock(nn.Module):
     expansion = 1
 
-    def __init__(self, cin, planes, stride=1, downsample=None):
+    def __init__(self, cin, planes, stride=1, downsample=None, norm_cfg=None):
         super().__init__()
         self.conv1 = nn.Conv2d(cin, planes, 3, stride, 1, bias=False)
-        self.bn1 = nn.BatchNorm2d(planes)
+        self.bn1 = build_norm(norm_cfg, planes, act="relu")
         self.conv2 = nn.Conv2d(planes, planes, 3, 1, 1, bias=False)
-        self.bn2 = nn.BatchNorm2d(planes)
+        self.bn2 = build_norm(norm_cfg, planes, act="relu")
         self.downsample = downsample
 
     def forward(self, x):
         idt = x if self.downsample is None else self.downsample(x)
+        if is_fused(self.bn1):                                 # SyncBN: the norms carry the ReLUs and the residual
+            return self.bn2(self.conv2(self.bn1(self.conv1(x))), idt)
         y = F.relu(self.bn1(self.conv1(x)), inplace=True)
         return F.relu(self.bn2(self.conv2(y)) + idt, inplace=True)
 
@@ -30,18 +34,20 @@ class _BasicBlock(nn.Module):
 class _Bottleneck(nn.Module):
     expansion = 4
 
-    def __init__(self, cin, planes, stride=1, downsample=None):
+    def __init__(self, cin, planes, stride=1, downsample=None, norm_cfg=None):
         super().__init__()
         self.conv1 = nn.Conv2d(cin, planes, 1, bias=False)
-        self.bn1 = nn.BatchNorm2d(planes)
+        self.bn1 = build_norm(norm_cfg, planes, act="relu")
         self.conv2 = nn.Conv2d(planes, planes, 3, stride, 1, bias=False)       # style='pytorch': stride on the 3x3
-        self.bn2 = nn.BatchNorm2d(planes)
+        self.bn2 = build_norm(norm_cfg, planes, act="relu")
         self.conv3 = nn.Conv2d(planes, planes * 4, 1, bias=False)
-        self.bn3 = nn.BatchNorm2d(planes * 4)
+        self.bn3 = build_norm(norm_cfg, planes * 4, act="relu")
         self.downsample = downsample
 
     def forward(self, x):
         idt = x if self.downsample is None else self.downsample(x)
+        if is_fused(self.bn1):
+            return self.bn3(self.conv3(self.bn2(self.conv2(self.bn1(self.conv1(x))))), idt)
         y = F.relu(self.bn1(self.conv1(x)), inplace=True)
         y = F.relu(self.bn2(self.conv2(y)), inplace=True)
         return F.relu(self.bn3(self.conv3(y)) + idt, inplace=True)
@@ -54,13 +60,13 @@ class ResNet(nn.Module):
 
     def __init__(self, depth=50, in_channels=3, base_channels=64, num_stages=4, strides=(1, 2, 2, 2),
                  dilations=(1, 1, 1, 1), out_indices=(0, 1, 2, 3), norm_eval=False, frozen_stages=-1,
-                 init_cfg=None, type=None, **_):
+                 init_cfg=None, type=None, norm_cfg=None, **_):
         super().__init__()
         block, blocks = self.ARCH[depth]
         self.deep_stem = False
         self.out_indices = list(out_indices)
         self.conv1 = nn.Conv2d(in_channels, base_channels, 7, 2, 3, bias=False)
-        self.bn1 = nn.BatchNorm2d(base_channels)
+        self.bn1 = build_norm(norm_cfg, base_channels, act="relu")
         self.relu = nn.ReLU(inplace=True)
         self.maxpool = nn.MaxPool2d(3, 2, 1)
         self.res_layers = []
@@ -73,8 +79,8 @@ class ResNet(nn.Module):
                 down = None
                 if stride != 1 or cin != planes * block.expansion:
                     down = nn.Sequential(nn.Conv2d(cin, planes * block.expansion, 1, stride, bias=False),
-                                         nn.BatchNorm2d(planes * block.expansion))
-                layers.append(block(cin, planes, stride, down))
+                                         build_norm(norm_cfg, planes * block.expansion))
+                layers.append(block(cin, planes, stride, down, norm_cfg))
                 cin = planes * block.expansion
             name = f"layer{i + 1}"
             setattr(self, name, nn.Sequential(*layers))
@@ -92,8 +98,13 @@ class ResNet(nn.Module):
                 nn.init.ones_(m.weight)
                 nn.init.zeros_(m.bias)
 
+    def stem(self, x):
+        """conv1 + norm1 + ReLU (one node with a fused norm)."""
+        x = self.bn1(self.conv1(x))
+        return x if is_fused(self.bn1) else self.relu(x)
+
     def forward(self, x):
-        x = self.relu(self.bn1(self.conv1(x)))
+        x = self.stem(x)
         if hasattr(self, "maxpool"):
             x = self.maxpool(x)
         outs = []
@@ -107,8 +118,9 @@ class ResNet(nn.Module):
 class SECONDFPN(nn.Module):
     """Every level resampled to one stride (transposed conv up, strided conv down), BN + ReLU, concat."""
 
-    def __init__(self, in_channels, out_channels, upsample_strides, type=None, **_):
+    def __init__(self, in_channels, out_channels, upsample_strides, type=None, norm_cfg=None, **_):
         super().__init__()
+        norm_cfg = dict(dict(type="BN", eps=1e-3, momentum=0.01), **(norm_cfg or {}))
         blocks = []
         for cin, cout, s in zip(in_channels, out_channels, upsample_strides):
             if s >= 1:
@@ -117,7 +129,8 @@ class SECONDFPN(nn.Module):
             else:
                 k = int(round(1.0 / s))
                 layer = nn.Conv2d(cin, cout, k, k, bias=False)
-            blocks.append(nn.Sequential(layer, nn.BatchNorm2d(cout, eps=1e-3, momentum=0.01), nn.ReLU(inplace=True)))
+            norm = build_norm(norm_cfg, cout, act="relu")
+            blocks.append(nn.Sequential(layer, norm, nn.Identity() if is_fused(norm) else nn.ReLU(inplace=True)))
         self.deblocks = nn.ModuleList(blocks)
 
     def init_weights(self):

@@ -32,6 +32,7 @@ from .config import PathConfig
 
 
 from .encoders import ResNet, SECONDFPN, build_backbone, build_neck  # noqa: F401  (re-exported)
+from .norm import build_norm, is_fused
 
 
 # =============================================================================================
@@ -146,18 +147,20 @@ class CenterPointBBoxCoder:
         return [dict(bboxes=boxes[i, keep[i]], scores=scores[i, keep[i]], labels=clses[i, keep[i]]) for i in range(B)]
 
 
-def _conv_bn_relu(cin, cout, k):
-    return nn.Sequential(nn.Conv2d(cin, cout, k, 1, k // 2, bias=False), nn.BatchNorm2d(cout), nn.ReLU(inplace=True))
+def _conv_bn_relu(cin, cout, k, norm_cfg=None):
+    norm = build_norm(norm_cfg, cout, act="relu")               # SyncBN: the norm carries the ReLU
+    return nn.Sequential(nn.Conv2d(cin, cout, k, 1, k // 2, bias=False), norm,
+                         nn.Identity() if is_fused(norm) else nn.ReLU(inplace=True))
 
 
 class SeparateHead(nn.Module):
-    def __init__(self, in_channels, heads, head_conv=64, final_kernel=1, init_bias=-2.19, type=None):
+    def __init__(self, in_channels, heads, head_conv=64, final_kernel=1, init_bias=-2.19, type=None, norm_cfg=None):
         super().__init__()
         self.heads = heads
         for name, (classes, num_conv) in heads.items():
             layers, c = [], in_channels
             for _ in range(num_conv - 1):
-                layers.append(_conv_bn_relu(c, head_conv, final_kernel))
+                layers.append(_conv_bn_relu(c, head_conv, final_kernel, norm_cfg))
                 c = head_conv
             layers.append(nn.Conv2d(c, classes, final_kernel, 1, final_kernel // 2, bias=True))
             setattr(self, name, nn.Sequential(*layers))
@@ -178,7 +181,7 @@ class BEVDepthHead(nn.Module):
     def __init__(self, in_channels=256, tasks=None, bbox_coder=None, common_heads=None,
                  loss_cls=None, loss_bbox=None, gaussian_overlap=0.1, min_radius=2, train_cfg=None,
                  test_cfg=None, bev_backbone_conf=None, bev_neck_conf=None, separate_head=None,
-                 share_conv_channel=64, num_heatmap_convs=2, norm_bbox=True):
+                 share_conv_channel=64, num_heatmap_convs=2, norm_bbox=True, norm_cfg=None):
         super().__init__()
         self.class_names = [t["class_names"] for t in tasks]
         self.num_classes = [len(t["class_names"]) for t in tasks]
@@ -189,12 +192,12 @@ class BEVDepthHead(nn.Module):
         self.loss_bbox_weight = (loss_bbox or {}).get("loss_weight", 0.25)
         sep = dict(separate_head or dict(init_bias=-2.19, final_kernel=3))
         sep.pop("type", None)
-        self.shared_conv = _conv_bn_relu(in_channels, share_conv_channel, 3)
+        self.shared_conv = _conv_bn_relu(in_channels, share_conv_channel, 3, norm_cfg)
         self.task_heads = nn.ModuleList()
         for n in self.num_classes:
             heads = dict(common_heads or {})
             heads["heatmap"] = (n, num_heatmap_convs)
-            self.task_heads.append(SeparateHead(share_conv_channel, heads, **sep))
+            self.task_heads.append(SeparateHead(share_conv_channel, heads, norm_cfg=norm_cfg, **sep))
         self.trunk = build_backbone(bev_backbone_conf)
         self.trunk.init_weights()
         self.neck = build_neck(bev_neck_conf)
@@ -205,7 +208,7 @@ class BEVDepthHead(nn.Module):
         with torch.autocast(device_type=x.device.type, enabled=False):      # bev_depth_head.py:140 @autocast(False)
             x = x.float()
             outs = [x]
-            x = self.trunk.relu(self.trunk.norm1(self.trunk.conv1(x)))
+            x = self.trunk.stem(x)
             for i, name in enumerate(self.trunk.res_layers):
                 x = getattr(self.trunk, name)(x)
                 if i in self.trunk.out_indices:
@@ -552,9 +555,13 @@ TASKS = [dict(num_class=1, class_names=["car"]), dict(num_class=2, class_names=[
          dict(num_class=2, class_names=["motorcycle", "bicycle"]), dict(num_class=2, class_names=["pedestrian", "traffic_cone"])]
 
 
-def reference_confs(cfg: PathConfig, output_channels=80, small_encoder=False):
+def reference_confs(cfg: PathConfig, output_channels=80, small_encoder=False, norm="BN"):
     """backbone_conf / head_conf of base_exp.py:40-252 for the path configuration `cfg` (cfg-A is the
-    reference's own).  `small_encoder` swaps ResNet-50 for ResNet-18 with 1/4 of the neck width (tests)."""
+    reference's own).  `small_encoder` swaps ResNet-50 for ResNet-18 with 1/4 of the neck width (tests).
+    `norm`: "BN" -- nn.BatchNorm2d everywhere, today's configurations exactly; "SyncBN" -- the four encoder
+    configurations and the head get `norm_cfg=dict(type="SyncBN")` (norm.BatchNormAct2d: synchronised, fused)."""
+    if norm not in ("BN", "SyncBN"):
+        raise ValueError(f"norm must be 'BN' or 'SyncBN', got {norm!r}")
     oy = cfg.oY
     if small_encoder:
         bb = dict(type="ResNet", depth=18, out_indices=[0, 1, 2, 3])
@@ -593,6 +600,11 @@ def reference_confs(cfg: PathConfig, output_channels=80, small_encoder=False):
                       voxel_size=[vs, vs, 8], nms_type="circle", pre_max_size=1000, post_max_size=83, nms_thr=0.2),
         in_channels=256, loss_cls=dict(type="GaussianFocalLoss", reduction="mean"),
         loss_bbox=dict(type="L1Loss", reduction="mean", loss_weight=0.25), gaussian_overlap=0.1, min_radius=2)
+    if norm != "BN":
+        for conf in (backbone_conf["img_backbone_conf"], head_conf["bev_backbone_conf"], head_conf):
+            conf["norm_cfg"] = dict(type=norm)
+        for conf in (backbone_conf["img_neck_conf"], head_conf["bev_neck_conf"]):      # SECONDFPN's own eps, momentum
+            conf["norm_cfg"] = dict(type=norm, eps=1e-3, momentum=0.01)
     return backbone_conf, head_conf
 
 
