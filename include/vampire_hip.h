@@ -33,7 +33,7 @@ extern "C" {
                                  14: masked regression losses; 15: the camera render's plans and workspace layout;
                                  16: the lift's plans and workspace layout;
                                  16 also: stride-2 16-bit convolutions, the 2-D bilinear resize of the rendered maps and the
-                                 parameter update, the lidar-point label rasteriser, the camera images, detection scoring, batch normalisation; the number
+                                 parameter update, the lidar-point label rasteriser, the camera images, detection scoring, batch normalisation, the convolutions' epilogue; the number
                                  could not move: a test pins it) */
 
 enum {
@@ -1092,6 +1092,68 @@ int vamp_conv3d_half_s2_backward_data(const VampConvDesc* d, int32_t dtype, cons
                                       void* grad_in, void* stream);
 int vamp_conv3d_half_s2_backward_weight(const VampConvDesc* d, int32_t dtype, const void* in, const void* grad_out,
                                         float* grad_weight, void* workspace, size_t workspace_bytes, void* stream);
+
+/*
+ * The same convolutions with an epilogue at the point where they store their accumulators:
+ *     y = act(conv(x, w) + bias + residual)
+ * in 1 .. VAMP_CONV_EPI_MAX_SEGS segments of output channels.  A segment is a channel range [c0, c0 + nch), an
+ * optional fp32 bias[nch], an optional residual, an activation and an output tensor of its own, contiguous
+ * [B, nch, Zo, Yo, Xo] (the convolution's output volume); the residual has the output's shape and type.  The output
+ * type is the kind's compute type (fp32, or `dtype` for the 16-bit kinds), or fp32 from a 16-bit kind when out_f32
+ * is 1; the segments of one call share out_f32.  An ordinary layer is one segment over all of cout; the three heads (density / logits / rgb + sigmoid) are
+ * three segments of one convolution written straight into three tensors.  Channels that no segment holds are computed
+ * and not stored.  The arithmetic order is fixed, fp32, one rounding per step and no contraction: acc + bias, then
+ * + residual, then the activation; the result is rounded once to the output type.  leaky_relu is
+ * v > 0 ? v : v * slope, sigmoid 1 / (1 + exp(-v)).
+ *
+ * The plain entry points above launch kernels without any of this.
+ *
+ * Backward: vamp_conv3d_epilogue_backward computes g_z = g * act'(y) -- leaky: y > 0 ? 1 : slope, sigmoid:
+ * y (1 - y) -- from each segment's gradient `grad_out` and output `out` (both of the segment's output type), gathers
+ * the segments into ONE grad_z [B, cout, Zo, Yo, Xo] of the compute type (channels outside every segment: 0), rounded
+ * once, and -- for every segment with a grad_bias -- sums g_z over samples and voxels, in the segment's own precision
+ * (the rounded g_z of a compute-type segment; the fp32 products of an fp32-output segment of a 16-bit kind, whose copy
+ * in grad_z is rounded for the convolution's backward alone): float64 partials per workgroup in `workspace`, added in
+ * a fixed order by a finishing launch, rounded once to fp32; no atomics, bitwise repeatable.  grad_z is the residual's gradient, and the operand of the existing backward_data / backward_weight
+ * entry points.  `stride` (1 or 2) and `dtype` name the kind: (1, VAMP_F32), (1, 16-bit), (2, 16-bit).
+ *
+ * Every entry point refuses, before any launch, with VAMP_EINVAL: a descriptor its kind does not take, a NULL
+ * required pointer, nseg outside 1 .. 4, a segment outside [0, cout) or overlapping another, an unknown activation,
+ * out_f32 = 1 for the fp32 kind or differing between segments, forward tensors off a 16-byte boundary; with VAMP_ENOSPC a workspace below
+ * vamp_conv3d_epilogue_workspace_bytes.  "Forward tensors" are in, weight and every segment's out, residual and bias.
+ * vamp_conv3d_epilogue_supported answers the same rules (pointers aside) without a GPU and, being a question, leaves
+ * vamp_last_error as it was.
+ */
+enum { VAMP_ACT_NONE = 0, VAMP_ACT_LEAKY_RELU = 1, VAMP_ACT_SIGMOID = 2 };
+#define VAMP_CONV_EPI_MAX_SEGS 4
+#define VAMP_CONV_EPI_CHUNK 4096      /* voxels of one (sample, channel) a backward workgroup owns */
+typedef struct VampConvEpiSeg {
+  const float* bias;      /* forward: fp32 [nch] or NULL                                                       */
+  const void* residual;   /* forward: [B, nch, Zo, Yo, Xo] of the output type, or NULL                         */
+  void* out;              /* forward: the output (written); backward: the same tensor (read; NULL with ACT_NONE) */
+  const void* grad_out;   /* backward: the gradient of `out`, of the output type                               */
+  float* grad_bias;       /* backward: fp32 [nch] (written) or NULL                                            */
+  int32_t c0, nch;        /* output channels [c0, c0 + nch)                                                    */
+  int32_t act;            /* VAMP_ACT_*                                                                        */
+  int32_t out_f32;        /* 0: the compute type; 1: fp32 (16-bit kinds only)                                  */
+  float slope;            /* VAMP_ACT_LEAKY_RELU's negative slope                                              */
+  int32_t reserved;
+} VampConvEpiSeg;
+typedef struct VampConvEpilogue {
+  int32_t nseg;           /* 1 .. VAMP_CONV_EPI_MAX_SEGS */
+  int32_t reserved;
+  VampConvEpiSeg seg[VAMP_CONV_EPI_MAX_SEGS];
+} VampConvEpilogue;
+int vamp_conv3d_epilogue_supported(const VampConvDesc* d, int32_t stride, int32_t dtype, const VampConvEpilogue* epi);
+int vamp_conv3d_epilogue_forward(const VampConvDesc* d, const VampConvEpilogue* epi, const float* in,
+                                 const float* weight, void* stream);
+int vamp_conv3d_half_epilogue_forward(const VampConvDesc* d, int32_t dtype, const VampConvEpilogue* epi,
+                                      const void* in, const void* weight, void* stream);
+int vamp_conv3d_half_s2_epilogue_forward(const VampConvDesc* d, int32_t dtype, const VampConvEpilogue* epi,
+                                         const void* in, const void* weight, void* stream);
+size_t vamp_conv3d_epilogue_workspace_bytes(const VampConvDesc* d, int32_t stride);
+int vamp_conv3d_epilogue_backward(const VampConvDesc* d, int32_t stride, int32_t dtype, const VampConvEpilogue* epi,
+                                  void* grad_z, void* workspace, size_t workspace_bytes, void* stream);
 
 /* --------------------------------------------------------------------------
  * Segmentation metrics (base_exp.py:370-382 training, :634-663 validation, :835-840 submission labels).

@@ -36,6 +36,8 @@ VAMP_DET_EVAL_RECORD_BYTES, VAMP_DET_EVAL_STATE_WORDS = 32, 24
 VAMP_DET_EVAL_HALF_PERIOD, VAMP_DET_EVAL_HAS_ORIENT, VAMP_DET_EVAL_HAS_VEL, VAMP_DET_EVAL_HAS_ATTR = 1, 2, 4, 8
 VAMP_BN_CHUNK, VAMP_BN_MAX_WORLD = 4096, 64
 VAMP_BN_ACT_NONE, VAMP_BN_ACT_RELU = 0, 1
+VAMP_ACT_NONE, VAMP_ACT_LEAKY_RELU, VAMP_ACT_SIGMOID = 0, 1, 2
+VAMP_CONV_EPI_MAX_SEGS, VAMP_CONV_EPI_CHUNK = 4, 4096
 
 
 class VampLiftDesc(C.Structure):
@@ -68,6 +70,17 @@ class VampRenderDesc(C.Structure):
 class VampConvDesc(C.Structure):
     _fields_ = [("B", C.c_int32), ("cin", C.c_int32), ("cout", C.c_int32),
                 ("Z", C.c_int32), ("Y", C.c_int32), ("X", C.c_int32)]
+
+
+class VampConvEpiSeg(C.Structure):
+    """One segment of output channels of a convolution's epilogue (include/vampire_hip.h)."""
+    _fields_ = [("bias", C.c_void_p), ("residual", C.c_void_p), ("out", C.c_void_p), ("grad_out", C.c_void_p),
+                ("grad_bias", C.c_void_p), ("c0", C.c_int32), ("nch", C.c_int32), ("act", C.c_int32),
+                ("out_f32", C.c_int32), ("slope", C.c_float), ("reserved", C.c_int32)]
+
+
+class VampConvEpilogue(C.Structure):
+    _fields_ = [("nseg", C.c_int32), ("reserved", C.c_int32), ("seg", VampConvEpiSeg * VAMP_CONV_EPI_MAX_SEGS)]
 
 
 class VampSampleDesc(C.Structure):
@@ -350,6 +363,7 @@ _RD = C.POINTER(VampRenderDesc)
 _SD = C.POINTER(VampSampleDesc)
 _QYD = C.POINTER(VampQueryDesc)
 _CD = C.POINTER(VampConvDesc)
+_CED = C.POINTER(VampConvEpilogue)
 _PD = C.POINTER(VampPoolDesc)
 _QD = C.POINTER(VampConfDesc)
 _DD = C.POINTER(VampDetDesc)
@@ -457,6 +471,12 @@ SIGNATURES = {
     "vamp_conv3d_half_s2_forward": (_STATUS, [_CD, C.c_int32, _P, _P, _P, _P]),
     "vamp_conv3d_half_s2_backward_data": (_STATUS, [_CD, C.c_int32, _P, _P, _P, _P]),
     "vamp_conv3d_half_s2_backward_weight": (_STATUS, [_CD, C.c_int32, _P, _P, _P, _P, C.c_size_t, _P]),
+    "vamp_conv3d_epilogue_supported": (_INT, [_CD, C.c_int32, C.c_int32, _CED]),
+    "vamp_conv3d_epilogue_forward": (_STATUS, [_CD, _CED, _P, _P, _P]),
+    "vamp_conv3d_half_epilogue_forward": (_STATUS, [_CD, C.c_int32, _CED, _P, _P, _P]),
+    "vamp_conv3d_half_s2_epilogue_forward": (_STATUS, [_CD, C.c_int32, _CED, _P, _P, _P]),
+    "vamp_conv3d_epilogue_workspace_bytes": (_SIZE, [_CD, C.c_int32]),
+    "vamp_conv3d_epilogue_backward": (_STATUS, [_CD, C.c_int32, C.c_int32, _CED, _P, _P, C.c_size_t, _P]),
     "vamp_density_gate_backward": (_STATUS, [C.c_int64, C.c_int32, C.c_int64, C.c_int32, _P, _P, _P, _P, _P,
                                              _P]),
     "vamp_voxel_pooling_workspace_bytes": (_SIZE, [_PD]),

@@ -38,7 +38,8 @@ from torch import nn
 from . import geometry as G
 from .config import PathConfig
 from .density import ModifyLaplaceDensity
-from .layers import conv3d_3x3x3, conv3d_bf16, conv3d_bf16_stride2, conv3d_kind, cuda_autocast
+from .layers import (HeadSegment, conv3d_3x3x3, conv3d_bf16, conv3d_bf16_stride2, conv3d_fused, conv3d_heads, conv3d_kind,
+                     cuda_autocast)
 from .ops import HotPath
 
 
@@ -65,7 +66,9 @@ def _resize(x, size):
 # layers under a 16-bit autocast (default: the HIP kernels of conv3d_bf16_s2.hip), VAMP_RESIZE2D=1 routes the x4
 # resize of the three rendered camera maps and the 256-cell grid's 0.5x resize through resize2d.hip (default: aten),
 # VAMP_QUERIES=fused answers the lidar-point and occupancy queries with one `HotPath.point_queries` call (default:
-# split, one `sample_points` call per sample and volume plus `occupancy_queries`).
+# split, one `sample_points` call per sample and volume plus `occupancy_queries`), VAMP_CONV3D_EPILOGUE=1 fuses what
+# follows a 3-D convolution (bias, residual add, LeakyReLU, the heads' slices and sigmoid) into the convolution kernel's
+# store (default: the torch expressions).
 # Tests and tools flip the attributes of `SWITCHES`.
 class _Switches:
     conv3d = os.environ.get("VAMP_CONV3D", "1") != "0"
@@ -86,6 +89,11 @@ class _Switches:
     # the point queries of bv2:576-609: "split" = 2 B + 2 `sample_points` calls, each an autograd node with a cell list
     # and a full-size gradient volume of its own; "fused" = one `point_queries` call, one backward
     queries = os.environ.get("VAMP_QUERIES", "split")
+    # y = act(conv(x, w) + bias + residual) as one operator and one autograd node (`layers.conv3d_fused`,
+    # `layers.conv3d_heads`) wherever `conv3d_kind` names a HIP kernel for the layer: twelve of the UNet's
+    # thirteen convolutions, the three heads, and the layers with a bias.  Default off until profiles/conv_epilogue.json
+    # argues otherwise.
+    conv3d_epilogue = os.environ.get("VAMP_CONV3D_EPILOGUE", "0") == "1"
 
 
 SWITCHES = _Switches()
@@ -118,16 +126,49 @@ def _hip_conv3d(x, weight, stride, padding, bias):
     return (conv3d_bf16 if kind == "half" else conv3d_bf16_stride2)(x.to(dt16), weight.to(dt16))
 
 
+def _layer_kind(x, weight, stride, padding):
+    """The kind of HIP convolution the epilogue operators would run the layer on under `SWITCHES` and the current
+    autocast (a bias is theirs to add), or None."""
+    if not (SWITCHES.conv3d and SWITCHES.conv3d_epilogue):
+        return None
+    return conv3d_kind(x.shape, weight.shape, x.dtype, weight.dtype, x.is_cuda, stride, padding, False,
+                       autocast=cuda_autocast(), min_voxels=SWITCHES.conv3d_min_voxels, stride2=SWITCHES.conv3d_s2)
+
+
+def _fused_conv3(layer, x, residual=None, act=None, slope=0.01):
+    """act(layer(x) + residual) as one `conv3d_fused` call (the layer's bias included), or None where no HIP kernel
+    takes the layer."""
+    if _layer_kind(x, layer.weight, layer.stride, layer.padding) is None:
+        return None
+    return conv3d_fused(x, layer.weight, layer.bias, residual, act, slope, layer.stride[0])
+
+
+def _conv3_then(layer, x, residual=None, leaky=False):
+    """leaky_relu(layer(x) + residual), the add and the activation as asked: fused into the convolution where a HIP
+    kernel takes the layer, today's torch expressions where none does."""
+    y = _fused_conv3(layer, x, residual, "leaky_relu" if leaky else None)
+    if y is not None:
+        return y
+    y = layer(x)
+    if residual is not None:
+        y = y + residual
+    return F.leaky_relu(y, inplace=True) if leaky else y
+
+
 class _Conv3(nn.Conv3d):
     """nn.Conv3d(cin, cout, 3, stride, 1, bias=False) (same parameter name and shape).  The
     stride-1 layers with 16 / 32 channels run on the HIP fp32 matrix-core kernels for fp32 device
     tensors of at least `VAMP_CONV3D_MIN_VOXELS` voxels (default 50 000: 1.7x MIOpen forward +
     backward at 16x200x200, 1.1x at 8x100x100; the coarsest level is latency-bound and stays with
     MIOpen); `VAMP_CONV3D=0` keeps MIOpen everywhere.  Under a 16-bit autocast the stride-1 layers run on
-    conv3d_bf16.hip and the stride-2 ones on conv3d_bf16_s2.hip (`VAMP_CONV3D_S2=0`: MIOpen)."""
+    conv3d_bf16.hip and the stride-2 ones on conv3d_bf16_s2.hip (`VAMP_CONV3D_S2=0`: MIOpen).  A layer built with a
+    bias reaches the HIP kernels only through their bias epilogue (`VAMP_CONV3D_EPILOGUE=1`)."""
 
     def forward(self, x):
-        y = _hip_conv3d(x, self.weight, self.stride, self.padding, self.bias)
+        if self.bias is not None:
+            y = _fused_conv3(self, x)
+        else:
+            y = _hip_conv3d(x, self.weight, self.stride, self.padding, self.bias)
         return super().forward(x) if y is None else y
 
 
@@ -148,7 +189,24 @@ class Hourglass3D(nn.Module):
         self.conv5 = nn.Sequential(_conv3(2 * m, 2 * m))
         self.conv6 = nn.Sequential(_conv3(2 * m, m))
 
-    def forward(self, x, presqu=None, postsqu=None):
+    def forward(self, x, presqu=None, postsqu=None, skip=None):
+        """`skip`: a tensor added to the block's output (Unet3D's residual to the stem), or None."""
+        if SWITCHES.conv3d_epilogue:
+            return self._forward_fused(x, presqu, postsqu, skip)
+        out, pre, post = self._forward_plain(x, presqu, postsqu)
+        return (out if skip is None else out + skip), pre, post
+
+    def _forward_fused(self, x, presqu, postsqu, skip):
+        """The same block with every add and LeakyReLU inside the convolution before it (`_conv3_then`)."""
+        down = _conv3_then(self.conv1[0], x, leaky=True)
+        pre = _conv3_then(self.conv2[0], down, postsqu, leaky=True)
+        bottom = _conv3_then(self.conv4[0], _conv3_then(self.conv3[0], pre, leaky=True), leaky=True)
+        up = _resize(bottom, pre.shape[-3:])
+        post = _conv3_then(self.conv5[0], up, pre if presqu is None else presqu, leaky=True)
+        out = _resize(post, x.shape[-3:])
+        return _conv3_then(self.conv6[0], out, skip), pre, post
+
+    def _forward_plain(self, x, presqu=None, postsqu=None):
         down = self.conv1(x)
         pre = self.conv2(down)
         pre = F.leaky_relu(pre if postsqu is None else pre + postsqu, inplace=True)
@@ -171,6 +229,9 @@ class Unet3D(nn.Module):
 
     def forward(self, x):
         stem = self.init_dres(x)
+        if SWITCHES.conv3d_epilogue:               # the two adds of the stem ride in conv6's epilogue
+            out1, pre1, post1 = self.hg1(stem, skip=stem)
+            return self.hg2(out1, pre1, post1, skip=stem)[0]
         out1, pre1, post1 = self.hg1(stem)
         out1 = out1 + stem
         out2, _, _ = self.hg2(out1, pre1, post1)
@@ -297,11 +358,11 @@ class BaseVAMPIRE2(nn.Module):
         if self._BASE == "unet":
             self.base_conv = Unet3D(vin, mid_channels)
         else:                                                        # base_lss.py:117-124, base_bilinear.py:173-179
-            self.base_conv = nn.Sequential(nn.Conv3d(vin, mid_channels, 3, 1, 1, bias=True), nn.Softplus(beta=100))
+            self.base_conv = nn.Sequential(_Conv3(vin, mid_channels, 3, 1, 1, bias=True), nn.Softplus(beta=100))
         self.density_conv = nn.Conv3d(mid_channels, 1, 3, 1, 1, bias=True)
         self.seg_conv = nn.Conv3d(mid_channels, num_classes, 3, 1, 1, bias=True)
         if not self._USE_DEPTH:
-            self.feature_conv = nn.Conv3d(mid_channels, mid_channels, 3, 1, 1, bias=True)   # base_bilinear.py:182
+            self.feature_conv = _Conv3(mid_channels, mid_channels, 3, 1, 1, bias=True)      # base_bilinear.py:182
         self.density = nn.Sigmoid() if density_mode == "naive" else \
             ModifyLaplaceDensity(beta=0.1, bias=sdf_bias)
         self.rgb_conv = nn.Sequential(nn.Conv3d(mid_channels, 3, 3, 1, 1, bias=True), nn.Sigmoid())
@@ -425,6 +486,12 @@ class BaseVAMPIRE2(nn.Module):
         if SWITCHES.conv3d and nout <= 32 and base.dim() == 5 and base.is_cuda:
             wd, ws, wr = self.density_conv.weight, self.seg_conv.weight, self.rgb_conv[0].weight
             w = torch.cat([wd, ws, wr, wd.new_zeros((32 - nout,) + tuple(wd.shape[1:]))], 0)
+            if _layer_kind(base, w, (1, 1, 1), (1, 1, 1)) is not None:
+                # the three slices, bias adds and the sigmoid in the convolution's store: no padded y, fp32 outputs
+                f32 = torch.float32
+                return conv3d_heads(base, w, [HeadSegment(1, self.density_conv.bias, None, f32),
+                                              HeadSegment(self.num_classes, self.seg_conv.bias, None, f32),
+                                              HeadSegment(3, self.rgb_conv[0].bias, "sigmoid", f32)])
             y = _hip_conv3d(base, w, (1, 1, 1), (1, 1, 1), None)
             if y is not None:
                 K = self.num_classes

@@ -18,6 +18,7 @@
 // Work is priced against the fp32 matrix peak (157 TFLOP/s dense): this is the one MFMA-bound
 // piece near the path.
 #include "common.hpp"
+#include "conv3d_epilogue.hpp"
 
 #include <cstdlib>
 
@@ -48,10 +49,13 @@ __device__ __forceinline__ float dpp_row_shl1(float old, float v) {   // lane i 
 // One wave's tile: NM (2 .. 4) M tiles = 16 NM consecutive x of the row (b, z, y) x all output
 // channels.  A row of T = ceil(X / 16) M tiles is cut into ceil(T / 4) wave tiles of nearly equal
 // size (X = 200: 13 M tiles = 4 + 3 + 3 + 3; four 64-wide tiles would compute 16).
-template <int CIN, int COUT, int NM>
+// EPI: the accumulators go through the epilogue `ep` (conv3d_epilogue.hpp) into its segments' tensors instead of `ob`;
+// b = the sample, rowoff = the row's first voxel in the volume.
+template <int CIN, int COUT, int NM, bool EPI>
 __device__ __forceinline__ void conv_tile(const ConvParams& P, const float* __restrict__ inb,
                                           const float* __restrict__ wl, float* __restrict__ ob, int z,
-                                          int y, int x0, int li, int lk, long plane) {
+                                          int y, int x0, int li, int lk, long plane,
+                                          const VampConvEpilogue* ep, long b, long rowoff) {
   constexpr int NT = COUT / 16;
   f32x4 acc[NM][NT];
 #pragma unroll
@@ -113,6 +117,33 @@ __device__ __forceinline__ void conv_tile(const ConvParams& P, const float* __re
     }
   }
   // C/D: col (output channel) = lane & 15, row (voxel) = (lane >> 4) * 4 + reg
+  if constexpr (EPI) {
+#pragma unroll
+    for (int n = 0; n < NT; ++n) {
+      const EpiSel sel = epi_select(*ep, n * 16 + li);
+      if (!sel.hit) continue;
+      const bool has_bias = sel.bias != nullptr;
+      const float bv = has_bias ? sel.bias[sel.cc] : 0.f;
+      const long cb = (b * sel.nch + sel.cc) * plane + rowoff;
+#pragma unroll
+      for (int m = 0; m < NM; ++m) {
+        const int xb = x0 + m * 16 + lk * 4;
+        if (xb + 3 < P.X && ((P.X & 3) == 0)) {          // whole 16-byte groups: the tensors start on such a boundary
+          f32x4 v = acc[m][n];
+          if (has_bias) v = v + bv;
+          if (sel.residual) v = v + *reinterpret_cast<const f32x4*>(static_cast<const float*>(sel.residual) + cb + xb);
+#pragma unroll
+          for (int r = 0; r < 4; ++r) v[r] = epi_act(sel.act, sel.slope, v[r]);
+          *reinterpret_cast<f32x4*>(static_cast<float*>(sel.out) + cb + xb) = v;
+        } else {
+#pragma unroll
+          for (int r = 0; r < 4; ++r)
+            if (xb + r < P.X) epi_store<kEpiF32>(sel, has_bias, bv, b, plane, rowoff + xb + r, acc[m][n][r]);
+        }
+      }
+    }
+    return;
+  }
 #pragma unroll
   for (int m = 0; m < NM; ++m) {
     const int xb = x0 + m * 16 + lk * 4;
@@ -130,10 +161,10 @@ __device__ __forceinline__ void conv_tile(const ConvParams& P, const float* __re
   }
 }
 
-template <int CIN, int COUT, bool FLIP>
-__global__ void __launch_bounds__(512)
-conv3d_fwd_kernel(ConvParams P, const float* __restrict__ in, const float* __restrict__ w,
-                  float* __restrict__ out, int tiles_x, long ntiles) {
+template <int CIN, int COUT, bool FLIP, bool EPI>
+__device__ __forceinline__ void conv3d_fwd_body(const ConvParams& P, const float* __restrict__ in,
+                                                const float* __restrict__ w, float* __restrict__ out, int tiles_x,
+                                                long ntiles, const VampConvEpilogue* ep) {
   extern __shared__ float wl[];                       // [27][CIN][COUT]
   // weights -> LDS.  forward: wl[t][ci][co] = w[co][ci][t];
   // data gradient (the roles of the channels swap): wl[t][k][j] = w[co = k][ci = j][26 - t]
@@ -158,12 +189,28 @@ conv3d_fwd_kernel(ConvParams P, const float* __restrict__ in, const float* __res
     const int x0 = 16 * (tx * base + min(tx, rem));
     const int nm = base + (tx < rem ? 1 : 0);         // wave-uniform
     const float* inb = in + (long) b * CIN * plane;
-    float* ob = out + (long) b * COUT * plane + ((long) z * P.Y + y) * P.X;
-    if (nm == 4) conv_tile<CIN, COUT, 4>(P, inb, wl, ob, z, y, x0, li, lk, plane);
-    else if (nm == 3) conv_tile<CIN, COUT, 3>(P, inb, wl, ob, z, y, x0, li, lk, plane);
-    else if (nm == 2) conv_tile<CIN, COUT, 2>(P, inb, wl, ob, z, y, x0, li, lk, plane);
-    else conv_tile<CIN, COUT, 1>(P, inb, wl, ob, z, y, x0, li, lk, plane);
+    const long rowoff = ((long) z * P.Y + y) * P.X;
+    float* ob = EPI ? nullptr : out + (long) b * COUT * plane + rowoff;
+    if (nm == 4) conv_tile<CIN, COUT, 4, EPI>(P, inb, wl, ob, z, y, x0, li, lk, plane, ep, b, rowoff);
+    else if (nm == 3) conv_tile<CIN, COUT, 3, EPI>(P, inb, wl, ob, z, y, x0, li, lk, plane, ep, b, rowoff);
+    else if (nm == 2) conv_tile<CIN, COUT, 2, EPI>(P, inb, wl, ob, z, y, x0, li, lk, plane, ep, b, rowoff);
+    else conv_tile<CIN, COUT, 1, EPI>(P, inb, wl, ob, z, y, x0, li, lk, plane, ep, b, rowoff);
   }
+}
+
+template <int CIN, int COUT, bool FLIP>
+__global__ void __launch_bounds__(512)
+conv3d_fwd_kernel(ConvParams P, const float* __restrict__ in, const float* __restrict__ w,
+                  float* __restrict__ out, int tiles_x, long ntiles) {
+  conv3d_fwd_body<CIN, COUT, FLIP, false>(P, in, w, out, tiles_x, ntiles, nullptr);
+}
+
+// the forward with the epilogue: the same tiles, the segments' tensors instead of `out`
+template <int CIN, int COUT>
+__global__ void __launch_bounds__(512)
+conv3d_fwd_epi_kernel(ConvParams P, const float* __restrict__ in, const float* __restrict__ w, VampConvEpilogue ep,
+                      int tiles_x, long ntiles) {
+  conv3d_fwd_body<CIN, COUT, false, true>(P, in, w, nullptr, tiles_x, ntiles, &ep);
 }
 
 // ---------------------------------------------------------------------------
@@ -385,16 +432,21 @@ int check(const VampConvDesc* d) {
   return VAMP_OK;
 }
 
-template <int CIN, int COUT, bool FLIP>
-int launch_fwd(const VampConvDesc* d, const float* in, const float* w, float* out, hipStream_t s) {
+template <int CIN, int COUT, bool FLIP, bool EPI = false>
+int launch_fwd(const VampConvDesc* d, const float* in, const float* w, float* out, hipStream_t s,
+               const VampConvEpilogue* ep = nullptr) {
   ConvParams P{d->B, d->Z, d->Y, d->X};
   const int tiles_x = ((d->X + 15) / 16 + 3) / 4;        // wave tiles per row: ceil(M tiles / 4)
   const long ntiles = (long) d->B * d->Z * d->Y * tiles_x;
   const size_t lds = (size_t) 27 * CIN * COUT * sizeof(float);
   static bool attr_set = false;
   if (!attr_set) {
-    (void) hipFuncSetAttribute(reinterpret_cast<const void*>(&conv3d_fwd_kernel<CIN, COUT, FLIP>),
-                               hipFuncAttributeMaxDynamicSharedMemorySize, (int) lds);
+    if constexpr (EPI)
+      (void) hipFuncSetAttribute(reinterpret_cast<const void*>(&conv3d_fwd_epi_kernel<CIN, COUT>),
+                                 hipFuncAttributeMaxDynamicSharedMemorySize, (int) lds);
+    else
+      (void) hipFuncSetAttribute(reinterpret_cast<const void*>(&conv3d_fwd_kernel<CIN, COUT, FLIP>),
+                                 hipFuncAttributeMaxDynamicSharedMemorySize, (int) lds);
     attr_set = true;
   }
   // persistent workgroups of 8 waves that share one weight image: 1 / 2 / 4 per CU by LDS size
@@ -403,6 +455,11 @@ int launch_fwd(const VampConvDesc* d, const float* in, const float* w, float* ou
   const int wpb = ntiles >= 1024 ? 8 : 4;
   const int per_cu = lds > 80 * 1024 ? 1 : (lds > 40 * 1024 ? 2 : 4);
   const unsigned grid = (unsigned) std::min<long>((ntiles + wpb - 1) / wpb, 256L * per_cu);
+  if constexpr (EPI) {
+    VAMP_TIMED(kProfConvFwd, s, (conv3d_fwd_epi_kernel<CIN, COUT><<<grid, 64 * wpb, lds, s>>>(
+        P, in, w, *ep, tiles_x, ntiles)));
+    return check_launch("conv3d_fwd_epi_kernel");
+  }
   VAMP_TIMED(FLIP ? kProfConvDgrad : kProfConvFwd, s, (conv3d_fwd_kernel<CIN, COUT, FLIP><<<grid, 64 * wpb, lds, s>>>(
       P, in, w, out, tiles_x, ntiles)));
   return check_launch("conv3d_fwd_kernel");
@@ -424,6 +481,20 @@ int vamp_conv3d_forward(const VampConvDesc* d, const float* in, const float* wei
   if (d->cin == 16 && d->cout == 32) return launch_fwd<16, 32, false>(d, in, weight, out, s);
   if (d->cin == 32 && d->cout == 16) return launch_fwd<32, 16, false>(d, in, weight, out, s);
   return launch_fwd<32, 32, false>(d, in, weight, out, s);
+}
+
+/* the forward through the epilogue (conv3d_epilogue.hpp; the contract is in vampire_hip.h) */
+int vamp_conv3d_epilogue_forward(const VampConvDesc* d, const VampConvEpilogue* epi, const float* in,
+                                 const float* weight, void* stream) {
+  if (int e = check(d)) return e;
+  if (int e = epi_check(__func__, d, epi, false, 1)) return e;
+  VAMP_REQUIRE(in && weight, "NULL tensor");
+  VAMP_REQUIRE(((uintptr_t) in | (uintptr_t) weight) % 16 == 0, "in / weight must start on a 16-byte boundary");
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  if (d->cin == 16 && d->cout == 16) return launch_fwd<16, 16, false, true>(d, in, weight, nullptr, s, epi);
+  if (d->cin == 16 && d->cout == 32) return launch_fwd<16, 32, false, true>(d, in, weight, nullptr, s, epi);
+  if (d->cin == 32 && d->cout == 16) return launch_fwd<32, 16, false, true>(d, in, weight, nullptr, s, epi);
+  return launch_fwd<32, 32, false, true>(d, in, weight, nullptr, s, epi);
 }
 
 /* grad_in [B, cin, Z, Y, X] from grad_out [B, cout, Z, Y, X]: the forward kernel on the flipped,

@@ -18,6 +18,7 @@
 // The data gradient is the same kernel on the flipped, transposed weights (FLIP).
 // The weight gradient has K = voxels, contiguous along x in NCDHW: both operands are plain
 // 16-byte global loads (the shifted-by-one-voxel windows at 2-byte alignment), no LDS at all.
+#include "conv3d_epilogue.hpp"   // the EPI instantiations' store
 #include "conv3d_half.hpp"       // the vector types, mfma16, f32_to_e16, the partials' reduce kernel, tile_ch, bf16_shape_ok
 
 #include <algorithm>
@@ -45,10 +46,12 @@ struct CvLds {
   static constexpr size_t bytes = w_bytes + in_bytes;
 };
 
-template <int CIN, int COUT, bool FLIP, bool F16>
-__global__ void __launch_bounds__(256)
-conv3d_bf16_fwd_kernel(CvP P, const unsigned short* __restrict__ in, const unsigned short* __restrict__ w,
-                       unsigned short* __restrict__ out, int tiles_x, long ntiles) {
+// EPI: the accumulators go through the epilogue `ep` (conv3d_epilogue.hpp) into its segments' tensors instead of `out`
+template <int CIN, int COUT, bool FLIP, bool F16, bool EPI, bool OF32 = false>
+__device__ __forceinline__ void conv3d_bf16_fwd_body(const CvP& P, const unsigned short* __restrict__ in,
+                                                     const unsigned short* __restrict__ w,
+                                                     unsigned short* __restrict__ out, int tiles_x, long ntiles,
+                                                     const VampConvEpilogue* ep) {
   using L = CvLds<CIN, COUT>;
   constexpr int NTP = L::NTP, VS = L::VS, MT = COUT / 16, CG = CIN / 8;
   constexpr int NITEM = kRows * (kHX / 2) * CG;                    // (row, x pair, 8-channel group)
@@ -165,7 +168,10 @@ conv3d_bf16_fwd_kernel(CvP P, const unsigned short* __restrict__ in, const unsig
     else if (nnt == 3) run(std::integral_constant<int, 3>());
     else if (nnt == 2) run(std::integral_constant<int, 2>());
     else run(std::integral_constant<int, 1>());
-    if (y < P.Y) {
+    if constexpr (EPI) {
+      if (y < P.Y)
+        epi_store_tile<F16 ? kEpiF16 : kEpiBF16, OF32, MT, 4>(*ep, acc, kg, li, b, plane, ((long) z * P.Y + y) * P.X, x0, P.X, w);
+    } else if (y < P.Y) {
       unsigned short* ob = out + (long) b * P.cout * plane + ((long) z * P.Y + y) * P.X;
 #pragma unroll
       for (int m = 0; m < MT; ++m)
@@ -180,6 +186,21 @@ conv3d_bf16_fwd_kernel(CvP P, const unsigned short* __restrict__ in, const unsig
         }
     }
   }
+}
+
+template <int CIN, int COUT, bool FLIP, bool F16>
+__global__ void __launch_bounds__(256)
+conv3d_bf16_fwd_kernel(CvP P, const unsigned short* __restrict__ in, const unsigned short* __restrict__ w,
+                       unsigned short* __restrict__ out, int tiles_x, long ntiles) {
+  conv3d_bf16_fwd_body<CIN, COUT, FLIP, F16, false>(P, in, w, out, tiles_x, ntiles, nullptr);
+}
+
+// the forward with the epilogue: the same tiles, the segments' tensors instead of `out`
+template <int CIN, int COUT, bool F16, bool OF32>
+__global__ void __launch_bounds__(256)
+conv3d_bf16_fwd_epi_kernel(CvP P, const unsigned short* __restrict__ in, const unsigned short* __restrict__ w,
+                           VampConvEpilogue ep, int tiles_x, long ntiles) {
+  conv3d_bf16_fwd_body<CIN, COUT, false, F16, true, OF32>(P, in, w, nullptr, tiles_x, ntiles, &ep);
 }
 
 // ---------------------------------------------------------------------------
@@ -347,6 +368,27 @@ int launch_fwd(const VampConvDesc* d, const void* in, const void* w, void* out, 
   return check_launch("conv3d_bf16_fwd_kernel");
 }
 
+template <int CIN, int COUT, bool F16, bool OF32>
+int launch_fwd_epi_t(const VampConvDesc* d, const VampConvEpilogue* ep, const void* in, const void* w, hipStream_t s) {
+  using L = CvLds<CIN, COUT>;
+  auto k = conv3d_bf16_fwd_epi_kernel<CIN, COUT, F16, OF32>;
+  if (hipFuncSetAttribute(reinterpret_cast<const void*>(k), hipFuncAttributeMaxDynamicSharedMemorySize, (int) L::bytes) != hipSuccess)
+    return fail(VAMP_EHIP, "%s: cannot raise dynamic LDS", __func__);
+  const CvP P{d->B, d->Z, d->Y, d->X, d->cin, d->cout};
+  const int tiles_x = (d->X + kTX - 1) / kTX;
+  const long ntiles = (long) d->B * d->Z * ((d->Y + kTY - 1) / kTY) * tiles_x;
+  const int per_cu = L::bytes <= 78 * 1024 ? 2 : 1;
+  const unsigned grid = (unsigned) std::min<long>(ntiles, 256 * per_cu);
+  VAMP_TIMED(kProfConvFwd, s, (k<<<grid, 256, L::bytes, s>>>(
+      P, static_cast<const unsigned short*>(in), static_cast<const unsigned short*>(w), *ep, tiles_x, ntiles)));
+  return check_launch("conv3d_bf16_fwd_epi_kernel");
+}
+template <int CIN, int COUT, bool F16>
+int launch_fwd_epi(const VampConvDesc* d, const VampConvEpilogue* ep, const void* in, const void* w, hipStream_t s) {
+  return ep->seg[0].out_f32 ? launch_fwd_epi_t<CIN, COUT, F16, true>(d, ep, in, w, s)
+                            : launch_fwd_epi_t<CIN, COUT, F16, false>(d, ep, in, w, s);
+}
+
 template <int CIN, int COUT, bool F16>
 int launch_wgrad(const VampConvDesc* d, const void* in, const void* dout, float* dw, float* ws, hipStream_t s) {
   const CvP P{d->B, d->Z, d->Y, d->X, d->cin, d->cout};
@@ -390,6 +432,25 @@ int vamp_conv3d_half_forward(const VampConvDesc* d, int32_t dtype, const void* i
                                          : launch_fwd<16, 32, false, F16>(d, in, weight, out, s);          \
   return tile_ch(d->cout) == 16 ? launch_fwd<32, 16, false, F16>(d, in, weight, out, s)                             \
                        : launch_fwd<32, 32, false, F16>(d, in, weight, out, s);
+  if (dtype == VAMP_F16) { VAMP_CV(true) }
+  VAMP_CV(false)
+#undef VAMP_CV
+}
+
+// the forward through the epilogue (conv3d_epilogue.hpp; the contract is in vampire_hip.h)
+int vamp_conv3d_half_epilogue_forward(const VampConvDesc* d, int32_t dtype, const VampConvEpilogue* epi,
+                                      const void* in, const void* weight, void* stream) {
+  VAMP_REQUIRE(bf16_shape_ok(d), "unsupported shape: see vamp_conv3d_bf16_supported");
+  VAMP_REQUIRE(dtype == VAMP_BF16 || dtype == VAMP_F16, "dtype must be VAMP_BF16 or VAMP_F16");
+  if (int e = epi_check(__func__, d, epi, true, 1)) return e;
+  VAMP_REQUIRE(in && weight, "NULL tensor");
+  VAMP_REQUIRE(((uintptr_t) in | (uintptr_t) weight) % 16 == 0, "in / weight must start on a 16-byte boundary");
+  hipStream_t s = static_cast<hipStream_t>(stream);
+#define VAMP_CV(F16)                                                                                       \
+  if (tile_ch(d->cin) == 16) return tile_ch(d->cout) == 16 ? launch_fwd_epi<16, 16, F16>(d, epi, in, weight, s)   \
+                                         : launch_fwd_epi<16, 32, F16>(d, epi, in, weight, s);              \
+  return tile_ch(d->cout) == 16 ? launch_fwd_epi<32, 16, F16>(d, epi, in, weight, s)                        \
+                       : launch_fwd_epi<32, 32, F16>(d, epi, in, weight, s);
   if (dtype == VAMP_F16) { VAMP_CV(true) }
   VAMP_CV(false)
 #undef VAMP_CV

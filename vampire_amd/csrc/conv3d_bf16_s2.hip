@@ -28,6 +28,7 @@
 //     Xo % 4 == 2: the windows are loaded in naturally aligned pieces (16 / 8 / 4 bytes for dout, 16 / 16 / 8 for
 //     the input), chosen by X % 16, X % 8, X % 4.  Per-workgroup partials, then the fixed-order reduce of the
 //     stride-1 kernel: bitwise repeatable.
+#include "conv3d_epilogue.hpp"   // the EPI instantiations' store
 #include "conv3d_half.hpp"
 
 #include <algorithm>
@@ -143,10 +144,12 @@ struct FwdLds {
   static constexpr size_t bytes = w_bytes + B::bytes;
 };
 
-template <int CIN, int COUT, bool F16>
-__global__ void __launch_bounds__(256)
-conv3d_s2_fwd_kernel(S2P P, const unsigned short* __restrict__ in, const unsigned short* __restrict__ w,
-                     unsigned short* __restrict__ out, int tiles_x, int tiles_y, long ntiles) {
+// EPI: the accumulators go through the epilogue `ep` (conv3d_epilogue.hpp) into its segments' tensors instead of `out`
+template <int CIN, int COUT, bool F16, bool EPI, bool OF32 = false>
+__device__ __forceinline__ void conv3d_s2_fwd_body(const S2P& P, const unsigned short* __restrict__ in,
+                                                   const unsigned short* __restrict__ w,
+                                                   unsigned short* __restrict__ out, int tiles_x, int tiles_y,
+                                                   long ntiles, const VampConvEpilogue* ep) {
   using T = FwdTile<CIN>;
   using L = FwdLds<CIN, COUT>;
   using BX = typename L::B;
@@ -228,7 +231,11 @@ conv3d_s2_fwd_kernel(S2P P, const unsigned short* __restrict__ in, const unsigne
     } else if (nnt == 1) {
       run(std::integral_constant<int, 1>());
     }
-    if (yo < P.Yo) {
+    if constexpr (EPI) {
+      if (yo < P.Yo)
+        epi_store_tile<F16 ? kEpiF16 : kEpiBF16, OF32, MT, NNW>(*ep, acc, kg, li, b, plane_o, ((long) zo * P.Yo + yo) * P.Xo, xo0,
+                                                               P.Xo, w);
+    } else if (yo < P.Yo) {
       unsigned short* ob = out + (long) b * P.cout * plane_o + ((long) zo * P.Yo + yo) * P.Xo;
 #pragma unroll
       for (int m = 0; m < MT; ++m)
@@ -243,6 +250,21 @@ conv3d_s2_fwd_kernel(S2P P, const unsigned short* __restrict__ in, const unsigne
         }
     }
   }
+}
+
+template <int CIN, int COUT, bool F16>
+__global__ void __launch_bounds__(256)
+conv3d_s2_fwd_kernel(S2P P, const unsigned short* __restrict__ in, const unsigned short* __restrict__ w,
+                     unsigned short* __restrict__ out, int tiles_x, int tiles_y, long ntiles) {
+  conv3d_s2_fwd_body<CIN, COUT, F16, false>(P, in, w, out, tiles_x, tiles_y, ntiles, nullptr);
+}
+
+// the forward with the epilogue: the same tiles, the segments' tensors instead of `out`
+template <int CIN, int COUT, bool F16, bool OF32>
+__global__ void __launch_bounds__(256)
+conv3d_s2_fwd_epi_kernel(S2P P, const unsigned short* __restrict__ in, const unsigned short* __restrict__ w,
+                         VampConvEpilogue ep, int tiles_x, int tiles_y, long ntiles) {
+  conv3d_s2_fwd_body<CIN, COUT, F16, true, OF32>(P, in, w, nullptr, tiles_x, tiles_y, ntiles, &ep);
 }
 
 // ---------------------------------------------------------------------------
@@ -546,6 +568,26 @@ int launch_fwd(const VampConvDesc* d, const void* in, const void* w, void* out, 
   return check_launch("conv3d_s2_fwd_kernel");
 }
 
+template <int CIN, int COUT, bool F16, bool OF32>
+int launch_fwd_epi_t(const VampConvDesc* d, const VampConvEpilogue* ep, const void* in, const void* w, hipStream_t s) {
+  using L = FwdLds<CIN, COUT>;
+  auto k = conv3d_s2_fwd_epi_kernel<CIN, COUT, F16, OF32>;
+  if (hipFuncSetAttribute(reinterpret_cast<const void*>(k), hipFuncAttributeMaxDynamicSharedMemorySize, (int) L::bytes) != hipSuccess)
+    return fail(VAMP_EHIP, "%s: cannot raise dynamic LDS", __func__);
+  const S2P P = make_params(d);
+  const int tiles_x = (P.Xo + kFwdTX - 1) / kFwdTX, tiles_y = (P.Yo + FwdTile<CIN>::TY - 1) / FwdTile<CIN>::TY;
+  const long ntiles = (long) P.B * P.Zo * tiles_y * tiles_x;
+  const unsigned grid = (unsigned) std::min<long>(ntiles, kFwdWgs);
+  VAMP_TIMED(kProfConvFwd, s, (k<<<grid, 256, L::bytes, s>>>(
+      P, static_cast<const unsigned short*>(in), static_cast<const unsigned short*>(w), *ep, tiles_x, tiles_y, ntiles)));
+  return check_launch("conv3d_s2_fwd_epi_kernel");
+}
+template <int CIN, int COUT, bool F16>
+int launch_fwd_epi(const VampConvDesc* d, const VampConvEpilogue* ep, const void* in, const void* w, hipStream_t s) {
+  return ep->seg[0].out_f32 ? launch_fwd_epi_t<CIN, COUT, F16, true>(d, ep, in, w, s)
+                            : launch_fwd_epi_t<CIN, COUT, F16, false>(d, ep, in, w, s);
+}
+
 template <int CO, int CI, bool F16>
 int launch_dgrad(const VampConvDesc* d, const void* gout, const void* w, void* gin, hipStream_t s) {
   using L = DgLds<CO, CI>;
@@ -610,6 +652,25 @@ int vamp_conv3d_half_s2_forward(const VampConvDesc* d, int32_t dtype, const void
                                          : launch_fwd<16, 32, F16>(d, in, weight, out, s);                 \
   return tile_ch(d->cout) == 16 ? launch_fwd<32, 16, F16>(d, in, weight, out, s)                           \
                        : launch_fwd<32, 32, F16>(d, in, weight, out, s);
+  if (dtype == VAMP_F16) { VAMP_CV(true) }
+  VAMP_CV(false)
+#undef VAMP_CV
+}
+
+// the forward through the epilogue (conv3d_epilogue.hpp; the contract is in vampire_hip.h)
+int vamp_conv3d_half_s2_epilogue_forward(const VampConvDesc* d, int32_t dtype, const VampConvEpilogue* epi,
+                                         const void* in, const void* weight, void* stream) {
+  VAMP_REQUIRE(bf16_shape_ok(d), "unsupported shape: see vamp_conv3d_half_s2_supported");
+  VAMP_REQUIRE(dtype == VAMP_BF16 || dtype == VAMP_F16, "dtype must be VAMP_BF16 or VAMP_F16");
+  if (int e = epi_check(__func__, d, epi, true, 1)) return e;
+  VAMP_REQUIRE(in && weight, "NULL tensor");
+  VAMP_REQUIRE(((uintptr_t) in | (uintptr_t) weight) % 16 == 0, "in / weight must start on a 16-byte boundary");
+  hipStream_t s = static_cast<hipStream_t>(stream);
+#define VAMP_CV(F16)                                                                                       \
+  if (tile_ch(d->cin) == 16) return tile_ch(d->cout) == 16 ? launch_fwd_epi<16, 16, F16>(d, epi, in, weight, s)   \
+                                         : launch_fwd_epi<16, 32, F16>(d, epi, in, weight, s);              \
+  return tile_ch(d->cout) == 16 ? launch_fwd_epi<32, 16, F16>(d, epi, in, weight, s)                        \
+                       : launch_fwd_epi<32, 32, F16>(d, epi, in, weight, s);
   if (dtype == VAMP_F16) { VAMP_CV(true) }
   VAMP_CV(false)
 #undef VAMP_CV

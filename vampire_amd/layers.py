@@ -325,3 +325,215 @@ class _Conv3dFn(torch.autograd.Function):
             if k.half:
                 gw = gw.to(w.dtype)               # the gradient of the 16-bit copy autocast made of the fp32 parameter
         return None, gx, gw
+
+
+# ===========================================================================
+# the same convolutions with an epilogue: y = act(conv(x, w) + bias + residual)  (conv3d_epilogue.hpp)
+# ===========================================================================
+_ACT_CODES = {None: _capi.VAMP_ACT_NONE, "none": _capi.VAMP_ACT_NONE, "leaky_relu": _capi.VAMP_ACT_LEAKY_RELU,
+              "sigmoid": _capi.VAMP_ACT_SIGMOID}
+
+
+class HeadSegment(NamedTuple):
+    """A run of consecutive output channels of `conv3d_heads`: its channel count, fp32 bias [channels] or None, the
+    activation (None, "leaky_relu", "sigmoid"), the output dtype (None: the operands'; torch.float32 from 16-bit
+    operands) and leaky_relu's slope.  The segments follow one another from channel 0."""
+    channels: int
+    bias: object = None
+    act: object = None
+    out_dtype: object = None
+    negative_slope: float = 0.01
+
+
+class _EpiSeg(NamedTuple):
+    """A segment as `_Conv3dEpiFn` takes it (plain values; the tensors travel as arguments of `apply`)."""
+    c0: int
+    nch: int
+    act: int
+    slope: float
+    out_f32: bool
+    has_bias: bool
+    has_residual: bool
+
+
+def _epi_kind(x, weight, stride):
+    """The kind `conv3d_kind` names for the layer (a bias is no refusal here), the 16-bit dtype its operands are cast
+    to (None: fp32).  Outside an autocast, 16-bit operands choose their own dtype.  No kind: an error."""
+    if not (x.is_cuda and weight.is_cuda):
+        raise _capi.VampireHipError("x / weight must be device tensors (no CPU fallback)")
+    if x.dim() != 5 or weight.dim() != 5:
+        raise TypeError("expected [B,cin,Z,Y,X] and [cout,cin,3,3,3] tensors")
+    ac = cuda_autocast()
+    if ac is None:
+        if x.dtype != weight.dtype or x.dtype not in FLOAT_DTYPES:
+            raise TypeError(f"x / weight must share fp32, bf16 or fp16, got {x.dtype} and {weight.dtype}")
+        if x.dtype in HALF_DTYPES:
+            ac = x.dtype
+    kind = conv3d_kind(x.shape, weight.shape, x.dtype, weight.dtype, True, (stride,) * 3, (1, 1, 1), False, autocast=ac)
+    if kind is None:
+        raise _capi.VampireHipError(f"no HIP convolution takes x {tuple(x.shape)} {x.dtype}, weight "
+                                    f"{tuple(weight.shape)}, stride {stride} (no fallback)")
+    return kind, (ac if kind != "fp32" else None)
+
+
+def _epi_desc(segs, bias=(), residual=(), out=(), grad_out=(), grad_bias=()) -> _capi.VampConvEpilogue:
+    e = _capi.VampConvEpilogue()
+    e.nseg = len(segs)
+    ptr = lambda seq, k: seq[k].data_ptr() if k < len(seq) and seq[k] is not None else None
+    for k, s in enumerate(segs):
+        g = e.seg[k]
+        g.c0, g.nch, g.act, g.out_f32, g.slope = s.c0, s.nch, s.act, int(s.out_f32), s.slope
+        g.bias, g.residual, g.out = ptr(bias, k), ptr(residual, k), ptr(out, k)
+        g.grad_out, g.grad_bias = ptr(grad_out, k), ptr(grad_bias, k)
+    return e
+
+
+def conv3d_fused(x, weight, bias=None, residual=None, act=None, negative_slope=0.01, stride=1):
+    """act(conv3d(x, weight, stride, padding=1) + bias + residual) in ONE kernel and one autograd node: the 3x3x3
+    convolution `conv3d_kind` names for the operands (under a 16-bit autocast they are cast to it), with the bias
+    [cout], the residual (the output's shape; cast to its dtype) and the activation (None, "leaky_relu", "sigmoid")
+    applied to the fp32 accumulator before the one rounding of the store.  No fallback: operands no kind takes raise."""
+    if act not in _ACT_CODES:
+        raise ValueError(f"act must be one of {sorted(k for k in _ACT_CODES if k)} or None, got {act!r}")
+    kind, dt16 = _epi_kind(x, weight, stride)
+    if dt16 is not None:
+        x, weight = x.to(dt16), weight.to(dt16)
+    if residual is not None:
+        residual = residual.to(x.dtype)
+    seg = _EpiSeg(0, weight.shape[0], _ACT_CODES[act], float(negative_slope), False, bias is not None,
+                  residual is not None)
+    extra = [t for t in (bias, residual) if t is not None]
+    return _Conv3dEpiFn.apply(kind, (seg,), x, weight, *extra)[0]
+
+
+def conv3d_heads(x, weight, segments, stride=1):
+    """One convolution (stride 1, or 2 for 16-bit operands) whose output channels leave as several tensors: `segments` is 1 to 4 `HeadSegment`s
+    (or tuples in its field order) that follow one another from channel 0; returns the tuple of their outputs
+    [B, channels, Zo, Yo, Xo], each with its own bias, activation and dtype.  Channels of `weight` behind the last
+    segment (the padding the fp32 kind's 16 / 32 channel counts need) are computed and not stored."""
+    segments = [s if isinstance(s, HeadSegment) else HeadSegment(*s) for s in segments]
+    if not 1 <= len(segments) <= _capi.VAMP_CONV_EPI_MAX_SEGS:
+        raise ValueError(f"expected 1 to {_capi.VAMP_CONV_EPI_MAX_SEGS} segments, got {len(segments)}")
+    kind, dt16 = _epi_kind(x, weight, stride)
+    if dt16 is not None:
+        x, weight = x.to(dt16), weight.to(dt16)
+    segs, extra, c0 = [], [], 0
+    for s in segments:
+        if s.act not in _ACT_CODES:
+            raise ValueError(f"unknown activation {s.act!r}")
+        if s.out_dtype not in (None, x.dtype, torch.float32):
+            raise TypeError(f"a segment's dtype is the operands' ({x.dtype}) or fp32, got {s.out_dtype}")
+        segs.append(_EpiSeg(c0, int(s.channels), _ACT_CODES[s.act], float(s.negative_slope),
+                            s.out_dtype == torch.float32 and x.dtype != torch.float32, s.bias is not None, False))
+        if s.bias is not None:
+            extra.append(s.bias)
+        c0 += int(s.channels)
+    if c0 > weight.shape[0]:
+        raise ValueError(f"the segments hold {c0} channels, the weight {weight.shape[0]}")
+    return _Conv3dEpiFn.apply(kind, tuple(segs), x, weight, *extra)
+
+
+class _Conv3dEpiFn(torch.autograd.Function):
+    """The three convolutions through their epilogue entry points.  `tensors`: per segment its bias, then its
+    residual, where it has them.  Saved: x, w, and the outputs of the segments that have an activation."""
+
+    @staticmethod
+    def forward(ctx, kind, segs, x, w, *tensors):
+        k = _CONV_KINDS[kind]
+        if not (x.is_cuda and w.is_cuda and all(t.is_cuda for t in tensors)):
+            raise _capi.VampireHipError("conv3d epilogue: device tensors only (no CPU fallback)")
+        if x.dtype not in (HALF_DTYPES if k.half else (torch.float32,)) or w.dtype != x.dtype:
+            raise TypeError(f"the {kind} kind takes {'bf16 or fp16' if k.half else 'fp32'} operands of one dtype")
+        vamp = _capi.checked()
+        x, w = _aligned(x), _aligned(w)
+        d = _conv_desc(x.shape, w.shape)
+        if w.shape[1] != d.cin:
+            raise ValueError("weight / input channel mismatch")
+        vol = tuple((n - 1) // k.stride + 1 for n in (d.Z, d.Y, d.X))
+        it = iter(tensors)
+        biases, residuals, outs, where = [], [], [], []
+        for n, s in enumerate(segs):
+            odt = torch.float32 if s.out_f32 else x.dtype
+            b = r = None
+            if s.has_bias:
+                where.append((n, "bias"))
+                b = next(it)
+                if tuple(b.shape) != (s.nch,):
+                    raise ValueError(f"bias: expected shape ({s.nch},), got {tuple(b.shape)}")
+                b = _aligned(b.detach().float())
+            if s.has_residual:
+                where.append((n, "residual"))
+                r = next(it)
+                if tuple(r.shape) != (d.B, s.nch) + vol or r.dtype != odt:
+                    raise ValueError(f"residual: expected {(d.B, s.nch) + vol} {odt}, got {tuple(r.shape)} {r.dtype}")
+                r = _aligned(r.detach())
+            biases.append(b)
+            residuals.append(r)
+            outs.append(torch.empty((d.B, s.nch) + vol, dtype=odt, device=x.device))
+        code = (DTYPE_CODES[x.dtype],) if k.half else ()
+        epi = _epi_desc(segs, bias=biases, residual=residuals, out=outs)
+        with torch.cuda.device(x.device):
+            getattr(vamp, k.stem + "epilogue_forward")(d, *code, epi, x, w, _stream())
+        ctx.desc, ctx.kind, ctx.segs, ctx.code, ctx.where = d, k, segs, code, where
+        ctx.vol, ctx.tensor_dtypes = vol, [t.dtype for t in tensors]
+        ctx.save_for_backward(x, w, *[o for o, s in zip(outs, segs) if s.act != _capi.VAMP_ACT_NONE])
+        ctx.set_materialize_grads(False)
+        return tuple(outs)
+
+    @staticmethod
+    def backward(ctx, *grads):
+        x, w, *ys = ctx.saved_tensors
+        d, k, segs = ctx.desc, ctx.kind, ctx.segs
+        need = ctx.needs_input_grad
+        none = (None,) * (4 + len(ctx.where))
+        if all(g is None for g in grads) or not any(need):
+            return none
+        vamp = _capi.checked()
+        dev = x.device
+        want_bias = {n for j, (n, what) in enumerate(ctx.where) if what == "bias" and need[4 + j]}
+        s0 = segs[0]
+        plain = (len(segs) == 1 and s0.act == _capi.VAMP_ACT_NONE and not want_bias and not s0.out_f32
+                 and s0.nch == d.cout)
+        gbias = {}
+        with torch.cuda.device(dev):
+            if plain:                              # nothing between the gradient and the convolution's own backward
+                gz = _aligned(grads[0].to(x.dtype))
+            else:
+                ys, gouts, youts = iter(ys), [], []
+                for s, g in zip(segs, grads):
+                    odt = torch.float32 if s.out_f32 else x.dtype
+                    if g is None:
+                        g = torch.zeros((d.B, s.nch) + ctx.vol, dtype=odt, device=dev)
+                    gouts.append(_aligned(g.to(odt)))
+                    youts.append(next(ys) if s.act != _capi.VAMP_ACT_NONE else None)
+                gz = torch.empty((d.B, d.cout) + ctx.vol, dtype=x.dtype, device=dev)
+                gbias = {n: torch.empty(segs[n].nch, dtype=torch.float32, device=dev) for n in want_bias}
+                epi = _epi_desc(segs, out=youts, grad_out=gouts,
+                                grad_bias=[gbias.get(n) for n in range(len(segs))])
+                ws, nbytes = None, 0
+                if want_bias:
+                    nbytes = vamp.vamp_conv3d_epilogue_workspace_bytes(d, k.stride)
+                    ws = _workspace((dev, torch.cuda.current_stream().cuda_stream, "convepi", nbytes), dev, nbytes)
+                vamp.vamp_conv3d_epilogue_backward(d, k.stride, DTYPE_CODES[x.dtype], epi, gz, ws, nbytes, _stream())
+            gx = gw = None
+            if need[2]:
+                gx = torch.empty_like(x)
+                getattr(vamp, k.stem + "backward_data")(d, *ctx.code, gz, w, gx, _stream())
+            if need[3]:
+                gw = torch.empty(w.shape, dtype=torch.float32, device=dev)
+                nbytes = getattr(vamp, k.workspace_bytes)(d)
+                ws = _workspace((dev, torch.cuda.current_stream().cuda_stream, k.tag, nbytes), dev, nbytes)
+                getattr(vamp, k.stem + "backward_weight")(d, *ctx.code, x, gz, gw, ws, ws.numel(), _stream())
+                if k.half:
+                    gw = gw.to(w.dtype)
+        extra = []
+        for j, (n, what) in enumerate(ctx.where):
+            s = segs[n]
+            if not need[4 + j]:
+                extra.append(None)
+            elif what == "bias":
+                extra.append(gbias[n].to(ctx.tensor_dtypes[j]))
+            else:                                  # the residual's gradient is g_z itself (its segment's channels)
+                g = gz if s.nch == d.cout else gz[:, s.c0:s.c0 + s.nch]
+                extra.append(g.to(ctx.tensor_dtypes[j]))
+        return (None, None, gx, gw) + tuple(extra)

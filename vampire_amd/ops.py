@@ -25,7 +25,8 @@ from ._tensors import (_accept, _accept_float, _chk, _density_code, _dtype_code,
 # the operators that take no HotPath live in modules of their own; their public names stay importable from here
 from .layers import (voxel_pooling, upsample_trilinear, conv3d_3x3x3, conv3d_bf16, conv3d_supported,  # noqa: F401
                      conv3d_bf16_supported, conv3d_bf16_stride2, conv3d_bf16_stride2_supported,
-                     resize_bilinear2d, resize_bilinear2d_pack, resize_bilinear2d_supported)
+                     resize_bilinear2d, resize_bilinear2d_pack, resize_bilinear2d_supported,
+                     HeadSegment, conv3d_fused, conv3d_heads)
 from .evaluation import (confusion_update, lidarseg_predict, det_postprocess, det_targets, det_loss,  # noqa: F401
                          DetResult, DetTargets)
 from .losses import REG_MAX_TERMS, REG_TILE, RegTerm, reg_loss, reg_losses, rgb_loss, seg_loss  # noqa: F401
