@@ -59,7 +59,7 @@ EPIS = {"none": (False, False, NONE), "bias": (True, False, NONE), "residual": (
         "leaky": (False, False, LEAKY), "residual+leaky": (False, True, LEAKY),
         "bias+residual+leaky": (True, True, LEAKY)}
 # name -> (kind, B, cin, cout, (Z, Y, X)): from each kernel's tile constants the smallest volumes with a partial tile
-# on every tiled axis, two tiles along x and B = 2.
+# on every tiled axis, two tiles along x and B = 2 (the two 24 -> 8 cells at the end apart: one tile, B = 1).
 #   fp32 (conv3d.hip): a wave tile is 2 .. 4 M tiles of 16 x of one row; 70 = 4 + 1 M tiles in two wave tiles, the last
 #     one 6 wide, rows off a 16-byte boundary (the scalar store); 68 and 36: whole 16-byte groups (the vector store) and
 #     a 4-wide last M tile; 20: one wave tile.  Every (cin, cout) pair the kind takes.  B Z Y < 16 keeps the weight
@@ -75,6 +75,10 @@ LAYER_CASES = {
     "half-32to32-x68": ("half", 2, 32, 32, (2, 4, 68)),
     "s2-16to32": ("half_s2", 2, 16, 32, (3, 5, 24)),
     "s2-32to32-x72": ("half_s2", 2, 32, 32, (3, 5, 72)),
+    # cin tile != cout tile in the other order than the heads' 16 -> 32 (the entry points' tile dispatch, and its swap
+    # in the data gradient), at the smallest volume the 16-bit kinds take
+    "half-24to8-x8": ("half", 1, 24, 8, (2, 3, 8)),
+    "s2-24to8-x8": ("half_s2", 1, 24, 8, (2, 3, 8)),
 }
 # the three-segment heads: (kind, B, cin, cout of the weight, volume, segment channel counts).  Half: 16 -> 22 =
 # 1 + 18 + 3, the boundaries at channels 1 and 19 fall inside an M tile and inside a lane's four rows.  fp32: the kind
@@ -202,7 +206,8 @@ EVERY_KIND = ["x tiles 1", "x tiles 2", "segments 1", "segments 3", "bias", "no 
 WANTED = ({(k, p) for k in KIND_STRIDE for p in EVERY_KIND}
           | {("fp32", p) for p in ("tile 16->16", "tile 16->32", "tile 32->16", "tile 32->32", "store vec4",
                                    "store scalar", "unstored channels")}
-          | {(k, p) for k in ("half", "half_s2") for p in ("tile 16->32", "tile 32->32", "dtype bf16", "dtype fp16")}
+          | {(k, p) for k in ("half", "half_s2") for p in ("tile 16->32", "tile 32->16", "tile 32->32", "dtype bf16",
+                                                           "dtype fp16")}
           | {("half", "out fp32 from 16-bit"), ("half_s2", "out fp32 from 16-bit"), ("half", "tile 16->16")})
 
 

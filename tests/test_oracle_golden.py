@@ -187,14 +187,19 @@ def _hourglass_from_fixture(g, device="cpu"):
     return hg.to(device)
 
 
-def test_hourglass_and_resize_oracle():
+@pytest.mark.parametrize("epilogue", [False, True])
+def test_hourglass_and_resize_oracle(monkeypatch, epilogue):
     """SURVEY 8f N3, resize piece: the mirror of Hourglass3D (bv2:32-78) with the fixture's weights
     reproduces the reference class's outputs and gradients on CPU; the oracle's resize equals the
-    recorded F.interpolate calls (bv2:66, 72)."""
+    recorded F.interpolate calls (bv2:66, 72).  With `SWITCHES.conv3d_epilogue` off and on: CPU tensors take the
+    torch expressions either way.  `skip` is the add of the block's output."""
+    from vampire_amd import backbone
+    monkeypatch.setattr(backbone.SWITCHES, "conv3d_epilogue", epilogue)
     g = load_golden("tiny_hourglass.npz")
     hg = _hourglass_from_fixture(g)
     x = g["x"].clone().requires_grad_(True)
     out1, pre1, post1 = hg(x)
+    assert torch.equal(hg(x, skip=x)[0], out1 + x)
     out2, _, _ = hg(out1 + x, pre1, post1)
     for name, t in (("out1", out1), ("pre1", pre1), ("post1", post1), ("out2", out2)):
         torch.testing.assert_close(t, g[name], rtol=1e-5, atol=1e-6, msg=name)

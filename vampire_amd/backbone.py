@@ -110,14 +110,19 @@ def _resize2d_pack(tensors, size):
     return resize_bilinear2d_pack(tensors, size)
 
 
+def _switched_kind(x, weight, stride, padding, has_bias):
+    """The kind `layers.conv3d_kind` names for the layer under `SWITCHES` and the current autocast, or None."""
+    if not SWITCHES.conv3d:
+        return None
+    return conv3d_kind(x.shape, weight.shape, x.dtype, weight.dtype, x.is_cuda, stride, padding, has_bias,
+                       autocast=cuda_autocast(), min_voxels=SWITCHES.conv3d_min_voxels, stride2=SWITCHES.conv3d_s2)
+
+
 def _hip_conv3d(x, weight, stride, padding, bias):
     """The layer on the HIP kernels `layers.conv3d_kind` names for it under `SWITCHES` and the current autocast (the
     reference's mixed-precision training: 16-bit operands, as autocast would hand them to MIOpen), or None: the caller
     keeps aten / MIOpen."""
-    if not SWITCHES.conv3d:
-        return None
-    kind = conv3d_kind(x.shape, weight.shape, x.dtype, weight.dtype, x.is_cuda, stride, padding, bias is not None,
-                       autocast=cuda_autocast(), min_voxels=SWITCHES.conv3d_min_voxels, stride2=SWITCHES.conv3d_s2)
+    kind = _switched_kind(x, weight, stride, padding, bias is not None)
     if kind is None:
         return None
     if kind == "fp32":
@@ -129,10 +134,7 @@ def _hip_conv3d(x, weight, stride, padding, bias):
 def _layer_kind(x, weight, stride, padding):
     """The kind of HIP convolution the epilogue operators would run the layer on under `SWITCHES` and the current
     autocast (a bias is theirs to add), or None."""
-    if not (SWITCHES.conv3d and SWITCHES.conv3d_epilogue):
-        return None
-    return conv3d_kind(x.shape, weight.shape, x.dtype, weight.dtype, x.is_cuda, stride, padding, False,
-                       autocast=cuda_autocast(), min_voxels=SWITCHES.conv3d_min_voxels, stride2=SWITCHES.conv3d_s2)
+    return _switched_kind(x, weight, stride, padding, False) if SWITCHES.conv3d_epilogue else None
 
 
 def _fused_conv3(layer, x, residual=None, act=None, slope=0.01):
@@ -190,14 +192,9 @@ class Hourglass3D(nn.Module):
         self.conv6 = nn.Sequential(_conv3(2 * m, m))
 
     def forward(self, x, presqu=None, postsqu=None, skip=None):
-        """`skip`: a tensor added to the block's output (Unet3D's residual to the stem), or None."""
-        if SWITCHES.conv3d_epilogue:
-            return self._forward_fused(x, presqu, postsqu, skip)
-        out, pre, post = self._forward_plain(x, presqu, postsqu)
-        return (out if skip is None else out + skip), pre, post
-
-    def _forward_fused(self, x, presqu, postsqu, skip):
-        """The same block with every add and LeakyReLU inside the convolution before it (`_conv3_then`)."""
+        """`skip`: a tensor added to the block's output (Unet3D's residual to the stem), or None.  Every add and
+        LeakyReLU goes through `_conv3_then`: inside the convolution before it under `SWITCHES.conv3d_epilogue`, else
+        (and on layers no HIP kernel takes) the torch expressions, slope 0.01 like the `nn.LeakyReLU` members."""
         down = _conv3_then(self.conv1[0], x, leaky=True)
         pre = _conv3_then(self.conv2[0], down, postsqu, leaky=True)
         bottom = _conv3_then(self.conv4[0], _conv3_then(self.conv3[0], pre, leaky=True), leaky=True)
@@ -205,17 +202,6 @@ class Hourglass3D(nn.Module):
         post = _conv3_then(self.conv5[0], up, pre if presqu is None else presqu, leaky=True)
         out = _resize(post, x.shape[-3:])
         return _conv3_then(self.conv6[0], out, skip), pre, post
-
-    def _forward_plain(self, x, presqu=None, postsqu=None):
-        down = self.conv1(x)
-        pre = self.conv2(down)
-        pre = F.leaky_relu(pre if postsqu is None else pre + postsqu, inplace=True)
-        bottom = self.conv4(self.conv3(pre))
-        up = _resize(bottom, pre.shape[-3:])
-        up = self.conv5(up)
-        post = F.leaky_relu(up + (pre if presqu is None else presqu), inplace=True)
-        out = _resize(post, x.shape[-3:])
-        return self.conv6(out), pre, post
 
 
 class Unet3D(nn.Module):
@@ -229,13 +215,8 @@ class Unet3D(nn.Module):
 
     def forward(self, x):
         stem = self.init_dres(x)
-        if SWITCHES.conv3d_epilogue:               # the two adds of the stem ride in conv6's epilogue
-            out1, pre1, post1 = self.hg1(stem, skip=stem)
-            return self.hg2(out1, pre1, post1, skip=stem)[0]
-        out1, pre1, post1 = self.hg1(stem)
-        out1 = out1 + stem
-        out2, _, _ = self.hg2(out1, pre1, post1)
-        return out2 + stem
+        out1, pre1, post1 = self.hg1(stem, skip=stem)      # the two adds of the stem: conv6's residual
+        return self.hg2(out1, pre1, post1, skip=stem)[0]
 
 
 class _StandInEncoder(nn.Module):

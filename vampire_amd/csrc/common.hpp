@@ -9,6 +9,8 @@
 #include <stdio.h>
 #include <string.h>
 
+#include <type_traits>
+
 #include "../../include/vampire_hip.h"
 #include "elem16.hpp"       // for ldf's bf16 widening alone: the hot-path kernels use nothing else of it
 
@@ -38,6 +40,16 @@ inline int check_launch(const char* what) {
 }
 
 inline size_t align_up(size_t v, size_t a) { return (v + a - 1) / a * a; }
+
+// f(CI, CO) with the channel tiles ci, co (16, else 32) as compile-time constants: the 3x3x3 convolutions' entry points
+// choose their kernel instantiation with it
+template <class F>
+int dispatch_tiles(int ci, int co, F&& f) {
+  using T16 = std::integral_constant<int, 16>;
+  using T32 = std::integral_constant<int, 32>;
+  if (ci == 16) return co == 16 ? f(T16(), T16()) : f(T16(), T32());
+  return co == 16 ? f(T32(), T16()) : f(T32(), T32());
+}
 
 // ---------------------------------------------------------------------------
 // optional HIP-event kernel timer (runtime.hip); slots name the kernels

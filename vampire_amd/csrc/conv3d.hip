@@ -477,10 +477,9 @@ int vamp_conv3d_forward(const VampConvDesc* d, const float* in, const float* wei
   if (int e = check(d)) return e;
   VAMP_REQUIRE(in && weight && out, "NULL tensor");
   hipStream_t s = static_cast<hipStream_t>(stream);
-  if (d->cin == 16 && d->cout == 16) return launch_fwd<16, 16, false>(d, in, weight, out, s);
-  if (d->cin == 16 && d->cout == 32) return launch_fwd<16, 32, false>(d, in, weight, out, s);
-  if (d->cin == 32 && d->cout == 16) return launch_fwd<32, 16, false>(d, in, weight, out, s);
-  return launch_fwd<32, 32, false>(d, in, weight, out, s);
+  return dispatch_tiles(d->cin, d->cout, [&](auto CI, auto CO) {
+    return launch_fwd<CI(), CO(), false>(d, in, weight, out, s);
+  });
 }
 
 /* the forward through the epilogue (conv3d_epilogue.hpp; the contract is in vampire_hip.h) */
@@ -491,10 +490,9 @@ int vamp_conv3d_epilogue_forward(const VampConvDesc* d, const VampConvEpilogue* 
   VAMP_REQUIRE(in && weight, "NULL tensor");
   VAMP_REQUIRE(((uintptr_t) in | (uintptr_t) weight) % 16 == 0, "in / weight must start on a 16-byte boundary");
   hipStream_t s = static_cast<hipStream_t>(stream);
-  if (d->cin == 16 && d->cout == 16) return launch_fwd<16, 16, false, true>(d, in, weight, nullptr, s, epi);
-  if (d->cin == 16 && d->cout == 32) return launch_fwd<16, 32, false, true>(d, in, weight, nullptr, s, epi);
-  if (d->cin == 32 && d->cout == 16) return launch_fwd<32, 16, false, true>(d, in, weight, nullptr, s, epi);
-  return launch_fwd<32, 32, false, true>(d, in, weight, nullptr, s, epi);
+  return dispatch_tiles(d->cin, d->cout, [&](auto CI, auto CO) {
+    return launch_fwd<CI(), CO(), false, true>(d, in, weight, nullptr, s, epi);
+  });
 }
 
 /* grad_in [B, cin, Z, Y, X] from grad_out [B, cout, Z, Y, X]: the forward kernel on the flipped,
@@ -504,10 +502,10 @@ int vamp_conv3d_backward_data(const VampConvDesc* d, const float* grad_out, cons
   if (int e = check(d)) return e;
   VAMP_REQUIRE(grad_out && weight && grad_in, "NULL tensor");
   hipStream_t s = static_cast<hipStream_t>(stream);
-  if (d->cin == 16 && d->cout == 16) return launch_fwd<16, 16, true>(d, grad_out, weight, grad_in, s);
-  if (d->cin == 16 && d->cout == 32) return launch_fwd<32, 16, true>(d, grad_out, weight, grad_in, s);
-  if (d->cin == 32 && d->cout == 16) return launch_fwd<16, 32, true>(d, grad_out, weight, grad_in, s);
-  return launch_fwd<32, 32, true>(d, grad_out, weight, grad_in, s);
+  // the tiles swapped: the kernel's input tensor is grad_out (cout channels), its output grad_in (cin channels)
+  return dispatch_tiles(d->cin, d->cout, [&](auto CI, auto CO) {
+    return launch_fwd<CO(), CI(), true>(d, grad_out, weight, grad_in, s);
+  });
 }
 
 /* 1 when all three entry points accept this descriptor (channel counts, row length against the
@@ -540,31 +538,25 @@ int vamp_conv3d_backward_weight(const VampConvDesc* d, const float* in, const fl
   VAMP_REQUIRE(lds <= 160 * 1024, "row too long for the LDS images");
   float* part = static_cast<float*>(workspace);
   if (int ze = launch_zero(grad_weight, (size_t) d->cout * d->cin * 27 * sizeof(float), s)) return ze;
-#define VAMP_WGRAD_N(CI, CO, NP)                                                                    \
-  do {                                                                                              \
-    static bool attr_set = false;                                                                   \
-    if (!attr_set) {                                                                                \
-      (void) hipFuncSetAttribute(reinterpret_cast<const void*>(&conv3d_wgrad_kernel<CI, CO, NP>),   \
-                                 hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);           \
-      attr_set = true;                                                                              \
-    }                                                                                               \
-    VAMP_TIMED(kProfConvWgrad, s, (conv3d_wgrad_kernel<CI, CO, NP><<<pl.nitems, kWgradThreads, lds, s>>>( \
-        P, in, grad_out, part, pl.nchunks, pl.rows_per_chunk, XS, pl.nitems)));                     \
-  } while (0)
+  // NP staging registers per thread as a compile-time constant: 13, 19 or kWgradPre, the least that holds a row
   const int npre = (int) (((long) (d->cin + d->cout) * d->X + kWgradThreads - 1) / kWgradThreads);
-#define VAMP_WGRAD(CI, CO)                                                                          \
-  do {                                                                                              \
-    if (npre <= 13) VAMP_WGRAD_N(CI, CO, 13);                                                       \
-    else if (npre <= 19) VAMP_WGRAD_N(CI, CO, 19);                                                  \
-    else VAMP_WGRAD_N(CI, CO, kWgradPre);                                                           \
-  } while (0)
-  if (d->cin == 16 && d->cout == 16) VAMP_WGRAD(16, 16);
-  else if (d->cin == 16 && d->cout == 32) VAMP_WGRAD(16, 32);
-  else if (d->cin == 32 && d->cout == 16) VAMP_WGRAD(32, 16);
-  else VAMP_WGRAD(32, 32);
-#undef VAMP_WGRAD_N
-#undef VAMP_WGRAD
-  if (int e = check_launch("conv3d_wgrad_kernel")) return e;
+  auto launch = [&](auto CI, auto CO, auto NP) {
+    static bool attr_set = false;                      // one per instantiation
+    if (!attr_set) {
+      (void) hipFuncSetAttribute(reinterpret_cast<const void*>(&conv3d_wgrad_kernel<CI(), CO(), NP()>),
+                                 hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+      attr_set = true;
+    }
+    VAMP_TIMED(kProfConvWgrad, s, (conv3d_wgrad_kernel<CI(), CO(), NP()><<<pl.nitems, kWgradThreads, lds, s>>>(
+        P, in, grad_out, part, pl.nchunks, pl.rows_per_chunk, XS, pl.nitems)));
+    return check_launch("conv3d_wgrad_kernel");
+  };
+  if (int e = dispatch_tiles(d->cin, d->cout, [&](auto CI, auto CO) {
+        if (npre <= 13) return launch(CI, CO, std::integral_constant<int, 13>());
+        if (npre <= 19) return launch(CI, CO, std::integral_constant<int, 19>());
+        return launch(CI, CO, std::integral_constant<int, kWgradPre>());
+      }))
+    return e;
   const int n = 27 * d->cout * d->cin;
   const int per_dz = pl.nitems / 3;
   const dim3 rgrid((unsigned) ((n + 255) / 256), (unsigned) std::max(1, std::min(16, per_dz / 8)));

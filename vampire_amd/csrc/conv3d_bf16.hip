@@ -19,7 +19,7 @@
 // The weight gradient has K = voxels, contiguous along x in NCDHW: both operands are plain
 // 16-byte global loads (the shifted-by-one-voxel windows at 2-byte alignment), no LDS at all.
 #include "conv3d_epilogue.hpp"   // the EPI instantiations' store
-#include "conv3d_half.hpp"       // the vector types, mfma16, f32_to_e16, the partials' reduce kernel, tile_ch, bf16_shape_ok
+#include "conv3d_half.hpp"       // what the two 16-bit files share: the staged Box, the tile store, the host dispatch, ...
 
 #include <algorithm>
 #include <type_traits>
@@ -31,6 +31,8 @@ struct CvP {
   int B, Z, Y, X;
   int cin, cout;        // real channel counts of the kernel's input / output tensors (<= the template tile sizes)
 };
+
+constexpr char kShapeRule[] = "vamp_conv3d_bf16_supported";      // where a refused shape's message points
 
 constexpr int kTY = 4;        // output rows per tile = waves per workgroup
 constexpr int kTX = 64;       // output x per tile (four 16-voxel N tiles per wave)
@@ -73,14 +75,15 @@ __device__ __forceinline__ void conv3d_bf16_fwd_body(const CvP& P, const unsigne
     reinterpret_cast<unsigned short*>(w_s)[e] = v;
   }
 
-  // staging: this thread's items of a tile, registers first (the next tile's loads fly during the MFMAs)
+  // staging: this thread's items of a tile, registers first (the next tile's loads fly during the MFMAs).  This is
+  // Box<CIN, 3, kTY + 2, kHX> of conv3d_half.hpp written out: with Box::fetch / commit in place of the two lambdas
+  // every forward instantiation compiles to another instruction stream (same registers), and the one timing of it
+  // had conv6's bf16 forward + backward 1.0 % slower; written out, every kernel of this file keeps the
+  // instruction stream it had before the helpers were shared.  A fix to the staging goes into both.
   unsigned st[NI][8];
   auto fetch = [&](long tile) {
-    const int tx = (int) (tile % tiles_x);
-    long r = tile / tiles_x;
-    const int ty = (int) (r % ((P.Y + kTY - 1) / kTY));
-    r /= ((P.Y + kTY - 1) / kTY);
-    const int z = (int) (r % P.Z), b = (int) (r / P.Z);
+    const TileIx t = tile_ix(tile, tiles_x, (P.Y + kTY - 1) / kTY, P.Z);
+    const int tx = t.tx, ty = t.ty, z = t.z, b = t.b;
     const __amdgpu_buffer_rsrc_t rs = __builtin_amdgcn_make_buffer_rsrc(
         const_cast<unsigned short*>(in + (long) b * P.cin * plane), 0, (int) ((size_t) P.cin * plane * 2), 0x00020000);   // planes >= cin read 0
 #pragma unroll
@@ -121,12 +124,8 @@ __device__ __forceinline__ void conv3d_bf16_fwd_body(const CvP& P, const unsigne
     __syncthreads();
     if (tile + gridDim.x < ntiles) fetch(tile + gridDim.x);
 
-    const int tx = (int) (tile % tiles_x);
-    long r = tile / tiles_x;
-    const int ty = (int) (r % ((P.Y + kTY - 1) / kTY));
-    r /= ((P.Y + kTY - 1) / kTY);
-    const int z = (int) (r % P.Z), b = (int) (r / P.Z);
-    const int y = ty * kTY + wv, x0 = tx * kTX;
+    const TileIx t = tile_ix(tile, tiles_x, (P.Y + kTY - 1) / kTY, P.Z);
+    const int z = t.z, b = t.b, y = t.ty * kTY + wv, x0 = t.tx * kTX;
     const int nnt = min(4, (P.X - x0 + 15) / 16);       // N tiles of this wave inside the volume (uniform)
     f32x4 acc[MT][4];
 #pragma unroll
@@ -172,18 +171,7 @@ __device__ __forceinline__ void conv3d_bf16_fwd_body(const CvP& P, const unsigne
       if (y < P.Y)
         epi_store_tile<F16 ? kEpiF16 : kEpiBF16, OF32, MT, 4>(*ep, acc, kg, li, b, plane, ((long) z * P.Y + y) * P.X, x0, P.X, w);
     } else if (y < P.Y) {
-      unsigned short* ob = out + (long) b * P.cout * plane + ((long) z * P.Y + y) * P.X;
-#pragma unroll
-      for (int m = 0; m < MT; ++m)
-#pragma unroll
-        for (int n = 0; n < 4; ++n) {
-          const int x = x0 + n * 16 + li;
-          if (x < P.X) {
-#pragma unroll
-            for (int rg = 0; rg < 4; ++rg)
-              if (m * 16 + 4 * kg + rg < P.cout) ob[(long) (m * 16 + 4 * kg + rg) * plane + x] = f32_to_e16<F16>(acc[m][n][rg]);
-          }
-        }
+      store_tile16<F16, MT, 4>(acc, out + (long) b * P.cout * plane + ((long) z * P.Y + y) * P.X, plane, x0, P.X, P.cout, kg, li);
     }
   }
 }
@@ -338,55 +326,28 @@ conv3d_bf16_wgrad_kernel(CvP P, const unsigned short* __restrict__ in, const uns
     compute(cur, nxt);
     cur = nxt;
   }
-  // partial sums: [workgroup][tap][co][ci]; D row (co) = 4 kg + reg, column (ci) = li
-  float* pb = part + (size_t) blockIdx.x * 27 * COUT * CIN;
-#pragma unroll
-  for (int t = 0; t < 9; ++t) {
-    const int tap = wv * 9 + t;
-#pragma unroll
-    for (int m = 0; m < MT; ++m)
-#pragma unroll
-      for (int n = 0; n < NT; ++n)
-#pragma unroll
-        for (int rg = 0; rg < 4; ++rg) pb[((size_t) tap * COUT + m * 16 + 4 * kg + rg) * CIN + n * 16 + li] = acc[t][m][n][rg];
-  }
+  store_wgrad_partials<CIN, COUT>(acc, part, wv, kg, li);
 }
 
-template <int CIN, int COUT, bool FLIP, bool F16>
-int launch_fwd(const VampConvDesc* d, const void* in, const void* w, void* out, hipStream_t s) {
+// CIN / COUT: the kernel's K and M channel tiles; the data gradient (FLIP) runs on grad_out, so the layer's cout is
+// its input count.  ep: through the epilogue (EPI; OF32: fp32 outputs) instead of into `out`
+template <int CIN, int COUT, bool FLIP, bool F16, bool EPI = false, bool OF32 = false>
+int launch_fwd(const VampConvDesc* d, const void* in, const void* w, void* out, hipStream_t s,
+               const VampConvEpilogue* ep = nullptr) {
   using L = CvLds<CIN, COUT>;
-  auto k = conv3d_bf16_fwd_kernel<CIN, COUT, FLIP, F16>;
-  if (hipFuncSetAttribute(reinterpret_cast<const void*>(k), hipFuncAttributeMaxDynamicSharedMemorySize, (int) L::bytes) != hipSuccess)
-    return fail(VAMP_EHIP, "%s: cannot raise dynamic LDS", __func__);
   const CvP P{d->B, d->Z, d->Y, d->X, FLIP ? d->cout : d->cin, FLIP ? d->cin : d->cout};
   const int tiles_x = (d->X + kTX - 1) / kTX;
   const long ntiles = (long) d->B * d->Z * ((d->Y + kTY - 1) / kTY) * tiles_x;
   const int per_cu = L::bytes <= 78 * 1024 ? 2 : 1;
   const unsigned grid = (unsigned) std::min<long>(ntiles, 256 * per_cu);
-  VAMP_TIMED(FLIP ? kProfConvDgrad : kProfConvFwd, s, (k<<<grid, 256, L::bytes, s>>>(
-      P, static_cast<const unsigned short*>(in), static_cast<const unsigned short*>(w), static_cast<unsigned short*>(out), tiles_x, ntiles)));
-  return check_launch("conv3d_bf16_fwd_kernel");
-}
-
-template <int CIN, int COUT, bool F16, bool OF32>
-int launch_fwd_epi_t(const VampConvDesc* d, const VampConvEpilogue* ep, const void* in, const void* w, hipStream_t s) {
-  using L = CvLds<CIN, COUT>;
-  auto k = conv3d_bf16_fwd_epi_kernel<CIN, COUT, F16, OF32>;
-  if (hipFuncSetAttribute(reinterpret_cast<const void*>(k), hipFuncAttributeMaxDynamicSharedMemorySize, (int) L::bytes) != hipSuccess)
-    return fail(VAMP_EHIP, "%s: cannot raise dynamic LDS", __func__);
-  const CvP P{d->B, d->Z, d->Y, d->X, d->cin, d->cout};
-  const int tiles_x = (d->X + kTX - 1) / kTX;
-  const long ntiles = (long) d->B * d->Z * ((d->Y + kTY - 1) / kTY) * tiles_x;
-  const int per_cu = L::bytes <= 78 * 1024 ? 2 : 1;
-  const unsigned grid = (unsigned) std::min<long>(ntiles, 256 * per_cu);
-  VAMP_TIMED(kProfConvFwd, s, (k<<<grid, 256, L::bytes, s>>>(
-      P, static_cast<const unsigned short*>(in), static_cast<const unsigned short*>(w), *ep, tiles_x, ntiles)));
-  return check_launch("conv3d_bf16_fwd_epi_kernel");
-}
-template <int CIN, int COUT, bool F16>
-int launch_fwd_epi(const VampConvDesc* d, const VampConvEpilogue* ep, const void* in, const void* w, hipStream_t s) {
-  return ep->seg[0].out_f32 ? launch_fwd_epi_t<CIN, COUT, F16, true>(d, ep, in, w, s)
-                            : launch_fwd_epi_t<CIN, COUT, F16, false>(d, ep, in, w, s);
+  const unsigned short* ip = static_cast<const unsigned short*>(in);
+  const unsigned short* wp = static_cast<const unsigned short*>(w);
+  if constexpr (EPI)
+    return launch_lds(conv3d_bf16_fwd_epi_kernel<CIN, COUT, F16, OF32>, "conv3d_bf16_fwd_epi_kernel", L::bytes, grid,
+                      kProfConvFwd, s, P, ip, wp, *ep, tiles_x, ntiles);
+  else
+    return launch_lds(conv3d_bf16_fwd_kernel<CIN, COUT, FLIP, F16>, "conv3d_bf16_fwd_kernel", L::bytes, grid,
+                      FLIP ? kProfConvDgrad : kProfConvFwd, s, P, ip, wp, static_cast<unsigned short*>(out), tiles_x, ntiles);
 }
 
 template <int CIN, int COUT, bool F16>
@@ -415,82 +376,53 @@ extern "C" {
 
 int vamp_conv3d_bf16_supported(const VampConvDesc* d) { return bf16_shape_ok(d) ? 1 : 0; }
 
-size_t vamp_conv3d_bf16_workspace_bytes(const VampConvDesc* d) {
-  if (!bf16_shape_ok(d)) return 0;
-  return (size_t) kWgradWgs * 27 * tile_ch(d->cin) * tile_ch(d->cout) * sizeof(float);
-}
+size_t vamp_conv3d_bf16_workspace_bytes(const VampConvDesc* d) { return half_workspace_bytes(d); }
 
 // dtype: VAMP_BF16 or VAMP_F16 (the reference's `precision=16` is IEEE half)
 int vamp_conv3d_half_forward(const VampConvDesc* d, int32_t dtype, const void* in, const void* weight, void* out,
                              void* stream) {
-  VAMP_REQUIRE(bf16_shape_ok(d), "unsupported shape: see vamp_conv3d_bf16_supported");
-  VAMP_REQUIRE(in && weight && out, "NULL tensor");
-  VAMP_REQUIRE(dtype == VAMP_BF16 || dtype == VAMP_F16, "dtype must be VAMP_BF16 or VAMP_F16");
+  if (int e = half_args_ok(__func__, kShapeRule, d, dtype, in && weight && out)) return e;
   hipStream_t s = static_cast<hipStream_t>(stream);
-#define VAMP_CV(F16)                                                                                       \
-  if (tile_ch(d->cin) == 16) return tile_ch(d->cout) == 16 ? launch_fwd<16, 16, false, F16>(d, in, weight, out, s)           \
-                                         : launch_fwd<16, 32, false, F16>(d, in, weight, out, s);          \
-  return tile_ch(d->cout) == 16 ? launch_fwd<32, 16, false, F16>(d, in, weight, out, s)                             \
-                       : launch_fwd<32, 32, false, F16>(d, in, weight, out, s);
-  if (dtype == VAMP_F16) { VAMP_CV(true) }
-  VAMP_CV(false)
-#undef VAMP_CV
+  return dispatch_half(d->cin, d->cout, dtype, [&](auto CI, auto CO, auto F16) {
+    return launch_fwd<CI(), CO(), false, F16()>(d, in, weight, out, s);
+  });
 }
 
 // the forward through the epilogue (conv3d_epilogue.hpp; the contract is in vampire_hip.h)
 int vamp_conv3d_half_epilogue_forward(const VampConvDesc* d, int32_t dtype, const VampConvEpilogue* epi,
                                       const void* in, const void* weight, void* stream) {
-  VAMP_REQUIRE(bf16_shape_ok(d), "unsupported shape: see vamp_conv3d_bf16_supported");
-  VAMP_REQUIRE(dtype == VAMP_BF16 || dtype == VAMP_F16, "dtype must be VAMP_BF16 or VAMP_F16");
+  if (int e = half_args_ok(__func__, kShapeRule, d, dtype, true)) return e;
   if (int e = epi_check(__func__, d, epi, true, 1)) return e;
   VAMP_REQUIRE(in && weight, "NULL tensor");
   VAMP_REQUIRE(((uintptr_t) in | (uintptr_t) weight) % 16 == 0, "in / weight must start on a 16-byte boundary");
   hipStream_t s = static_cast<hipStream_t>(stream);
-#define VAMP_CV(F16)                                                                                       \
-  if (tile_ch(d->cin) == 16) return tile_ch(d->cout) == 16 ? launch_fwd_epi<16, 16, F16>(d, epi, in, weight, s)   \
-                                         : launch_fwd_epi<16, 32, F16>(d, epi, in, weight, s);              \
-  return tile_ch(d->cout) == 16 ? launch_fwd_epi<32, 16, F16>(d, epi, in, weight, s)                        \
-                       : launch_fwd_epi<32, 32, F16>(d, epi, in, weight, s);
-  if (dtype == VAMP_F16) { VAMP_CV(true) }
-  VAMP_CV(false)
-#undef VAMP_CV
+  return dispatch_half(d->cin, d->cout, dtype, [&](auto CI, auto CO, auto F16) {
+    return epi->seg[0].out_f32 ? launch_fwd<CI(), CO(), false, F16(), true, true>(d, in, weight, nullptr, s, epi)
+                               : launch_fwd<CI(), CO(), false, F16(), true, false>(d, in, weight, nullptr, s, epi);
+  });
 }
 
 int vamp_conv3d_half_backward_data(const VampConvDesc* d, int32_t dtype, const void* grad_out, const void* weight,
                                    void* grad_in, void* stream) {
-  VAMP_REQUIRE(bf16_shape_ok(d), "unsupported shape: see vamp_conv3d_bf16_supported");
-  VAMP_REQUIRE(grad_out && weight && grad_in, "NULL tensor");
-  VAMP_REQUIRE(dtype == VAMP_BF16 || dtype == VAMP_F16, "dtype must be VAMP_BF16 or VAMP_F16");
+  if (int e = half_args_ok(__func__, kShapeRule, d, dtype, grad_out && weight && grad_in)) return e;
   hipStream_t s = static_cast<hipStream_t>(stream);
-  // the kernel's input tensor is grad_out (cout channels), its output grad_in (cin channels)
-#define VAMP_CV(F16)                                                                                       \
-  if (tile_ch(d->cout) == 16) return tile_ch(d->cin) == 16 ? launch_fwd<16, 16, true, F16>(d, grad_out, weight, grad_in, s)  \
-                                         : launch_fwd<16, 32, true, F16>(d, grad_out, weight, grad_in, s); \
-  return tile_ch(d->cin) == 16 ? launch_fwd<32, 16, true, F16>(d, grad_out, weight, grad_in, s)                     \
-                      : launch_fwd<32, 32, true, F16>(d, grad_out, weight, grad_in, s);
-  if (dtype == VAMP_F16) { VAMP_CV(true) }
-  VAMP_CV(false)
-#undef VAMP_CV
+  // the tiles swapped: the kernel's input tensor is grad_out (cout channels), its output grad_in (cin channels)
+  return dispatch_half(d->cout, d->cin, dtype, [&](auto CO, auto CI, auto F16) {
+    return launch_fwd<CO(), CI(), true, F16()>(d, grad_out, weight, grad_in, s);
+  });
 }
 
 int vamp_conv3d_half_backward_weight(const VampConvDesc* d, int32_t dtype, const void* in, const void* grad_out,
                                      float* grad_weight, void* workspace, size_t workspace_bytes, void* stream) {
-  VAMP_REQUIRE(bf16_shape_ok(d), "unsupported shape: see vamp_conv3d_bf16_supported");
-  VAMP_REQUIRE(in && grad_out && grad_weight, "NULL tensor");
-  VAMP_REQUIRE(dtype == VAMP_BF16 || dtype == VAMP_F16, "dtype must be VAMP_BF16 or VAMP_F16");
-  const size_t need = vamp_conv3d_bf16_workspace_bytes(d);
+  if (int e = half_args_ok(__func__, kShapeRule, d, dtype, in && grad_out && grad_weight)) return e;
+  const size_t need = half_workspace_bytes(d);
   if (!workspace || workspace_bytes < need)
     return fail(VAMP_ENOSPC, "%s: workspace %ld < %ld bytes", __func__, (long) workspace_bytes, (long) need);
   hipStream_t s = static_cast<hipStream_t>(stream);
   float* ws = static_cast<float*>(workspace);
-#define VAMP_CV(F16)                                                                                       \
-  if (tile_ch(d->cin) == 16) return tile_ch(d->cout) == 16 ? launch_wgrad<16, 16, F16>(d, in, grad_out, grad_weight, ws, s)  \
-                                         : launch_wgrad<16, 32, F16>(d, in, grad_out, grad_weight, ws, s); \
-  return tile_ch(d->cout) == 16 ? launch_wgrad<32, 16, F16>(d, in, grad_out, grad_weight, ws, s)                    \
-                       : launch_wgrad<32, 32, F16>(d, in, grad_out, grad_weight, ws, s);
-  if (dtype == VAMP_F16) { VAMP_CV(true) }
-  VAMP_CV(false)
-#undef VAMP_CV
+  return dispatch_half(d->cin, d->cout, dtype, [&](auto CI, auto CO, auto F16) {
+    return launch_wgrad<CI(), CO(), F16()>(d, in, grad_out, grad_weight, ws, s);
+  });
 }
 
 int vamp_conv3d_bf16_forward(const VampConvDesc* d, const void* in, const void* weight, void* out, void* stream) {

@@ -47,6 +47,8 @@ S2P make_params(const VampConvDesc* d) {
   return S2P{d->B, d->Z, d->Y, d->X, (d->Z - 1) / 2 + 1, (d->Y - 1) / 2 + 1, (d->X - 1) / 2 + 1, d->cin, d->cout};
 }
 
+constexpr char kShapeRule[] = "vamp_conv3d_half_s2_supported";      // where a refused shape's message points
+
 constexpr int kFwdTX = 32;        // output x per forward tile (two 16-voxel N tiles)
 constexpr int kFwdHX = 66;        // staged x: 2 xo0 - 2 .. 2 xo0 + 63 (pairs at even x)
 constexpr int kDgTY = 4;          // grad_in rows per tile = waves per workgroup
@@ -70,51 +72,6 @@ __device__ __forceinline__ void load_wimage(unsigned char* w_s, const unsigned s
     reinterpret_cast<unsigned short*>(w_s)[e] = v;
   }
 }
-
-// The staged box: NZ x NY rows of HX voxels (HX even) from (z0, y0, x0), x0 even, of a [ch, Zt, Yt, Xt] sample
-// (Xt even).  Item = (row, x pair, 8-channel group): eight dword loads, two 16-byte LDS stores.
-template <int KC, int NZ, int NY, int HX>
-struct Box {
-  static constexpr int CG = KC / 8, VS = KC * 2 + 16, ROWS = NZ * NY;
-  static constexpr int NITEM = ROWS * (HX / 2) * CG, NI = (NITEM + 255) / 256;
-  static constexpr size_t bytes = (size_t) ROWS * HX * VS;
-
-  static __device__ __forceinline__ void fetch(unsigned (&st)[NI][8], const unsigned short* sample, int ch, int Zt,
-                                               int Yt, int Xt, int z0, int y0, int x0, int tid) {
-    const long plane = (long) Zt * Yt * Xt;
-    const __amdgpu_buffer_rsrc_t rs = __builtin_amdgcn_make_buffer_rsrc(
-        const_cast<unsigned short*>(sample), 0, (int) ((size_t) ch * plane * 2), 0x00020000);   // planes >= ch read 0
-#pragma unroll
-    for (int i = 0; i < NI; ++i) {
-      const int it = tid + i * 256;
-      const int px = it % (HX / 2), rr = (it / (HX / 2)) % ROWS, cg = it / ((HX / 2) * ROWS);
-      const int zz = z0 + rr / NY, yy = y0 + rr % NY, xx = x0 + 2 * px;
-      const bool ok = it < NITEM && zz >= 0 && zz < Zt && yy >= 0 && yy < Yt && xx >= 0 && xx < Xt;
-      const unsigned voff = ok ? (unsigned) ((((long) cg * 8 * Zt + zz) * Yt + yy) * Xt + xx) * 2u : 0xfffffff0u;
-#pragma unroll
-      for (int j = 0; j < 8; ++j) st[i][j] = __builtin_amdgcn_raw_buffer_load_b32(rs, voff, (unsigned) (j * plane * 2), 0);
-    }
-  }
-
-  static __device__ __forceinline__ void commit(const unsigned (&st)[NI][8], unsigned char* in_s, int tid) {
-#pragma unroll
-    for (int i = 0; i < NI; ++i) {
-      const int it = tid + i * 256;
-      if (it < NITEM) {
-        const int px = it % (HX / 2), rr = (it / (HX / 2)) % ROWS, cg = it / ((HX / 2) * ROWS);
-        u32x4 lo, hi;
-#pragma unroll
-        for (int q = 0; q < 4; ++q) {
-          lo[q] = __builtin_amdgcn_perm(st[i][2 * q + 1], st[i][2 * q], 0x05040100u);   // the even-x voxel: low halves
-          hi[q] = __builtin_amdgcn_perm(st[i][2 * q + 1], st[i][2 * q], 0x07060302u);   // the odd-x voxel: high halves
-        }
-        unsigned char* p = in_s + ((size_t) rr * HX + 2 * px) * VS + cg * 16;
-        *reinterpret_cast<u32x4*>(p) = lo;
-        *reinterpret_cast<u32x4*>(p + VS) = hi;
-      }
-    }
-  }
-};
 
 // this lane's 16 bytes of the A fragment (weights of `tap`, row `row`) / of the B fragment (staged voxel `vox`):
 // 32 K-channels: chunk kg of the one tap; 16: chunk kg & 1 of the tap that kg >> 1 selected
@@ -166,12 +123,8 @@ __device__ __forceinline__ void conv3d_s2_fwd_body(const S2P& P, const unsigned 
 
   unsigned st[BX::NI][8];
   auto fetch = [&](long tile) {
-    const int tx = (int) (tile % tiles_x);
-    long r = tile / tiles_x;
-    const int ty = (int) (r % tiles_y);
-    r /= tiles_y;
-    const int zo = (int) (r % P.Zo), b = (int) (r / P.Zo);
-    BX::fetch(st, in + (long) b * P.cin * plane_i, P.cin, P.Z, P.Y, P.X, 2 * zo - 1, 2 * ty * TY - 1, 2 * tx * kFwdTX - 2, tid);
+    const TileIx t = tile_ix(tile, tiles_x, tiles_y, P.Zo);
+    BX::fetch(st, in + (long) t.b * P.cin * plane_i, P.cin, P.Z, P.Y, P.X, 2 * t.z - 1, 2 * t.ty * TY - 1, 2 * t.tx * kFwdTX - 2, tid);
   };
 
   // this wave's row of the tile and its first N tile
@@ -185,12 +138,8 @@ __device__ __forceinline__ void conv3d_s2_fwd_body(const S2P& P, const unsigned 
     __syncthreads();
     if (tile + gridDim.x < ntiles) fetch(tile + gridDim.x);
 
-    const int tx = (int) (tile % tiles_x);
-    long r = tile / tiles_x;
-    const int ty = (int) (r % tiles_y);
-    r /= tiles_y;
-    const int zo = (int) (r % P.Zo), b = (int) (r / P.Zo);
-    const int yo = ty * TY + wr, xo0 = tx * kFwdTX + n0 * 16;
+    const TileIx t = tile_ix(tile, tiles_x, tiles_y, P.Zo);
+    const int zo = t.z, b = t.b, yo = t.ty * TY + wr, xo0 = t.tx * kFwdTX + n0 * 16;
     const int nnt = max(0, min(NNW, (P.Xo - xo0 + 15) / 16));       // N tiles of this wave inside the volume (uniform)
     f32x4 acc[MT][NNW];
 #pragma unroll
@@ -236,18 +185,8 @@ __device__ __forceinline__ void conv3d_s2_fwd_body(const S2P& P, const unsigned 
         epi_store_tile<F16 ? kEpiF16 : kEpiBF16, OF32, MT, NNW>(*ep, acc, kg, li, b, plane_o, ((long) zo * P.Yo + yo) * P.Xo, xo0,
                                                                P.Xo, w);
     } else if (yo < P.Yo) {
-      unsigned short* ob = out + (long) b * P.cout * plane_o + ((long) zo * P.Yo + yo) * P.Xo;
-#pragma unroll
-      for (int m = 0; m < MT; ++m)
-#pragma unroll
-        for (int n = 0; n < NNW; ++n) {
-          const int x = xo0 + n * 16 + li;
-          if (x < P.Xo) {
-#pragma unroll
-            for (int rg = 0; rg < 4; ++rg)
-              if (m * 16 + 4 * kg + rg < P.cout) ob[(long) (m * 16 + 4 * kg + rg) * plane_o + x] = f32_to_e16<F16>(acc[m][n][rg]);
-          }
-        }
+      store_tile16<F16, MT, NNW>(acc, out + (long) b * P.cout * plane_o + ((long) zo * P.Yo + yo) * P.Xo, plane_o, xo0, P.Xo,
+                                 P.cout, kg, li);
     }
   }
 }
@@ -295,12 +234,8 @@ conv3d_s2_dgrad_kernel(S2P P, const unsigned short* __restrict__ gout, const uns
 
   unsigned st[BX::NI][8];
   auto fetch = [&](long tile) {
-    const int tx = (int) (tile % tiles_x);
-    long r = tile / tiles_x;
-    const int ty = (int) (r % tiles_y);
-    r /= tiles_y;
-    const int z = (int) (r % P.Z), b = (int) (r / P.Z);
-    BX::fetch(st, gout + (long) b * P.cout * plane_o, P.cout, P.Zo, P.Yo, P.Xo, z >> 1, ty * (kDgTY / 2), tx * (kDgTX / 2), tid);
+    const TileIx t = tile_ix(tile, tiles_x, tiles_y, P.Z);
+    BX::fetch(st, gout + (long) t.b * P.cout * plane_o, P.cout, P.Zo, P.Yo, P.Xo, t.z >> 1, t.ty * (kDgTY / 2), t.tx * (kDgTX / 2), tid);
   };
 
   long tile = blockIdx.x;
@@ -311,12 +246,8 @@ conv3d_s2_dgrad_kernel(S2P P, const unsigned short* __restrict__ gout, const uns
     __syncthreads();
     if (tile + gridDim.x < ntiles) fetch(tile + gridDim.x);
 
-    const int tx = (int) (tile % tiles_x);
-    long r = tile / tiles_x;
-    const int ty = (int) (r % tiles_y);
-    r /= tiles_y;
-    const int z = (int) (r % P.Z), b = (int) (r / P.Z);
-    const int y = ty * kDgTY + wv, x0 = tx * kDgTX;
+    const TileIx t = tile_ix(tile, tiles_x, tiles_y, P.Z);
+    const int z = t.z, b = t.b, y = t.ty * kDgTY + wv, x0 = t.tx * kDgTX;
     const int npair = min(2, (P.X - x0 + 31) / 32);         // (even, odd) N-tile pairs inside the volume (uniform)
     // the z and y tap lists of this wave's row: (tap index, staged plane / row); an even coordinate has the one tap
     // d = 1 from c / 2, an odd one d = 0 from (c + 1) / 2 and d = 2 from (c - 1) / 2
@@ -537,72 +468,40 @@ conv3d_s2_wgrad_kernel(S2P P, const unsigned short* __restrict__ in, const unsig
     compute(cur);
     cur = nxt;
   }
-  // partial sums: [workgroup][tap][co][ci]; D row (co) = 4 kg + reg, column (ci) = li
-  float* pb = part + (size_t) blockIdx.x * 27 * COUT * CIN;
-#pragma unroll
-  for (int t = 0; t < 9; ++t) {
-    const int tap = wv * 9 + t;
-#pragma unroll
-    for (int m = 0; m < MT; ++m)
-#pragma unroll
-      for (int n = 0; n < NT; ++n)
-#pragma unroll
-        for (int rg = 0; rg < 4; ++rg) pb[((size_t) tap * COUT + m * 16 + 4 * kg + rg) * CIN + n * 16 + li] = acc[t][m][n][rg];
-  }
+  store_wgrad_partials<CIN, COUT>(acc, part, wv, kg, li);
 }
 
-template <int CIN, int COUT, bool F16>
-int launch_fwd(const VampConvDesc* d, const void* in, const void* w, void* out, hipStream_t s) {
+// ep: through the epilogue (EPI; OF32: fp32 outputs) instead of into `out`
+template <int CIN, int COUT, bool F16, bool EPI = false, bool OF32 = false>
+int launch_fwd(const VampConvDesc* d, const void* in, const void* w, void* out, hipStream_t s,
+               const VampConvEpilogue* ep = nullptr) {
   using L = FwdLds<CIN, COUT>;
-  auto k = conv3d_s2_fwd_kernel<CIN, COUT, F16>;
-  if (hipFuncSetAttribute(reinterpret_cast<const void*>(k), hipFuncAttributeMaxDynamicSharedMemorySize, (int) L::bytes) != hipSuccess)
-    return fail(VAMP_EHIP, "%s: cannot raise dynamic LDS", __func__);
   const S2P P = make_params(d);
   const int tiles_x = (P.Xo + kFwdTX - 1) / kFwdTX, tiles_y = (P.Yo + FwdTile<CIN>::TY - 1) / FwdTile<CIN>::TY;
   const long ntiles = (long) P.B * P.Zo * tiles_y * tiles_x;
   static_assert(L::bytes <= 160 * 1024, "the box and the weight image share the LDS");
   const unsigned grid = (unsigned) std::min<long>(ntiles, kFwdWgs);
-  VAMP_TIMED(kProfConvFwd, s, (k<<<grid, 256, L::bytes, s>>>(
-      P, static_cast<const unsigned short*>(in), static_cast<const unsigned short*>(w), static_cast<unsigned short*>(out),
-      tiles_x, tiles_y, ntiles)));
-  return check_launch("conv3d_s2_fwd_kernel");
-}
-
-template <int CIN, int COUT, bool F16, bool OF32>
-int launch_fwd_epi_t(const VampConvDesc* d, const VampConvEpilogue* ep, const void* in, const void* w, hipStream_t s) {
-  using L = FwdLds<CIN, COUT>;
-  auto k = conv3d_s2_fwd_epi_kernel<CIN, COUT, F16, OF32>;
-  if (hipFuncSetAttribute(reinterpret_cast<const void*>(k), hipFuncAttributeMaxDynamicSharedMemorySize, (int) L::bytes) != hipSuccess)
-    return fail(VAMP_EHIP, "%s: cannot raise dynamic LDS", __func__);
-  const S2P P = make_params(d);
-  const int tiles_x = (P.Xo + kFwdTX - 1) / kFwdTX, tiles_y = (P.Yo + FwdTile<CIN>::TY - 1) / FwdTile<CIN>::TY;
-  const long ntiles = (long) P.B * P.Zo * tiles_y * tiles_x;
-  const unsigned grid = (unsigned) std::min<long>(ntiles, kFwdWgs);
-  VAMP_TIMED(kProfConvFwd, s, (k<<<grid, 256, L::bytes, s>>>(
-      P, static_cast<const unsigned short*>(in), static_cast<const unsigned short*>(w), *ep, tiles_x, tiles_y, ntiles)));
-  return check_launch("conv3d_s2_fwd_epi_kernel");
-}
-template <int CIN, int COUT, bool F16>
-int launch_fwd_epi(const VampConvDesc* d, const VampConvEpilogue* ep, const void* in, const void* w, hipStream_t s) {
-  return ep->seg[0].out_f32 ? launch_fwd_epi_t<CIN, COUT, F16, true>(d, ep, in, w, s)
-                            : launch_fwd_epi_t<CIN, COUT, F16, false>(d, ep, in, w, s);
+  const unsigned short* ip = static_cast<const unsigned short*>(in);
+  const unsigned short* wp = static_cast<const unsigned short*>(w);
+  if constexpr (EPI)
+    return launch_lds(conv3d_s2_fwd_epi_kernel<CIN, COUT, F16, OF32>, "conv3d_s2_fwd_epi_kernel", L::bytes, grid,
+                      kProfConvFwd, s, P, ip, wp, *ep, tiles_x, tiles_y, ntiles);
+  else
+    return launch_lds(conv3d_s2_fwd_kernel<CIN, COUT, F16>, "conv3d_s2_fwd_kernel", L::bytes, grid, kProfConvFwd, s, P, ip,
+                      wp, static_cast<unsigned short*>(out), tiles_x, tiles_y, ntiles);
 }
 
 template <int CO, int CI, bool F16>
 int launch_dgrad(const VampConvDesc* d, const void* gout, const void* w, void* gin, hipStream_t s) {
   using L = DgLds<CO, CI>;
-  auto k = conv3d_s2_dgrad_kernel<CO, CI, F16>;
-  if (hipFuncSetAttribute(reinterpret_cast<const void*>(k), hipFuncAttributeMaxDynamicSharedMemorySize, (int) L::bytes) != hipSuccess)
-    return fail(VAMP_EHIP, "%s: cannot raise dynamic LDS", __func__);
   const S2P P = make_params(d);
   const int tiles_x = (P.X + kDgTX - 1) / kDgTX, tiles_y = (P.Y + kDgTY - 1) / kDgTY;
   const long ntiles = (long) P.B * P.Z * tiles_y * tiles_x;
   static_assert(2 * L::bytes <= 160 * 1024, "two workgroups per CU");
   const unsigned grid = (unsigned) std::min<long>(ntiles, kDgWgs);
-  VAMP_TIMED(kProfConvDgrad, s, (k<<<grid, 256, L::bytes, s>>>(
-      P, static_cast<const unsigned short*>(gout), static_cast<const unsigned short*>(w), static_cast<unsigned short*>(gin),
-      tiles_x, tiles_y, ntiles)));
-  return check_launch("conv3d_s2_dgrad_kernel");
+  return launch_lds(conv3d_s2_dgrad_kernel<CO, CI, F16>, "conv3d_s2_dgrad_kernel", L::bytes, grid, kProfConvDgrad, s, P,
+                    static_cast<const unsigned short*>(gout), static_cast<const unsigned short*>(w),
+                    static_cast<unsigned short*>(gin), tiles_x, tiles_y, ntiles);
 }
 
 template <int CIN, int COUT, bool F16>
@@ -635,83 +534,55 @@ extern "C" {
 // makes Xo even)
 int vamp_conv3d_half_s2_supported(const VampConvDesc* d) { return bf16_shape_ok(d) ? 1 : 0; }
 
-size_t vamp_conv3d_half_s2_workspace_bytes(const VampConvDesc* d) {
-  if (!bf16_shape_ok(d)) return 0;
-  return (size_t) kWgradWgs * 27 * tile_ch(d->cin) * tile_ch(d->cout) * sizeof(float);
-}
+size_t vamp_conv3d_half_s2_workspace_bytes(const VampConvDesc* d) { return half_workspace_bytes(d); }
 
 // Hourglass3D.conv1 / conv3 forward (base_vampire2.py:34-46) under a 16-bit autocast
 int vamp_conv3d_half_s2_forward(const VampConvDesc* d, int32_t dtype, const void* in, const void* weight, void* out,
                                 void* stream) {
-  VAMP_REQUIRE(bf16_shape_ok(d), "unsupported shape: see vamp_conv3d_half_s2_supported");
-  VAMP_REQUIRE(in && weight && out, "NULL tensor");
-  VAMP_REQUIRE(dtype == VAMP_BF16 || dtype == VAMP_F16, "dtype must be VAMP_BF16 or VAMP_F16");
+  if (int e = half_args_ok(__func__, kShapeRule, d, dtype, in && weight && out)) return e;
   hipStream_t s = static_cast<hipStream_t>(stream);
-#define VAMP_CV(F16)                                                                                       \
-  if (tile_ch(d->cin) == 16) return tile_ch(d->cout) == 16 ? launch_fwd<16, 16, F16>(d, in, weight, out, s)  \
-                                         : launch_fwd<16, 32, F16>(d, in, weight, out, s);                 \
-  return tile_ch(d->cout) == 16 ? launch_fwd<32, 16, F16>(d, in, weight, out, s)                           \
-                       : launch_fwd<32, 32, F16>(d, in, weight, out, s);
-  if (dtype == VAMP_F16) { VAMP_CV(true) }
-  VAMP_CV(false)
-#undef VAMP_CV
+  return dispatch_half(d->cin, d->cout, dtype, [&](auto CI, auto CO, auto F16) {
+    return launch_fwd<CI(), CO(), F16()>(d, in, weight, out, s);
+  });
 }
 
 // the forward through the epilogue (conv3d_epilogue.hpp; the contract is in vampire_hip.h)
 int vamp_conv3d_half_s2_epilogue_forward(const VampConvDesc* d, int32_t dtype, const VampConvEpilogue* epi,
                                          const void* in, const void* weight, void* stream) {
-  VAMP_REQUIRE(bf16_shape_ok(d), "unsupported shape: see vamp_conv3d_half_s2_supported");
-  VAMP_REQUIRE(dtype == VAMP_BF16 || dtype == VAMP_F16, "dtype must be VAMP_BF16 or VAMP_F16");
+  if (int e = half_args_ok(__func__, kShapeRule, d, dtype, true)) return e;
   if (int e = epi_check(__func__, d, epi, true, 1)) return e;
   VAMP_REQUIRE(in && weight, "NULL tensor");
   VAMP_REQUIRE(((uintptr_t) in | (uintptr_t) weight) % 16 == 0, "in / weight must start on a 16-byte boundary");
   hipStream_t s = static_cast<hipStream_t>(stream);
-#define VAMP_CV(F16)                                                                                       \
-  if (tile_ch(d->cin) == 16) return tile_ch(d->cout) == 16 ? launch_fwd_epi<16, 16, F16>(d, epi, in, weight, s)   \
-                                         : launch_fwd_epi<16, 32, F16>(d, epi, in, weight, s);              \
-  return tile_ch(d->cout) == 16 ? launch_fwd_epi<32, 16, F16>(d, epi, in, weight, s)                        \
-                       : launch_fwd_epi<32, 32, F16>(d, epi, in, weight, s);
-  if (dtype == VAMP_F16) { VAMP_CV(true) }
-  VAMP_CV(false)
-#undef VAMP_CV
+  return dispatch_half(d->cin, d->cout, dtype, [&](auto CI, auto CO, auto F16) {
+    return epi->seg[0].out_f32 ? launch_fwd<CI(), CO(), F16(), true, true>(d, in, weight, nullptr, s, epi)
+                               : launch_fwd<CI(), CO(), F16(), true, false>(d, in, weight, nullptr, s, epi);
+  });
 }
 
 // autograd's data gradient of the same layers (base_vampire2.py:34-46): grad_in is fully overwritten
 int vamp_conv3d_half_s2_backward_data(const VampConvDesc* d, int32_t dtype, const void* grad_out, const void* weight,
                                       void* grad_in, void* stream) {
-  VAMP_REQUIRE(bf16_shape_ok(d), "unsupported shape: see vamp_conv3d_half_s2_supported");
-  VAMP_REQUIRE(grad_out && weight && grad_in, "NULL tensor");
-  VAMP_REQUIRE(dtype == VAMP_BF16 || dtype == VAMP_F16, "dtype must be VAMP_BF16 or VAMP_F16");
+  if (int e = half_args_ok(__func__, kShapeRule, d, dtype, grad_out && weight && grad_in)) return e;
   hipStream_t s = static_cast<hipStream_t>(stream);
-#define VAMP_CV(F16)                                                                                       \
-  if (tile_ch(d->cout) == 16) return tile_ch(d->cin) == 16 ? launch_dgrad<16, 16, F16>(d, grad_out, weight, grad_in, s)  \
-                                         : launch_dgrad<16, 32, F16>(d, grad_out, weight, grad_in, s);     \
-  return tile_ch(d->cin) == 16 ? launch_dgrad<32, 16, F16>(d, grad_out, weight, grad_in, s)                \
-                      : launch_dgrad<32, 32, F16>(d, grad_out, weight, grad_in, s);
-  if (dtype == VAMP_F16) { VAMP_CV(true) }
-  VAMP_CV(false)
-#undef VAMP_CV
+  // the tiles swapped: the kernel's K channels are grad_out's (cout), its M rows grad_in's (cin)
+  return dispatch_half(d->cout, d->cin, dtype, [&](auto CO, auto CI, auto F16) {
+    return launch_dgrad<CO(), CI(), F16()>(d, grad_out, weight, grad_in, s);
+  });
 }
 
 // autograd's weight gradient of the same layers (base_vampire2.py:34-46): fp32 [cout, cin, 3, 3, 3], fully overwritten
 int vamp_conv3d_half_s2_backward_weight(const VampConvDesc* d, int32_t dtype, const void* in, const void* grad_out,
                                         float* grad_weight, void* workspace, size_t workspace_bytes, void* stream) {
-  VAMP_REQUIRE(bf16_shape_ok(d), "unsupported shape: see vamp_conv3d_half_s2_supported");
-  VAMP_REQUIRE(in && grad_out && grad_weight, "NULL tensor");
-  VAMP_REQUIRE(dtype == VAMP_BF16 || dtype == VAMP_F16, "dtype must be VAMP_BF16 or VAMP_F16");
-  const size_t need = vamp_conv3d_half_s2_workspace_bytes(d);
+  if (int e = half_args_ok(__func__, kShapeRule, d, dtype, in && grad_out && grad_weight)) return e;
+  const size_t need = half_workspace_bytes(d);
   if (!workspace || workspace_bytes < need)
     return fail(VAMP_ENOSPC, "%s: workspace %ld < %ld bytes", __func__, (long) workspace_bytes, (long) need);
   hipStream_t s = static_cast<hipStream_t>(stream);
   float* ws = static_cast<float*>(workspace);
-#define VAMP_CV(F16)                                                                                       \
-  if (tile_ch(d->cin) == 16) return tile_ch(d->cout) == 16 ? launch_wgrad<16, 16, F16>(d, in, grad_out, grad_weight, ws, s)  \
-                                         : launch_wgrad<16, 32, F16>(d, in, grad_out, grad_weight, ws, s); \
-  return tile_ch(d->cout) == 16 ? launch_wgrad<32, 16, F16>(d, in, grad_out, grad_weight, ws, s)           \
-                       : launch_wgrad<32, 32, F16>(d, in, grad_out, grad_weight, ws, s);
-  if (dtype == VAMP_F16) { VAMP_CV(true) }
-  VAMP_CV(false)
-#undef VAMP_CV
+  return dispatch_half(d->cin, d->cout, dtype, [&](auto CI, auto CO, auto F16) {
+    return launch_wgrad<CI(), CO(), F16()>(d, in, grad_out, grad_weight, ws, s);
+  });
 }
 
 }  // extern "C"

@@ -280,50 +280,70 @@ def conv3d_bf16_stride2(x, weight):
     return _Conv3dFn.apply("half_s2", x, weight)
 
 
+def _conv_operands(kind, x, w, others=None):
+    """The operand side of both autograd functions.  Refusals, in order: a host tensor, then a wrong dtype.  The plain
+    wrappers (`others` None) refuse a wrong rank with the dtype, and a `dtype_first` kind of theirs refuses both
+    before a host tensor; the epilogue (`others`: its further tensors) has texts of its own and leaves the rank to
+    `_epi_kind`.  Returns the kind's row, the aligned operands, the descriptor (it holds the input volume), the output
+    volume and the dtype code the kind's entry points take."""
+    k = _CONV_KINDS[kind]
+    bad_dtype = x.dtype not in (HALF_DTYPES if k.half else (torch.float32,)) or w.dtype != x.dtype
+    if others is not None:                         # the epilogue
+        if not (x.is_cuda and w.is_cuda and all(t.is_cuda for t in others)):
+            raise _capi.VampireHipError("conv3d epilogue: device tensors only (no CPU fallback)")
+        if bad_dtype:
+            raise TypeError(f"the {kind} kind takes {'bf16 or fp16' if k.half else 'fp32'} operands of one dtype")
+    else:                                          # the plain wrappers
+        on_host = not (x.is_cuda and w.is_cuda)
+        if on_host and not k.dtype_first:
+            raise _capi.VampireHipError("x / weight must be device tensors (no CPU fallback)")
+        if bad_dtype or x.dim() != 5 or w.dim() != 5:
+            raise TypeError(f"{k.name} takes {'bf16 (or fp16)' if k.half else 'fp32'} [B,cin,Z,Y,X] and "
+                            f"[cout,cin,3,3,3] tensors{' of one dtype' if k.half else ''}")
+        if on_host:
+            raise _capi.VampireHipError("x / weight must be device tensors (no CPU fallback)")
+    _capi.checked()
+    x, w = _aligned(x), _aligned(w)
+    d = _conv_desc(x.shape, w.shape)
+    if w.shape[1] != d.cin:
+        raise ValueError("weight / input channel mismatch")
+    vol = tuple((n - 1) // k.stride + 1 for n in (d.Z, d.Y, d.X))
+    return k, x, w, d, vol, ((DTYPE_CODES[x.dtype],) if k.half else ())
+
+
+def _conv_backward(k, d, code, x, w, gz, need_x, need_w):
+    """The convolution's own backward from the aligned gradient `gz` of its output: (gx, gw), None where not needed."""
+    vamp = _capi.checked()
+    gx = gw = None
+    if need_x:
+        gx = torch.empty_like(x)
+        getattr(vamp, k.stem + "backward_data")(d, *code, gz, w, gx, _stream())
+    if need_w:
+        gw = torch.empty(w.shape, dtype=torch.float32, device=w.device)
+        nbytes = getattr(vamp, k.workspace_bytes)(d)
+        ws = _workspace((gz.device, torch.cuda.current_stream().cuda_stream, k.tag, nbytes), gz.device, nbytes)
+        getattr(vamp, k.stem + "backward_weight")(d, *code, x, gz, gw, ws, ws.numel(), _stream())
+        if k.half:
+            gw = gw.to(w.dtype)                   # the gradient of the 16-bit copy autocast made of the fp32 parameter
+    return gx, gw
+
+
 class _Conv3dFn(torch.autograd.Function):
     """The three convolutions, told apart by their row of `_CONV_KINDS`."""
 
     @staticmethod
     def forward(ctx, kind, x, w):
-        k = _CONV_KINDS[kind]
-        on_host = not (x.is_cuda and w.is_cuda)
-        if on_host and not k.dtype_first:
-            raise _capi.VampireHipError("x / weight must be device tensors (no CPU fallback)")
-        if (x.dtype not in (HALF_DTYPES if k.half else (torch.float32,)) or w.dtype != x.dtype or x.dim() != 5
-                or w.dim() != 5):
-            raise TypeError(f"{k.name} takes {'bf16 (or fp16)' if k.half else 'fp32'} [B,cin,Z,Y,X] and "
-                            f"[cout,cin,3,3,3] tensors{' of one dtype' if k.half else ''}")
-        if on_host:
-            raise _capi.VampireHipError("x / weight must be device tensors (no CPU fallback)")
-        vamp = _capi.checked()
-        x, w = _aligned(x), _aligned(w)
-        d = _conv_desc(x.shape, w.shape)          # the descriptor holds the input volume
-        if w.shape[1] != d.cin:
-            raise ValueError("weight / input channel mismatch")
-        out = torch.empty((d.B, d.cout) + tuple((n - 1) // k.stride + 1 for n in (d.Z, d.Y, d.X)), dtype=x.dtype,
-                          device=x.device)
-        ctx.code = (DTYPE_CODES[x.dtype],) if k.half else ()
-        getattr(vamp, k.stem + "forward")(d, *ctx.code, x, w, out, _stream())
-        ctx.vamp, ctx.desc, ctx.kind = vamp, d, k
+        k, x, w, d, vol, ctx.code = _conv_operands(kind, x, w)
+        out = torch.empty((d.B, d.cout) + vol, dtype=x.dtype, device=x.device)
+        getattr(_capi.checked(), k.stem + "forward")(d, *ctx.code, x, w, out, _stream())
+        ctx.desc, ctx.kind = d, k
         ctx.save_for_backward(x, w)
         return out
 
     @staticmethod
     def backward(ctx, g):
         x, w = ctx.saved_tensors
-        vamp, d, k = ctx.vamp, ctx.desc, ctx.kind
-        g = _aligned(g.to(x.dtype))
-        gx = gw = None
-        if ctx.needs_input_grad[1]:
-            gx = torch.empty_like(x)
-            getattr(vamp, k.stem + "backward_data")(d, *ctx.code, g, w, gx, _stream())
-        if ctx.needs_input_grad[2]:
-            gw = torch.empty(w.shape, dtype=torch.float32, device=w.device)
-            nbytes = getattr(vamp, k.workspace_bytes)(d)
-            ws = _workspace((g.device, torch.cuda.current_stream().cuda_stream, k.tag, nbytes), g.device, nbytes)
-            getattr(vamp, k.stem + "backward_weight")(d, *ctx.code, x, g, gw, ws, ws.numel(), _stream())
-            if k.half:
-                gw = gw.to(w.dtype)               # the gradient of the 16-bit copy autocast made of the fp32 parameter
+        gx, gw = _conv_backward(ctx.kind, ctx.desc, ctx.code, x, w, _aligned(g.to(x.dtype)), *ctx.needs_input_grad[1:])
         return None, gx, gw
 
 
@@ -439,17 +459,7 @@ class _Conv3dEpiFn(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, kind, segs, x, w, *tensors):
-        k = _CONV_KINDS[kind]
-        if not (x.is_cuda and w.is_cuda and all(t.is_cuda for t in tensors)):
-            raise _capi.VampireHipError("conv3d epilogue: device tensors only (no CPU fallback)")
-        if x.dtype not in (HALF_DTYPES if k.half else (torch.float32,)) or w.dtype != x.dtype:
-            raise TypeError(f"the {kind} kind takes {'bf16 or fp16' if k.half else 'fp32'} operands of one dtype")
-        vamp = _capi.checked()
-        x, w = _aligned(x), _aligned(w)
-        d = _conv_desc(x.shape, w.shape)
-        if w.shape[1] != d.cin:
-            raise ValueError("weight / input channel mismatch")
-        vol = tuple((n - 1) // k.stride + 1 for n in (d.Z, d.Y, d.X))
+        k, x, w, d, vol, code = _conv_operands(kind, x, w, tensors)
         it = iter(tensors)
         biases, residuals, outs, where = [], [], [], []
         for n, s in enumerate(segs):
@@ -470,10 +480,9 @@ class _Conv3dEpiFn(torch.autograd.Function):
             biases.append(b)
             residuals.append(r)
             outs.append(torch.empty((d.B, s.nch) + vol, dtype=odt, device=x.device))
-        code = (DTYPE_CODES[x.dtype],) if k.half else ()
         epi = _epi_desc(segs, bias=biases, residual=residuals, out=outs)
         with torch.cuda.device(x.device):
-            getattr(vamp, k.stem + "epilogue_forward")(d, *code, epi, x, w, _stream())
+            getattr(_capi.checked(), k.stem + "epilogue_forward")(d, *code, epi, x, w, _stream())
         ctx.desc, ctx.kind, ctx.segs, ctx.code, ctx.where = d, k, segs, code, where
         ctx.vol, ctx.tensor_dtypes = vol, [t.dtype for t in tensors]
         ctx.save_for_backward(x, w, *[o for o, s in zip(outs, segs) if s.act != _capi.VAMP_ACT_NONE])
@@ -515,17 +524,7 @@ class _Conv3dEpiFn(torch.autograd.Function):
                     nbytes = vamp.vamp_conv3d_epilogue_workspace_bytes(d, k.stride)
                     ws = _workspace((dev, torch.cuda.current_stream().cuda_stream, "convepi", nbytes), dev, nbytes)
                 vamp.vamp_conv3d_epilogue_backward(d, k.stride, DTYPE_CODES[x.dtype], epi, gz, ws, nbytes, _stream())
-            gx = gw = None
-            if need[2]:
-                gx = torch.empty_like(x)
-                getattr(vamp, k.stem + "backward_data")(d, *ctx.code, gz, w, gx, _stream())
-            if need[3]:
-                gw = torch.empty(w.shape, dtype=torch.float32, device=dev)
-                nbytes = getattr(vamp, k.workspace_bytes)(d)
-                ws = _workspace((dev, torch.cuda.current_stream().cuda_stream, k.tag, nbytes), dev, nbytes)
-                getattr(vamp, k.stem + "backward_weight")(d, *ctx.code, x, gz, gw, ws, ws.numel(), _stream())
-                if k.half:
-                    gw = gw.to(w.dtype)
+            gx, gw = _conv_backward(k, d, ctx.code, x, w, gz, need[2], need[3])
         extra = []
         for j, (n, what) in enumerate(ctx.where):
             s = segs[n]
