@@ -70,7 +70,7 @@ int vamp_profile_enable(int on);
 int vamp_profile_slots(void);
 /* time only this kernel slot (-1 = all): one event pair per step instead of ~40 */
 int vamp_profile_select(int slot);
-int vamp_profile_read(int slot, const char** name, int* launches, double* total_ms);
+int vamp_profile_read(int slot, const char** name_host, int* launches_host, double* total_ms_host);
 
 /* ------------------------------------------------------------------------- *
  * LIFT: voxel <- mean over cameras of trilinear samples of depth (x) feat.

@@ -8,15 +8,11 @@ handed such a tensor returns different numbers, not an error: the guard is how t
 TABLE maps (function, parameter name as spelled in include/vampire_hip.h) to what the header's comments say the
 parameter holds; test_call_guard.py holds it against the header's prototypes."""
 import math
-import os
-import re
 import types
 
 import torch
 
-from vampire_amd import _capi
-
-HEADER = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "include", "vampire_hip.h")
+from vampire_amd import _capi, _header
 
 
 class ContractViolation(Exception):
@@ -27,20 +23,9 @@ class ContractViolation(Exception):
         self.function, self.parameter, self.reason = function, parameter, reason
 
 
-def header_prototypes(path=HEADER):
-    """{function: [(C type, parameter name)]} of every prototype in the header (comments stripped)."""
-    text = re.sub(r"/\*.*?\*/", "", open(path).read(), flags=re.S)
-    out = {}
-    for name, params in re.findall(r"\b(vamp_[a-z_0-9]+)\s*\(([^)]*)\)\s*;", text):
-        plist = []
-        for prm in (p.strip() for p in params.split(",")):
-            if prm in ("", "void"):
-                continue
-            m = re.match(r"(.*?)(\w+)\s*(\[\d*\])?$", prm, flags=re.S)
-            ctype = " ".join(m.group(1).split()) + ("*" if m.group(3) else "")
-            plist.append((ctype.replace(" *", "*"), m.group(2)))
-        out[name] = plist
-    return out
+def header_prototypes():
+    """{function: [(C type, parameter name)]} of every prototype in the header, as the package's reader gives them."""
+    return {name: params for name, (_, params) in _header.read().prototypes.items()}
 
 
 # C pointer type -> bytes per element, for the parameters whose type says it (void* parameters name their source below)

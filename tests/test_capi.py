@@ -2,14 +2,12 @@
 include/vampire_hip.h declares, rejects bad descriptors without touching a GPU, and the
 Python host refuses CPU tensors (there is no fallback)."""
 import ctypes as C
-import os
 import re
 
 import pytest
 import torch
 
-from conftest import ROOT
-from vampire_amd import _capi
+from vampire_amd import _capi, _header
 from vampire_amd.build import build_library
 
 
@@ -20,9 +18,7 @@ def lib():
 
 
 def header_symbols():
-    text = open(os.path.join(ROOT, "include", "vampire_hip.h")).read()
-    text = re.sub(r"/\*.*?\*/", "", text, flags=re.S)
-    return sorted(set(re.findall(r"\b(vamp_[a-z_0-9]+)\s*\(", text)))
+    return sorted(_header.read().prototypes)
 
 
 def test_exports_every_declared_symbol(lib):
@@ -235,12 +231,10 @@ def test_checked_calls_go_through_a_stand_in_library(lib):
 def test_descriptor_parameters_are_typed_pointers():
     """Every `const VampXDesc*` (or VampDetTask*) parameter of the header is a POINTER(VampXDesc) in the table, so that
     a bare structure instance is passed by reference -- a void* parameter would refuse it."""
-    text = open(os.path.join(ROOT, "include", "vampire_hip.h")).read()
-    text = re.sub(r"/\*.*?\*/", "", text, flags=re.S)
     seen = 0
-    for name, params in re.findall(r"\b(vamp_[a-z_0-9]+)\s*\(([^)]*)\)\s*;", text):
-        for i, prm in enumerate(p.strip() for p in params.split(",")):
-            m = re.match(r"const\s+(Vamp\w+)\s*\*", prm)
+    for name, (_, params) in _header.read().prototypes.items():
+        for i, (ctype, _) in enumerate(params):
+            m = re.fullmatch(r"const (Vamp\w+)\*", ctype)
             if m:
                 seen += 1
                 want = C.POINTER(getattr(_capi, m.group(1)))

@@ -16,7 +16,6 @@ import ctypes as C
 import dataclasses
 import math
 import os
-import re
 import sys
 
 import numpy as np
@@ -26,7 +25,7 @@ import torch
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 
-from vampire_amd import _capi, metrics                       # noqa: E402
+from vampire_amd import _capi, _header, metrics              # noqa: E402
 from vampire_amd import evaluation as E                      # noqa: E402
 from vampire_amd import multitask as M                       # noqa: E402
 from vampire_amd.build import build_library                  # noqa: E402
@@ -441,21 +440,15 @@ def _desc(**kw):
 
 def test_descriptor_layout_matches_the_header(lib):
     assert C.sizeof(_capi.VampDetEvalDesc) == 408
-    text = open(os.path.join(ROOT, "include", "vampire_hip.h")).read()
-    body = re.search(r"typedef struct VampDetEvalDesc \{(.*?)\} VampDetEvalDesc;", text, flags=re.S).group(1)
-    body = re.sub(r"/\*.*?\*/", "", body, flags=re.S)
-    fields = []
-    for decl in body.split(";"):
-        decl = decl.strip()
-        if decl:
-            ctype, rest = decl.split(None, 1)
-            fields += [(ctype, re.sub(r"\[.*?\]", "", n).strip()) for n in rest.split(",")]
+    header = _header.read()
+    fields = [(ctype, name) for name, ctype, _ in header.structs["VampDetEvalDesc"]]
     ctypes_of = {"double": C.c_double, "int32_t": C.c_int32}
     got = [(n, t._type_ if issubclass(t, C.Array) else t) for n, t in _capi.VampDetEvalDesc._fields_]
     assert got == [(n, ctypes_of[t]) for t, n in fields]
-    for macro in ("MAX_CLASSES", "GT_CAP", "MAX_WIDTH", "RECORD_BYTES", "STATE_WORDS"):
-        value = int(re.search(rf"#define VAMP_DET_EVAL_{macro} (\d+)", text).group(1))
-        assert getattr(_capi, f"VAMP_DET_EVAL_{macro}") == value
+    for macro, pinned in (("MAX_CLASSES", 16), ("GT_CAP", 256), ("MAX_WIDTH", 2048), ("RECORD_BYTES", 32),
+                          ("STATE_WORDS", 24)):
+        value = header.constants[f"VAMP_DET_EVAL_{macro}"]
+        assert getattr(_capi, f"VAMP_DET_EVAL_{macro}") == value == pinned
     assert _capi.VAMP_DET_EVAL_GT_CAP == GT_CAP >= 256
 
 

@@ -13,14 +13,11 @@ The largest fractions of the bars seen on an MI355X are in test_gradients_agains
 import ctypes as C
 import dataclasses
 import math
-import os
-import re
 
 import pytest
 import torch
 
-from conftest import ROOT
-from vampire_amd import _capi
+from vampire_amd import _capi, _header
 from vampire_amd.config import CFG_TINY
 from test_hip_parity import close
 from test_sample_points_sweep import (ACT_BETA_BAR, ACT_GRAD_BAR, BF16_GRAD_REL, GRAD_CAP, GRAD_CAP_CROWD, K_BWD_TREE,
@@ -634,19 +631,13 @@ def query_desc(K=18, X=33, Y=16, Z=5, B=2, M=63, P=385):
 
 
 def test_descriptor_size_matches_the_header():
-    text = re.sub(r"/\*.*?\*/", "", open(os.path.join(ROOT, "include", "vampire_hip.h")).read(), flags=re.S)
-    body = re.search(r"typedef struct \{([^}]*)\} VampQueryDesc;", text).group(1)
+    fields = _header.read().structs["VampQueryDesc"]
     words = 0
-    for decl in body.split(";"):
-        decl = decl.strip()
-        if not decl:
-            continue
-        assert re.match(r"(int32_t|float)\s", decl), decl
-        for name in decl.split(None, 1)[1].split(","):
-            m = re.search(r"\[(\d+)\]", name)
-            words += int(m.group(1)) if m else 1
+    for name, ctype, dims in fields:
+        assert ctype in ("int32_t", "float"), (name, ctype)
+        words += math.prod(dims)
     assert words == 23 and C.sizeof(_capi.VampQueryDesc) == 4 * words
-    assert [f[0] for f in _capi.VampQueryDesc._fields_] == re.findall(r"(\w+)(?:\[\d+\])?\s*[,;]", body)
+    assert [f[0] for f in _capi.VampQueryDesc._fields_] == [name for name, _, _ in fields]
 
 
 def test_refusals_need_no_pointer(lib):

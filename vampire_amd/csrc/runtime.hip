@@ -383,20 +383,20 @@ int vamp_profile_select(int slot) {
   return VAMP_OK;
 }
 
-int vamp_profile_read(int slot, const char** name, int* launches, double* total_ms) {
-  if (slot < 0 || slot >= kProfSlots || !name || !launches || !total_ms)
+int vamp_profile_read(int slot, const char** name_host, int* launches_host, double* total_ms_host) {
+  if (slot < 0 || slot >= kProfSlots || !name_host || !launches_host || !total_ms_host)
     return fail(VAMP_EINVAL, "%s: bad argument", __func__);
   std::lock_guard<std::mutex> lk(g_mu);
-  *name = g_names[slot];
-  *launches = 0;
-  *total_ms = 0.0;
+  *name_host = g_names[slot];
+  *launches_host = 0;
+  *total_ms_host = 0.0;
   for (auto& p : g_pairs) {
     if (p.slot != slot) continue;
     if (hipEventSynchronize(p.b) != hipSuccess) return fail(VAMP_EHIP, "%s: hipEventSynchronize", __func__);
     float ms = 0.f;
     if (hipEventElapsedTime(&ms, p.a, p.b) != hipSuccess) return fail(VAMP_EHIP, "%s: hipEventElapsedTime", __func__);
-    *launches += 1;
-    *total_ms += ms;
+    *launches_host += 1;
+    *total_ms_host += ms;
   }
   return VAMP_OK;
 }
