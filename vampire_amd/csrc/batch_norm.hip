@@ -45,7 +45,7 @@ constexpr int kBnBlock = 256;
 constexpr int kBnWaves = kBnBlock / 64;
 constexpr int kBnSmallPlane = 32;
 static_assert(VAMP_BN_CHUNK % (8 * kBnBlock) == 0, "a chunk is whole rounds of the workgroup's 16-byte vectors");
-static_assert(sizeof(VampBatchNormDesc) == 64, "VampBatchNormDesc layout (vampire_amd/_capi.py mirrors it)");
+static_assert(sizeof(VampBatchNormDesc) == 64, "VampBatchNormDesc layout: part of the ABI (the binding reads it from include/vampire_hip.h)");
 
 template <int DT>
 struct BnElem {
@@ -429,16 +429,6 @@ inline BnShape bn_shape(const VampBatchNormDesc* d) {
   return BnShape{d->C, (int) hw, (int) nhw, (int) ((nhw + VAMP_BN_CHUNK - 1) / VAMP_BN_CHUNK)};
 }
 
-inline bool bn_aligned(const void* p, uintptr_t a) { return (reinterpret_cast<uintptr_t>(p) & (a - 1)) == 0; }
-
-#define BN_WORKSPACE(d, workspace, workspace_bytes)                                                      \
-  do {                                                                                                   \
-    const size_t need = vamp_bn_workspace_bytes(d);                                                      \
-    if (!(workspace) || (workspace_bytes) < need)                                                        \
-      return fail(VAMP_ENOSPC, "%s: workspace %ld < %ld bytes", __func__, (long) (workspace_bytes), (long) need); \
-    VAMP_REQUIRE(bn_aligned(workspace, 8), "the workspace must be 8-byte aligned");                    \
-  } while (0)
-
 // f(integral_constant<int, DT>) for the descriptor's element type, f(true_type | false_type) for a flag
 template <typename F>
 inline void bn_by_dtype(int dtype, F&& f) {
@@ -470,9 +460,10 @@ int vamp_bn_partial_stats(const VampBatchNormDesc* d, const void* x, double* row
                           size_t workspace_bytes, void* stream) {
   if (int e = bn_validate(d)) return e;
   VAMP_REQUIRE(x && row, "x or row is NULL");
-  VAMP_REQUIRE(bn_aligned(x, 16), "x must be 16-byte aligned");
-  VAMP_REQUIRE(bn_aligned(row, 8), "the float64 row must be 8-byte aligned");
-  BN_WORKSPACE(d, workspace, workspace_bytes);
+  VAMP_REQUIRE(aligned(x, 16), "x must be 16-byte aligned");
+  VAMP_REQUIRE(aligned(row, 8), "the float64 row must be 8-byte aligned");
+  if (int e = workspace_fits(__func__, workspace, workspace_bytes, vamp_bn_workspace_bytes(d))) return e;
+  VAMP_REQUIRE(aligned(workspace, 8), "the workspace must be 8-byte aligned");
   hipStream_t st = static_cast<hipStream_t>(stream);
   const BnShape sh = bn_shape(d);
   double* slots = static_cast<double*>(workspace);
@@ -492,18 +483,18 @@ int vamp_bn_apply(const VampBatchNormDesc* d, const void* x, const void* residua
   if (int e = bn_validate(d)) return e;
   VAMP_REQUIRE(!d->has_residual || residual, "has_residual is set but residual is NULL");
   VAMP_REQUIRE(x && y && weight && bias, "x, y, weight or bias is NULL");
-  VAMP_REQUIRE(bn_aligned(x, 16) && bn_aligned(y, 16) && bn_aligned(residual, 16),
+  VAMP_REQUIRE(aligned(x, 16) && aligned(y, 16) && aligned(residual, 16),
                "x, y and residual must be 16-byte aligned");
   if (d->training) {
     VAMP_REQUIRE(rows, "training needs the float64 rows");
-    VAMP_REQUIRE(bn_aligned(rows, 8), "the float64 rows must be 8-byte aligned");
+    VAMP_REQUIRE(aligned(rows, 8), "the float64 rows must be 8-byte aligned");
     VAMP_REQUIRE(saved, "training needs saved");
     VAMP_REQUIRE(!d->update_running || (running_mean && running_var), "update_running needs running_mean and running_var");
   } else {
     VAMP_REQUIRE(running_mean && running_var, "evaluation needs running_mean and running_var");
     VAMP_REQUIRE(!d->update_running, "update_running needs training");
   }
-  VAMP_REQUIRE(bn_aligned(num_batches_tracked, 8), "num_batches_tracked must be 8-byte aligned");
+  VAMP_REQUIRE(aligned(num_batches_tracked, 8), "num_batches_tracked must be 8-byte aligned");
   hipStream_t st = static_cast<hipStream_t>(stream);
   const BnShape sh = bn_shape(d);
   BnApply a{x, d->has_residual ? residual : nullptr, y, rows, weight, bias, running_mean, running_var,
@@ -528,9 +519,10 @@ int vamp_bn_backward_partial(const VampBatchNormDesc* d, const void* dy, const v
   VAMP_REQUIRE(d->training, "the backward needs training statistics (evaluation mode has no backward)");
   VAMP_REQUIRE(dy && x && saved && row && grad_weight && grad_bias, "dy, x, saved, row, grad_weight or grad_bias is NULL");
   VAMP_REQUIRE(d->act == VAMP_BN_ACT_NONE || y, "act VAMP_BN_ACT_RELU needs the saved output y");
-  VAMP_REQUIRE(bn_aligned(dy, 16) && bn_aligned(x, 16) && bn_aligned(y, 16), "dy, x and y must be 16-byte aligned");
-  VAMP_REQUIRE(bn_aligned(row, 8), "the float64 row must be 8-byte aligned");
-  BN_WORKSPACE(d, workspace, workspace_bytes);
+  VAMP_REQUIRE(aligned(dy, 16) && aligned(x, 16) && aligned(y, 16), "dy, x and y must be 16-byte aligned");
+  VAMP_REQUIRE(aligned(row, 8), "the float64 row must be 8-byte aligned");
+  if (int e = workspace_fits(__func__, workspace, workspace_bytes, vamp_bn_workspace_bytes(d))) return e;
+  VAMP_REQUIRE(aligned(workspace, 8), "the workspace must be 8-byte aligned");
   hipStream_t st = static_cast<hipStream_t>(stream);
   const BnShape sh = bn_shape(d);
   BnBwdStats a{dy, x, y, saved, static_cast<double*>(workspace), row, grad_weight, grad_bias, sh};
@@ -554,9 +546,9 @@ int vamp_bn_backward_apply(const VampBatchNormDesc* d, const void* dy, const voi
   VAMP_REQUIRE(!d->has_residual || grad_residual, "has_residual is set but grad_residual is NULL");
   VAMP_REQUIRE(dy && x && saved && weight && rows && stat_rows && dx, "dy, x, saved, weight, rows, stat_rows or dx is NULL");
   VAMP_REQUIRE(d->act == VAMP_BN_ACT_NONE || y, "act VAMP_BN_ACT_RELU needs the saved output y");
-  VAMP_REQUIRE(bn_aligned(dy, 16) && bn_aligned(x, 16) && bn_aligned(y, 16) && bn_aligned(dx, 16) &&
-               bn_aligned(grad_residual, 16), "dy, x, y, dx and grad_residual must be 16-byte aligned");
-  VAMP_REQUIRE(bn_aligned(rows, 8) && bn_aligned(stat_rows, 8), "the float64 rows must be 8-byte aligned");
+  VAMP_REQUIRE(aligned(dy, 16) && aligned(x, 16) && aligned(y, 16) && aligned(dx, 16) &&
+               aligned(grad_residual, 16), "dy, x, y, dx and grad_residual must be 16-byte aligned");
+  VAMP_REQUIRE(aligned(rows, 8) && aligned(stat_rows, 8), "the float64 rows must be 8-byte aligned");
   hipStream_t st = static_cast<hipStream_t>(stream);
   const BnShape sh = bn_shape(d);
   BnBwdApply a{dy, x, y, saved, weight, rows, stat_rows, dx, d->has_residual ? grad_residual : nullptr, d->world, sh};

@@ -267,7 +267,7 @@ __global__ void __launch_bounds__(kImgBlock) img_finish_kernel(ImgParams p) {
 // ---------------------------------------------------------------------------------------------------------
 // host side
 // ---------------------------------------------------------------------------------------------------------
-static_assert(sizeof(VampImageDesc) == 104, "VampImageDesc layout (vampire_amd/_capi.py mirrors it)");
+static_assert(sizeof(VampImageDesc) == 104, "VampImageDesc layout: part of the ABI (the binding reads it from include/vampire_hip.h)");
 
 int img_validate(const VampImageDesc* d) {
   VAMP_REQUIRE(d, "desc is NULL");
@@ -316,12 +316,11 @@ int vamp_camera_images(const VampImageDesc* d, const uint8_t* raw, const int32_t
                "out must be given exactly when out_dtype is not VAMP_IMG_OUT_NONE");
   VAMP_REQUIRE(raw && col_first && col_count && col_taps && row_first && row_count && row_taps && consts,
                "raw or a plan table is NULL");
-  VAMP_REQUIRE(!out || reinterpret_cast<uintptr_t>(out) % 16 == 0, "out must be 16-byte aligned");
-  VAMP_REQUIRE(!out_u8 || reinterpret_cast<uintptr_t>(out_u8) % 4 == 0, "out_u8 must be 4-byte aligned");
+  VAMP_REQUIRE(aligned(out, 16), "out must be 16-byte aligned");
+  VAMP_REQUIRE(aligned(out_u8, 4), "out_u8 must be 4-byte aligned");
   const size_t need = vamp_camera_images_workspace_bytes(d);
-  if (!workspace || workspace_bytes < need)
-    return fail(VAMP_ENOSPC, "%s: workspace %ld < %ld bytes", __func__, (long) workspace_bytes, (long) need);
-  VAMP_REQUIRE(reinterpret_cast<uintptr_t>(workspace) % 16 == 0, "workspace must be 16-byte aligned");
+  if (int e = workspace_fits(__func__, workspace, workspace_bytes, need)) return e;
+  VAMP_REQUIRE(aligned(workspace, 16), "workspace must be 16-byte aligned");
 
   ImgParams q{};
   q.raw = raw;

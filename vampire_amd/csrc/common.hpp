@@ -41,6 +41,38 @@ inline int check_launch(const char* what) {
 
 inline size_t align_up(size_t v, size_t a) { return (v + a - 1) / a * a; }
 
+// host-side pointer alignment (a: a power of two); NULL counts as aligned
+inline bool aligned(const void* p, uintptr_t a) { return (reinterpret_cast<uintptr_t>(p) & (a - 1)) == 0; }
+
+// The one refusal of a workspace that is missing or too small.  An entry point calls workspace_fits where its checks
+// always had the refusal; `code` is VAMP_ENOSPC everywhere but in vamp_reg_loss_forward.
+inline int workspace_refused(const char* who, size_t workspace_bytes, size_t need, int code) {
+  return fail(code, "%s: workspace %ld < %ld bytes", who, (long) workspace_bytes, (long) need);
+}
+inline int workspace_fits(const char* who, const void* workspace, size_t workspace_bytes, size_t need, int code = VAMP_ENOSPC) {
+  return !workspace || workspace_bytes < need ? workspace_refused(who, workspace_bytes, need, code) : VAMP_OK;
+}
+// ... for the plans, which are given a size and no pointer (their callers pass 0 bytes for a NULL workspace)
+inline int workspace_fits(const char* who, size_t workspace_bytes, size_t need) {
+  return workspace_bytes < need ? workspace_refused(who, workspace_bytes, need, VAMP_ENOSPC) : VAMP_OK;
+}
+
+// Every operator cuts its caller's workspace into regions with one of these, in one function per family that fills
+// the family's pointers: regions back to back in the order of the take() calls, each rounded up to 256 bytes.  With a
+// NULL base the pointers come out NULL and `off` is the size (what the *_workspace_bytes entry points return).  `off`
+// is public: a layout reads it to note where a region lies and sets it back to overlay regions (cam_workspace).
+struct Carve {
+  char* base;
+  size_t off = 0;
+  explicit Carve(void* workspace) : base(static_cast<char*>(workspace)) {}
+  template <class T>
+  T* take(size_t count) {
+    T* p = base ? reinterpret_cast<T*>(base + off) : nullptr;
+    off += align_up(count * sizeof(T), 256);
+    return p;
+  }
+};
+
 // f(CI, CO) with the channel tiles ci, co (16, else 32) as compile-time constants: the 3x3x3 convolutions' entry points
 // choose their kernel instantiation with it
 template <class F>
@@ -94,6 +126,20 @@ struct ScanDuty {
 };
 int launch_cell_scan(int* cnt, int* off, int* bsum, int* boff, int* aux, long ncell,
                      hipStream_t s, const ScanDuty* duty = nullptr);
+// The scan's five regions for `ncell` counters, in the order and with the paddings described above.  `take(p, count)`
+// sets p to a region of `count` ints: the lift's and the camera's layouts pass the lambda that fills their region table.
+template <class Take>
+void take_scan(Take&& take, size_t ncell, int*& cnt, int*& off, int*& bsum, int*& boff, int*& aux) {
+  const size_t ntile = ncell / kScanTile;
+  take(cnt, ncell + kScanPad);
+  take(off, ncell);
+  take(bsum, ntile);
+  take(boff, ntile);
+  take(aux, ntile + 4);
+}
+inline void take_scan(Carve& c, size_t ncell, int*& cnt, int*& off, int*& bsum, int*& boff, int*& aux) {
+  take_scan([&c](int*& p, size_t count) { p = c.take<int>(count); }, ncell, cnt, off, bsum, boff, aux);
+}
 // the same scan as a job description, and two jobs in one launch (runtime.hip: cell_scan_pair_kernel)
 struct ScanJob {
   int *cnt, *off, *bsum, *boff, *fill, *total, *ticket;

@@ -488,7 +488,7 @@ int vamp_conv3d_epilogue_forward(const VampConvDesc* d, const VampConvEpilogue* 
   if (int e = check(d)) return e;
   if (int e = epi_check(__func__, d, epi, false, 1)) return e;
   VAMP_REQUIRE(in && weight, "NULL tensor");
-  VAMP_REQUIRE(((uintptr_t) in | (uintptr_t) weight) % 16 == 0, "in / weight must start on a 16-byte boundary");
+  VAMP_REQUIRE(aligned(in, 16) && aligned(weight, 16), "in / weight must start on a 16-byte boundary");
   hipStream_t s = static_cast<hipStream_t>(stream);
   return dispatch_tiles(d->cin, d->cout, [&](auto CI, auto CO) {
     return launch_fwd<CI(), CO(), false, true>(d, in, weight, nullptr, s, epi);

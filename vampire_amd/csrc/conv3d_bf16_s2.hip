@@ -552,7 +552,7 @@ int vamp_conv3d_half_s2_epilogue_forward(const VampConvDesc* d, int32_t dtype, c
   if (int e = half_args_ok(__func__, kShapeRule, d, dtype, true)) return e;
   if (int e = epi_check(__func__, d, epi, true, 1)) return e;
   VAMP_REQUIRE(in && weight, "NULL tensor");
-  VAMP_REQUIRE(((uintptr_t) in | (uintptr_t) weight) % 16 == 0, "in / weight must start on a 16-byte boundary");
+  VAMP_REQUIRE(aligned(in, 16) && aligned(weight, 16), "in / weight must start on a 16-byte boundary");
   hipStream_t s = static_cast<hipStream_t>(stream);
   return dispatch_half(d->cin, d->cout, dtype, [&](auto CI, auto CO, auto F16) {
     return epi->seg[0].out_f32 ? launch_fwd<CI(), CO(), F16(), true, true>(d, in, weight, nullptr, s, epi)
@@ -576,8 +576,7 @@ int vamp_conv3d_half_s2_backward_weight(const VampConvDesc* d, int32_t dtype, co
                                         float* grad_weight, void* workspace, size_t workspace_bytes, void* stream) {
   if (int e = half_args_ok(__func__, kShapeRule, d, dtype, in && grad_out && grad_weight)) return e;
   const size_t need = half_workspace_bytes(d);
-  if (!workspace || workspace_bytes < need)
-    return fail(VAMP_ENOSPC, "%s: workspace %ld < %ld bytes", __func__, (long) workspace_bytes, (long) need);
+  if (int e = workspace_fits(__func__, workspace, workspace_bytes, need)) return e;
   hipStream_t s = static_cast<hipStream_t>(stream);
   float* ws = static_cast<float*>(workspace);
   return dispatch_half(d->cin, d->cout, dtype, [&](auto CI, auto CO, auto F16) {

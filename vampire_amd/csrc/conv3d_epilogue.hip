@@ -155,8 +155,7 @@ int vamp_conv3d_epilogue_backward(const VampConvDesc* d, int32_t stride, int32_t
   const int nchunks = nchunks_of(v.plane);
   if (want_bias) {
     const size_t need = vamp_conv3d_epilogue_workspace_bytes(d, stride);
-    if (!workspace || workspace_bytes < need)
-      return fail(VAMP_ENOSPC, "%s: workspace %ld < %ld bytes", __func__, (long) workspace_bytes, (long) need);
+    if (int e = workspace_fits(__func__, workspace, workspace_bytes, need)) return e;
   }
   hipStream_t s = static_cast<hipStream_t>(stream);
   double* part = want_bias ? static_cast<double*>(workspace) : nullptr;

@@ -193,7 +193,7 @@ inline int epi_check(const char* who, const VampConvDesc* d, const VampConvEpilo
       VAMP_EPI_REQ(g.c0 >= e->seg[j].c0 + e->seg[j].nch || e->seg[j].c0 >= g.c0 + g.nch, "segments overlap");
     if (mode == 1) {
       VAMP_EPI_REQ(g.out != nullptr, "NULL segment output");
-      VAMP_EPI_REQ(((uintptr_t) g.out | (uintptr_t) g.residual | (uintptr_t) g.bias) % 16 == 0,
+      VAMP_EPI_REQ(aligned(g.out, 16) && aligned(g.residual, 16) && aligned(g.bias, 16),
                    "segment tensors must start on a 16-byte boundary");
     } else if (mode == 2) {
       VAMP_EPI_REQ(g.grad_out != nullptr, "NULL segment gradient");

@@ -336,7 +336,7 @@ __global__ void __launch_bounds__(kEvBlock) det_eval_kernel(EvParams p) {
 // ---------------------------------------------------------------------------------------------------------
 // host side
 // ---------------------------------------------------------------------------------------------------------
-static_assert(sizeof(VampDetEvalDesc) == 408, "VampDetEvalDesc layout (vampire_amd/_capi.py mirrors it)");
+static_assert(sizeof(VampDetEvalDesc) == 408, "VampDetEvalDesc layout: part of the ABI (the binding reads it from include/vampire_hip.h)");
 static_assert(VAMP_DET_EVAL_RECORD_BYTES == 2 * sizeof(uint4), "a record is two 16-byte stores");
 static_assert(VAMP_DET_EVAL_STATE_WORDS >= kEvStNpos + kEvMaxCls, "state holds the counters and npos");
 
@@ -394,7 +394,7 @@ int vamp_det_eval_update(const VampDetEvalDesc* d, const float* boxes, const voi
   VAMP_REQUIRE(d->G == 0 || (gt_boxes && gt_labels), "gt_boxes or gt_labels is NULL");
   VAMP_REQUIRE(d->has_attrs == 0 || d->G == 0 || gt_attrs, "has_attrs is set and gt_attrs is NULL");
   VAMP_REQUIRE(records && state, "records or state is NULL");
-  VAMP_REQUIRE(reinterpret_cast<uintptr_t>(records) % 16 == 0, "records must be 16-byte aligned");
+  VAMP_REQUIRE(aligned(records, 16), "records must be 16-byte aligned");
   EvParams q{};
   q.boxes = boxes; q.scores = scores; q.labels = labels; q.counts = counts;
   q.gt_boxes = gt_boxes; q.gt_labels = gt_labels; q.gt_attrs = d->has_attrs ? gt_attrs : nullptr;

@@ -317,7 +317,7 @@ __global__ void __launch_bounds__(kLossBlock) grad_box_kernel(LossParams p) {
 // ---------------------------------------------------------------------------------------------------------
 // host side
 // ---------------------------------------------------------------------------------------------------------
-static_assert(sizeof(VampDetLossDesc) == 112, "VampDetLossDesc layout (vampire_amd/_capi.py mirrors it)");
+static_assert(sizeof(VampDetLossDesc) == 112, "VampDetLossDesc layout: part of the ABI (the binding reads it from include/vampire_hip.h)");
 static_assert(sizeof(LossParams) <= 4096, "kernel arguments");
 
 int loss_validate(const VampDetLossDesc* d) {
@@ -411,8 +411,7 @@ int vamp_det_loss_forward(const VampDetLossDesc* d, const VampDetTask* preds, co
   loss_params(d, &q);
   if (int e = loss_tasks(d, preds, q.pred, true)) return e;
   const size_t need = loss_workspace(d);
-  if (!workspace || workspace_bytes < need)
-    return fail(VAMP_ENOSPC, "%s: workspace %ld < %ld bytes", __func__, (long) workspace_bytes, (long) need);
+  if (int e = workspace_fits(__func__, workspace, workspace_bytes, need)) return e;
   q.heat = heat; q.anno = anno; q.inds = inds; q.masks = masks; q.counts = counts; q.loss = loss; q.terms = terms;
   q.part = static_cast<double*>(workspace);
   hipStream_t s = static_cast<hipStream_t>(stream);
@@ -433,8 +432,7 @@ int vamp_det_loss_backward(const VampDetLossDesc* d, const VampDetTask* preds, c
   if (int e = loss_tasks(d, preds, q.pred, true)) return e;
   loss_tasks(d, grads, q.grad, false);
   const size_t need = loss_workspace(d);              // (the backward stores nothing there: one size for both)
-  if (!workspace || workspace_bytes < need)
-    return fail(VAMP_ENOSPC, "%s: workspace %ld < %ld bytes", __func__, (long) workspace_bytes, (long) need);
+  if (int e = workspace_fits(__func__, workspace, workspace_bytes, need)) return e;
   q.heat = heat; q.anno = anno; q.inds = inds; q.masks = masks; q.counts = counts; q.grad_loss = grad_loss;
   hipStream_t s = static_cast<hipStream_t>(stream);
   const int grid = q.chunk_off[d->T] + d->T * q.zchunks;

@@ -482,13 +482,7 @@ __global__ void __launch_bounds__(256) det_merge_kernel(DetParams p, float* __re
 // ---------------------------------------------------------------------------------------------------------
 // host side
 // ---------------------------------------------------------------------------------------------------------
-static_assert(sizeof(VampDetDesc) == 58 * 4, "VampDetDesc layout (vampire_amd/_capi.py mirrors it)");
-
-struct DetLayout {
-  size_t keys, cand, ncand, masks, kept, nkept, total;
-  long nstride;
-  int KP;
-};
+static_assert(sizeof(VampDetDesc) == 58 * 4, "VampDetDesc layout: part of the ABI (the binding reads it from include/vampire_hip.h)");
 
 int det_validate(const VampDetDesc* d) {
   VAMP_REQUIRE(d, "desc is NULL");
@@ -513,26 +507,26 @@ int det_validate(const VampDetDesc* d) {
   return VAMP_OK;
 }
 
-DetLayout det_layout(const VampDetDesc* d) {
-  DetLayout L{};
+// the padded counts of *q and its regions carved from `workspace` (NULL: only the size, which is returned, is of use)
+size_t det_workspace(const VampDetDesc* d, DetParams* q, void* workspace) {
   long nmax = 0, kmax = 0;
   for (int t = 0; t < d->T; ++t) {
     const long N = (long) d->ncls[t] * d->H * d->W;
     nmax = std::max(nmax, N);
     kmax = std::max(kmax, std::min<long>(d->max_num, N));
   }
-  const long BT = (long) d->B * d->T;
-  L.nstride = (long) align_up(nmax, 64);
-  L.KP = (int) align_up(kmax, 64);
-  size_t o = 0;
-  L.keys = o;  o = align_up(o + (size_t) BT * L.nstride * 4, 256);
-  L.cand = o;  o = align_up(o + (size_t) BT * L.KP * kRow * 4, 256);
-  L.ncand = o; o = align_up(o + (size_t) BT * 4, 256);
-  L.masks = o; o = align_up(o + (size_t) BT * L.KP * kMaxWords * 8, 256);
-  L.kept = o;  o = align_up(o + (size_t) BT * d->post_max_size * 4, 256);
-  L.nkept = o; o = align_up(o + (size_t) BT * 4, 256);
-  L.total = o;
-  return L;
+  const size_t BT = (size_t) d->B * d->T;
+  q->nstride = (long) align_up(nmax, 64);
+  q->KP = (int) align_up(kmax, 64);
+  q->nblk = q->KP / 64;
+  Carve c(workspace);
+  q->keys = c.take<uint32_t>(BT * q->nstride);
+  q->cand = c.take<float>(BT * q->KP * kRow);
+  q->ncand = c.take<int>(BT);
+  q->masks = c.take<uint64_t>(BT * q->KP * kMaxWords);
+  q->kept = c.take<int>(BT * d->post_max_size);
+  q->nkept = c.take<int>(BT);
+  return c.off;
 }
 
 template <int DT>
@@ -553,7 +547,8 @@ extern "C" {
 
 size_t vamp_det_workspace_bytes(const VampDetDesc* d) {
   if (det_validate(d)) return 0;
-  return det_layout(d).total;
+  DetParams q{};
+  return det_workspace(d, &q, nullptr);
 }
 
 int vamp_det_postprocess(const VampDetDesc* d, const VampDetTask* tasks, float* boxes, void* scores, int32_t* labels,
@@ -566,10 +561,8 @@ int vamp_det_postprocess(const VampDetDesc* d, const VampDetTask* tasks, float* 
     VAMP_REQUIRE(!d->has_vel || k.vel, "has_vel is set but a task's vel is NULL");
   }
   VAMP_REQUIRE(boxes && scores && labels && counts, "an output pointer is NULL");
-  const DetLayout L = det_layout(d);
-  if (!workspace || workspace_bytes < L.total)
-    return fail(VAMP_ENOSPC, "%s: workspace %ld < %ld bytes", __func__, (long) workspace_bytes, (long) L.total);
   DetParams q{};
+  if (int e = workspace_fits(__func__, workspace, workspace_bytes, det_workspace(d, &q, workspace))) return e;
   int flag = 0;
   for (int t = 0; t < d->T; ++t) {
     q.task[t] = tasks[t];
@@ -589,16 +582,6 @@ int vamp_det_postprocess(const VampDetDesc* d, const VampDetTask* tasks, float* 
   q.thr = d->score_threshold; q.osf = d->out_size_factor;
   q.vs0 = d->voxel_size[0]; q.vs1 = d->voxel_size[1]; q.pc0 = d->pc_range[0]; q.pc1 = d->pc_range[1];
   for (int i = 0; i < 6; ++i) q.rng[i] = d->post_center_range[i];
-  q.KP = L.KP;
-  q.nblk = L.KP / 64;
-  q.nstride = L.nstride;
-  char* ws = static_cast<char*>(workspace);
-  q.keys = reinterpret_cast<uint32_t*>(ws + L.keys);
-  q.cand = reinterpret_cast<float*>(ws + L.cand);
-  q.ncand = reinterpret_cast<int*>(ws + L.ncand);
-  q.masks = reinterpret_cast<uint64_t*>(ws + L.masks);
-  q.kept = reinterpret_cast<int*>(ws + L.kept);
-  q.nkept = reinterpret_cast<int*>(ws + L.nkept);
   hipStream_t s = static_cast<hipStream_t>(stream);
   if (d->in_dtype == VAMP_F32) det_launch<VAMP_F32>(q, boxes, scores, labels, counts, s);
   else if (d->in_dtype == VAMP_BF16) det_launch<VAMP_BF16>(q, boxes, scores, labels, counts, s);

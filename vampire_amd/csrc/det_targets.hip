@@ -276,11 +276,7 @@ __global__ void __launch_bounds__(kTgtBlock) tgt_heatmap_kernel(TgtParams p) {
 // ---------------------------------------------------------------------------------------------------------
 // host side
 // ---------------------------------------------------------------------------------------------------------
-static_assert(sizeof(VampDetTargetDesc) == 112, "VampDetTargetDesc layout (vampire_amd/_capi.py mirrors it)");
-
-struct TgtLayout {
-  size_t rec, nrec, total;
-};
+static_assert(sizeof(VampDetTargetDesc) == 112, "VampDetTargetDesc layout: part of the ABI (the binding reads it from include/vampire_hip.h)");
 
 int tgt_validate(const VampDetTargetDesc* d) {
   VAMP_REQUIRE(d, "desc is NULL");
@@ -305,14 +301,13 @@ int tgt_validate(const VampDetTargetDesc* d) {
   return VAMP_OK;
 }
 
-TgtLayout tgt_layout(const VampDetTargetDesc* d) {
-  TgtLayout L{};
+// the regions of *q carved from `workspace` (NULL: only the size, which is returned, is of use)
+size_t tgt_workspace(const VampDetTargetDesc* d, TgtParams* q, void* workspace) {
   const size_t BT = (size_t) d->B * d->T;
-  size_t o = 0;
-  L.rec = o;  o = align_up(o + BT * d->max_objs * sizeof(int4), 256);
-  L.nrec = o; o = align_up(o + BT * 4, 256);
-  L.total = o;
-  return L;
+  Carve c(workspace);
+  q->rec = c.take<int4>(BT * d->max_objs);
+  q->nrec = c.take<int>(BT);
+  return c.off;
 }
 
 }  // namespace
@@ -324,7 +319,8 @@ extern "C" {
 
 size_t vamp_det_targets_workspace_bytes(const VampDetTargetDesc* d) {
   if (tgt_validate(d)) return 0;
-  return tgt_layout(d).total;
+  TgtParams q{};
+  return tgt_workspace(d, &q, nullptr);
 }
 
 int vamp_det_targets(const VampDetTargetDesc* d, const float* boxes, const void* labels, float* heatmaps, float* anno,
@@ -332,14 +328,9 @@ int vamp_det_targets(const VampDetTargetDesc* d, const float* boxes, const void*
   if (int e = tgt_validate(d)) return e;
   VAMP_REQUIRE(d->M == 0 || (boxes && labels), "boxes or labels is NULL");
   VAMP_REQUIRE(heatmaps && anno && inds && masks, "an output pointer is NULL");
-  const TgtLayout L = tgt_layout(d);
-  if (!workspace || workspace_bytes < L.total)
-    return fail(VAMP_ENOSPC, "%s: workspace %ld < %ld bytes", __func__, (long) workspace_bytes, (long) L.total);
   TgtParams q{};
+  if (int e = workspace_fits(__func__, workspace, workspace_bytes, tgt_workspace(d, &q, workspace))) return e;
   q.boxes = boxes; q.labels = labels; q.heat = heatmaps; q.anno = anno; q.inds = inds; q.masks = masks;
-  char* ws = static_cast<char*>(workspace);
-  q.rec = reinterpret_cast<int4*>(ws + L.rec);
-  q.nrec = reinterpret_cast<int*>(ws + L.nrec);
   long off = 0;
   int flag = 0;
   for (int t = 0; t < d->T; ++t) {

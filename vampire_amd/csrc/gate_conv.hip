@@ -494,8 +494,7 @@ int vamp_gate_conv1x1_backward(int64_t B, int32_t C, int32_t oZ, int64_t cells, 
   VAMP_REQUIRE(g.mb != 0, "shape not supported (C * oZ <= 160, Cout <= 80, oZ <= 32, and oZ <= 20 when C * oZ > 64 and Cout > 16: the "
                "backward's LDS image): see vamp_gate_conv1x1_supported");
   const size_t need = vamp_gate_conv1x1_workspace_bytes(C, oZ, Cout);
-  if (!workspace || workspace_bytes < need)
-    return fail(VAMP_ENOSPC, "%s: workspace %ld < %ld bytes", __func__, (long) workspace_bytes, (long) need);
+  if (int e = workspace_fits(__func__, workspace, workspace_bytes, need)) return e;
   hipStream_t s = static_cast<hipStream_t>(stream);
   return VAMP_GC_DISPATCH(launch_bwd, B, C * oZ, oZ, cells, Cout, density_mode, grad_out, voxel_output,
                           voxel_density, weight, grad_voxel_output, grad_voxel_density, grad_weight, grad_bias,

@@ -196,11 +196,7 @@ __global__ void __launch_bounds__(kLLBlock) ll_resolve_kernel(LLParams p) {
 // ---------------------------------------------------------------------------------------------------------
 // host side
 // ---------------------------------------------------------------------------------------------------------
-static_assert(sizeof(VampLidarLabelDesc) == 88, "VampLidarLabelDesc layout (vampire_amd/_capi.py mirrors it)");
-
-struct LLLayout {
-  size_t cam, bev, cam_bytes, bev_bytes, total;
-};
+static_assert(sizeof(VampLidarLabelDesc) == 88, "VampLidarLabelDesc layout: part of the ABI (the binding reads it from include/vampire_hip.h)");
 
 int ll_validate(const VampLidarLabelDesc* d) {
   VAMP_REQUIRE(d, "desc is NULL");
@@ -223,16 +219,22 @@ int ll_validate(const VampLidarLabelDesc* d) {
   return VAMP_OK;
 }
 
-LLLayout ll_layout(const VampLidarLabelDesc* d) {
-  LLLayout L{};
-  const size_t cam_cells = (size_t) d->B * d->N * (d->H / d->stride) * (d->W / d->stride);
-  const size_t bev_cells = (size_t) d->B * d->ny * d->nx;
-  L.cam_bytes = align_up(cam_cells * 8, 256);
-  L.bev_bytes = align_up(bev_cells * 8, 256);
-  L.cam = 0;
-  L.bev = L.cam_bytes;
-  L.total = L.cam_bytes + L.bev_bytes;
-  return L;
+// The two key tables, the camera maps' then the BEV maps', carved from `workspace` (NULL: only `bytes` is of use), each
+// with the count of 16-byte units the fill kernel writes: its whole padded region.
+struct LLWs {
+  unsigned long long *cam_keys, *bev_keys;
+  long cam_units, bev_units;
+  size_t bytes;
+};
+LLWs ll_workspace(const VampLidarLabelDesc* d, void* workspace) {
+  Carve c(workspace);
+  LLWs w;
+  w.cam_keys = c.take<unsigned long long>((size_t) d->B * d->N * (d->H / d->stride) * (d->W / d->stride));
+  w.cam_units = (long) (c.off / 16);
+  w.bev_keys = c.take<unsigned long long>((size_t) d->B * d->ny * d->nx);
+  w.bev_units = (long) (c.off / 16) - w.cam_units;
+  w.bytes = c.off;
+  return w;
 }
 
 }  // namespace
@@ -244,7 +246,7 @@ extern "C" {
 
 size_t vamp_lidar_labels_workspace_bytes(const VampLidarLabelDesc* d) {
   if (ll_validate(d)) return 0;
-  return ll_layout(d).total;
+  return ll_workspace(d, nullptr).bytes;
 }
 
 int vamp_lidar_labels(const VampLidarLabelDesc* d, const float* points, const void* labels, const int32_t* counts,
@@ -258,29 +260,27 @@ int vamp_lidar_labels(const VampLidarLabelDesc* d, const float* points, const vo
   VAMP_REQUIRE(!bev || (bev_seg && bev_height && bev_mask), "bev_seg, bev_height, bev_mask must be NULL together or not at all");
   VAMP_REQUIRE(d->M == 0 || (points && labels), "points or labels is NULL");
   VAMP_REQUIRE(!cam || (lidar2cam && intrin && aug), "lidar2cam, intrin or aug is NULL");
-  VAMP_REQUIRE(!cam || reinterpret_cast<uintptr_t>(aug) % 8 == 0, "aug must be 8-byte aligned");
-  const LLLayout L = ll_layout(d);
-  if (!workspace || workspace_bytes < L.total)
-    return fail(VAMP_ENOSPC, "%s: workspace %ld < %ld bytes", __func__, (long) workspace_bytes, (long) L.total);
-  VAMP_REQUIRE(reinterpret_cast<uintptr_t>(workspace) % 16 == 0, "workspace must be 16-byte aligned");
+  VAMP_REQUIRE(!cam || aligned(aug, 8), "aug must be 8-byte aligned");
+  const LLWs w = ll_workspace(d, workspace);
+  if (int e = workspace_fits(__func__, workspace, workspace_bytes, w.bytes)) return e;
+  VAMP_REQUIRE(aligned(workspace, 16), "workspace must be 16-byte aligned");
 
   LLParams q{};
   q.points = points; q.labels = labels; q.counts = counts;
   q.lidar2cam = lidar2cam; q.intrin = intrin; q.aug = aug;
   q.cam_depth = cam_depth; q.cam_seg = cam_seg; q.cam_fg = cam_fg;
   q.bev_seg = bev_seg; q.bev_height = bev_height; q.bev_mask = bev_mask;
-  char* ws = static_cast<char*>(workspace);
   q.B = d->B; q.N = d->N; q.M = d->M; q.cols = d->point_cols; q.lab64 = d->label_dtype == VAMP_I64;
   q.H = d->H; q.W = d->W; q.stride = d->stride; q.h = d->H / d->stride; q.w = d->W / d->stride;
   q.ny = d->ny; q.nx = d->nx;
   if (cam) {
-    q.cam_keys = reinterpret_cast<unsigned long long*>(ws + L.cam);
-    q.cam_units = (long) (L.cam_bytes / 16);
+    q.cam_keys = w.cam_keys;
+    q.cam_units = w.cam_units;
     q.cam_cells = (long) d->B * d->N * q.h * q.w;
   }
   if (bev) {
-    q.bev_keys = reinterpret_cast<unsigned long long*>(ws + L.bev);
-    q.bev_units = (long) (L.bev_bytes / 16);
+    q.bev_keys = w.bev_keys;
+    q.bev_units = w.bev_units;
     q.bev_cells = (long) d->B * d->ny * d->nx;
   }
   q.origin_x = d->origin_x; q.origin_y = d->origin_y; q.size = d->size;

@@ -1051,7 +1051,7 @@ static int lift_forward_plan(const char* who, const VampLiftDesc* d, bool has_lo
   p.grid[0] = (d->X + VAMP_LIFT_TX - 1) / VAMP_LIFT_TX;
   p.grid[1] = (d->Y + VAMP_LIFT_TY - 1) / VAMP_LIFT_TY;
   p.grid[2] = d->Z * d->B;
-  return lift_workspace_fits(who, w, workspace_bytes);
+  return workspace_fits(who, workspace_bytes, w.bytes);
 }
 
 // the forward kernel, as the plan says (T: the depth planes' type)
@@ -1199,9 +1199,9 @@ int vamp_lift_forward_ex(const VampLiftDesc* d, const float* mats, const float* 
                          uint64_t* hits, void* workspace, size_t workspace_bytes, int flags, void* stream) {
   if (int e = lift_validate(d)) return e;
   VAMP_REQUIRE(mats && xs && ys && zs && feat && out, "null pointer");
-  VAMP_REQUIRE(((uintptr_t) mats & 15) == 0, "mats must be 16-byte aligned (the cull reads whole matrix rows)");
+  VAMP_REQUIRE(aligned(mats, 16), "mats must be 16-byte aligned (the cull reads whole matrix rows)");
   VAMP_REQUIRE(depth || !d->use_depth, "depth is NULL");
-  VAMP_REQUIRE(!(flags & VAMP_LIFTFWD_FEAT_CHANNEL_LAST) || ((uintptr_t) feat & 15) == 0, "channel-last feat must be 16-byte aligned");
+  VAMP_REQUIRE(!(flags & VAMP_LIFTFWD_FEAT_CHANNEL_LAST) || aligned(feat, 16), "channel-last feat must be 16-byte aligned");
   VampLiftForwardPlan p;
   if (int e = lift_forward_plan(__func__, d, false, 0, flags, workspace ? workspace_bytes : 0, &p)) return e;
   return launch_lift_forward(d, p, lift_workspace(d, workspace), mats, xs, ys, zs, nullptr, 0, nullptr, depth, feat, out,
@@ -1222,8 +1222,8 @@ int vamp_lift_forward_logits_ex(const VampLiftDesc* d, const float* mats, const 
                                 size_t workspace_bytes, int flags, void* stream) {
   if (int e = lift_validate(d)) return e;
   VAMP_REQUIRE(mats && xs && ys && zs && logits && feat && depth_out && out, "null pointer");
-  VAMP_REQUIRE(((uintptr_t) mats & 15) == 0, "mats must be 16-byte aligned (the cull reads whole matrix rows)");
-  VAMP_REQUIRE(!(flags & VAMP_LIFTFWD_FEAT_CHANNEL_LAST) || ((uintptr_t) feat & 15) == 0, "channel-last feat must be 16-byte aligned");
+  VAMP_REQUIRE(aligned(mats, 16), "mats must be 16-byte aligned (the cull reads whole matrix rows)");
+  VAMP_REQUIRE(!(flags & VAMP_LIFTFWD_FEAT_CHANNEL_LAST) || aligned(feat, 16), "channel-last feat must be 16-byte aligned");
   VampLiftForwardPlan p;
   if (int e = lift_forward_plan(__func__, d, true, logits_dtype, flags, workspace ? workspace_bytes : 0, &p)) return e;
   return launch_lift_forward(d, p, lift_workspace(d, workspace), mats, xs, ys, zs, logits, logits_dtype, depth_out,
@@ -1234,7 +1234,7 @@ int vamp_lift_forward_logits_ex(const VampLiftDesc* d, const float* mats, const 
 int vamp_lift_finish_cells(const VampLiftDesc* d, void* workspace, size_t workspace_bytes, void* stream) {
   if (int e = lift_validate(d)) return e;
   const LiftWorkspace w = lift_workspace(d, workspace);
-  if (int e = lift_workspace_fits(__func__, w, workspace ? workspace_bytes : 0)) return e;
+  if (int e = workspace_fits(__func__, workspace ? workspace_bytes : 0, w.bytes)) return e;
   return launch_lift_cells_end(w, static_cast<hipStream_t>(stream));
 }
 
@@ -1242,7 +1242,7 @@ int vamp_lift_finish_cells(const VampLiftDesc* d, void* workspace, size_t worksp
 int lift_scan_job(const VampLiftDesc* d, void* workspace, size_t workspace_bytes, ScanJob* job) {
   if (int e = lift_validate(d)) return e;
   const LiftWorkspace w = lift_workspace(d, workspace);
-  if (int e = lift_workspace_fits(__func__, w, workspace ? workspace_bytes : 0)) return e;
+  if (int e = workspace_fits(__func__, workspace ? workspace_bytes : 0, w.bytes)) return e;
   return lift_cells_scan_job(w, job);
 }
 
@@ -1253,7 +1253,7 @@ int vamp_lift_prepare(const VampLiftDesc* d, const float* mats, const float* xs,
   VAMP_REQUIRE(depth || !d->use_depth, "depth is NULL");
   if (int e = lift_cells_fit(__func__, d)) return e;
   const LiftWorkspace w = lift_workspace(d, workspace);
-  if (int e = lift_workspace_fits(__func__, w, workspace ? workspace_bytes : 0)) return e;
+  if (int e = workspace_fits(__func__, workspace ? workspace_bytes : 0, w.bytes)) return e;
   return launch_lift_cell_prepare(d, to_params(d), w, mats, xs, ys, zs, depth, static_cast<hipStream_t>(stream));
 }
 
@@ -1322,7 +1322,7 @@ int vamp_lift_cull_words(const VampLiftDesc* d, const float* mats, const float* 
   grid[0] = cull.nxp; grid[1] = cull.nyp;
   if (!words) return VAMP_OK;
   VAMP_REQUIRE(mats && xs && ys && zs, "null pointer");
-  VAMP_REQUIRE(((uintptr_t) mats & 15) == 0, "mats must be 16-byte aligned (the cull reads whole matrix rows)");
+  VAMP_REQUIRE(aligned(mats, 16), "mats must be 16-byte aligned (the cull reads whole matrix rows)");
   cull.words = words;
   lift_cull_kernel<<<(unsigned) ((long) d->B * cull.bps), 256, 0, static_cast<hipStream_t>(stream)>>>(
       to_params(d), mats, xs, ys, zs, cull);

@@ -732,7 +732,7 @@ int lift_backward_plan(const char* who, const VampLiftDesc* d, int flags, size_t
     p.splat_grid[0] = (d->X + VAMP_LIFT_TX - 1) / VAMP_LIFT_TX;
     p.splat_grid[1] = (d->Y + VAMP_LIFT_TY - 1) / VAMP_LIFT_TY;
     p.splat_grid[2] = d->Z * d->B;
-    return lift_workspace_fits(who, w, workspace_bytes);
+    return workspace_fits(who, workspace_bytes, w.bytes);
   }
   p.path = VAMP_LIFTPLAN_BWD_CELL;
   p.prepare = !(flags & VAMP_LIFTBWD_CELLS_VALID);
@@ -754,7 +754,7 @@ int lift_backward_plan(const char* who, const VampLiftDesc* d, int flags, size_t
   p.vec = d->in_dtype == VAMP_F32 && d->fW % 4 == 0;
   p.strip_grid = (int32_t) ((unsigned) BN * d->fH * ((d->fW + kS - 1) / kS));
   p.softmax_bwd = (flags & VAMP_LIFTBWD_LOGITS) != 0;
-  return lift_workspace_fits(who, w, workspace_bytes);
+  return workspace_fits(who, workspace_bytes, w.bytes);
 }
 
 // the fill, as the plan says (the counters are the fill cursors: the scan left them at zero)

@@ -160,7 +160,7 @@ inline LiftWorkspace lift_workspace(const VampLiftDesc* d, void* workspace) {
   w.ch = d->fH + 1;
   const long nc = (long) d->B * d->N * w.cw * w.ch + 2;
   w.ncell = (nc + kScanTile - 1) / kScanTile * kScanTile;
-  const size_t ncell = (size_t) w.ncell, ntile = ncell / kScanTile;
+  const size_t ncell = (size_t) w.ncell;
   // every (voxel, camera) pair can be valid
   const size_t V = (size_t) d->Z * d->Y * d->X;
   const size_t cap = (size_t) d->B * d->N * V;
@@ -176,39 +176,26 @@ inline LiftWorkspace lift_workspace(const VampLiftDesc* d, void* workspace) {
   w.cull.bps = (int) ((per_sample + ppb - 1) / ppb);
   const long tiles = (long) d->N * (((long) d->fH * d->fW + 63) / 64);
   w.cull.ppt = (int) ((per_sample + tiles - 1) / tiles);
-  size_t off = 0;
+  Carve c(workspace);
   int region = 0;
-  auto take = [&](size_t n) {
-    char* p = workspace ? static_cast<char*>(workspace) + off : nullptr;
-    n = align_up(n, 256);
-    w.offset[region] = off;
-    w.region_bytes[region++] = n;
-    off += n;
-    return p;
+  auto take = [&](auto*& p, size_t count) {      // the next region of the table: `count` elements for p
+    w.offset[region] = c.off;
+    p = c.take<std::remove_reference_t<decltype(*p)>>(count);
+    w.region_bytes[region] = c.off - w.offset[region];
+    ++region;
   };
-  const size_t feat_bytes = (size_t) d->B * d->N * d->fH * d->fW * d->C * sizeof(float);
-  w.feat_cl = reinterpret_cast<float*>(take(feat_bytes));
-  w.gfeat_cl = reinterpret_cast<float*>(take(feat_bytes));
-  w.cnt = reinterpret_cast<int*>(take((ncell + kScanPad) * sizeof(int)));
-  w.off = reinterpret_cast<int*>(take(ncell * sizeof(int)));
-  w.bsum = reinterpret_cast<int*>(take(ntile * sizeof(int)));
-  w.boff = reinterpret_cast<int*>(take(ntile * sizeof(int)));
-  w.aux = reinterpret_cast<int*>(take((ntile + 4) * sizeof(int)));
-  w.amask = reinterpret_cast<unsigned*>(take((size_t) d->B * V * sizeof(unsigned)));
-  w.ptaps = reinterpret_cast<float4*>(take(cap * 2 * sizeof(float4)));
-  w.pcell = reinterpret_cast<int*>(take(cap * sizeof(int)));
-  w.recs = reinterpret_cast<float4*>(take(cap * (size_t) (2 + (d->C + 3) / 4) * sizeof(float4)));
-  w.rowq = reinterpret_cast<int*>(take((size_t) d->B * d->N * d->fH * sizeof(int)));
-  w.cull.words = reinterpret_cast<unsigned*>(take((size_t) w.ncull * sizeof(unsigned)));
-  w.bytes = off;
+  const size_t feat = (size_t) d->B * d->N * d->fH * d->fW * d->C;
+  take(w.feat_cl, feat);
+  take(w.gfeat_cl, feat);
+  take_scan(take, ncell, w.cnt, w.off, w.bsum, w.boff, w.aux);
+  take(w.amask, (size_t) d->B * V);
+  take(w.ptaps, cap * 2);
+  take(w.pcell, cap);
+  take(w.recs, cap * (size_t) (2 + (d->C + 3) / 4));
+  take(w.rowq, (size_t) d->B * d->N * d->fH);
+  take(w.cull.words, (size_t) w.ncull);
+  w.bytes = c.off;
   return w;
-}
-
-// the one refusal of a workspace that is too small (callers pass 0 bytes for a NULL workspace)
-inline int lift_workspace_fits(const char* who, const LiftWorkspace& w, size_t workspace_bytes) {
-  if (workspace_bytes < w.bytes)
-    return fail(VAMP_ENOSPC, "%s: workspace %ld < %ld bytes", who, (long) workspace_bytes, (long) w.bytes);
-  return VAMP_OK;
 }
 
 // VAMP_REQUIRE in a function that refuses in the name of its caller `who` (the plans)

@@ -64,9 +64,9 @@ constexpr int kUpdRounds = VAMP_UPDATE_CHUNK / kUpdRoundElems;
 constexpr int kUpdChunk = kUpdRoundElems * kUpdRounds;
 constexpr int kUpdFinishBlock = 1024;                           // one workgroup over 8 bytes per parameter chunk
 static_assert(kUpdChunk == VAMP_UPDATE_CHUNK, "VAMP_UPDATE_CHUNK is the workgroup's chunk");
-static_assert(sizeof(VampUpdateChunk) == 32, "VampUpdateChunk layout (vampire_amd/_capi.py mirrors it)");
-static_assert(sizeof(VampUpdateScalars) == 128, "VampUpdateScalars layout (vampire_amd/_capi.py mirrors it)");
-static_assert(sizeof(VampParamUpdateDesc) == 64, "VampParamUpdateDesc layout (vampire_amd/_capi.py mirrors it)");
+static_assert(sizeof(VampUpdateChunk) == 32, "VampUpdateChunk layout: part of the ABI (the binding reads it from include/vampire_hip.h)");
+static_assert(sizeof(VampUpdateScalars) == 128, "VampUpdateScalars layout: part of the ABI (the binding reads it from include/vampire_hip.h)");
+static_assert(sizeof(VampParamUpdateDesc) == 64, "VampParamUpdateDesc layout: part of the ABI (the binding reads it from include/vampire_hip.h)");
 
 __device__ __forceinline__ bool upd_aligned16(const void* a, const void* b) {
   return ((reinterpret_cast<uintptr_t>(a) | reinterpret_cast<uintptr_t>(b)) & 15u) == 0;
@@ -248,8 +248,6 @@ int upd_validate(const VampParamUpdateDesc* d) {
   return VAMP_OK;
 }
 
-inline bool upd_host_aligned(const void* p, uintptr_t a) { return (reinterpret_cast<uintptr_t>(p) & (a - 1)) == 0; }
-
 }  // namespace
 }  // namespace vamp
 
@@ -270,13 +268,12 @@ int vamp_param_update_step(const VampParamUpdateDesc* d, const void* table, floa
   VAMP_REQUIRE(scalars, "the scalar block is NULL");
   VAMP_REQUIRE(d->n_param_chunks == 0 || (exp_avg && exp_avg_sq), "exp_avg or exp_avg_sq is NULL");
   VAMP_REQUIRE(d->ema_decay <= 0.0 || ema, "ema_decay > 0 needs the ema array");
-  VAMP_REQUIRE(upd_host_aligned(table, 8) && upd_host_aligned(scalars, 8), "table and scalars must be 8-byte aligned");
-  VAMP_REQUIRE(upd_host_aligned(exp_avg, 16) && upd_host_aligned(exp_avg_sq, 16) && upd_host_aligned(ema, 16),
+  VAMP_REQUIRE(aligned(table, 8) && aligned(scalars, 8), "table and scalars must be 8-byte aligned");
+  VAMP_REQUIRE(aligned(exp_avg, 16) && aligned(exp_avg_sq, 16) && aligned(ema, 16),
                "the state arrays must be 16-byte aligned");
   const size_t need = vamp_param_update_workspace_bytes(d);
-  if (!workspace || workspace_bytes < need)
-    return fail(VAMP_ENOSPC, "%s: workspace %ld < %ld bytes", __func__, (long) workspace_bytes, (long) need);
-  VAMP_REQUIRE(upd_host_aligned(workspace, 8), "the workspace must be 8-byte aligned");
+  if (int e = workspace_fits(__func__, workspace, workspace_bytes, need)) return e;
+  VAMP_REQUIRE(aligned(workspace, 8), "the workspace must be 8-byte aligned");
   hipStream_t st = static_cast<hipStream_t>(stream);
   const VampUpdateChunk* tb = static_cast<const VampUpdateChunk*>(table);
   double* slots = static_cast<double*>(workspace);

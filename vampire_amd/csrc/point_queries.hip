@@ -385,36 +385,10 @@ point_queries_heavy_kernel(QueryParams Q, const TD* __restrict__ den, const floa
 // ---------------------------------------------------------------------------
 // host side
 // ---------------------------------------------------------------------------
-struct QryWs {
-  int *cnt, *off, *bsum, *boff, *aux, *heavy, *key, *rank;
-  float4 *F, *R;
-  float *G, *beta_part;
-  size_t bytes;
-};
-
-static QryWs qry_ws(const VampQueryDesc* d, void* scratch) {
-  const long ncell = cell_count_padded(d->B, d->Z, d->Y, d->X);
-  const long ntile = ncell / kScanTile;
-  const size_t src = (size_t) d->B * ((size_t) d->M + 2 * (size_t) d->P_occ);
-  const size_t voxels = (size_t) d->B * d->Z * d->Y * d->X;
-  const int CP = (d->K + 1 + 3) / 4 * 4;
-  char* p = static_cast<char*>(scratch);
-  QryWs w;
-  w.cnt = reinterpret_cast<int*>(p); p += align_up((size_t) (ncell + kScanPad) * sizeof(int), 256);   // + the scan's ticket word
-  w.off = reinterpret_cast<int*>(p); p += align_up((size_t) ncell * sizeof(int), 256);
-  w.bsum = reinterpret_cast<int*>(p); p += align_up((size_t) ntile * sizeof(int), 256);
-  w.boff = reinterpret_cast<int*>(p); p += align_up((size_t) ntile * sizeof(int), 256);
-  w.aux = reinterpret_cast<int*>(p); p += align_up((size_t) (ntile + 4) * sizeof(int), 256);
-  w.heavy = reinterpret_cast<int*>(p); p += align_up(voxels * sizeof(int), 256);
-  w.key = reinterpret_cast<int*>(p); p += align_up(src * sizeof(int), 256);
-  w.rank = reinterpret_cast<int*>(p); p += align_up(src * sizeof(int), 256);
-  w.F = reinterpret_cast<float4*>(p); p += align_up(src * sizeof(float4), 256);
-  w.R = reinterpret_cast<float4*>(p); p += align_up(src * sizeof(float4), 256);
-  w.G = reinterpret_cast<float*>(p); p += align_up(src * CP * sizeof(float), 256);
-  const size_t nblk = (size_t) ((d->X + PVPB - 1) / PVPB) * d->Y * d->Z * d->B;
-  w.beta_part = reinterpret_cast<float*>(p); p += align_up((nblk + kHeavyGrid) * sizeof(float), 256);
-  w.bytes = (size_t) (p - static_cast<char*>(scratch));
-  return w;
+static PointWs qry_ws(const VampQueryDesc* d, void* workspace) {
+  const size_t nblk = (size_t) ((d->X + PVPB - 1) / PVPB) * d->Y * d->Z * d->B;     // one partial per gather workgroup, + the heavy kernel's
+  return point_ws(d->B, d->Z, d->Y, d->X, (size_t) d->B * ((size_t) d->M + 2 * (size_t) d->P_occ), (d->K + 1 + 3) / 4 * 4,
+                  nblk + kHeavyGrid, workspace);
 }
 
 template <typename TD>
@@ -423,7 +397,7 @@ static int backward_t(const VampQueryDesc* d, const QueryParams& Q, const void* 
                       const float* g_pts_logits, const float* g_pts_sdf, const float* g_occ_logits,
                       const float* g_occ_density, float* grad_semantic, float* grad_density, float* grad_beta,
                       void* workspace, hipStream_t s) {
-  const QryWs w = qry_ws(d, workspace);
+  const PointWs w = qry_ws(d, workspace);
   const long ncell = cell_count_padded(d->B, d->Z, d->Y, d->X);
   const long ntile = ncell / kScanTile;
   const long ncell_b = (long) (d->Z + 1) * (d->Y + 1) * (d->X + 1);
@@ -546,8 +520,7 @@ int vamp_point_queries_backward(const VampQueryDesc* d, const void* density, con
   VAMP_REQUIRE((d->M == 0 || points) && (d->P_occ == 0 || occ_points), "null pointer");
   VAMP_REQUIRE(beta || d->P_occ == 0 || d->density_mode == VAMP_DENSITY_SIGMOID, "beta is NULL");
   const size_t need = vamp_point_queries_workspace_bytes(d);
-  if (!workspace || workspace_bytes < need)
-    return fail(VAMP_ENOSPC, "%s: workspace %ld < %ld bytes", __func__, (long) workspace_bytes, (long) need);
+  if (int e = workspace_fits(__func__, workspace, workspace_bytes, need)) return e;
   const QueryParams Q = to_params(d);
   hipStream_t s = static_cast<hipStream_t>(stream);
   if (d->den_dtype == VAMP_F32)

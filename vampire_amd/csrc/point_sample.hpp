@@ -134,4 +134,28 @@ __device__ __forceinline__ void point_accumulate(const CellRanges& cr, int k, co
   record_accumulate<CP4, false>(cr, k, R, G, fix, fiy, fiz, acc, 0, unused);
 }
 
+// The workspace of either file's backward (cell_list.hpp's lists over the source rows, then the gradient rows), every
+// region 256-byte aligned and back to back.  `rows`: source rows of all samples; `CP`: floats of a gradient row;
+// `nbeta`: d beta partial sums.  `workspace` may be nullptr (only `bytes` is of use then).
+struct PointWs {
+  int *cnt, *off, *bsum, *boff, *aux, *heavy, *key, *rank;
+  float4 *F, *R;
+  float *G, *beta_part;
+  size_t bytes;
+};
+inline PointWs point_ws(int B, int Z, int Y, int X, size_t rows, int CP, size_t nbeta, void* workspace) {
+  Carve c(workspace);
+  PointWs w;
+  take_scan(c, (size_t) cell_count_padded(B, Z, Y, X), w.cnt, w.off, w.bsum, w.boff, w.aux);
+  w.heavy = c.take<int>((size_t) B * Z * Y * X);
+  w.key = c.take<int>(rows);
+  w.rank = c.take<int>(rows);
+  w.F = c.take<float4>(rows);
+  w.R = c.take<float4>(rows);
+  w.G = c.take<float>(rows * CP);
+  w.beta_part = c.take<float>(nbeta);
+  w.bytes = c.off;
+  return w;
+}
+
 }  // namespace vamp

@@ -230,7 +230,7 @@ __global__ void __launch_bounds__(kRegBlock) reg_bwd_kernel(RegPack p) {
 // ---------------------------------------------------------------------------------------------------------
 // host side
 // ---------------------------------------------------------------------------------------------------------
-static_assert(sizeof(VampRegTerm) == 32, "VampRegTerm layout (vampire_amd/_capi.py mirrors it)");
+static_assert(sizeof(VampRegTerm) == 32, "VampRegTerm layout: part of the ABI (the binding reads it from include/vampire_hip.h)");
 static_assert(sizeof(VampRegLossDesc) == 8 + 32 * VAMP_REG_MAX_TERMS, "VampRegLossDesc layout");
 
 int reg_validate(const VampRegLossDesc* d) {
@@ -249,8 +249,6 @@ int reg_validate(const VampRegLossDesc* d) {
   }
   return VAMP_OK;
 }
-
-inline bool reg_aligned(const void* p, uintptr_t a) { return (reinterpret_cast<uintptr_t>(p) & (a - 1)) == 0; }
 
 // the descriptor and the operands into the kernels' argument; grad_host == nullptr: the forward
 int reg_pack(const VampRegLossDesc* d, const void* const* pred, const float* const* target, const uint8_t* const* mask,
@@ -273,8 +271,8 @@ int reg_pack(const VampRegLossDesc* d, const void* const* pred, const float* con
     q->cval[t] = m.target_value;
     q->kind[t] = (uint8_t) m.kind; q->side[t] = (uint8_t) m.side; q->bf16[t] = bf; q->cst[t] = (uint8_t) m.target_is_const;
     const uintptr_t ea = bf ? 8 : 16;
-    q->vec[t] = reg_aligned(pred[t], ea) && (m.target_is_const || reg_aligned(target[t], 16)) &&
-                (!mask[t] || reg_aligned(mask[t], 4)) && (!q->grad[t] || reg_aligned(q->grad[t], ea));
+    q->vec[t] = aligned(pred[t], ea) && (m.target_is_const || aligned(target[t], 16)) &&
+                (!mask[t] || aligned(mask[t], 4)) && (!q->grad[t] || aligned(q->grad[t], ea));
     blocks += (m.n + kRegTile - 1) / kRegTile;
   }
   q->first[d->T] = (int) blocks;
@@ -288,6 +286,15 @@ size_t reg_blocks(const VampRegLossDesc* d) {
   return blocks;
 }
 
+// the forward's two tables of per-workgroup partials carved from `workspace` (NULL: only the returned size is of use)
+size_t reg_workspace(const VampRegLossDesc* d, RegPack* q, void* workspace) {
+  const size_t blocks = reg_blocks(d);
+  Carve c(workspace);
+  q->psum = c.take<double>(blocks * 2);
+  q->pcnt = c.take<int>(blocks * 2);
+  return c.off;
+}
+
 }  // namespace
 }  // namespace vamp
 
@@ -297,8 +304,8 @@ extern "C" {
 
 size_t vamp_reg_loss_workspace_bytes(const VampRegLossDesc* d) {
   if (reg_validate(d)) return 0;
-  const size_t blocks = reg_blocks(d);
-  return align_up(blocks * 2 * sizeof(double), 256) + align_up(blocks * 2 * sizeof(int), 256);
+  RegPack q{};
+  return reg_workspace(d, &q, nullptr);
 }
 
 int vamp_reg_loss_forward(const VampRegLossDesc* d, const void* const* pred_host, const float* const* target_host,
@@ -308,17 +315,12 @@ int vamp_reg_loss_forward(const VampRegLossDesc* d, const void* const* pred_host
   RegPack q{};
   if (int e = reg_pack(d, pred_host, target_host, mask_host, nullptr, &q)) return e;
   VAMP_REQUIRE(losses && counts, "an output pointer is NULL");
-  const size_t need = vamp_reg_loss_workspace_bytes(d);
-  if (!workspace || workspace_bytes < need)
-    return fail(VAMP_EINVAL, "%s: workspace %ld < %ld bytes", __func__, (long) workspace_bytes, (long) need);
-  VAMP_REQUIRE(reg_aligned(workspace, 8), "the workspace must be 8-byte aligned");
-  const size_t blocks = reg_blocks(d);
-  q.psum = static_cast<double*>(workspace);
-  q.pcnt = reinterpret_cast<int*>(static_cast<char*>(workspace) + align_up(blocks * 2 * sizeof(double), 256));
+  if (int e = workspace_fits(__func__, workspace, workspace_bytes, reg_workspace(d, &q, workspace), VAMP_EINVAL)) return e;
+  VAMP_REQUIRE(aligned(workspace, 8), "the workspace must be 8-byte aligned");
   q.losses = losses;
   q.counts = counts;
   hipStream_t st = static_cast<hipStream_t>(stream);
-  VAMP_TIMED(kProfAux, st, (reg_partial_kernel<<<(unsigned) blocks, kRegBlock, 0, st>>>(q)));
+  VAMP_TIMED(kProfAux, st, (reg_partial_kernel<<<(unsigned) reg_blocks(d), kRegBlock, 0, st>>>(q)));
   VAMP_TIMED(kProfAux, st, (reg_finish_kernel<<<1, kRegBlock, 0, st>>>(q)));
   return check_launch("reg_loss_forward");
 }

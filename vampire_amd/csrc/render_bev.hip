@@ -1428,8 +1428,7 @@ int vamp_render_bev_backward_ex(const VampRenderDesc* d, const float* oxs, const
                              grad_density_feature, grad_semantic, grad_rgb, grad_base, grad_beta, stream);
   }
   const BevWorkspace w = bev_workspace(d, workspace);
-  if (!workspace || workspace_bytes < w.bytes)
-    return fail(VAMP_ENOSPC, "%s: workspace %ld < %ld bytes", __func__, (long) workspace_bytes, (long) w.bytes);
+  if (int e = workspace_fits(__func__, workspace, workspace_bytes, w.bytes)) return e;
   if (p.outside)
     if (int e = bev_bwd_zero(c, p)) return e;
   if (p.scan)

@@ -219,8 +219,7 @@ int vamp_render_bev_forward_ex(const VampRenderDesc* d, const float* oxs, const 
   float *s0_save = nullptr, *ss_save = nullptr;
   if (flags & VAMP_BEVFWD_SAVE) {
     const BevWorkspace w = bev_workspace(d, workspace);
-    if (!workspace || workspace_bytes < w.bytes)
-      return fail(VAMP_ENOSPC, "%s: workspace %ld < %ld bytes", __func__, (long) workspace_bytes, (long) w.bytes);
+    if (int e = workspace_fits(__func__, workspace, workspace_bytes, w.bytes)) return e;
     s0_save = w.s0_saved;
     ss_save = w.ss_saved;
   }

@@ -343,8 +343,7 @@ int camera_backward_plan(const char* who, const VampRenderDesc* d, bool has_geom
   const RenderParams P = to_params(d);
   const CamWorkspace w = cam_workspace(d, nullptr);
   p.bytes_needed = (int64_t) w.base_bytes;
-  if (workspace_bytes < w.base_bytes)
-    return fail(VAMP_ENOSPC, "%s: workspace %ld < %ld bytes", who, (long) workspace_bytes, (long) w.base_bytes);
+  if (int e = workspace_fits(who, workspace_bytes, w.base_bytes)) return e;
   p.accumulate = (flags & VAMP_CAMBWD_ACCUMULATE) != 0;
   const bool part_ray = !(flags & (VAMP_CAMBWD_PART_GATHER | VAMP_CAMBWD_PART_HEAVY)) || (flags & VAMP_CAMBWD_PART_RAY);
   // Default: per-ray pass + cell-list gather (render_bwd_ray.hip, render_bwd_cell.hip), which evaluates the frustum
@@ -426,8 +425,7 @@ static int camera_prepare(const char* who, const VampRenderDesc* d, const float*
                           void* stream) {
   if (int e = validate(d)) return e;
   const CamWorkspace w = cam_workspace(d, workspace);
-  if (!workspace || workspace_bytes < w.base_bytes)
-    return fail(VAMP_ENOSPC, "%s: workspace %ld < %ld bytes", who, (long) workspace_bytes, (long) w.base_bytes);
+  if (int e = workspace_fits(who, workspace, workspace_bytes, w.base_bytes)) return e;
   // VAMP_CAMPREP_RANKED: the ranks are drawn (vamp_render_forward_merged with VAMP_RENDERFWD_RANK): the cell scan only
   const bool ranked = (flags & VAMP_CAMPREP_RANKED) != 0;
   if (!ranked && !(mats && us && vs && ds)) return fail(VAMP_EINVAL, "%s: requirement failed: null pointer", who);

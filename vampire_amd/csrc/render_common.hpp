@@ -325,40 +325,35 @@ inline CamWorkspace cam_workspace(const VampRenderDesc* d, void* workspace) {
   CamWorkspace w;
   w.ncell = cell_count_padded(d->B, d->Z, d->Y, d->X);
   w.ntile = w.ncell / kScanTile;
-  const size_t ncell = (size_t) w.ncell, ntile = (size_t) w.ntile;
-  size_t off = 0;
+  const size_t ncell = (size_t) w.ncell;
+  Carve c(workspace);
   int region = 0;
-  auto take = [&](size_t n) {
-    char* p = workspace ? static_cast<char*>(workspace) + off : nullptr;
-    w.offset[region] = off;
-    w.bytes[region++] = n;
-    off += n;
-    return p;
+  auto take = [&](auto*& p, size_t count) {      // the next region of the table: `count` elements for p
+    w.offset[region] = c.off;
+    p = c.take<std::remove_reference_t<decltype(*p)>>(count);
+    w.bytes[region] = c.off - w.offset[region];
+    ++region;
   };
-  const size_t pb = align_up((size_t) d->B * d->Z * d->Y * d->X * CP * sizeof(float), 256);
-  w.packed = reinterpret_cast<float*>(take(pb));
-  w.gpacked = reinterpret_cast<float*>(take(pb));
-  off -= pb;
-  w.Gcl = reinterpret_cast<float*>(take(align_up(rays * CP * sizeof(float), 256)));
-  w.cnt = reinterpret_cast<int*>(take(align_up((ncell + kScanPad) * sizeof(int), 256)));
-  w.off = reinterpret_cast<int*>(take(align_up(ncell * sizeof(int), 256)));
-  w.bsum = reinterpret_cast<int*>(take(align_up(ntile * sizeof(int), 256)));
-  w.boff = reinterpret_cast<int*>(take(align_up(ntile * sizeof(int), 256)));
-  w.aux = reinterpret_cast<int*>(take(align_up((ntile + 4) * sizeof(int), 256)));
-  w.hcells = reinterpret_cast<int2*>(take(align_up((ncell > samples / 16 + 4096 ? ncell : samples / 16 + 4096) * sizeof(int2), 256)));
-  w.part = reinterpret_cast<float*>(take(align_up((samples / kCellHeavy + 2) * 8 * CP * sizeof(float), 256)));
-  w.runs = reinterpret_cast<int*>(take(align_up((size_t) d->B * d->Z * d->Y * ((d->X + kRunVox - 1) / kRunVox) * sizeof(int), 256)));
-  w.rank = reinterpret_cast<int*>(take(align_up(tsamples * sizeof(int), 256)));
-  w.slot = reinterpret_cast<int*>(take(align_up(tsamples * sizeof(int), 256)));
-  w.tile_se = reinterpret_cast<int*>(take(align_up(tiles * sizeof(int), 256)));
-  w.tile_order = reinterpret_cast<int*>(take(align_up(tiles * sizeof(int), 256)));
-  w.R = reinterpret_cast<float4*>(take(align_up(samples * 2 * sizeof(float4), 256)));
-  w.beta_part = reinterpret_cast<float*>(take(align_up((size_t) ray_grid<4>(to_params(d)) * sizeof(float), 256)));   // one per workgroup of the per-ray pass
-  if (off < 2 * pb) off = 2 * pb;
-  w.term = reinterpret_cast<int*>(take(align_up(rays * sizeof(int), 256)));
-  w.base_bytes = off;
-  w.rows = reinterpret_cast<float*>(take(align_up(tiles * 64 * (d->D - 1) * CP * sizeof(float), 256)));
-  w.bytes_with_rows = off;
+  take(w.packed, (size_t) d->B * d->Z * d->Y * d->X * CP);
+  const size_t pb = c.off;
+  take(w.gpacked, pb / sizeof(float));
+  c.off -= pb;                                   // Gcl .. beta_part lie over gpacked
+  take(w.Gcl, rays * CP);
+  take_scan(take, ncell, w.cnt, w.off, w.bsum, w.boff, w.aux);
+  take(w.hcells, ncell > samples / 16 + 4096 ? ncell : samples / 16 + 4096);
+  take(w.part, (samples / kCellHeavy + 2) * 8 * CP);
+  take(w.runs, (size_t) d->B * d->Z * d->Y * ((d->X + kRunVox - 1) / kRunVox));
+  take(w.rank, tsamples);
+  take(w.slot, tsamples);
+  take(w.tile_se, tiles);
+  take(w.tile_order, tiles);
+  take(w.R, samples * 2);
+  take(w.beta_part, (size_t) ray_grid<4>(to_params(d)));   // one per workgroup of the per-ray pass
+  if (c.off < 2 * pb) c.off = 2 * pb;
+  take(w.term, rays);
+  w.base_bytes = c.off;
+  take(w.rows, tiles * 64 * (d->D - 1) * CP);
+  w.bytes_with_rows = c.off;
   return w;
 }
 
@@ -429,26 +424,20 @@ struct BevWorkspace {
 };
 // `workspace` may be nullptr (only `bytes` is of use then)
 inline BevWorkspace bev_workspace(const VampRenderDesc* d, void* workspace) {
-  const size_t one = align_up((size_t) d->B * d->oZ * d->oY * d->oX * sizeof(float), 256);
-  const size_t tab = align_up((size_t) 2 * (d->X + d->Y + d->Z) * sizeof(int4), 256);
+  const size_t one = (size_t) d->B * d->oZ * d->oY * d->oX, tab = (size_t) 2 * (d->X + d->Y + d->Z);   // elements
+  const size_t one_padded = align_up(one * sizeof(float), 256) / sizeof(float);      // ... of a region of `one`
   const size_t nsaved = bev_scan_blocks(d, true), nscan = bev_scan_blocks(d, false);
-  const size_t nbeta = nsaved > nscan ? nsaved : nscan;
-  size_t off = 0;
-  auto take = [&](size_t n) {
-    char* p = workspace ? static_cast<char*>(workspace) + off : nullptr;
-    off += n;
-    return p;
-  };
+  Carve c(workspace);
   BevWorkspace w;
-  w.Q = reinterpret_cast<float*>(take(one));
-  w.Wb = reinterpret_cast<float*>(take(one));
-  w.DS0 = reinterpret_cast<float*>(take(one));
-  w.tab[0] = reinterpret_cast<int4*>(take(tab));
-  w.tab[1] = reinterpret_cast<int4*>(take(tab));
-  w.beta_part = reinterpret_cast<float*>(take(align_up(nbeta * sizeof(float), 256)));
-  w.s0_saved = reinterpret_cast<float*>(take(one));
-  w.ss_saved = reinterpret_cast<float*>(take((size_t) (d->K + 3) * one));
-  w.bytes = off;
+  w.Q = c.take<float>(one);
+  w.Wb = c.take<float>(one);
+  w.DS0 = c.take<float>(one);
+  w.tab[0] = c.take<int4>(tab);
+  w.tab[1] = c.take<int4>(tab);
+  w.beta_part = c.take<float>(nsaved > nscan ? nsaved : nscan);
+  w.s0_saved = c.take<float>(one);
+  w.ss_saved = c.take<float>((size_t) (d->K + 3) * one_padded);
+  w.bytes = c.off;
   return w;
 }
 

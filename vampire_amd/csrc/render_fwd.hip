@@ -530,9 +530,7 @@ int camera_forward_plan(const char* who, const VampRenderDesc* d, bool has_geom,
     p.body = P.CP / 4;
     if (p.pack_only) p.body = p.grid = 0;
   }
-  if (workspace_bytes < (size_t) p.bytes_needed)
-    return fail(VAMP_ENOSPC, "%s: workspace %ld < %ld bytes", who, (long) workspace_bytes, (long) p.bytes_needed);
-  return VAMP_OK;
+  return workspace_fits(who, workspace_bytes, (size_t) p.bytes_needed);
 }
 
 // the channel-last copy's marches, as the plan says
@@ -600,8 +598,7 @@ int vamp_render_camera_terminate(const VampRenderDesc* d, const float* mats, con
   VAMP_REQUIRE(mats && us && vs && ds && density_feature, "null pointer");
   VAMP_REQUIRE(beta || d->density_mode == VAMP_DENSITY_SIGMOID, "beta is NULL");
   const CamWorkspace w = cam_workspace(d, workspace);
-  if (!workspace || workspace_bytes < w.base_bytes)
-    return fail(VAMP_ENOSPC, "%s: workspace %ld < %ld bytes", __func__, (long) workspace_bytes, (long) w.base_bytes);
+  if (int e = workspace_fits(__func__, workspace, workspace_bytes, w.base_bytes)) return e;
   return launch_cam_term(d, to_params(d), mats, us, vs, ds, beta, density_feature, w.term,
                          static_cast<hipStream_t>(stream));
 }

@@ -330,7 +330,7 @@ bool wide_ok(const VampResize2dDesc* d, bool hi_is_dst) {
   if (d->ow % 4 != 0) return false;
   for (int k = 0; k < d->nseg; ++k) {
     const void* p = hi_is_dst ? d->seg[k].dst : d->seg[k].src;
-    if (reinterpret_cast<uintptr_t>(p) % 16 != 0) return false;
+    if (!aligned(p, 16)) return false;
   }
   return true;
 }

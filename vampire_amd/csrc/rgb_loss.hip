@@ -76,10 +76,6 @@ struct RgbParams {
   double w[kRgbTaps];
 };
 
-struct RgbLayout {
-  size_t part, vd, fac, prodn, pyr, adj, gco, total;  // byte offsets
-};
-
 // ---------------------------------------------------------------------------------------------------------
 // forward
 // ---------------------------------------------------------------------------------------------------------
@@ -310,7 +306,7 @@ __global__ void __launch_bounds__(kRgbBlock) rgb_bwd_kernel(RgbParams p, int s, 
 // ---------------------------------------------------------------------------------------------------------
 // host side
 // ---------------------------------------------------------------------------------------------------------
-static_assert(sizeof(VampRgbLossDesc) == 28, "VampRgbLossDesc layout (vampire_amd/_capi.py mirrors it)");
+static_assert(sizeof(VampRgbLossDesc) == 28, "VampRgbLossDesc layout: part of the ABI (the binding reads it from include/vampire_hip.h)");
 static_assert(sizeof(RgbParams) <= 4096, "kernel arguments");
 
 int rgb_validate(const VampRgbLossDesc* d) {
@@ -326,7 +322,8 @@ int rgb_validate(const VampRgbLossDesc* d) {
   return VAMP_OK;
 }
 
-RgbLayout rgb_params(const VampRgbLossDesc* d, RgbParams* q) {
+// the shapes of *q, and its regions carved from `workspace` (NULL: only the size, which is returned, is of use)
+size_t rgb_params(const VampRgbLossDesc* d, RgbParams* q, void* workspace) {
   q->N = d->N; q->C = d->C; q->P = d->N * d->C;
   const long P = q->P;
   long npart = 0, npyr = 0, nadj = 0, ng = 0;
@@ -360,28 +357,15 @@ RgbLayout rgb_params(const VampRgbLossDesc* d, RgbParams* q) {
     sum += q->w[k];
   }
   for (int k = 0; k < kRgbTaps; ++k) q->w[k] /= sum;
-  RgbLayout L;
-  size_t off = 0;
-  L.part = off;  off = align_up(off + (size_t) npart * sizeof(double), 256);
-  L.vd = off;    off = align_up(off + (size_t) d->N * kRgbScales * sizeof(double), 256);
-  L.fac = off;   off = align_up(off + (size_t) d->N * kRgbScales * sizeof(double), 256);
-  L.prodn = off; off = align_up(off + (size_t) d->N * sizeof(double), 256);
-  L.pyr = off;   off = align_up(off + (size_t) npyr * sizeof(float), 256);
-  L.adj = off;   off = align_up(off + (size_t) nadj * sizeof(float), 256);
-  L.gco = off;   off = align_up(off + (size_t) ng * sizeof(float), 256);
-  L.total = off;
-  return L;
-}
-
-void rgb_bind(const RgbLayout& L, void* ws, RgbParams* q) {
-  char* b = static_cast<char*>(ws);
-  q->part = reinterpret_cast<double*>(b + L.part);
-  q->vd = reinterpret_cast<double*>(b + L.vd);
-  q->fac = reinterpret_cast<double*>(b + L.fac);
-  q->prodn = reinterpret_cast<double*>(b + L.prodn);
-  q->pyr = reinterpret_cast<float*>(b + L.pyr);
-  q->adj = reinterpret_cast<float*>(b + L.adj);
-  q->gco = reinterpret_cast<float*>(b + L.gco);
+  Carve c(workspace);
+  q->part = c.take<double>((size_t) npart);
+  q->vd = c.take<double>((size_t) d->N * kRgbScales);
+  q->fac = c.take<double>((size_t) d->N * kRgbScales);
+  q->prodn = c.take<double>((size_t) d->N);
+  q->pyr = c.take<float>((size_t) npyr);
+  q->adj = c.take<float>((size_t) nadj);
+  q->gco = c.take<float>((size_t) ng);
+  return c.off;
 }
 
 }  // namespace
@@ -394,7 +378,7 @@ extern "C" {
 size_t vamp_rgb_loss_workspace_bytes(const VampRgbLossDesc* d) {
   if (rgb_validate(d)) return 0;
   RgbParams q{};
-  return rgb_params(d, &q).total;
+  return rgb_params(d, &q, nullptr);
 }
 
 int vamp_rgb_loss_forward(const VampRgbLossDesc* d, const float* pred, const float* target, float* loss, float* terms,
@@ -403,12 +387,9 @@ int vamp_rgb_loss_forward(const VampRgbLossDesc* d, const float* pred, const flo
   if (!pred || !target || !loss || !terms || !vals)
     return fail(VAMP_ENOSPC, "%s: an input or output pointer is NULL", __func__);
   RgbParams q{};
-  const RgbLayout L = rgb_params(d, &q);
-  if (!workspace || workspace_bytes < L.total)
-    return fail(VAMP_ENOSPC, "%s: workspace %ld < %ld bytes", __func__, (long) workspace_bytes, (long) L.total);
-  if (reinterpret_cast<uintptr_t>(workspace) & 7)
+  if (int e = workspace_fits(__func__, workspace, workspace_bytes, rgb_params(d, &q, workspace))) return e;
+  if (!aligned(workspace, 8))
     return fail(VAMP_ENOSPC, "%s: the workspace must be 8-byte aligned", __func__);
-  rgb_bind(L, workspace, &q);
   q.x0 = pred; q.y0 = target; q.loss = loss; q.terms = terms; q.vals = vals;
   hipStream_t st = static_cast<hipStream_t>(stream);
   for (int s = 0; s < kRgbScales; ++s) {
@@ -425,12 +406,9 @@ int vamp_rgb_loss_backward(const VampRgbLossDesc* d, const float* pred, const fl
   if (!pred || !target || !grad_loss || !grad_pred)
     return fail(VAMP_ENOSPC, "%s: an input or output pointer is NULL", __func__);
   RgbParams q{};
-  const RgbLayout L = rgb_params(d, &q);
-  if (!workspace || workspace_bytes < L.total)
-    return fail(VAMP_ENOSPC, "%s: workspace %ld < %ld bytes", __func__, (long) workspace_bytes, (long) L.total);
-  if (reinterpret_cast<uintptr_t>(workspace) & 7)
+  if (int e = workspace_fits(__func__, workspace, workspace_bytes, rgb_params(d, &q, workspace))) return e;
+  if (!aligned(workspace, 8))
     return fail(VAMP_ENOSPC, "%s: the workspace must be 8-byte aligned", __func__);
-  rgb_bind(L, workspace, &q);
   q.x0 = pred; q.y0 = target; q.grad_loss = grad_loss; q.grad = grad_pred;
   hipStream_t st = static_cast<hipStream_t>(stream);
   for (int s = kRgbScales - 1; s >= 0; --s) {

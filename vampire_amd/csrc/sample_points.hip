@@ -317,43 +317,16 @@ sample_points_heavy_kernel(SampleParams P, const T* __restrict__ vol, const floa
 // ---------------------------------------------------------------------------
 // host side
 // ---------------------------------------------------------------------------
-struct PtsWs {
-  int *cnt, *off, *bsum, *boff, *aux, *heavy, *key, *rank;
-  float4 *F, *R;
-  float *G, *beta_part;
-  size_t bytes;
-};
-
-static PtsWs pts_ws(const VampSampleDesc* d, long n, void* scratch) {
-  const long ncell = cell_count_padded(d->B, d->Z, d->Y, d->X);
-  const long ntile = ncell / kScanTile;
-  const size_t pts = (size_t) d->B * n;
-  const size_t voxels = (size_t) d->B * d->Z * d->Y * d->X;
-  const int CP = (d->C + 3) / 4 * 4;
-  char* p = static_cast<char*>(scratch);
-  PtsWs w;
-  w.cnt = reinterpret_cast<int*>(p); p += align_up((size_t) (ncell + kScanPad) * sizeof(int), 256);   // + the scan's ticket word
-  w.off = reinterpret_cast<int*>(p); p += align_up((size_t) ncell * sizeof(int), 256);
-  w.bsum = reinterpret_cast<int*>(p); p += align_up((size_t) ntile * sizeof(int), 256);
-  w.boff = reinterpret_cast<int*>(p); p += align_up((size_t) ntile * sizeof(int), 256);
-  w.aux = reinterpret_cast<int*>(p); p += align_up((size_t) (ntile + 4) * sizeof(int), 256);
-  w.heavy = reinterpret_cast<int*>(p); p += align_up(voxels * sizeof(int), 256);
-  w.key = reinterpret_cast<int*>(p); p += align_up(pts * sizeof(int), 256);
-  w.rank = reinterpret_cast<int*>(p); p += align_up(pts * sizeof(int), 256);
-  w.F = reinterpret_cast<float4*>(p); p += align_up(pts * sizeof(float4), 256);
-  w.R = reinterpret_cast<float4*>(p); p += align_up(pts * sizeof(float4), 256);
-  w.G = reinterpret_cast<float*>(p); p += align_up(pts * CP * sizeof(float), 256);
-  const size_t nblk = (size_t) ((d->X + PVPB - 1) / PVPB) * d->Y * d->Z * d->B;
-  w.beta_part = reinterpret_cast<float*>(p); p += align_up(nblk * sizeof(float), 256);
-  w.bytes = (size_t) (p - static_cast<char*>(scratch));
-  return w;
+static PointWs pts_ws(const VampSampleDesc* d, long n, void* workspace) {
+  const size_t nblk = (size_t) ((d->X + PVPB - 1) / PVPB) * d->Y * d->Z * d->B;     // one partial per gather workgroup
+  return point_ws(d->B, d->Z, d->Y, d->X, (size_t) d->B * n, (d->C + 3) / 4 * 4, nblk, workspace);
 }
 
 template <typename T>
 static int backward_t(const VampSampleDesc* d, const SampleParams& P, const void* volume, const float* beta,
                       const float* points, long n, const float* grad_out, float* grad_volume,
                       float* grad_beta, void* workspace, hipStream_t s) {
-  const PtsWs w = pts_ws(d, n, workspace);
+  const PointWs w = pts_ws(d, n, workspace);
   const long ncell = cell_count_padded(d->B, d->Z, d->Y, d->X);
   const long ntile = ncell / kScanTile;
   const long ncell_b = (long) (d->Z + 1) * (d->Y + 1) * (d->X + 1);
@@ -446,8 +419,7 @@ int vamp_sample_points_backward(const VampSampleDesc* d, const void* volume, con
   VAMP_REQUIRE(!d->activation || d->density_mode == VAMP_DENSITY_SIGMOID || (beta && grad_beta),
                "beta / grad_beta is NULL");
   const size_t need = vamp_sample_points_workspace_bytes(d, points_per_sample);
-  if (!workspace || workspace_bytes < need)
-    return fail(VAMP_ENOSPC, "%s: workspace %ld < %ld bytes", __func__, (long) workspace_bytes, (long) need);
+  if (int e = workspace_fits(__func__, workspace, workspace_bytes, need)) return e;
   const SampleParams P = to_params(d, (int) points_per_sample);
   hipStream_t s = static_cast<hipStream_t>(stream);
   if (d->in_dtype == VAMP_F32)

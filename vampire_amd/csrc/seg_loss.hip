@@ -78,11 +78,6 @@ struct SegParams {
   float w_ce, w_lv;
 };
 
-struct SegLayout {
-  size_t key[2], pay[2], hist, tilefg, rowcnt, cepart, lvpart, total;   // workspace byte offsets
-  size_t ug, kept;                                                      // kept: header at 0
-};
-
 __device__ __forceinline__ long seg_label(const void* l, int dt, long i) {
   if (dt == VAMP_I64) return static_cast<const int64_t*>(l)[i];
   if (dt == VAMP_I32) return static_cast<const int32_t*>(l)[i];
@@ -420,7 +415,7 @@ __global__ void __launch_bounds__(kSegBlock) seg_bwd_kernel(SegParams p) {
 // ---------------------------------------------------------------------------------------------------------
 // host side
 // ---------------------------------------------------------------------------------------------------------
-static_assert(sizeof(VampSegLossDesc) == 40, "VampSegLossDesc layout (vampire_amd/_capi.py mirrors it)");
+static_assert(sizeof(VampSegLossDesc) == 40, "VampSegLossDesc layout: part of the ABI (the binding reads it from include/vampire_hip.h)");
 
 int seg_validate(const VampSegLossDesc* d) {
   VAMP_REQUIRE(d, "desc is NULL");
@@ -436,46 +431,36 @@ int seg_validate(const VampSegLossDesc* d) {
   return VAMP_OK;
 }
 
-SegLayout seg_params(const VampSegLossDesc* d, SegParams* q) {
+void seg_params(const VampSegLossDesc* d, SegParams* q) {
   q->P = d->B * d->S; q->S = d->S; q->C = d->C;
   q->T = (int) ((q->P + kSegTile - 1) / kSegTile);
   q->nrow = (int) ((q->P + kSegBlock - 1) / kSegBlock);
   q->layout = d->layout; q->label_dtype = d->label_dtype;
   q->w_ce = d->w_ce; q->w_lv = d->w_lv;
-  const size_t rec = (size_t) q->C * q->P, tiles = (size_t) q->C * q->T;
-  SegLayout L;
-  size_t off = 0;
-  for (int j = 0; j < 2; ++j) {
-    L.key[j] = off; off = align_up(off + rec * sizeof(uint32_t), 256);
-    L.pay[j] = off; off = align_up(off + rec * sizeof(uint32_t), 256);
-  }
-  L.hist = off;   off = align_up(off + tiles * kSegRadix * sizeof(int), 256);
-  L.tilefg = off; off = align_up(off + tiles * sizeof(int), 256);
-  L.rowcnt = off; off = align_up(off + (size_t) q->nrow * sizeof(int), 256);
-  L.cepart = off; off = align_up(off + (size_t) q->nrow * sizeof(double), 256);
-  L.lvpart = off; off = align_up(off + tiles * sizeof(double), 256);
-  L.total = off;
-  L.ug = align_up(kSegHdrInts * sizeof(int), 256);
-  L.kept = align_up(L.ug + rec * sizeof(float), 256);
-  return L;
 }
 
-void seg_bind(const SegLayout& L, void* ws, void* kept, SegParams* q) {
-  char* b = static_cast<char*>(ws);
-  if (b) {
-    for (int j = 0; j < 2; ++j) {
-      q->key[j] = reinterpret_cast<uint32_t*>(b + L.key[j]);
-      q->pay[j] = reinterpret_cast<uint32_t*>(b + L.pay[j]);
-    }
-    q->hist = reinterpret_cast<int*>(b + L.hist);
-    q->tilefg = reinterpret_cast<int*>(b + L.tilefg);
-    q->rowcnt = reinterpret_cast<int*>(b + L.rowcnt);
-    q->cepart = reinterpret_cast<double*>(b + L.cepart);
-    q->lvpart = reinterpret_cast<double*>(b + L.lvpart);
+// The two buffers of seg_params' shapes, each with its own carve (NULL: only the size, which is returned, is of use):
+// the forward's workspace ...
+size_t seg_workspace(SegParams* q, void* workspace) {
+  const size_t rec = (size_t) q->C * q->P, tiles = (size_t) q->C * q->T;
+  Carve c(workspace);
+  for (int j = 0; j < 2; ++j) {
+    q->key[j] = c.take<uint32_t>(rec);
+    q->pay[j] = c.take<uint32_t>(rec);
   }
-  char* k = static_cast<char*>(kept);
-  q->hdr = reinterpret_cast<int*>(k);
-  q->ug = reinterpret_cast<float*>(k + L.ug);
+  q->hist = c.take<int>(tiles * kSegRadix);
+  q->tilefg = c.take<int>(tiles);
+  q->rowcnt = c.take<int>((size_t) q->nrow);
+  q->cepart = c.take<double>((size_t) q->nrow);
+  q->lvpart = c.take<double>(tiles);
+  return c.off;
+}
+// ... and what the forward keeps for the backward: the header at offset 0, the gradient rows behind it
+size_t seg_kept(SegParams* q, void* kept) {
+  Carve c(kept);
+  q->hdr = c.take<int>(kSegHdrInts);
+  q->ug = c.take<float>((size_t) q->C * q->P);
+  return c.off;
 }
 
 }  // namespace
@@ -488,13 +473,15 @@ extern "C" {
 size_t vamp_seg_loss_workspace_bytes(const VampSegLossDesc* d) {
   if (seg_validate(d)) return 0;
   SegParams q{};
-  return seg_params(d, &q).total;
+  seg_params(d, &q);
+  return seg_workspace(&q, nullptr);
 }
 
 size_t vamp_seg_loss_kept_bytes(const VampSegLossDesc* d) {
   if (seg_validate(d)) return 0;
   SegParams q{};
-  return seg_params(d, &q).kept;
+  seg_params(d, &q);
+  return seg_kept(&q, nullptr);
 }
 
 int vamp_seg_loss_forward(const VampSegLossDesc* d, const float* logits, const void* labels, const uint8_t* mask,
@@ -504,14 +491,13 @@ int vamp_seg_loss_forward(const VampSegLossDesc* d, const float* logits, const v
   if (!logits || !labels || !loss || !terms || !counts)
     return fail(VAMP_ENOSPC, "%s: an input or output pointer is NULL", __func__);
   SegParams q{};
-  const SegLayout L = seg_params(d, &q);
-  if (!kept || kept_bytes < L.kept)
-    return fail(VAMP_ENOSPC, "%s: kept %ld < %ld bytes", __func__, (long) kept_bytes, (long) L.kept);
-  if (!workspace || workspace_bytes < L.total)
-    return fail(VAMP_ENOSPC, "%s: workspace %ld < %ld bytes", __func__, (long) workspace_bytes, (long) L.total);
-  if ((reinterpret_cast<uintptr_t>(workspace) | reinterpret_cast<uintptr_t>(kept)) & 7)
+  seg_params(d, &q);
+  const size_t need = seg_workspace(&q, workspace), keep = seg_kept(&q, kept);
+  if (!kept || kept_bytes < keep)
+    return fail(VAMP_ENOSPC, "%s: kept %ld < %ld bytes", __func__, (long) kept_bytes, (long) keep);
+  if (int e = workspace_fits(__func__, workspace, workspace_bytes, need)) return e;
+  if (!aligned(workspace, 8) || !aligned(kept, 8))
     return fail(VAMP_ENOSPC, "%s: the workspace and the kept buffer must be 8-byte aligned", __func__);
-  seg_bind(L, workspace, kept, &q);
   q.logits = logits; q.labels = labels; q.mask = mask;
   q.loss = loss; q.terms = terms; q.counts = counts; q.sorted_err = sorted_err; q.perm = perm;
   hipStream_t st = static_cast<hipStream_t>(stream);
@@ -538,12 +524,12 @@ int vamp_seg_loss_backward(const VampSegLossDesc* d, const float* logits, const 
   if (!logits || !labels || !grad_loss || !grad_logits)
     return fail(VAMP_ENOSPC, "%s: an input or output pointer is NULL", __func__);
   SegParams q{};
-  const SegLayout L = seg_params(d, &q);
-  if (!kept || kept_bytes < L.kept)
-    return fail(VAMP_ENOSPC, "%s: kept %ld < %ld bytes", __func__, (long) kept_bytes, (long) L.kept);
-  if (reinterpret_cast<uintptr_t>(kept) & 7)
+  seg_params(d, &q);
+  const size_t keep = seg_kept(&q, const_cast<void*>(kept));
+  if (!kept || kept_bytes < keep)
+    return fail(VAMP_ENOSPC, "%s: kept %ld < %ld bytes", __func__, (long) kept_bytes, (long) keep);
+  if (!aligned(kept, 8))
     return fail(VAMP_ENOSPC, "%s: the kept buffer must be 8-byte aligned", __func__);
-  seg_bind(L, nullptr, const_cast<void*>(kept), &q);
   q.logits = logits; q.labels = labels; q.mask = mask; q.grad_loss = grad_loss; q.grad = grad_logits;
   hipStream_t st = static_cast<hipStream_t>(stream);
   VAMP_TIMED(kProfAux, st, (seg_bwd_kernel<<<q.nrow, kSegBlock, 0, st>>>(q)));

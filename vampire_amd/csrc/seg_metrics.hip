@@ -234,8 +234,6 @@ int conf_validate(const VampConfDesc* d) {
   return VAMP_OK;
 }
 
-bool aligned(const void* p, uintptr_t a) { return (reinterpret_cast<uintptr_t>(p) & (a - 1)) == 0; }
-
 template <typename PT, typename TT>
 void conf_launch(int mode, unsigned grid, const ConfParams& q, const void* pred, const void* tgt, const uint8_t* mask,
                  uint32_t* slabs, hipStream_t s) {
@@ -279,19 +277,19 @@ struct LsWs {
 LsWs ls_ws(long P, long R, void* ws) {
   LsWs w;
   w.ncell = (R + 1 + kScanTile - 1) / kScanTile * kScanTile;
-  const long ntile = w.ncell / kScanTile;
-  char* p = static_cast<char*>(ws);
-  auto take = [&](size_t n) { char* r = p; p += align_up(n, 256); return r; };
-  // counters, the scan's ticket and pad, then the count of points with an index out of range: one zero fill
-  w.cnt = reinterpret_cast<int*>(take((w.ncell + kScanPad + 1) * sizeof(int)));
-  w.bad = w.cnt + w.ncell + kScanPad;
-  w.off = reinterpret_cast<int*>(take(w.ncell * sizeof(int)));
-  w.bsum = reinterpret_cast<int*>(take(ntile * sizeof(int)));
-  w.boff = reinterpret_cast<int*>(take(ntile * sizeof(int)));
-  w.aux = reinterpret_cast<int*>(take((ntile + 4) * sizeof(int)));
-  w.ids = reinterpret_cast<int*>(take(std::max(P, 1L) * sizeof(int)));
-  w.sorted = reinterpret_cast<int*>(take(std::max(P, 1L) * sizeof(int)));
-  w.bytes = (size_t) (p - static_cast<char*>(ws));
+  const size_t ncell = (size_t) w.ncell, ntile = ncell / kScanTile;
+  Carve c(ws);
+  // counters, the scan's ticket and pad, then the count of points with an index out of range: one zero fill (the one
+  // word more than take_scan's counters is why the five regions are taken here)
+  w.cnt = c.take<int>(ncell + kScanPad + 1);
+  w.bad = w.cnt + ncell + kScanPad;
+  w.off = c.take<int>(ncell);
+  w.bsum = c.take<int>(ntile);
+  w.boff = c.take<int>(ntile);
+  w.aux = c.take<int>(ntile + 4);
+  w.ids = c.take<int>((size_t) std::max(P, 1L));
+  w.sorted = c.take<int>((size_t) std::max(P, 1L));
+  w.bytes = c.off;
   return w;
 }
 
@@ -402,8 +400,7 @@ int vamp_confusion_update(const VampConfDesc* d, const void* pred, const void* t
   if (n == 0) return VAMP_OK;
   VAMP_REQUIRE(pred && target, "pred / target is NULL");
   const size_t need = vamp_confusion_workspace_bytes(d);
-  if (!workspace || workspace_bytes < need)
-    return fail(VAMP_ENOSPC, "%s: workspace %ld < %ld bytes", __func__, (long) workspace_bytes, (long) need);
+  if (int e = workspace_fits(__func__, workspace, workspace_bytes, need)) return e;
   const size_t tsize = d->target_dtype == VAMP_I64 ? 8 : (d->target_dtype == VAMP_I32 ? 4 : 1);
   int mode = kRows;
   if (!is_int_pred(d->pred_dtype) && d->layout == VAMP_SEG_PLANES) {
@@ -438,8 +435,7 @@ int vamp_lidarseg_predict(int64_t P, int32_t K, int32_t dtype, int32_t lo, int32
   VAMP_REQUIRE(P == 0 || (pts_logits && ref_index), "pts_logits / ref_index is NULL");
   VAMP_REQUIRE(num_ref == 0 || labels, "labels is NULL");
   const LsWs w = ls_ws(P, num_ref, workspace);
-  if (!workspace || workspace_bytes < w.bytes)
-    return fail(VAMP_ENOSPC, "%s: workspace %ld < %ld bytes", __func__, (long) workspace_bytes, (long) w.bytes);
+  if (int e = workspace_fits(__func__, workspace, workspace_bytes, w.bytes)) return e;
   hipStream_t s = static_cast<hipStream_t>(stream);
   const int np = (int) P, R = (int) num_ref;
   if (int e = launch_zero(w.cnt, (size_t) (w.ncell + kScanPad + 1) * sizeof(int), s)) return e;

@@ -141,17 +141,11 @@ PoolWs pool_ws(const VampPoolDesc* d, void* ws) {
   PoolWs w;
   const long cells = (long) d->B * d->ny * d->nx;
   w.ncell = (cells + 1 + kScanTile - 1) / kScanTile * kScanTile;
-  const long ntile = w.ncell / kScanTile;
-  char* p = static_cast<char*>(ws);
-  auto take = [&](size_t n) { char* r = p; p += align_up(n, 256); return r; };
-  w.cnt = reinterpret_cast<int*>(take((w.ncell + kScanPad) * sizeof(int)));
-  w.off = reinterpret_cast<int*>(take(w.ncell * sizeof(int)));
-  w.bsum = reinterpret_cast<int*>(take(ntile * sizeof(int)));
-  w.boff = reinterpret_cast<int*>(take(ntile * sizeof(int)));
-  w.aux = reinterpret_cast<int*>(take((ntile + 4) * sizeof(int)));
-  w.rank = reinterpret_cast<int*>(take((size_t) d->B * d->P * sizeof(int)));
-  w.ids = reinterpret_cast<int*>(take((size_t) d->B * d->P * sizeof(int)));
-  w.bytes = (size_t) (p - static_cast<char*>(ws));
+  Carve c(ws);
+  take_scan(c, (size_t) w.ncell, w.cnt, w.off, w.bsum, w.boff, w.aux);
+  w.rank = c.take<int>((size_t) d->B * d->P);
+  w.ids = c.take<int>((size_t) d->B * d->P);
+  w.bytes = c.off;
   return w;
 }
 
@@ -182,8 +176,7 @@ int vamp_voxel_pooling_forward(const VampPoolDesc* d, const int32_t* geom_xyz, c
   if (int e = pool_validate(d)) return e;
   VAMP_REQUIRE(geom_xyz && feat && out, "NULL tensor");
   const PoolWs w = pool_ws(d, workspace);
-  if (!workspace || workspace_bytes < w.bytes)
-    return fail(VAMP_ENOSPC, "%s: workspace %ld < %ld bytes", __func__, (long) workspace_bytes, (long) w.bytes);
+  if (int e = workspace_fits(__func__, workspace, workspace_bytes, w.bytes)) return e;
   hipStream_t s = static_cast<hipStream_t>(stream);
   const PoolParams q{d->B, d->C, d->nx, d->ny, d->nz, d->P};
   const long npts = (long) d->B * d->P, cells = (long) d->B * d->ny * d->nx;
