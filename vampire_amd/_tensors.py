@@ -105,23 +105,91 @@ def _scalar(t: torch.Tensor, name):
     return t.reshape(1).float().contiguous()
 
 
-def _pad_samples(*lists):
-    """Per-sample lists of tensors [n_b, ...] (the lists agreeing on every n_b) -> one padded [B, M, ...] tensor per
-    list, zero-filled behind each sample's rows, and the int32 counts [B] on the samples' device.  The counts come
-    from the shapes, one scalar fill per sample: nothing is read back from the device and nothing is copied to it."""
+def need_device(name, *tensors):
+    """Raises unless every tensor is on a device; None is skipped, lists and tuples are walked."""
+    for t in tensors:
+        if isinstance(t, (list, tuple)):
+            need_device(name, *t)
+        elif t is not None and not t.is_cuda:
+            raise _capi.VampireHipError(f"{name} needs device tensors (no CPU fallback)")
+
+
+def as_mask(mask):
+    """A mask as the kernels read it: bool (anything else is taken as `!= 0`), contiguous; None passes through."""
+    return None if mask is None else (mask if mask.dtype == torch.bool else mask != 0).contiguous()
+
+
+def as_labels(labels, dtypes):
+    """Integer labels as the kernels read them: one of `dtypes` (anything else is cast to int64), contiguous."""
+    return (labels if labels.dtype in dtypes else labels.long()).contiguous()
+
+
+def check_out(x, shape, dtype, dev, name, *, align=0, terse=False):
+    """`x`, a caller's output buffer, when it is a contiguous `shape` `dtype` tensor on `dev` (on an `align`-byte
+    boundary), else ValueError.  `name` opens the text; the buffer is described as "name: (shape, dtype, device)", or,
+    `terse`, as "name shape dtype" -- the sites' own wordings."""
+    shape = tuple(shape)
+    if x is None or tuple(x.shape) != shape or x.dtype != dtype or not x.is_contiguous() or x.device != dev \
+            or (align and x.data_ptr() % align):
+        if terse:
+            got = f" {tuple(x.shape)} {x.dtype}"
+        else:
+            got = f": {None if x is None else (tuple(x.shape), x.dtype, x.device)}"
+        how = f"contiguous, {align}-byte aligned" if align else "contiguous"
+        raise ValueError(f"{name}{got} is not a {how} {shape} {dtype} on {dev}")
+    return x
+
+
+def refused(vamp, name, exc=ValueError):
+    """The exception for a descriptor the library refused: `name` and the library's own sentence."""
+    return exc(f"{name}: {vamp.vamp_last_error().decode('utf-8', 'replace')}")
+
+
+def workspace_bytes(size_fn, desc, refuse):
+    """size_fn(desc); where that is 0 -- a descriptor the library refuses -- `refuse()` first, the entry point's own
+    call without operands, which raises with the entry point's name and the library's reason."""
+    nbytes = size_fn(desc)
+    if nbytes == 0:
+        refuse()
+    return nbytes
+
+
+def list_dtype(tensors, name, dtype=None, what=None):
+    """A per-sample list's dtype check: all `dtype` (spelt `what` in the text), or, without one, all alike."""
+    got = {t.dtype for t in tensors}
+    if dtype is None and len(got) != 1:
+        raise TypeError(f"{name} must share one dtype, got {sorted(str(g) for g in got)}")
+    if dtype is not None and got - {dtype}:
+        raise TypeError(f"{name} must be {what}, got {sorted(str(g) for g in got)}")
+
+
+def pad_lists(lists, fills=None, counts=False):
+    """Per-sample lists of tensors [n_b, ...] (the lists agreeing on every n_b; a None list stays None) -> one padded
+    [B, M, ...] tensor per list, `fills[i]` (0) behind each sample's rows, and with `counts` the int32 counts [B] on
+    the samples' device.  The counts come from the shapes, one scalar fill per sample: nothing is read back from the
+    device and nothing is copied to it."""
     pad = torch.nn.utils.rnn.pad_sequence
-    dev = lists[0][0].device
-    counts = torch.stack([torch.full((), p.shape[0], dtype=torch.int32, device=dev) for p in lists[0]])
-    return tuple(pad(list(l), batch_first=True) for l in lists) + (counts,)
+    out = tuple(None if l is None else pad(list(l), batch_first=True, padding_value=f)
+                for l, f in zip(lists, fills or [0] * len(lists)))
+    if counts:
+        dev = lists[0][0].device
+        out += (torch.stack([torch.full((), p.shape[0], dtype=torch.int32, device=dev) for p in lists[0]]),)
+    return out
+
+
+def _pad_samples(*lists):
+    """pad_lists with zero fill and the counts: (one padded tensor per list ..., counts)."""
+    return pad_lists(lists, counts=True)
 
 
 _scratch = {}
 
 
-def _workspace(key, device, nbytes):
-    """The uint8 scratch buffer kept under `key`: reused while it is large enough, otherwise allocated anew with
-    max(nbytes, 256) bytes (uninitialised).  The key is the caller's: whatever it holds besides the device -- the
-    stream, the operator, the size -- decides who shares a buffer and whether one is ever regrown."""
+def scratch(kind, device, nbytes, *, per_size=False):
+    """The uninitialised uint8 workspace of the operator `kind` on `device`'s current stream, max(nbytes, 256) bytes
+    when it is made.  Regrown when a call needs more (the old buffer goes back to the allocator), or, `per_size`, one
+    buffer per size that is never regrown: DESIGN 8.26 says what either means under graph capture."""
+    key = (kind, device, torch.cuda.current_stream(device).cuda_stream) + ((nbytes,) if per_size else ())
     ws = _scratch.get(key)
     if ws is None or ws.numel() < nbytes:
         ws = _scratch[key] = torch.empty(max(nbytes, 256), dtype=torch.uint8, device=device)

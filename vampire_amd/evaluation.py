@@ -6,18 +6,14 @@ import dataclasses
 import torch
 
 from . import _capi
-from ._tensors import DTYPE_CODES, FLOAT_DTYPES, _accept, _dtype_code, _logit_layout, _stream, _workspace
+from ._tensors import (DTYPE_CODES, FLOAT_DTYPES, _accept, _dtype_code, _logit_layout, _stream, as_labels, as_mask,
+                       check_out, list_dtype, need_device, pad_lists, refused, scratch, workspace_bytes)
 
 
 # ===========================================================================
 # segmentation metrics (base_exp.py:370-382, :634-663, :835-840)
 # ===========================================================================
 _TARGET_DTYPES = (torch.int64, torch.int32, torch.uint8)
-
-
-def _scratch(kind, device, nbytes):
-    """This operator's workspace on the device's current stream (regrown when a call needs more)."""
-    return _workspace((kind, device, torch.cuda.current_stream(device).cuda_stream), device, nbytes)
 
 
 def confusion_update(confmat, invalid, logits_or_preds, target, mask=None, *, class_window=None, ignore_index=None):
@@ -28,8 +24,7 @@ def confusion_update(confmat, invalid, logits_or_preds, target, mask=None, *, cl
     target / mask shaped like logits[..., 0] (or like the integer predictions); target int64 | int32 | uint8.
     One HIP pass on the current stream; no host synchronisation, capturable in a graph."""
     x = logits_or_preds
-    if not (confmat.is_cuda and invalid.is_cuda and x.is_cuda and target.is_cuda and (mask is None or mask.is_cuda)):
-        raise _capi.VampireHipError("confusion_update needs device tensors (no CPU fallback)")
+    need_device("confusion_update", confmat, invalid, x, target, mask)
     if confmat.dtype != torch.int64 or confmat.dim() != 2 or confmat.shape[0] != confmat.shape[1] \
             or not confmat.is_contiguous():
         raise ValueError("confmat must be a contiguous int64 [Kc, Kc] tensor")
@@ -40,9 +35,7 @@ def confusion_update(confmat, invalid, logits_or_preds, target, mask=None, *, cl
     if integer:
         if tuple(x.shape) != tuple(target.shape):
             raise ValueError(f"predictions {tuple(x.shape)} and target {tuple(target.shape)} differ in shape")
-        if x.dtype not in (torch.int64, torch.int32):
-            x = x.long()
-        layout, B, S, x, K = _capi.VAMP_SEG_ROWS, 1, x.numel(), x.contiguous(), 1
+        layout, B, S, x, K = _capi.VAMP_SEG_ROWS, 1, x.numel(), as_labels(x, (torch.int64, torch.int32)), 1
         lo, hi = 0, 1
     else:
         x = _accept(x)
@@ -51,21 +44,17 @@ def confusion_update(confmat, invalid, logits_or_preds, target, mask=None, *, cl
         K = x.shape[-1]
         lo, hi = (0, K) if class_window is None else (int(class_window[0]), int(class_window[1]))
         layout, B, S, x = _logit_layout(x)
-    if target.dtype not in _TARGET_DTYPES:
-        target = target.long()
-    target = target.contiguous()
-    if mask is not None:
-        if tuple(mask.shape) != tuple(target.shape):
-            raise ValueError(f"mask {tuple(mask.shape)} does not match target {tuple(target.shape)}")
-        mask = (mask if mask.dtype == torch.bool else mask != 0).contiguous()
+    target = as_labels(target, _TARGET_DTYPES)
+    if mask is not None and tuple(mask.shape) != tuple(target.shape):
+        raise ValueError(f"mask {tuple(mask.shape)} does not match target {tuple(target.shape)}")
+    mask = as_mask(mask)
     d = _capi.VampConfDesc(B, S, K, layout, DTYPE_CODES[x.dtype], DTYPE_CODES[target.dtype], Kc, lo, hi,
                            0 if ignore_index is None else int(ignore_index), 0 if ignore_index is None else 1, 0)
     vamp = _capi.checked()
-    nbytes = vamp.vamp_confusion_workspace_bytes(d)
-    if nbytes == 0:
-        vamp.vamp_confusion_update(d, None, None, None, None, None, None, 0, None)
+    nbytes = workspace_bytes(vamp.vamp_confusion_workspace_bytes, d,
+                             lambda: vamp.vamp_confusion_update(d, None, None, None, None, None, None, 0, None))
     with torch.cuda.device(x.device):
-        ws = _scratch("confusion", x.device, nbytes)
+        ws = scratch("confusion", x.device, nbytes)
         vamp.vamp_confusion_update(d, x, target, mask, confmat, invalid, ws, ws.numel(), _stream())
     return confmat
 
@@ -76,8 +65,7 @@ def lidarseg_predict(pts_logits, ref_index, num_ref, class_window):
     point order (bit-exact against a sequential CPU index_add_).  Returns (labels int64 [num_ref], invalid
     int64 0-dim: the number of points whose index lies outside [0, num_ref)).  HIP kernels on the current
     stream; no host synchronisation."""
-    if not (pts_logits.is_cuda and ref_index.is_cuda):
-        raise _capi.VampireHipError("lidarseg_predict needs device tensors (no CPU fallback)")
+    need_device("lidarseg_predict", pts_logits, ref_index)
     if pts_logits.dim() != 2 or ref_index.dim() != 1 or ref_index.shape[0] != pts_logits.shape[0]:
         raise ValueError(f"expected pts_logits [P, K] and ref_index [P], got {tuple(pts_logits.shape)} "
                          f"and {tuple(ref_index.shape)}")
@@ -90,7 +78,7 @@ def lidarseg_predict(pts_logits, ref_index, num_ref, class_window):
     invalid = torch.empty((), dtype=torch.int64, device=x.device)
     vamp = _capi.checked()
     with torch.cuda.device(x.device):
-        ws = _scratch("lidarseg", x.device, vamp.vamp_lidarseg_workspace_bytes(P, num_ref))
+        ws = scratch("lidarseg", x.device, vamp.vamp_lidarseg_workspace_bytes(P, num_ref))
         vamp.vamp_lidarseg_predict(P, K, _dtype_code(x), lo, hi, x, idx, num_ref, labels, invalid, ws, ws.numel(),
                                   _stream())
     return labels, invalid
@@ -151,8 +139,7 @@ def det_postprocess(task_preds, coder_cfg, test_cfg, num_classes, norm_bbox, out
     if has_vel:
         keys.append("vel")
     tensors = [[h[k] for k in keys] for h in heads]
-    if not all(x.is_cuda for ts in tensors for x in ts):
-        raise _capi.VampireHipError("det_postprocess needs device tensors (no CPU fallback)")
+    need_device("det_postprocess", tensors)
     dtype = heads[0]["heatmap"].dtype
     if dtype not in FLOAT_DTYPES or any(x.dtype != dtype for ts in tensors for x in ts):
         raise TypeError(f"head tensors must all be fp32, bf16 or fp16 of one dtype, got {dtype}")
@@ -198,9 +185,8 @@ def det_postprocess(task_preds, coder_cfg, test_cfg, num_classes, norm_bbox, out
     for t in range(T):
         d.min_radius[t], d.thresh_scale[t], d.nms_thr[t] = mr[t], ts[t], nt[t]
     vamp = _capi.checked()
-    nbytes = vamp.vamp_det_workspace_bytes(d)
-    if nbytes == 0:
-        vamp.vamp_det_postprocess(d, None, None, None, None, None, None, 0, None)
+    nbytes = workspace_bytes(vamp.vamp_det_workspace_bytes, d,
+                             lambda: vamp.vamp_det_postprocess(d, None, None, None, None, None, None, 0, None))
     P, cs = d.post_max_size, 9 if has_vel else 7
     dev = heads[0]["heatmap"].device
     if out is None:
@@ -212,13 +198,10 @@ def det_postprocess(task_preds, coder_cfg, test_cfg, num_classes, norm_bbox, out
         want = [(out.boxes, (B, T * P, cs), torch.float32), (out.scores, (B, T * P), dtype),
                 (out.labels, (B, T * P), torch.int32), (out.counts, (B,), torch.int32)]
         for x, shape, dt in want:
-            if tuple(x.shape) != shape or x.dtype != dt or not x.is_contiguous() or x.device != dev:
-                raise ValueError(f"out buffer {tuple(x.shape)} {x.dtype} is not a contiguous {shape} {dt} on {dev}")
-    table = (_capi.VampDetTask * T)()
-    for t, ts_ in enumerate(tensors):
-        table[t] = _capi.VampDetTask(*[x.data_ptr() for x in ts_], *([] if has_vel else [None]))
+            check_out(x, shape, dt, dev, "out buffer", terse=True)
+    table = _det_task_table(T, [ts_ + [None] * (6 - len(keys)) for ts_ in tensors])
     with torch.cuda.device(dev):
-        ws = _scratch("det", dev, nbytes)
+        ws = scratch("det", dev, nbytes)
         vamp.vamp_det_postprocess(d, table, out.boxes, out.scores, out.labels, out.counts, ws, ws.numel(), _stream())
     return out
 
@@ -261,14 +244,10 @@ def _pack_targets_input(boxes, labels):
         return boxes, labels
     if len(boxes) != len(labels) or len(boxes) == 0:
         raise ValueError(f"{len(boxes)} box tensors and {len(labels)} label tensors (one per sample, at least one)")
-    if any(b.dtype != torch.float32 for b in boxes):
-        raise TypeError(f"boxes must be fp32, got {sorted({str(b.dtype) for b in boxes})}")
-    if len({l.dtype for l in labels}) != 1:
-        raise TypeError(f"labels must share one dtype, got {sorted({str(l.dtype) for l in labels})}")
-    if not all(b.is_cuda for b in boxes) or not all(l.is_cuda for l in labels):
-        raise _capi.VampireHipError("det_targets needs device tensors (no CPU fallback)")
-    pad = torch.nn.utils.rnn.pad_sequence
-    return pad(list(boxes), batch_first=True), pad(list(labels), batch_first=True, padding_value=-1)
+    list_dtype(boxes, "boxes", torch.float32, "fp32")
+    list_dtype(labels, "labels")
+    need_device("det_targets", list(boxes), list(labels))
+    return pad_lists((boxes, labels), (0, -1))
 
 
 def det_targets(boxes, labels, tasks_ncls, train_cfg, norm_bbox, out=None):
@@ -279,13 +258,14 @@ def det_targets(boxes, labels, tasks_ncls, train_cfg, norm_bbox, out=None):
     padding) or packed [B, M, 7 | 9] and [B, M] tensors whose padding rows carry label -1.  tasks_ncls: classes
     per task, labels flat over the tasks.  out: a DetTargets of preallocated buffers to write (graph capture).
     Returns a DetTargets; as_tuple() is get_targets's (heatmaps, anno_boxes, inds, masks)."""
+    packed = isinstance(boxes, torch.Tensor)
     boxes, labels = _pack_targets_input(boxes, labels)
     if boxes.dtype != torch.float32:
         raise TypeError(f"boxes must be fp32, got {boxes.dtype}")
     if labels.dtype not in _LABEL_DTYPES:
         raise TypeError(f"labels must be int32 or int64, got {labels.dtype}")
-    if not (boxes.is_cuda and labels.is_cuda):
-        raise _capi.VampireHipError("det_targets needs device tensors (no CPU fallback)")
+    if packed:                             # (per-sample lists were checked before they were padded)
+        need_device("det_targets", boxes, labels)
     if boxes.dim() != 3 or boxes.shape[2] not in (7, 9) or tuple(labels.shape) != tuple(boxes.shape[:2]):
         raise ValueError(f"expected boxes [B, M, 7 | 9] and labels [B, M], got {tuple(boxes.shape)} "
                          f"and {tuple(labels.shape)}")
@@ -310,9 +290,8 @@ def det_targets(boxes, labels, tasks_ncls, train_cfg, norm_bbox, out=None):
     d.voxel_size[0], d.voxel_size[1] = float(vs[0]), float(vs[1])
     d.pc_range[0], d.pc_range[1] = float(pc[0]), float(pc[1])
     vamp = _capi.checked()
-    nbytes = vamp.vamp_det_targets_workspace_bytes(d)
-    if nbytes == 0:
-        vamp.vamp_det_targets(d, None, None, None, None, None, None, None, 0, None)
+    nbytes = workspace_bytes(vamp.vamp_det_targets_workspace_bytes, d,
+                             lambda: vamp.vamp_det_targets(d, None, None, None, None, None, None, None, 0, None))
     dev = boxes.device
     boxes, labels = boxes.contiguous(), labels.contiguous()
     if out is None:
@@ -324,12 +303,11 @@ def det_targets(boxes, labels, tasks_ncls, train_cfg, norm_bbox, out=None):
         want = [(out.heat, (B * sum(ncls) * fh * fw,), torch.float32), (out.anno, (T, B, max_objs, code), torch.float32),
                 (out.inds, (T, B, max_objs), torch.int64), (out.masks, (T, B, max_objs), torch.uint8)]
         for x, shape, dt in want:
-            if tuple(x.shape) != shape or x.dtype != dt or not x.is_contiguous() or x.device != dev:
-                raise ValueError(f"out buffer {tuple(x.shape)} {x.dtype} is not a contiguous {shape} {dt} on {dev}")
+            check_out(x, shape, dt, dev, "out buffer", terse=True)
         if tuple(out.ncls) != ncls or (out.fh, out.fw) != (fh, fw):
             raise ValueError(f"out was made for classes {out.ncls} on {out.fh} x {out.fw}, not {ncls} on {fh} x {fw}")
     with torch.cuda.device(dev):
-        ws = _scratch("det_targets", dev, nbytes)
+        ws = scratch("det_targets", dev, nbytes)
         vamp.vamp_det_targets(d, boxes, labels, out.heat, out.anno, out.inds, out.masks, ws, ws.numel(), _stream())
     return out
 
@@ -349,8 +327,7 @@ def _pack_loss_targets(targets, dev):
     heat, anno, inds, masks = targets
     if not (len(heat) == len(anno) == len(inds) == len(masks)) or len(heat) == 0:
         raise ValueError("targets must be a DetTargets or (heatmaps, anno_boxes, inds, masks) lists of one length")
-    if not all(x.is_cuda for lst in (heat, anno, inds, masks) for x in lst):
-        raise _capi.VampireHipError("det_loss needs device tensors (no CPU fallback)")
+    need_device("det_loss", list(heat), list(anno), list(inds), list(masks))
     if any(h.dim() != 4 for h in heat):
         raise ValueError("every target heatmap must be [B, ncls, H, W]")
     return DetTargets(torch.cat([h.reshape(-1) for h in heat]), torch.stack(list(anno)), torch.stack(list(inds)),
@@ -364,6 +341,11 @@ def _det_task_table(T, rows):
     return table
 
 
+def _loss_table(tensors, nk, T):
+    """The task table of a flat list of `nk` tensors per task: the predictions, or their gradients (None: not wanted)."""
+    return _det_task_table(T, [list(tensors[t * nk:(t + 1) * nk]) + [None] * (6 - nk) for t in range(T)])
+
+
 class _DetLoss(torch.autograd.Function):
     """loss, terms = apply(desc, nk, heat, anno, inds, masks, counts, *predictions): the predictions task by task
     in the order of _LOSS_KEYS (nk = 6 with vel, 5 without)."""
@@ -372,13 +354,12 @@ class _DetLoss(torch.autograd.Function):
     def forward(ctx, desc, nk, heat, anno, inds, masks, counts, *preds):
         dev = heat.device
         T = desc.T
-        rows = [list(preds[t * nk:(t + 1) * nk]) + [None] * (6 - nk) for t in range(T)]
         loss = torch.empty((), dtype=torch.float32, device=dev)
         terms = torch.empty(T, 2, dtype=torch.float32, device=dev)
         vamp = _capi.checked()
         with torch.cuda.device(dev):
-            ws = _scratch("det_loss", dev, vamp.vamp_det_loss_workspace_bytes(desc))
-            vamp.vamp_det_loss_forward(desc, _det_task_table(T, rows), heat, anno, inds, masks, counts, loss, terms, ws,
+            ws = scratch("det_loss", dev, vamp.vamp_det_loss_workspace_bytes(desc))
+            vamp.vamp_det_loss_forward(desc, _loss_table(preds, nk, T), heat, anno, inds, masks, counts, loss, terms, ws,
                                        ws.numel(), _stream())
         ctx.desc, ctx.nk = desc, nk
         ctx.save_for_backward(heat, anno, inds, masks, counts, *preds)
@@ -393,14 +374,12 @@ class _DetLoss(torch.autograd.Function):
         want = ctx.needs_input_grad[7:]
         grads = [torch.empty_like(x) if w else None for x, w in zip(preds, want)]
         if any(want):
-            rows = [list(preds[t * nk:(t + 1) * nk]) + [None] * (6 - nk) for t in range(T)]
-            grows = [grads[t * nk:(t + 1) * nk] + [None] * (6 - nk) for t in range(T)]
             gl = grad_loss.to(torch.float32).contiguous()
             vamp = _capi.checked()
             with torch.cuda.device(dev):
-                ws = _scratch("det_loss", dev, vamp.vamp_det_loss_workspace_bytes(desc))
-                vamp.vamp_det_loss_backward(desc, _det_task_table(T, rows), heat, anno, inds, masks, counts, gl,
-                                            _det_task_table(T, grows), ws, ws.numel(), _stream())
+                ws = scratch("det_loss", dev, vamp.vamp_det_loss_workspace_bytes(desc))
+                vamp.vamp_det_loss_backward(desc, _loss_table(preds, nk, T), heat, anno, inds, masks, counts, gl,
+                                            _loss_table(grads, nk, T), ws, ws.numel(), _stream())
         return (None,) * 7 + tuple(grads)
 
 
@@ -438,12 +417,10 @@ def det_loss(task_preds, targets, code_weights, loss_bbox_weight=0.25, *, counts
     tensors = [[h[k] for k in keys] for h in heads]
     if any(x.dtype != torch.float32 for ts in tensors for x in ts):
         raise TypeError(f"head tensors must be fp32, got {sorted({str(x.dtype) for ts in tensors for x in ts})}")
-    if not all(x.is_cuda for ts in tensors for x in ts):
-        raise _capi.VampireHipError("det_loss needs device tensors (no CPU fallback)")
+    need_device("det_loss", tensors)
     dev = tensors[0][0].device
     tg = _pack_loss_targets(targets, dev)
-    if not (tg.heat.is_cuda and tg.anno.is_cuda and tg.inds.is_cuda and tg.masks.is_cuda):
-        raise _capi.VampireHipError("det_loss needs device tensors (no CPU fallback)")
+    need_device("det_loss", tg.heat, tg.anno, tg.inds, tg.masks)
     if (tg.heat.dtype, tg.anno.dtype, tg.inds.dtype, tg.masks.dtype) != (torch.float32, torch.float32, torch.int64,
                                                                          torch.uint8):
         raise TypeError("targets must be fp32 heat and anno, int64 inds, uint8 masks")
@@ -478,7 +455,7 @@ def det_loss(task_preds, targets, code_weights, loss_bbox_weight=0.25, *, counts
     d.loss_bbox_weight = float(loss_bbox_weight)
     vamp = _capi.checked()
     if vamp.vamp_det_loss_workspace_bytes(d) == 0:
-        raise _capi.VampireHipError(f"det_loss: {vamp.vamp_last_error().decode('utf-8', 'replace')}")
+        raise refused(vamp, "det_loss", _capi.VampireHipError)
     heat, anno, inds, masks = tg.heat.contiguous(), tg.anno.contiguous(), tg.inds.contiguous(), tg.masks.contiguous()
     if counts is None:
         counts = det_loss_counts(d, heat, masks)
@@ -486,8 +463,7 @@ def det_loss(task_preds, targets, code_weights, loss_bbox_weight=0.25, *, counts
             from .multitask import reduce_mean
             counts = reduce_mean(counts)
     else:
-        if not counts.is_cuda:
-            raise _capi.VampireHipError("det_loss needs device tensors (no CPU fallback)")
+        need_device("det_loss", counts)
         if counts.dtype != torch.float32:
             raise TypeError(f"counts must be fp32, got {counts.dtype}")
         if tuple(counts.shape) != (T, 2):
@@ -558,7 +534,7 @@ class DetEvalState:
         self.dist_ths = tuple(float(t) for t in self.dist_ths)
         nbytes = _capi.checked().vamp_det_eval_record_bytes(self.desc(1, 0, 9, torch.float32, torch.int64, False))
         if nbytes == 0:
-            raise ValueError(f"det_eval: {_capi.checked().vamp_last_error().decode('utf-8', 'replace')}")
+            raise refused(_capi.checked(), "det_eval")
         self.records = torch.zeros(nbytes // 32, 8, dtype=torch.int32, device=device)
         self.state = torch.zeros(_capi.VAMP_DET_EVAL_STATE_WORDS, dtype=torch.int64, device=device)
         return self
@@ -598,14 +574,11 @@ def _pack_gt(gt_boxes, gt_labels, gt_attrs):
     lists = [gt_boxes, gt_labels] + ([] if gt_attrs is None else [gt_attrs])
     if any(len(l) != len(gt_boxes) for l in lists) or len(gt_boxes) == 0:
         raise ValueError(f"{[len(l) for l in lists]} tensors per list (one per sample, at least one)")
-    if not all(x.is_cuda for l in lists for x in l):
-        raise _capi.VampireHipError("det_eval_update needs device tensors (no CPU fallback)")
-    if any(b.dtype != torch.float32 for b in gt_boxes):
-        raise TypeError(f"gt_boxes must be fp32, got {sorted({str(b.dtype) for b in gt_boxes})}")
-    if len({l.dtype for l in gt_labels}) != 1:
-        raise TypeError(f"gt_labels must share one dtype, got {sorted({str(l.dtype) for l in gt_labels})}")
-    if gt_attrs is not None and any(a.dtype != torch.int8 for a in gt_attrs):
-        raise TypeError(f"gt_attrs must be int8, got {sorted({str(a.dtype) for a in gt_attrs})}")
+    need_device("det_eval_update", [list(l) for l in lists])
+    list_dtype(gt_boxes, "gt_boxes", torch.float32, "fp32")
+    list_dtype(gt_labels, "gt_labels")
+    if gt_attrs is not None:
+        list_dtype(gt_attrs, "gt_attrs", torch.int8, "int8")
     for s, (bx, lb) in enumerate(zip(gt_boxes, gt_labels)):
         if bx.dim() != 2 or lb.dim() != 1 or bx.shape[0] != lb.shape[0] \
                 or (gt_attrs is not None and tuple(gt_attrs[s].shape) != tuple(lb.shape)):
@@ -613,9 +586,7 @@ def _pack_gt(gt_boxes, gt_labels, gt_attrs):
                              f"{tuple(bx.shape)} and {tuple(lb.shape)}")
     if len({b.shape[1] for b in gt_boxes}) != 1:
         raise ValueError(f"gt_boxes differ in width: {sorted({b.shape[1] for b in gt_boxes})}")
-    pad = torch.nn.utils.rnn.pad_sequence
-    return (pad(list(gt_boxes), batch_first=True), pad(list(gt_labels), batch_first=True, padding_value=-1),
-            None if gt_attrs is None else pad(list(gt_attrs), batch_first=True, padding_value=-1))
+    return pad_lists((gt_boxes, gt_labels, gt_attrs), (0, -1, -1))
 
 
 def det_eval_update(state, det, gt_boxes, gt_labels, gt_attrs=None):
@@ -630,11 +601,9 @@ def det_eval_update(state, det, gt_boxes, gt_labels, gt_attrs=None):
     `state.state` (see DetEvalState); nothing is raised for them here."""
     if not isinstance(det, DetResult):
         raise TypeError(f"det must be a DetResult, got {type(det).__name__}")
-    if not all(x.is_cuda for x in (det.boxes, det.scores, det.labels, det.counts)):
-        raise _capi.VampireHipError("det_eval_update needs device tensors (no CPU fallback)")
+    need_device("det_eval_update", det.boxes, det.scores, det.labels, det.counts)
     gtb, gtl, gta = _pack_gt(gt_boxes, gt_labels, gt_attrs)
-    if not (gtb.is_cuda and gtl.is_cuda and (gta is None or gta.is_cuda)):
-        raise _capi.VampireHipError("det_eval_update needs device tensors (no CPU fallback)")
+    need_device("det_eval_update", gtb, gtl, gta)
     if det.boxes.dtype != torch.float32 or det.labels.dtype != torch.int32 or det.counts.dtype != torch.int32:
         raise TypeError("det must hold fp32 boxes, int32 labels and int32 counts")
     if det.scores.dtype not in FLOAT_DTYPES:
@@ -661,7 +630,7 @@ def det_eval_update(state, det, gt_boxes, gt_labels, gt_attrs=None):
     d = state.desc(B, G, cols, det.scores.dtype, gtl.dtype, gta is not None)
     vamp = _capi.checked()
     if not vamp.vamp_det_eval_supported(d):
-        raise ValueError(f"det_eval_update: {vamp.vamp_last_error().decode('utf-8', 'replace')}")
+        raise refused(vamp, "det_eval_update")
     dev = det.boxes.device
     with torch.cuda.device(dev):
         vamp.vamp_det_eval_update(d, det.boxes.contiguous(), det.scores.contiguous(), det.labels.contiguous(),

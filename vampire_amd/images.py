@@ -17,17 +17,12 @@ import numpy as np
 import torch
 
 from . import _capi
-from ._tensors import DTYPE_CODES, _stream, _workspace
+from ._tensors import DTYPE_CODES, _stream, check_out, need_device, scratch, workspace_bytes
 
 IMG_MEAN, IMG_STD = (123.675, 116.28, 103.53), (58.395, 57.12, 57.375)      # the reference's img_conf
 _TABLES = ("col_first", "col_count", "col_taps", "row_first", "row_count", "row_taps", "consts")
 _K, _TW, _TH = _capi.VAMP_IMG_MAX_TAPS, _capi.VAMP_IMG_TILE_W, _capi.VAMP_IMG_TILE_H
 _OUT_DTYPES = (torch.float32, torch.bfloat16)
-
-
-def _need_device(*tensors):
-    if not all(t.is_cuda for t in tensors):
-        raise _capi.VampireHipError("camera_images needs device tensors (no CPU fallback)")
 
 
 def _cubic(x):
@@ -207,14 +202,6 @@ def plan_camera_images(augs, raw_dim, final_dim, resize_min=None):
     return ImagePlan(B=B, N=N, raw_dim=(raw_h, raw_w), final_dim=(H, W), foot_w=foot_w, foot_h=foot_h, **t)
 
 
-def _check_out(x, shape, dtype, dev, name):
-    if tuple(x.shape) != tuple(shape) or x.dtype != dtype or not x.is_contiguous() or x.device != dev \
-            or x.data_ptr() % 16:
-        raise ValueError(f"{name}: {(tuple(x.shape), x.dtype, x.device)} is not a contiguous, 16-byte aligned "
-                         f"{tuple(shape)} {dtype} on {dev}")
-    return x
-
-
 def camera_images(raw, plan, *, mean=IMG_MEAN, std=IMG_STD, to_rgb=True, dtype=torch.float32, out=None, out_u8=None):
     """Resize, crop, flip, rotate and normalise raw camera frames as the reference loader does (vamp_camera_images),
     in two launches on the current stream, without a host synchronisation; capturable in a graph, and a replay
@@ -228,10 +215,10 @@ def camera_images(raw, plan, *, mean=IMG_MEAN, std=IMG_STD, to_rgb=True, dtype=t
     tensor to write again, to get the transformed uint8 image (rule 4's) as well.
     Returns the normalised [B, N, 3, H, W] tensor, or (normalised | None, uint8 image) when out_u8 is asked for.
     The parity of the normalisation with OpenCV is unpinned (module docstring)."""
-    _need_device(raw)
+    need_device("camera_images", raw)
     if plan.device_tables is None:
         raise ValueError("the plan's tables are on the host: call plan.to(device) first")
-    _need_device(plan._flat)
+    need_device("camera_images", plan._flat)
     if raw.dtype != torch.uint8:
         raise TypeError(f"raw must be uint8, got {raw.dtype}")
     raw_h, raw_w = plan.raw_dim
@@ -270,18 +257,17 @@ def camera_images(raw, plan, *, mean=IMG_MEAN, std=IMG_STD, to_rgb=True, dtype=t
         d.std_inv[c] = float(np.float32(1.0 / np.float64(std[c])))
 
     vamp = _capi.checked()
-    nbytes = vamp.vamp_camera_images_workspace_bytes(d)
-    if nbytes == 0:                        # a descriptor the library refuses: let it say why
-        vamp.vamp_camera_images(d, *([None] * 11), 0, None)
+    nbytes = workspace_bytes(vamp.vamp_camera_images_workspace_bytes, d,
+                             lambda: vamp.vamp_camera_images(d, *([None] * 11), 0, None))
     if dtype is not None:
         out = (torch.empty(B, N, 3, H, W, dtype=dtype, device=dev) if out is None
-               else _check_out(out, (B, N, 3, H, W), dtype, dev, "out"))
+               else check_out(out, (B, N, 3, H, W), dtype, dev, "out", align=16))
     if want_u8:
         out_u8 = (torch.empty(B, N, H, W, 3, dtype=torch.uint8, device=dev) if out_u8 is True
-                  else _check_out(out_u8, (B, N, H, W, 3), torch.uint8, dev, "out_u8"))
+                  else check_out(out_u8, (B, N, H, W, 3), torch.uint8, dev, "out_u8", align=16))
     t = plan.device_tables
     with torch.cuda.device(dev):
-        ws = _workspace(("camera_images", dev, torch.cuda.current_stream(dev).cuda_stream), dev, nbytes)
+        ws = scratch("camera_images", dev, nbytes)
         vamp.vamp_camera_images(d, raw, *(t[k] for k in _TABLES), out, out_u8 if want_u8 else None, ws, ws.numel(),
                                 _stream())
     return (out, out_u8) if want_u8 else out

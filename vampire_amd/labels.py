@@ -10,7 +10,8 @@ import numpy as np
 import torch
 
 from . import _capi
-from ._tensors import DTYPE_CODES, _aligned, _pad_samples, _stream, _workspace
+from ._tensors import (DTYPE_CODES, _aligned, _pad_samples, _stream, check_out, list_dtype, need_device, scratch,
+                       workspace_bytes)
 
 _LABEL_DTYPES = (torch.uint8, torch.int64)
 
@@ -27,11 +28,6 @@ class LidarLabels:
     bev_mask: torch.Tensor = None      # [B, 1, 1, ny, nx] bool
 
 
-def _need_device(*tensors):
-    if not all(t.is_cuda for t in tensors):
-        raise _capi.VampireHipError("lidar_labels needs device tensors (no CPU fallback)")
-
-
 def _pack_points(points, labels, counts):
     """Per-sample lists ([n_b, 3 | 4] points, [n_b] labels) -> padded [B, M, 3 | 4], [B, M] and int32 counts [B] on
     the device.  The counts come from the shapes, one scalar fill per sample: nothing is read back from the device
@@ -44,11 +40,9 @@ def _pack_points(points, labels, counts):
         raise ValueError("counts belongs to packed points: per-sample lists carry their own lengths")
     if len(points) != len(labels) or len(points) == 0:
         raise ValueError(f"{len(points)} point tensors and {len(labels)} label tensors (one per sample, at least one)")
-    _need_device(*points, *labels)
-    if any(p.dtype != torch.float32 for p in points):
-        raise TypeError(f"points must be fp32, got {sorted({str(p.dtype) for p in points})}")
-    if len({l.dtype for l in labels}) != 1:
-        raise TypeError(f"labels must share one dtype, got {sorted({str(l.dtype) for l in labels})}")
+    need_device("lidar_labels", list(points), list(labels))
+    list_dtype(points, "points", torch.float32, "fp32")
+    list_dtype(labels, "labels")
     if any(p.dim() != 2 or l.dim() != 1 or p.shape[0] != l.shape[0] for p, l in zip(points, labels)):
         raise ValueError("every sample needs points [n, 3 | 4] and labels [n]")
     if len({p.shape[1] for p in points}) != 1:
@@ -70,13 +64,6 @@ def _bev_grid(bev):
     return ny, nx, xb[0] - size / 2.0, yb[0] - size / 2.0, size, float(zb[0]), float(zb[1])
 
 
-def _check_out(x, shape, dtype, dev, name):
-    if x is None or tuple(x.shape) != tuple(shape) or x.dtype != dtype or not x.is_contiguous() or x.device != dev:
-        got = None if x is None else (tuple(x.shape), x.dtype, x.device)
-        raise ValueError(f"out.{name}: {got} is not a contiguous {tuple(shape)} {dtype} on {dev}")
-    return x
-
-
 def lidar_labels(points, labels, *, lidar2cam=None, intrins=None, aug=None, final_dim=None, raw_dim=None, stride=1,
                  bev=None, counts=None, out=None):
     """Rasterise lidar points into camera depth / segmentation labels and BEV segmentation / height / mask labels
@@ -95,7 +82,7 @@ def lidar_labels(points, labels, *, lidar2cam=None, intrins=None, aug=None, fina
     out: a LidarLabels of an earlier call with the same shapes, whose buffers are written again.
     Returns a LidarLabels."""
     points, labels, counts = _pack_points(points, labels, counts)
-    _need_device(points, labels)
+    need_device("lidar_labels", points, labels)
     if points.dtype != torch.float32:
         raise TypeError(f"points must be fp32, got {points.dtype}")
     if labels.dtype not in _LABEL_DTYPES:
@@ -106,7 +93,7 @@ def lidar_labels(points, labels, *, lidar2cam=None, intrins=None, aug=None, fina
     B, M, cols = points.shape
     dev = points.device
     if counts is not None:
-        _need_device(counts)
+        need_device("lidar_labels", counts)
         if counts.dtype != torch.int32 or tuple(counts.shape) != (B,):
             raise ValueError(f"counts must be int32 [{B}], got {counts.dtype} {tuple(counts.shape)}")
         counts = _aligned(counts)
@@ -124,7 +111,7 @@ def lidar_labels(points, labels, *, lidar2cam=None, intrins=None, aug=None, fina
     if cam:
         if intrins is None or aug is None or final_dim is None or raw_dim is None:
             raise ValueError("the camera part needs lidar2cam, intrins, aug, final_dim and raw_dim")
-        _need_device(lidar2cam, intrins, aug)
+        need_device("lidar_labels", lidar2cam, intrins, aug)
         if lidar2cam.dim() != 4 or tuple(lidar2cam.shape[2:]) != (4, 4) or lidar2cam.shape[0] != B:
             raise ValueError(f"lidar2cam: expected [{B}, N, 4, 4], got {tuple(lidar2cam.shape)}")
         N = lidar2cam.shape[1]
@@ -149,9 +136,8 @@ def lidar_labels(points, labels, *, lidar2cam=None, intrins=None, aug=None, fina
         d.ny, d.nx, d.origin_x, d.origin_y, d.size, d.z_lo, d.z_hi = ny, nx, ox, oy, size, z_lo, z_hi
 
     vamp = _capi.checked()
-    nbytes = vamp.vamp_lidar_labels_workspace_bytes(d)
-    if nbytes == 0:                        # a descriptor the library refuses: let it say why
-        vamp.vamp_lidar_labels(d, *([None] * 13), 0, None)
+    nbytes = workspace_bytes(vamp.vamp_lidar_labels_workspace_bytes, d,
+                             lambda: vamp.vamp_lidar_labels(d, *([None] * 13), 0, None))
     points, labels = _aligned(points), _aligned(labels)
     if out is None:
         out = LidarLabels()
@@ -165,18 +151,18 @@ def lidar_labels(points, labels, *, lidar2cam=None, intrins=None, aug=None, fina
             out.bev_mask = torch.empty(B, 1, 1, ny, nx, dtype=torch.uint8, device=dev).view(torch.bool)
     else:
         if cam:
-            _check_out(out.cam_depth, (B, N, h, w), torch.float32, dev, "cam_depth")
-            _check_out(out.cam_seg, (B, N, h, w), torch.int64, dev, "cam_seg")
-            _check_out(out.cam_fg, (B, N, h, w), torch.bool, dev, "cam_fg")
+            check_out(out.cam_depth, (B, N, h, w), torch.float32, dev, "out.cam_depth")
+            check_out(out.cam_seg, (B, N, h, w), torch.int64, dev, "out.cam_seg")
+            check_out(out.cam_fg, (B, N, h, w), torch.bool, dev, "out.cam_fg")
         if do_bev:
-            _check_out(out.bev_seg, (B, 1, 1, ny, nx), torch.int64, dev, "bev_seg")
-            _check_out(out.bev_height, (B, 1, 1, ny, nx), torch.float32, dev, "bev_height")
-            _check_out(out.bev_mask, (B, 1, 1, ny, nx), torch.bool, dev, "bev_mask")
+            check_out(out.bev_seg, (B, 1, 1, ny, nx), torch.int64, dev, "out.bev_seg")
+            check_out(out.bev_height, (B, 1, 1, ny, nx), torch.float32, dev, "out.bev_height")
+            check_out(out.bev_mask, (B, 1, 1, ny, nx), torch.bool, dev, "out.bev_mask")
     u8 = lambda t: t.view(torch.uint8)
     cam_args = (out.cam_depth, out.cam_seg, u8(out.cam_fg)) if cam else (None, None, None)
     bev_args = (out.bev_seg, out.bev_height, u8(out.bev_mask)) if do_bev else (None, None, None)
     with torch.cuda.device(dev):
-        ws = _workspace(("lidar_labels", dev, torch.cuda.current_stream(dev).cuda_stream), dev, nbytes)
+        ws = scratch("lidar_labels", dev, nbytes)
         vamp.vamp_lidar_labels(d, points, labels, counts, lidar2cam if cam else None, intrins if cam else None,
                                aug if cam else None, *cam_args, *bev_args, ws, ws.numel(), _stream())
     return out

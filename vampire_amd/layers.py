@@ -9,7 +9,7 @@ import torch
 
 from . import _capi
 from ._tensors import (DTYPE_CODES, FLOAT_DTYPES, HALF_DTYPES, _accept, _aligned, _chk, _dtype_code, _stream,
-                       _workspace)
+                       need_device, scratch)
 
 
 # ===========================================================================
@@ -26,8 +26,7 @@ def voxel_pooling(geom_xyz, input_features, voxel_num):
 class _VoxelPoolingFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, geom, feat, voxel_num):
-        if not (geom.is_cuda and feat.is_cuda):
-            raise _capi.VampireHipError("voxel_pooling needs device tensors (no CPU fallback)")
+        need_device("voxel_pooling", geom, feat)
         vamp = _capi.checked()
         B, C_ = feat.shape[0], feat.shape[-1]
         P = feat[0].numel() // C_
@@ -36,8 +35,7 @@ class _VoxelPoolingFn(torch.autograd.Function):
         geom = _aligned(_chk(geom.reshape(B, P, 3).to(torch.int32), (B, P, 3), "geom_xyz"))
         d = _capi.VampPoolDesc(B, C_, P, voxel_num[0], voxel_num[1], voxel_num[2], _dtype_code(feat))
         out = torch.empty(B, voxel_num[1], voxel_num[0], C_, dtype=torch.float32, device=feat.device)
-        nbytes = vamp.vamp_voxel_pooling_workspace_bytes(d)
-        ws = _workspace((feat.device, torch.cuda.current_stream().cuda_stream), feat.device, nbytes)
+        ws = scratch("voxel_pooling", feat.device, vamp.vamp_voxel_pooling_workspace_bytes(d))
         with torch.cuda.device(feat.device):
             vamp.vamp_voxel_pooling_forward(d, geom, feat, out, ws, ws.numel(), _stream())
         ctx.desc = d
@@ -95,8 +93,7 @@ class _UpsampleTrilinearFn(torch.autograd.Function):
         if gin.numel() and g.numel():
             vamp = ctx.vamp
             nbytes = vamp.vamp_upsample_trilinear_workspace_bytes(*ctx.dims[1:4])
-            # (one table per stream and size: the size in the key, so a buffer is never regrown)
-            ws = _workspace((g.device, torch.cuda.current_stream().cuda_stream, nbytes), g.device, nbytes)
+            ws = scratch("upsample_trilinear", g.device, nbytes, per_size=True)         # (one table per size)
             vamp.vamp_upsample_trilinear_backward_ex(*ctx.dims, ctx.code, g, gin, ws, ws.numel(), _stream())
         else:
             gin.zero_()
@@ -142,8 +139,7 @@ class _Resize2dFn(torch.autograd.Function):
         if len(size) != 2:
             raise ValueError("size must be (H, W)")
         for t in tensors:
-            if not t.is_cuda:
-                raise _capi.VampireHipError("resize_bilinear2d needs device tensors (no CPU fallback)")
+            need_device("resize_bilinear2d", t)
             if t.dim() < 2 or t.dtype != torch.float32 or t.numel() == 0:
                 raise ValueError("expected non-empty fp32 tensors [..., H, W]")
             if tuple(t.shape[-2:]) != tuple(tensors[0].shape[-2:]) or t.device != tensors[0].device:
@@ -170,7 +166,7 @@ class _Resize2dFn(torch.autograd.Function):
         if pairs:
             dev = pairs[0][0].device
             nbytes = vamp.vamp_resize2d_workspace_bytes(*ctx.dims)
-            ws = _workspace((dev, torch.cuda.current_stream().cuda_stream, "resize2d"), dev, nbytes) if nbytes else None
+            ws = scratch("resize2d", dev, nbytes) if nbytes else None
             with torch.cuda.device(dev):
                 vamp.vamp_resize2d_backward(_resize2d_desc(*ctx.dims, pairs), ws, nbytes, _stream())
         return (None,) + tuple(gins)
@@ -321,7 +317,7 @@ def _conv_backward(k, d, code, x, w, gz, need_x, need_w):
     if need_w:
         gw = torch.empty(w.shape, dtype=torch.float32, device=w.device)
         nbytes = getattr(vamp, k.workspace_bytes)(d)
-        ws = _workspace((gz.device, torch.cuda.current_stream().cuda_stream, k.tag, nbytes), gz.device, nbytes)
+        ws = scratch(k.tag, gz.device, nbytes, per_size=True)
         getattr(vamp, k.stem + "backward_weight")(d, *code, x, gz, gw, ws, ws.numel(), _stream())
         if k.half:
             gw = gw.to(w.dtype)                   # the gradient of the 16-bit copy autocast made of the fp32 parameter
@@ -522,7 +518,7 @@ class _Conv3dEpiFn(torch.autograd.Function):
                 ws, nbytes = None, 0
                 if want_bias:
                     nbytes = vamp.vamp_conv3d_epilogue_workspace_bytes(d, k.stride)
-                    ws = _workspace((dev, torch.cuda.current_stream().cuda_stream, "convepi", nbytes), dev, nbytes)
+                    ws = scratch("convepi", dev, nbytes, per_size=True)
                 vamp.vamp_conv3d_epilogue_backward(d, k.stride, DTYPE_CODES[x.dtype], epi, gz, ws, nbytes, _stream())
             gx, gw = _conv_backward(k, d, ctx.code, x, w, gz, need[2], need[3])
         extra = []

@@ -6,7 +6,7 @@ import ctypes as C
 import torch
 
 from . import _capi
-from ._tensors import DTYPE_CODES, _logit_layout, _stream
+from ._tensors import DTYPE_CODES, _logit_layout, _stream, as_labels, as_mask, need_device, refused
 
 RGB_MIN_SIDE, RGB_MAX_CHANNELS, RGB_SCALES = 176, 4, 5
 SEG_MIN_CLASSES, SEG_MAX_CLASSES = 2, 32
@@ -69,9 +69,8 @@ def rgb_loss(pred, target, data_range=1.0):
     d = _capi.VampRgbLossDesc(N, C, H, W, float(data_range), 0.01, 0.03)
     vamp = _capi.checked()
     if vamp.vamp_rgb_loss_workspace_bytes(d) == 0:
-        raise ValueError(f"rgb_loss: {vamp.vamp_last_error().decode('utf-8', 'replace')}")
-    if not (pred.is_cuda and target.is_cuda):
-        raise _capi.VampireHipError("rgb_loss needs device tensors (no CPU fallback)")
+        raise refused(vamp, "rgb_loss")
+    need_device("rgb_loss", pred, target)
     loss, terms, vals = _RgbLoss.apply(d, pred.contiguous(), target.contiguous())
     loss.terms, loss.vals = terms, vals
     return loss
@@ -134,20 +133,15 @@ def _seg_inputs(logits, labels, mask, ce_weight, lovasz_weight, name="seg_loss")
         raise ValueError(f"{name}: {C} classes are outside {SEG_MIN_CLASSES} <= C <= {SEG_MAX_CLASSES}")
     if labels.is_floating_point() or labels.requires_grad:
         raise TypeError(f"{name}: labels must be integers, got {labels.dtype}")
-    if not (logits.is_cuda and labels.is_cuda and (mask is None or mask.is_cuda)):
-        raise _capi.VampireHipError(f"{name} needs device tensors (no CPU fallback)")
+    need_device(name, logits, labels, mask)
     if logits.dtype != torch.float32:
         logits = logits.float()                          # (keeps a permuted view's channel-first memory)
     layout, B, S, logits = _logit_layout(logits)
-    if labels.dtype not in _SEG_LABEL_DTYPES:
-        labels = labels.long()
-    labels = labels.contiguous()
-    if mask is not None:
-        mask = (mask if mask.dtype == torch.bool else mask != 0).contiguous()
+    labels, mask = as_labels(labels, _SEG_LABEL_DTYPES), as_mask(mask)
     d = _capi.VampSegLossDesc(B, S, C, layout, DTYPE_CODES[labels.dtype], 0, float(ce_weight), float(lovasz_weight))
     vamp = _capi.checked()
     if vamp.vamp_seg_loss_workspace_bytes(d) == 0:
-        raise ValueError(f"{name}: {vamp.vamp_last_error().decode('utf-8', 'replace')}")
+        raise refused(vamp, name)
     return d, logits, labels, mask
 
 
@@ -238,20 +232,19 @@ def _reg_inputs(terms, name="reg_losses"):
             raise ValueError(f"{name}: term {k}: side {side!r} needs a mask")
         if pred.numel() < 1:
             raise ValueError(f"{name}: term {k}: pred is empty")
-        if not (pred.is_cuda and (const or target.is_cuda) and (mask is None or mask.is_cuda)):
-            raise _capi.VampireHipError(f"{name} needs device tensors (no CPU fallback)")
+        need_device(name, pred, None if const else target, mask)
         if pred.dtype not in (torch.float32, torch.bfloat16):
             pred = pred.float()
         preds.append(pred.contiguous())
         targets.append(None if const else target.detach().to(torch.float32).contiguous())
-        masks.append(None if mask is None else (mask if mask.dtype == torch.bool else mask != 0).contiguous())
+        masks.append(as_mask(mask))
         m = d.terms[k]
         m.n, m.kind, m.side, m.pred_dtype = pred.numel(), _REG_KINDS[kind], _REG_SIDES[side], DTYPE_CODES[pred.dtype]
         m.target_is_const, m.target_value = int(const), float(target) if const else 0.0
     vamp = _capi.checked()
     nbytes = vamp.vamp_reg_loss_workspace_bytes(d)
     if nbytes == 0:
-        raise ValueError(f"{name}: {vamp.vamp_last_error().decode('utf-8', 'replace')}")
+        raise refused(vamp, name)
     return (d, nbytes, targets, masks), preds
 
 

@@ -13,7 +13,7 @@ import torch.distributed as dist
 from torch import nn
 
 from . import _capi
-from ._tensors import DTYPE_CODES, FLOAT_DTYPES, _aligned, _stream, _workspace
+from ._tensors import DTYPE_CODES, FLOAT_DTYPES, _aligned, _stream, scratch
 
 BN_CHUNK = _capi.VAMP_BN_CHUNK        # elements of one channel per workgroup: the split the tests' shapes are built on
 MAX_WORLD = _capi.VAMP_BN_MAX_WORLD
@@ -71,11 +71,6 @@ def _desc(x, act=None, residual=False, training=True, world=1, eps=1e-5, momentu
     return d
 
 
-def _bn_workspace(vamp, d, dev):
-    nbytes = vamp.vamp_bn_workspace_bytes(d)
-    return _workspace(("batch_norm", dev, torch.cuda.current_stream(dev).cuda_stream), dev, nbytes)
-
-
 # =============================================================================================
 # the four steps on plain tensors
 # =============================================================================================
@@ -84,7 +79,7 @@ def bn_partial_stats(x):
     x = _operand(x, "x")
     vamp, d = _capi.checked(), _desc(x)
     row = torch.empty(2 * x.shape[1] + 1, dtype=torch.float64, device=x.device)
-    ws = _bn_workspace(vamp, d, x.device)
+    ws = scratch("batch_norm", x.device, vamp.vamp_bn_workspace_bytes(d))
     vamp.vamp_bn_partial_stats(d, x, row, ws, ws.numel(), _stream())
     return row
 
@@ -138,7 +133,7 @@ def bn_backward_partial(dy, x, y, saved, act=None):
     vamp, d = _capi.checked(), _desc(x, act)
     row = torch.empty(2 * C_, dtype=torch.float64, device=x.device)
     gw, gb = torch.empty(C_, dtype=torch.float32, device=x.device), torch.empty(C_, dtype=torch.float32, device=x.device)
-    ws = _bn_workspace(vamp, d, x.device)
+    ws = scratch("batch_norm", x.device, vamp.vamp_bn_workspace_bytes(d))
     vamp.vamp_bn_backward_partial(d, dy, x, y, _saved(saved, C_), row, gw, gb, ws, ws.numel(), _stream())
     return row, gw, gb
 

@@ -21,7 +21,7 @@ from . import _capi
 from .config import PathConfig
 from . import geometry as G
 from ._tensors import (_accept, _accept_float, _chk, _density_code, _dtype_code, _is_channel_last, _mats, _scalar,
-                       _stream)
+                       _stream, need_device)
 # the operators that take no HotPath live in modules of their own; their public names stay importable from here
 from .layers import (voxel_pooling, upsample_trilinear, conv3d_3x3x3, conv3d_bf16, conv3d_supported,  # noqa: F401
                      conv3d_bf16_supported, conv3d_bf16_stride2, conv3d_bf16_stride2_supported,
@@ -1184,8 +1184,7 @@ class _DensityGateFn(torch.autograd.Function):
 class _GateConvFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, hp: HotPath, vo, vd, weight, bias):
-        if not (vo.is_cuda and vd.is_cuda and weight.is_cuda):
-            raise _capi.VampireHipError("gate_conv1x1 needs device tensors (no CPU fallback)")
+        need_device("gate_conv1x1", vo, vd, weight)
         B, C_, oZ = vo.shape[:3]
         plane = tuple(vo.shape[3:])
         cells = int(math.prod(plane))

@@ -16,7 +16,7 @@ import numpy as np
 import torch
 
 from . import _capi
-from ._tensors import _stream
+from ._tensors import _stream, refused
 
 UPDATE_CHUNK = _capi.VAMP_UPDATE_CHUNK
 KIND_PARAM, KIND_EMA_ONLY = _capi.VAMP_UPDATE_PARAM, _capi.VAMP_UPDATE_EMA_ONLY
@@ -168,7 +168,7 @@ class ParamUpdate:
         vamp = _capi.checked()
         need = vamp.vamp_param_update_workspace_bytes(self.desc)
         if need == 0:
-            raise ValueError(f"ParamUpdate: {vamp.vamp_last_error().decode('utf-8', 'replace')}")
+            raise refused(vamp, "ParamUpdate")
         dev = self.device
         with torch.cuda.device(dev):
             self.exp_avg = torch.zeros(pl.param_state, dtype=torch.float32, device=dev)
