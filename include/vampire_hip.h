@@ -1114,8 +1114,10 @@ int vamp_conv3d_half_s2_backward_weight(const VampConvDesc* d, int32_t dtype, co
  * once, and -- for every segment with a grad_bias -- sums g_z over samples and voxels, in the segment's own precision
  * (the rounded g_z of a compute-type segment; the fp32 products of an fp32-output segment of a 16-bit kind, whose copy
  * in grad_z is rounded for the convolution's backward alone): float64 partials per workgroup in `workspace`, added in
- * a fixed order by a finishing launch, rounded once to fp32; no atomics, bitwise repeatable.  grad_z is the residual's gradient, and the operand of the existing backward_data / backward_weight
- * entry points.  `stride` (1 or 2) and `dtype` name the kind: (1, VAMP_F32), (1, 16-bit), (2, 16-bit).
+ * a fixed order by a finishing launch, rounded once to fp32; no atomics, bitwise repeatable.  grad_z is the residual's
+ * gradient, and the operand of the existing backward_data / backward_weight entry points.  A residual's gradient is its
+ * segment's channels of grad_z as stored: rounded once to the compute type, and for the fp32 residual of an fp32-output
+ * segment of a 16-bit kind those 16-bit values widened, not the fp32 products.  `stride` (1 or 2) and `dtype` name the kind: (1, VAMP_F32), (1, 16-bit), (2, 16-bit).
  *
  * Every entry point refuses, before any launch, with VAMP_EINVAL: a descriptor its kind does not take, a NULL
  * required pointer, nseg outside 1 .. 4, a segment outside [0, cout) or overlapping another, an unknown activation,

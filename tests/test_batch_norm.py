@@ -33,7 +33,9 @@ SHAPES = [(3, 5, 7, 9),            # odd planes: every plane starts off the 16-b
           (2, 4, 3, 4),            # H W = 12: whole vectors in fp32, the small-plane walk in 16 bits
           (2, 3, 64, 100),         # 12800 per channel: four workgroups, the flat walk
           (1, 2, 17, 241),         # CH + 1 per channel: the second workgroup has one element
-          (3, 2, 59, 71)]          # odd planes of 4189 that straddle the splits, four workgroups
+          (3, 2, 59, 71),          # odd planes of 4189 that straddle the splits, four workgroups
+          (1, 257, 17, 241)]       # two chunks per channel AND more channels than the 256 threads of one merge
+                                   # workgroup: the merges' second workgroup, one live thread in it (the c >= C guard)
 assert 2 * 64 * 100 >= 3 * CH and 17 * 241 == CH + 1 and 3 * 59 * 71 >= 3 * CH
 DTYPES = [torch.float32, torch.bfloat16, torch.float16]
 COMBOS = [(None, False), ("relu", False), (None, True), ("relu", True)]
@@ -230,10 +232,8 @@ def test_backward_against_float64_autograd(shape, dtype):
             assert float(hip["gb"][0]) == 0.0 and float(hip["gw"][0]) == 0.0
 
 
-@gpu
-@pytest.mark.parametrize("dtype", DTYPES, ids=lambda d: str(d)[6:])
-def test_evaluation_mode_against_float64_batch_norm(dtype):
-    for shape in [(3, 5, 7, 9), (2, 3, 64, 100)]:
+def _evaluation_mode(shapes, dtype):
+    for shape in shapes:
         for act, res in COMBOS:
             c = make_case(shape, dtype, act, res)
             dev = "cuda"
@@ -248,6 +248,95 @@ def test_evaluation_mode_against_float64_batch_norm(dtype):
                                    c["r"].to(dev) if res else None)
             check(_label(shape, dtype, act, res, "eval y"), y, run(False, dev), run(True, "cpu"), dtype)
             assert torch.equal(rm.cpu(), c["rm"]) and torch.equal(rv.cpu(), c["rv"])
+
+
+@gpu
+@pytest.mark.parametrize("dtype", DTYPES, ids=lambda d: str(d)[6:])
+def test_evaluation_mode_against_float64_batch_norm(dtype):
+    _evaluation_mode([(3, 5, 7, 9), (2, 3, 64, 100)], dtype)
+
+
+@gpu
+@pytest.mark.parametrize("dtype", DTYPES, ids=lambda d: str(d)[6:])
+@pytest.mark.parametrize("shape", SHAPES + [(1, 3, 1, 1)], ids=lambda s: "x".join(map(str, s)))
+def test_evaluation_mode_over_every_shape(shape, dtype):
+    """Every walk of a chunk, one and several chunks per channel, and the one value per channel that evaluation mode
+    accepts and training refuses; the running statistics stay as they were."""
+    _evaluation_mode([shape], dtype)
+
+
+@gpu
+@pytest.mark.parametrize("dtype", DTYPES, ids=lambda d: str(d)[6:])
+@pytest.mark.parametrize("shape", [(3, 5, 7, 9), (1, 2, 17, 241)], ids=lambda s: "x".join(map(str, s)))
+def test_training_without_running_statistics_or_counter(shape, dtype):
+    """update_running = 0 and no batch counter: y and saved have the bits of the call that has them."""
+    for act, res in COMBOS:
+        c, _, _, hip = results(shape, dtype, act, res)
+        y, saved = norm.bn_apply(c["x"].to("cuda"), hip["rows"], c["w"].to("cuda"), c["b"].to("cuda"), EPS, act,
+                                 c["r"].to("cuda") if res else None)
+        assert torch.equal(y, hip["y"]) and torch.equal(saved, hip["saved"]), _label(shape, dtype, act, res, "bits")
+
+
+@gpu
+@pytest.mark.parametrize("dtype", [torch.float32, torch.bfloat16], ids=lambda d: str(d)[6:])
+def test_merge_kernels_write_every_channel_of_their_rows(dtype):
+    """C = 257 with two chunks per channel, into rows and gradients that hold NaN beforehand: the second workgroup of
+    bn_merge_stats_kernel / bn_merge_bwd_kernel writes channel 256, and the rows have the bits of the wrappers' own."""
+    shape, dev = (1, 257, 17, 241), "cuda"
+    c, _, _, hip = results(shape, dtype, "relu", True)
+    x, dy = c["x"].to(dev), c["dy"].to(dev)
+    vamp, nan = _capi.checked(), float("nan")
+    d = norm._desc(x)
+    ws = norm.scratch("batch_norm", x.device, vamp.vamp_bn_workspace_bytes(d))
+    row = torch.full((2 * shape[1] + 1,), nan, dtype=torch.float64, device=dev)
+    vamp.vamp_bn_partial_stats(d, x, row, ws, ws.numel(), norm._stream())
+    assert torch.equal(row, hip["rows"][0]), "the forward's row"
+    brow = torch.full((2 * shape[1],), nan, dtype=torch.float64, device=dev)
+    gw, gb = (torch.full((shape[1],), nan, device=dev) for _ in range(2))
+    vamp.vamp_bn_backward_partial(norm._desc(x, "relu"), dy, x, hip["y"], hip["saved"], brow, gw, gb, ws, ws.numel(),
+                                  norm._stream())
+    for what, got, want in (("row", brow, hip["brow"]), ("grad_weight", gw, hip["gw"]), ("grad_bias", gb, hip["gb"])):
+        assert torch.equal(got, want), f"the backward's {what}"
+
+
+def _poisoned(dtype, act, where):
+    """(2, 4, 7, 9): channel 0 holds one NaN, channel 1 one +inf -- at the channel's first element (the pivot of the
+    statistics' sums) or inside its second plane -- and channels 2 and 3 are clean.  The case and its clean twin."""
+    clean = make_case((2, 4, 7, 9), dtype, act, False)
+    x = clean["x"].clone()
+    n, h, w = (0, 0, 0) if where == "first" else (1, 3, 5)
+    x[n, 0, h, w], x[n, 1, h, w] = float("nan"), float("inf")
+    return dict(clean, x=x), clean
+
+
+@gpu
+@pytest.mark.parametrize("where", ["first", "inner"])
+@pytest.mark.parametrize("act", [None, "relu"], ids=["none", "relu"])
+@pytest.mark.parametrize("dtype", [torch.float32, torch.bfloat16], ids=lambda d: str(d)[6:])
+def test_non_finite_inputs_stay_in_their_channel(dtype, act, where):
+    """The file comment's two claims: "a NaN stays" (through max(M2, 0) and through the ReLU, as torch.relu keeps it)
+    and "a mean of +-inf: inf - inf" (the low word of such a mean is 0, not NaN).  The NaN masks of y, mean and invstd
+    are those of torch's own sequence on the device and of the float64 formula; the clean channels have the bits of
+    the run in which no channel is poisoned."""
+    dev = "cuda"
+    c, clean = _poisoned(dtype, act, where)
+    hip, hip_clean, own = run_hip(c, dev), run_hip(clean, dev), run_torch(c, dev)
+    y64, mean64, invstd64, _ = formula(c["x"].double(), c["w"].double(), c["b"].double(), None, act)
+    for k, ref in (("y", y64), ("mean", mean64), ("invstd", invstd64)):
+        got, tor, want = (t.detach().cpu().isnan() for t in (hip[k], own[k], ref))
+        print(f"(2, 4, 7, 9) {str(dtype)[6:]} act={act} poison={where} {k}: NaN in hip {int(got.sum())}, torch "
+              f"{int(tor.sum())}, float64 {int(want.sum())} of {got.numel()}; mean of the inf channel: hip "
+              f"{float(hip['mean'][1])}, torch {float(own['mean'][1])}, float64 {float(mean64[1])}")
+        assert torch.equal(got, want), f"{k}: NaN mask differs from the float64 formula's"
+        assert torch.equal(got, tor), f"{k}: NaN mask differs from torch's own"
+    assert bool(hip["y"][:, :2].isnan().all()) and not bool(hip["y"][:, 2:].isnan().any())
+    for k in ("y", "y2"):
+        assert torch.equal(hip[k][:, 2:], hip_clean[k][:, 2:]), k
+    for k in ("saved", "saved2"):
+        assert torch.equal(hip[k][:, 2:], hip_clean[k][:, 2:]), k
+    for k in ("rm1", "rv1", "rm2", "rv2"):
+        assert torch.equal(hip[k][2:], hip_clean[k][2:]), k
+    assert torch.equal(hip["rows"][0, 5:], hip_clean["rows"][0, 5:]) and int(hip["nbt"]) == 2
 
 
 # =============================================================================================
@@ -293,6 +382,65 @@ def test_two_ranks_on_one_gpu(shape, dtype):
             assert torch.equal(a[k], bb[k]), (tag, k)
         check(lab(f"{tag} grad_weight"), a["gw"].double() + bb["gw"].double(), own["gw"], ref["gw"])
         check(lab(f"{tag} grad_bias"), a["gb"].double() + bb["gb"].double(), own["gb"], ref["gb"])
+
+
+@gpu
+@pytest.mark.parametrize("dtype", [torch.float32, torch.bfloat16], ids=lambda d: str(d)[6:])
+@pytest.mark.parametrize("shape,sizes", [((64, 3, 2, 3), (1,) * 64),       # the most ranks the contract allows
+                                         ((7, 3, 5, 7), (1, 2, 4)),        # unequal ranks
+                                         ((3, 2, 1, 1), (1, 1, 1))],       # every rank: n = 1 and M2 = 0 exactly
+                         ids=["64-ranks", "ranks-of-1-2-4", "one-element-ranks"])
+def test_many_and_unequal_ranks_on_one_gpu(shape, sizes, dtype):
+    """The rank loops of bn_apply_kernel and bn_bwd_apply_kernel past their second trip, with ranks of unequal size,
+    and with ranks of one element per channel, where Chan's merge does all the work: relu + residual against the
+    float64 oracle of the whole batch, rows in rank order and in one permuted order (every rank sees the same rows,
+    so saved and running statistics are bit-equal on all of them in either order)."""
+    act, res, dev = "relu", True, "cuda"
+    c, ref = make_case(shape, dtype, act, res), oracle(shape, dtype, act, res)
+    own = run_torch(c, dev)
+    world, starts = len(sizes), [sum(sizes[:k]) for k in range(len(sizes))]
+    parts = [slice(s, s + n) for s, n in zip(starts, sizes)]
+    assert starts[-1] + sizes[-1] == shape[0]
+    x, r, dy = c["x"].to(dev), c["r"].to(dev), c["dy"].to(dev)
+    w, b = c["w"].to(dev), c["b"].to(dev)
+
+    def ranks(order):
+        own_rows = [norm.bn_partial_stats(x[h]) for h in parts]
+        if shape[2] * shape[3] == 1:
+            for row in own_rows:                                # one element per channel: n = 1, M2 = 0
+                assert float(row[0]) == 1.0 and bool((row[2::2] == 0).all())
+        rows = torch.stack(own_rows)[order]
+        outs = []
+        for h in parts:
+            rm, rv = c["rm"].to(dev), c["rv"].to(dev)
+            y, saved = norm.bn_apply(x[h], rows, w, b, EPS, act, r[h], rm, rv, MOM)
+            outs.append(dict(y=y, saved=saved, rm=rm, rv=rv))
+        for h, o in zip(parts, outs):
+            o["brow"], o["gw"], o["gb"] = norm.bn_backward_partial(dy[h], x[h], o["y"], o["saved"], act)
+        brows = torch.stack([o["brow"] for o in outs])[order]
+        for h, o in zip(parts, outs):
+            o["dx"], o["gr"] = norm.bn_backward_apply(dy[h], x[h], o["y"], o["saved"], w, brows, rows, act, True)
+        return outs
+
+    lab = functools.partial(_label, shape, dtype, act, res)
+    permuted = [(5 * i + 3) % world for i in range(world)]
+    assert sorted(permuted) == list(range(world)) and permuted != list(range(world))
+    for order, tag in ((list(range(world)), f"{world} ranks"), (permuted, f"{world} ranks, rows permuted")):
+        outs = ranks(order)
+        cat = lambda k: torch.cat([o[k] for o in outs])
+        check(lab(f"{tag} y"), cat("y"), own["y"], ref["y"], dtype)
+        check(lab(f"{tag} dx"), cat("dx"), own["dx"], ref["dx"], dtype)
+        check(lab(f"{tag} grad_residual"), cat("gr"), own["gr"], ref["gr"], dtype)
+        check(lab(f"{tag} mean"), outs[0]["saved"][0], own["mean"], ref["mean"])
+        check(lab(f"{tag} invstd"), outs[0]["saved"][1], own["invstd"], ref["invstd"])
+        check(lab(f"{tag} running_mean"), outs[0]["rm"], own["rm1"], ref["rm1"])
+        check(lab(f"{tag} running_var"), outs[0]["rv"], own["rv1"], ref["rv1"])
+        for o in outs[1:]:
+            for k in ("saved", "rm", "rv"):
+                assert torch.equal(outs[0][k], o[k]), (tag, k)
+        total = lambda k: torch.stack([o[k].double() for o in outs]).sum(0)
+        check(lab(f"{tag} grad_weight"), total("gw"), own["gw"], ref["gw"])
+        check(lab(f"{tag} grad_bias"), total("gb"), own["gb"], ref["gb"])
 
 
 # =============================================================================================

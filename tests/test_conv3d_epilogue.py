@@ -8,10 +8,16 @@ torch's adds, F.leaky_relu); the half kinds to the project's 16-bit bars (tests/
 outputs, to the bound of fp32 accumulation in any order.
 
 The CPU tests map the case table through a Python mirror of the host-side dispatch and fail with the name of any
-(kind x epilogue path) no case reaches, compare the mirror with the library's own answers, and pin the refusals."""
+(kind x epilogue path) no case reaches, compare the mirror with the library's own answers, and pin the refusals.
+
+SEG_CASES drives `layers._Conv3dEpiFn.apply` with explicit segments (any first channel, order, residual, slope and
+output type: what `conv3d_heads` does not expose) and with output volumes of more than one VAMP_CONV_EPI_CHUNK; those
+cases hold g_z, read where the backward's entry point wrote it, bit for bit to the operator's own outputs."""
+import contextlib
 import ctypes as C
 import functools
 import os
+from typing import NamedTuple
 
 import pytest
 import torch
@@ -90,6 +96,66 @@ HEAD_CASES = {
 }
 KIND_STRIDE = {"fp32": 1, "half": 1, "half_s2": 2}
 KIND_DTYPES = {"fp32": (F32,), "half": (BF16, FP16), "half_s2": (BF16, FP16)}
+
+
+class SegCase(NamedTuple):
+    """A case driven through `layers._Conv3dEpiFn.apply` with explicit segments.  segs, in descriptor order:
+    (c0, nch, activation, slope, bias, residual).  modes: the out_f32 flags it runs with (1: every output fp32 from a
+    16-bit kind, with fp32 residuals).  dtypes: None = all of the kind's.  no_grad: the segments the loss leaves out."""
+    kind: str
+    B: int
+    cin: int
+    cout: int
+    vol: tuple
+    segs: tuple
+    modes: tuple = (0,)
+    dtypes: object = None
+    no_grad: tuple = ()
+
+
+# four segments out of channel order over a 32-channel weight: channels 16 and 29..31 lie in no segment (16 below three
+# stored ones); the boundaries 3 | 17 | 20 fall inside an M tile and inside a lane's four rows, 16 | 17 on the M-tile
+# boundary; two slopes; a residual with and without a bias, a bias without a residual, neither
+SEG4 = ((20, 9, LEAKY, 0.2, False, True), (0, 3, NONE, 0.0, True, False), (3, 13, SIGMOID, 0.0, True, True),
+        (17, 3, LEAKY, 0.01, False, False))
+SEG2 = ((0, 8, LEAKY, SLOPE, False, False), (8, 8, NONE, 0.0, False, True))       # one M tile
+SEG1_PARTIAL = ((5, 7, LEAKY, SLOPE, True, True),)                                 # `hit` varies per lane
+HEADS3 = ((0, 1, NONE, 0.0, True, False), (1, 18, NONE, 0.0, True, False), (19, 3, SIGMOID, 0.0, True, False))
+FULL16 = ((0, 16, LEAKY, SLOPE, True, True),)                                      # bias + residual + leaky
+# The volumes of the segment cases are those of LAYER_CASES / HEAD_CASES above (x70: the fp32 kind's scalar store; x68:
+# its 16-byte store, here with a residual).  The chunk cases are the smallest planes past VAMP_CONV_EPI_CHUNK = 4096
+# voxels: 3 * 21 * 70 = 4410 = 4096 + 256 + 58 (the last chunk ends inside its second round of 256 threads),
+# 4 * 17 * 64 = 4352 = 4096 + 256 (on a round), 3 * 23 * 60 = 4140 (inside the first round).  bias-65: B * nchunks =
+# 65 partials per channel, one more than the finishing kernel's 64 lanes.
+SEG_CASES = {
+    "seg4-half": SegCase("half", 2, 16, 32, (2, 5, 20), SEG4, (0, 1)),
+    "seg4-s2": SegCase("half_s2", 2, 16, 32, (3, 5, 24), SEG4, (0, 1)),
+    "seg4-fp32-x70": SegCase("fp32", 2, 16, 32, (2, 3, 70), SEG4),
+    "seg4-fp32-x68": SegCase("fp32", 2, 16, 32, (2, 2, 68), SEG4),
+    "seg2-half": SegCase("half", 2, 16, 16, (2, 5, 20), SEG2),
+    "seg2-s2": SegCase("half_s2", 2, 16, 16, (3, 5, 24), SEG2),
+    "seg2-fp32-x70": SegCase("fp32", 2, 16, 16, (2, 3, 70), SEG2),
+    "seg2-fp32-x68": SegCase("fp32", 2, 16, 16, (2, 2, 68), SEG2),
+    "seg1-partial-half": SegCase("half", 2, 16, 16, (2, 5, 20), SEG1_PARTIAL, (0, 1)),
+    "seg1-partial-s2": SegCase("half_s2", 2, 16, 16, (3, 5, 24), SEG1_PARTIAL, (0, 1)),
+    "seg1-partial-fp32": SegCase("fp32", 2, 16, 16, (2, 3, 70), SEG1_PARTIAL),
+    "seg4-unused": SegCase("half", 2, 16, 32, (2, 5, 20), SEG4, (0,), (BF16,), no_grad=(1, 3)),
+    "fp32-chunks": SegCase("fp32", 3, 16, 16, (3, 21, 70), FULL16),
+    "fp32-chunks-round": SegCase("fp32", 2, 16, 16, (4, 17, 64), FULL16),
+    "half-chunks": SegCase("half", 3, 16, 16, (3, 23, 60), FULL16),
+    "s2-chunks": SegCase("half_s2", 2, 16, 16, (5, 45, 120), FULL16),
+    "heads-chunks": SegCase("half", 2, 16, 22, (3, 23, 60), HEADS3, (1,), (BF16,)),
+    "bias-65-fp32": SegCase("fp32", 65, 16, 16, (2, 3, 8), FULL16),
+    "bias-65-half": SegCase("half", 65, 16, 16, (2, 3, 8), FULL16, (0,), (BF16,)),
+    "bias-65-s2": SegCase("half_s2", 65, 16, 16, (2, 3, 8), FULL16, (0,), (BF16,)),
+}
+assert 3 * 21 * 70 == 4096 + 256 + 58 and 4 * 17 * 64 == 4096 + 256 and 3 * 23 * 60 == 4096 + 44
+
+
+def seg_params(names=None):
+    return [pytest.param(name, dt, f32, id=f"{name}-{DT_NAME[dt]}-{'f32out' if f32 else 'own'}")
+            for name, c in SEG_CASES.items() if names is None or name in names
+            for dt in (c.dtypes or KIND_DTYPES[c.kind]) for f32 in c.modes]
 KIND_FORWARD = {"fp32": "vamp_conv3d_epilogue_forward", "half": "vamp_conv3d_half_epilogue_forward",
                 "half_s2": "vamp_conv3d_half_s2_epilogue_forward"}
 
@@ -155,14 +221,16 @@ def mirror_workspace(kind, B, cout, vol):
     return cdiv(cout * B * cdiv(zo * yo * xo, CHUNK) * 8, 256) * 256
 
 
-def mirror_paths(kind, dt, B, cin, cout, vol, segs, has_bias, has_res):
+def mirror_paths(kind, dt, B, cin, cout, vol, segs, has_bias, has_res, no_grad=()):
     """The (kind x epilogue path) pairs a case reaches: the forward instantiation, its store variants, what a segment's
-    epilogue does, and the backward's plan."""
+    epilogue does, and the backward's plan.  no_grad: the segments whose output receives no gradient."""
     zo, yo, xo = out_vol(kind, vol)
     p = {(kind, f"tile {tile_ch(cin)}->{tile_ch(cout)}")}
+    stores = []
     if kind == "fp32":
         groups = [xb for xb in range(0, cdiv(xo, 16) * 16, 4)]
-        p |= {(kind, "store vec4" if xo % 4 == 0 and xb + 3 < xo else "store scalar") for xb in groups if xb < xo}
+        stores = sorted({"store vec4" if xo % 4 == 0 and xb + 3 < xo else "store scalar" for xb in groups if xb < xo})
+        p |= {(kind, s) for s in stores}
         p.add((kind, "x tiles 2" if cdiv(cdiv(xo, 16), 4) > 1 else "x tiles 1"))
     else:
         tx = 64 if kind == "half" else 32
@@ -181,7 +249,46 @@ def mirror_paths(kind, dt, B, cin, cout, vol, segs, has_bias, has_res):
     p.add((kind, "backward skipped" if plain else "backward pass"))
     if any(has_bias):
         p.add((kind, "bias partials"))
-    return p
+    # ---- the forward's segment selection (epi_store_tile's two paths; the fp32 kind's store selects per lane always)
+    multi = len(segs) > 1
+    more = set()
+    if multi:
+        if [s[0] for s in segs] != sorted(s[0] for s in segs):
+            more.add("segments out of channel order")
+        if any(has_res):
+            more.add("multi-seg residual")
+            if segs[0][3]:
+                more.add("multi-seg residual fp32")         # the raw 32-bit load under OF32
+        if any(s[2] == LEAKY for s in segs):
+            more.add("multi-seg leaky")
+        if any(has_bias) and not all(has_bias):
+            more.add("multi-seg mixed bias")
+        if not segs[0][3]:
+            more.add("multi-seg compute dtype")
+        more.add(f"segments {len(segs)}")
+        # the fp32 kind has one store per 16 bytes or per element: a multi-segment path is reached per store variant
+        p |= {(kind, f"{m} {s}") for m in more for s in stores}
+    elif segs[0][0] > 0 or segs[0][1] < cout:
+        more.add("one segment partial")
+    stored = set().union(*[range(c0, c0 + n) for c0, n, _, _ in segs])
+    if set(range(max(stored))) - stored:
+        more.add("gap channel")
+    if any(f32 and r for (_, _, _, f32), r in zip(segs, has_res)):
+        more.add("out fp32 + residual")
+    if no_grad:
+        more.add("segment without gradient")
+    # ---- the backward's chunks (conv3d_epi_bwd_kernel, conv3d_epi_bias_kernel)
+    if not plain:
+        plane = zo * yo * xo
+        nchunks = cdiv(plane, CHUNK)
+        more.add("bwd chunks 1" if nchunks == 1 else "bwd chunks 2+")
+        if nchunks > 1:
+            more.add("multi-seg bwd chunks 2+" if multi else "one-seg bwd chunks 2+")
+            rest = plane - (nchunks - 1) * CHUNK
+            more.add("bwd last chunk ends on a round" if rest % 256 == 0 else "bwd last chunk ends inside a round")
+        if any(has_bias) and B * nchunks > 64:
+            more.add("bias partials wrap the 64 lanes")
+    return p | {(kind, m) for m in more}
 
 
 def case_table():
@@ -197,27 +304,55 @@ def case_table():
             segs = [(0, chans[0], NONE, f32), (chans[0], chans[1], NONE, f32),
                     (chans[0] + chans[1], chans[2], SIGMOID, f32)]
             rows.append((name, kind, dt, B, cin, cout, vol, segs, [True] * 3, [False] * 3))
+    for name, c in SEG_CASES.items():
+        for dt in c.dtypes or KIND_DTYPES[c.kind]:
+            for f32 in c.modes:
+                rows.append((name, c.kind, dt, c.B, c.cin, c.cout, c.vol, [(c0, n, act, f32) for c0, n, act, _, _, _ in c.segs],
+                             [s[4] for s in c.segs], [s[5] for s in c.segs]))
     return rows
 
 
 EVERY_KIND = ["x tiles 1", "x tiles 2", "segments 1", "segments 3", "bias", "no bias", "residual",
               "no residual", "act none", "act leaky", "act sigmoid", "out compute dtype", "backward skipped",
-              "backward pass", "bias partials"]
+              "backward pass", "bias partials",
+              # the segment selection and the backward's chunks
+              "segments 2", "segments 4", "segments out of channel order", "gap channel", "multi-seg residual",
+              "multi-seg leaky", "multi-seg mixed bias", "multi-seg compute dtype", "one segment partial",
+              "bwd chunks 1", "bwd chunks 2+", "one-seg bwd chunks 2+", "bwd last chunk ends inside a round",
+              "bias partials wrap the 64 lanes"]
+# Per kind where the kind has a kernel of its own for the path (the stores); once where the code is shared and a kind
+# adds nothing: the backward kernel is instantiated per dtype, not per kind (a last chunk that ends on a round and the
+# three-segment heads over two chunks run on one kind), and a segment without a gradient is the wrapper's affair.
 WANTED = ({(k, p) for k in KIND_STRIDE for p in EVERY_KIND}
           | {("fp32", p) for p in ("tile 16->16", "tile 16->32", "tile 32->16", "tile 32->32", "store vec4",
-                                   "store scalar", "unstored channels")}
+                                   "store scalar", "unstored channels", "bwd last chunk ends on a round")}
+          | {("fp32", f"{p} {s}") for p in ("segments 2", "segments 4", "multi-seg residual", "multi-seg leaky",
+                                            "multi-seg mixed bias") for s in ("store vec4", "store scalar")}
           | {(k, p) for k in ("half", "half_s2") for p in ("tile 16->32", "tile 32->16", "tile 32->32", "dtype bf16",
-                                                           "dtype fp16")}
-          | {("half", "out fp32 from 16-bit"), ("half_s2", "out fp32 from 16-bit"), ("half", "tile 16->16")})
+                                                           "dtype fp16", "out fp32 + residual",
+                                                           "multi-seg residual fp32")}
+          | {("half", "out fp32 from 16-bit"), ("half_s2", "out fp32 from 16-bit"), ("half", "tile 16->16"),
+             ("half", "multi-seg bwd chunks 2+"), ("half", "segment without gradient")})
+
+
+def reached_paths(rows):
+    reached = set()
+    for name, *args in rows:
+        assert mirror_supported(*args[:7]) == 1, f"{name}: the mirror refuses the case"
+        reached |= mirror_paths(*args, no_grad=SEG_CASES[name].no_grad if name in SEG_CASES else ())
+    return reached
 
 
 def test_case_table_reaches_every_path():
-    reached = set()
-    for name, *args in case_table():
-        assert mirror_supported(*args[:7]) == 1, f"{name}: the mirror refuses the case"
-        reached |= mirror_paths(*args)
-    missing = sorted(WANTED - reached)
+    missing = sorted(WANTED - reached_paths(case_table()))
     assert not missing, f"no case reaches: {missing}"
+
+
+def test_every_segment_case_is_needed():
+    """Without any one of the SEG_CASES the reach check fails: no case of that table is a duplicate of the others."""
+    rows = case_table()
+    for name in SEG_CASES:
+        assert WANTED - reached_paths([r for r in rows if r[0] != name]), f"{name} reaches nothing of its own"
 
 
 def _desc(B, cin, cout, vol):
@@ -411,7 +546,7 @@ def _act64(v, act):
 def _operands(name, dt):
     """The operands of a case, rounded to its dtype, on the CPU: x, w, bias (fp32), residual, the upstream gradient;
     and the float64 convolution of the rounded values with its absolute-value companion sum |w x|."""
-    kind, B, cin, cout, vol = (LAYER_CASES.get(name) or HEAD_CASES[name][:5])
+    kind, B, cin, cout, vol = (LAYER_CASES.get(name) or HEAD_CASES.get(name) or SEG_CASES[name])[:5]
     g = torch.Generator().manual_seed(sum(map(ord, name)))
     ov = out_vol(kind, vol)
     x = torch.randn(B, cin, *vol, generator=g).to(dt)
@@ -626,6 +761,215 @@ def test_sigmoid_layer(dev, name, dt):
         assert e <= max(2 * e_unf, SIG_FLOOR)
     else:
         close(out, ref.float(), what="sigmoid out", **H_OUT)
+
+
+# =====================================================================================================================
+# GPU: explicit segments (any c0, order, residual, slope, output type) and output volumes of more than one chunk
+# =====================================================================================================================
+class _Keeper:
+    """The library with the arguments of every vamp_conv3d_epilogue_backward call kept (grad_z is the fifth)."""
+
+    def __init__(self, lib, kept):
+        self._lib, self._kept = lib, kept
+
+    def __getattr__(self, name):
+        fn = getattr(self._lib, name)
+        if name != "vamp_conv3d_epilogue_backward":
+            return fn
+
+        def call(*a):
+            self._kept.append(a)
+            return fn(*a)
+        return call
+
+
+@contextlib.contextmanager
+def _kept_backward_calls():
+    kept, own = [], _capi.checked
+    via = own(_Keeper(_capi.load(), kept))
+    _capi.checked = lambda through=None: via
+    try:
+        yield kept
+    finally:
+        _capi.checked = own
+
+
+@functools.lru_cache(maxsize=None)
+def _res32(name):
+    """The fp32 residual of a case's fp32-output run: unit normal, not rounded to 16 bits (all 32 bits are read)."""
+    c = SEG_CASES[name]
+    g = torch.Generator().manual_seed(sum(map(ord, name)) + 1)
+    return torch.randn(c.B, c.cout, *out_vol(c.kind, c.vol), generator=g)
+
+
+def _run_segments(name, dt, f32, dev):
+    """`_Conv3dEpiFn.apply` on the case's operands and the backward of sum(out * up) over the segments with a gradient.
+    The operator's results as device tensors, grad_z as the backward's entry point wrote it, the gradients fed in."""
+    from vampire_amd.layers import _Conv3dEpiFn, _EpiSeg
+    c = SEG_CASES[name]
+    x, w, bias, res, up, _, _ = _operands(name, dt)
+    odt, res = (F32, _res32(name)) if f32 else (dt, res)
+    xs, ws = x.to(dev).requires_grad_(True), w.to(dev).requires_grad_(True)
+    segs, tensors, bs, rs, gups = [], [], {}, {}, {}
+    for n, (c0, nch, act, slope, has_b, has_r) in enumerate(c.segs):
+        segs.append(_EpiSeg(c0, nch, act, float(slope), bool(f32), has_b, has_r))
+        if has_b:
+            bs[n] = bias[c0:c0 + nch].to(dev).requires_grad_(True)
+            tensors.append(bs[n])
+        if has_r:
+            rs[n] = res[:, c0:c0 + nch].contiguous().to(dev).requires_grad_(True)
+            tensors.append(rs[n])
+        if n not in c.no_grad:
+            gups[n] = up[:, c0:c0 + nch].to(odt).contiguous().to(dev)
+    with _kept_backward_calls() as kept:
+        outs = _Conv3dEpiFn.apply(c.kind, tuple(segs), xs, ws, *tensors)
+        torch.autograd.backward([outs[n] for n in gups], [gups[n] for n in gups])
+    assert len(kept) == 1, f"{name}: expected one epilogue backward, saw {len(kept)}"
+    return dict(outs=[o.detach() for o in outs], gx=xs.grad, gw=ws.grad, gb={n: b.grad for n, b in bs.items()},
+                gr={n: r.grad for n, r in rs.items()}, gz=kept[0][4], gups=gups)
+
+
+def _gz_own(c, dt, f32, outs, gups, dev):
+    """g_z from the operator's own outputs: the [B, cout, Zo, Yo, Xo] tensor of the compute type (rounded once; 0 in a
+    channel of no segment and in a segment without a gradient), and per segment g_z in the segment's own precision
+    (what its bias gradient sums: fp32 for an fp32-output segment of a 16-bit kind)."""
+    full = torch.zeros((c.B, c.cout) + out_vol(c.kind, c.vol), dtype=dt, device=dev)
+    own = {}
+    for n, (c0, nch, act, slope, _, _) in enumerate(c.segs):
+        if n not in gups:
+            continue
+        g, y = gups[n], outs[n]
+        if act == LEAKY:
+            z = torch.ops.aten.leaky_relu_backward(g, y, slope, True)
+        elif act == SIGMOID:
+            z = ((g.float() * (1.0 - y.float())) * y.float()).to(g.dtype)
+        else:
+            z = g
+        own[n] = z
+        full[:, c0:c0 + nch] = z.to(dt)
+    return full, own
+
+
+def _held(case, what, got, ref, bar, failed):
+    """`close` with the fraction of the bar on record."""
+    a, b = got.detach().cpu().float(), ref.detach().cpu().float()
+    err = (a - b).abs()
+    lim = bar["atol"] + bar["rtol"] * (b.abs().max() if bar.get("scale") == "max" else b.abs())
+    print(f"[conv3d_epilogue:{case}] {what}: max err {float(err.max()):.3e}, bar {bar['atol']:g} + {bar['rtol']:g} "
+          f"{'max ' if bar.get('scale') == 'max' else ''}|ref|, fraction {float((err / lim).max()):.4f}")
+    if not bool((err <= lim).all()):
+        failed.append(f"{what}: max err {float(err.max()):.3e} beyond the bar")
+
+
+@gpu
+@pytest.mark.parametrize("name,dt,f32", seg_params())
+def test_segment_and_chunk_cases(dev, name, dt, f32):
+    """Outputs: compute-dtype ones to the 16-bit bars; the fp32 kind bit for bit to the unfused sequence on the device
+    (conv3d_3x3x3, slice, adds, F.leaky_relu), a sigmoid segment within max(2 x the unfused error, 2^-22); fp32 outputs
+    of a 16-bit kind within (27 cin + 5) 2^-24 (sum |w x| + |bias| + |residual|) of the float64 value, element by
+    element -- the bound of fp32 accumulation in any order with one more addend for the residual; unchanged behind
+    leaky (slope <= 1), a quarter of it plus 2^-22 behind the sigmoid.  g_z bit for bit from the operator's own
+    outputs, a residual's gradient its segment's slice of it (widened for an fp32 residual of a 16-bit kind), the
+    weight-gradient rows of channels without a gradient exactly 0.  grad_x and grad_w against the float64 convolution
+    backward of the operator's own g_z (an element whose pre-activation lies within fp32 rounding of 0 may take either
+    branch of the activation: a draw, and no element is left out this way).  grad_bias within one fp32 ulp of the
+    float64 sum of the operator's own g_z in the segment's precision."""
+    from vampire_amd.layers import conv3d_3x3x3
+    c = SEG_CASES[name]
+    case = f"{name}-{DT_NAME[dt]}-{'f32out' if f32 else 'own'}"
+    odt, stride = (F32 if f32 else dt), KIND_STRIDE[c.kind]
+    got = _run_segments(name, dt, f32, dev)
+    x, w, bias, res, up, conv, absum = _operands(name, dt)
+    res = _res32(name) if f32 else res
+    failed = []
+    if c.kind == "fp32":
+        plain = conv3d_3x3x3(x.to(dev), w.to(dev))
+    for n, (c0, nch, act, slope, has_b, has_r) in enumerate(c.segs):
+        ch, what = slice(c0, c0 + nch), f"out[{n}]"
+        v, mag = conv[:, ch], absum[:, ch]
+        if has_b:
+            v, mag = v + bias[ch].double().view(1, -1, 1, 1, 1), mag + bias[ch].double().abs().view(1, -1, 1, 1, 1)
+        if has_r:
+            v, mag = v + res[:, ch].double(), mag + res[:, ch].double().abs()
+        ref = torch.where(v > 0, v, v * slope) if act == LEAKY else torch.sigmoid(v) if act == SIGMOID else v
+        out = got["outs"][n]
+        assert out.dtype == odt and tuple(out.shape) == tuple(ref.shape), what
+        err = (out.cpu().double() - ref).abs()
+        if c.kind == "fp32":
+            u = plain[:, ch]
+            if has_b:
+                u = u + bias[ch].to(dev).view(1, -1, 1, 1, 1)
+            if has_r:
+                u = u + res[:, ch].to(dev)
+            u = F.leaky_relu(u, slope) if act == LEAKY else torch.sigmoid(u) if act == SIGMOID else u
+            e_unf = float((u.cpu().double() - ref).abs().max())
+            lim = max(2 * e_unf, SIG_FLOOR) if act == SIGMOID else 0.0
+            diff = float((out - u).abs().max())
+            print(f"[conv3d_epilogue:{case}] {what}: max err {float(err.max()):.3e}, unfused {e_unf:.3e}, max |fused - "
+                  f"unfused| {diff:.3e}, bar {'bit-equal' if act != SIGMOID else f'{lim:.3e}'}")
+            if not (float(err.max()) <= lim if act == SIGMOID else torch.equal(out, u)):
+                failed.append(f"{what}: not the unfused sequence's value (max diff {diff:.3e})")
+        elif f32:
+            lim = (27 * c.cin + 5) * 2.0 ** -24 * mag
+            lim = 0.25 * lim + SIG_FLOOR if act == SIGMOID else lim
+            print(f"[conv3d_epilogue:{case}] {what}: max err {float(err.max()):.3e}, smallest bar {float(lim.min()):.3e}, "
+                  f"fraction {float((err / lim).max()):.4f}")
+            if not bool((err <= lim).all()):
+                failed.append(f"{what}: beyond the fp32 accumulation bound (max err {float(err.max()):.3e})")
+        else:
+            _held(case, what, out, ref, H_OUT, failed)
+    # g_z, bit for bit
+    full, own = _gz_own(c, dt, f32, got["outs"], got["gups"], dev)
+    gz = got["gz"]
+    assert gz.dtype == dt and gz.shape == full.shape
+    wrong = int((gz != full).sum())
+    print(f"[conv3d_epilogue:{case}] g_z: {wrong} of {gz.numel()} elements differ from the operator's own outputs' (bar 0)")
+    if wrong:
+        failed.append(f"g_z: {wrong} elements differ")
+    for n, g in got["gr"].items():
+        c0, nch = c.segs[n][:2]
+        if not (g.dtype == odt and torch.equal(g, full[:, c0:c0 + nch].to(odt))):
+            failed.append(f"grad_residual[{n}] is not its segment's slice of g_z")
+    live = set().union(*[range(c.segs[n][0], c.segs[n][0] + c.segs[n][1]) for n in got["gups"]])
+    dead = [ch for ch in range(c.cout) if ch not in live]
+    if dead and bool((got["gw"][dead] != 0).any()):
+        failed.append(f"grad_w: rows of channels without a gradient are not 0 ({dead})")
+    # the convolution's backward of that g_z
+    xd, wd = x.double().requires_grad_(True), w.double().requires_grad_(True)
+    r_gx, r_gw = torch.autograd.grad(F.conv3d(xd, wd, stride=stride, padding=1), (xd, wd), full.double().cpu())
+    assert got["gx"].dtype == dt and got["gw"].dtype == dt
+    _held(case, "grad_x", got["gx"], r_gx, H_GIN, failed)
+    _held(case, "grad_w", got["gw"], r_gw, H_GW, failed)
+    # the bias gradients
+    for n, gb in got["gb"].items():
+        assert gb.dtype == F32 and tuple(gb.shape) == (c.segs[n][1],)
+        if n in own:
+            want = own[n].double().sum(dim=(0, 2, 3, 4)).cpu()
+        else:
+            want = torch.zeros(c.segs[n][1], dtype=F64)
+        ulps = (gb.double().cpu() - want).abs() / _ulp32(want)
+        print(f"[conv3d_epilogue:{case}] grad_bias[{n}] vs sum(g_z): max err {float((gb.double().cpu() - want).abs().max()):.3e}, "
+              f"bar one fp32 ulp, fraction {float(ulps.max()):.3f}")
+        if not bool((ulps <= 1.0).all()):
+            failed.append(f"grad_bias[{n}] beyond one fp32 ulp of sum(g_z): {float(ulps.max()):.3f} ulp")
+    assert not failed, f"{case}: " + "; ".join(failed)
+
+
+@gpu
+@pytest.mark.parametrize("name,dt,f32", [("seg4-half", BF16, 1), ("seg4-s2", FP16, 1), ("half-chunks", BF16, 0),
+                                         ("bias-65-fp32", F32, 0), ("bias-65-half", BF16, 0)])
+def test_segment_and_chunk_runs_are_bitwise_equal(dev, name, dt, f32):
+    """Everything but the fp32 kind's weight gradient where its reduce spans slices (B Z Y >= 16: float atomics)."""
+    c = SEG_CASES[name]
+    a, b = _run_segments(name, dt, f32, dev), _run_segments(name, dt, f32, dev)
+    pairs = [(f"out[{n}]", p, q) for n, (p, q) in enumerate(zip(a["outs"], b["outs"]))]
+    pairs += [("g_z", a["gz"], b["gz"]), ("grad_x", a["gx"], b["gx"])]
+    pairs += [(f"grad_bias[{n}]", a["gb"][n], b["gb"][n]) for n in a["gb"]]
+    pairs += [(f"grad_residual[{n}]", a["gr"][n], b["gr"][n]) for n in a["gr"]]
+    if c.kind != "fp32" or c.B * c.vol[0] * c.vol[1] < 16:
+        pairs.append(("grad_w", a["gw"], b["gw"]))
+    for what, p, q in pairs:
+        assert torch.equal(p, q), f"{name}: {what} differs between two runs"
 
 
 # =====================================================================================================================

@@ -14,7 +14,7 @@
 // A lane adds its elements in the order it meets them, so every sum below has one fixed order per shape.
 //
 //  stats      bn_stats_kernel: the chunk's count, mean and M2 = sum (x - mean)^2 in float64.  The sums are taken of
-//             x - K with K the chunk's first element: t1 = sum (x - K), t2 = sum (x - K)^2, each difference exact in
+//             x - K with K the chunk's first element (0 if that one is not finite): t1 = sum (x - K), t2 = sum (x - K)^2, each difference exact in
 //             float64, lanes then the butterfly of wave_reduce.hpp then the waves in index order; mean = K + t1 / cnt,
 //             M2 = max(t2 - t1^2 / cnt, 0).  A constant chunk gives mean = K and M2 = 0 exactly, and a channel with
 //             |mean| >> sigma loses nothing to cancellation.  S = 1: straight into the row; else into the chunk's slot
@@ -171,7 +171,10 @@ __global__ void __launch_bounds__(kBnBlock) bn_stats_kernel(const void* __restri
   __shared__ double red[kBnWaves];
   int c, s, j0, j1;
   bn_chunk(sh, c, s, j0, j1);
-  const double K = (double) bn_ld<DT>(x, bn_offset(sh, c, (unsigned) j0));
+  // (a first element of +-inf or NaN is no pivot: x - K would be NaN for the +-inf itself and the mean NaN, where the
+  // mean of a channel that holds one +-inf is that +-inf)
+  const double K0 = (double) bn_ld<DT>(x, bn_offset(sh, c, (unsigned) j0));
+  const double K = K0 - K0 == 0.0 ? K0 : 0.0;
   double s1 = 0.0, s2 = 0.0;
   bn_walk<V>(sh, c, j0, j1, [&](long off, auto cnt) {
     constexpr int CNT = decltype(cnt)::value;
